@@ -12,14 +12,20 @@ gloo — the line then says so in ``comm``.
 One step = masked-phoneme forward -> per-sample masked cross-entropy -> backward -> gradient
 all-reduce (N > 1: RCCL behind the C ABI, issued piecewise inside the backward) -> AdamW, on one synthetic
 fixed-length batch per rank (BASELINE.json configs[1]: ALBERT hidden 768 / 12 shared layers / FFN 2048, seq
-512, batch 32 per GPU; weak scaling).  ``value`` times the step with its batch resident in HBM;
-``staged`` repeats the K steps with a FRESH host batch staged every step (pinned buffers, copy stream,
-double buffered) as a real input pipeline would.  Prints ONE JSON line on rank 0.
+512, batch 32 per GPU; weak scaling).  ``value`` times the step with its batch resident in HBM.
+Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up (W steps), times the K steps, writes their outputs (--dump-outputs DIR) and prints
+the line. Everything else it can report runs only with --full (each part can be left out with its --no-* option):
+loss_parity: the first steps from fresh weights against the reference's trajectory (tests/golden).
+staged: the K steps again with a FRESH host batch staged every step (pinned buffers, copy stream,
+double buffered) as a real input pipeline would.
+comm: with the engine's own exchange, the piece trace and the exchange's cost (serial, overlapped, none).
 roofline: the dominant kernel class of the step, algorithmic FLOPs per launch / average launch
 duration, from per-launch HIP events recorded on the launch stream during a re-run of the same K
-steps (the clean timed region carries no events).  cpu_baseline: the numpy oracle's training step
-(oracle/albert_np.py, kind "port") on the host cores, rank 0 at N=1 only, bounded sample.
+steps (the clean timed region carries no events); roofline.traffic from rocprofv3 PMC child runs.
+cpu_baseline: the numpy oracle's training step (oracle/albert_np.py, kind "port") on the host cores, rank 0 at N=1
+only, bounded sample.  secondary: BASELINE.json's other configurations and the real input pipeline, as child runs.
 """
 from __future__ import annotations
 
@@ -54,6 +60,12 @@ def parse():
     # 100 timed steps = ~1 s: a single burst of box noise (a clock excursion, a host hiccup) cannot move the line by 1 %
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: loss parity against the reference, per-step staging, "
+                         "exchange cost, roofline and PMC traffic, CPU baseline, secondary workloads (see the --no-* options)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameters after its update, its gradients) "
+                         "as float32 .npy files into DIR (see dump_outputs)")
     ap.add_argument("--batch", type=int, default=32, help="samples per GPU")
     ap.add_argument("--seq", type=int, default=512)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -222,7 +234,7 @@ def secondary_lines():
     out = {}
     for key, extra in (("large", ["--model", "large"]), ("fp8", ["--dtype", "fp8"]), ("large_fp8", ["--model", "large", "--dtype", "fp8"]),
                        ("dual_head", ["--num-tokens", "5000", "--no-roofline"])):   # configs[1]'s "dual-head loss", anchored to the reference
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "40", "--warmup", "8", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "40", "--warmup", "8", "--full", "--no-cpu-baseline",
                "--no-traffic", "--no-staged", "--no-secondary", *extra]
         note(f"secondary.{key}")
         try:
@@ -443,6 +455,32 @@ def loss_parity(trainer, batch, args, world, B, S):
             "note": None if args.dtype == "bf16" else "fp8 call: step 1 is the bf16 calibration call; tolerance is the mode's own 2e-2"}
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: all arrays together stay below this
+
+
+def dump_outputs(out_dir, eng, loss, dual):
+    """--dump-outputs DIR, called right after the timed region: what the timed path handed its caller in its last step,
+    as float32 .npy files. loss.npy: that step's loss; loss_parts.npy: its (phoneme, token) parts (dual-head step only);
+    params.npy: the engine's flat fp32 parameter buffer after that step's AdamW update; grads.npy: the gradients the
+    update applied (the flat buffer, same layout). Weights and batches are seeded, so runs with the same arguments start
+    from identical inputs and two builds can be compared file by file. When params and grads together exceed
+    DUMP_BYTES (--model large, a token head), both hold the same fixed, seeded sample of positions, in ascending order."""
+    arrays = {"loss": loss.detach().float().cpu().numpy().reshape(-1)}
+    if dual:
+        arrays["loss_parts"] = eng.loss_parts.detach().float().cpu().numpy().reshape(-1)
+    params = eng.params.detach().cpu().numpy()
+    grads = eng.grads.detach().cpu().numpy()
+    cap = (DUMP_BYTES - 1_000_000) // (2 * 4)
+    if params.size > cap:
+        keep = np.sort(np.random.RandomState(0).choice(params.size, cap, replace=False))
+        params, grads = params[keep], grads[keep]
+    arrays.update(params=params, grads=grads)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(arrays)
+
+
 class StagedFeeder:
     """Per-step staging of a FRESH host batch: K distinct synthetic batches are generated (and validated — host work a
     real pipeline does in its loader workers) before the timed region; each step's batch is packed into ONE pinned host
@@ -613,8 +651,8 @@ def main():
         token_ids = np.random.RandomState(4321 + rank).randint(0, args.num_tokens, size=(B, S)).astype(np.int64)
         model_desc += f" + token head {args.num_tokens}"
     batch = trainer.stage_batch(labels, masked, lengths, idx, token_ids=token_ids)  # resident in HBM before timing
-    # the run's first steps from fresh weights against the reference's own trajectory on the same inputs (untimed)
-    parity = loss_parity(trainer, batch, args, world, B, S)
+    # --full: the run's first steps from fresh weights against the reference's own trajectory on the same inputs (untimed)
+    parity = loss_parity(trainer, batch, args, world, B, S) if args.full else None
     if parity is not None and rank != 0:
         parity = None
 
@@ -693,6 +731,8 @@ def main():
     run_steps(args.warmup)
     dt, loss = timed(run_steps, args.steps)
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, loss, batch.token_ids is not None)
     if trainer.comm == "rccl":  # which form of the exchange the timed steps really ran
         n_coll, n_floats = eng.comm_pieces()
         comm_info.update(pieces_per_step=n_coll, floats_per_step=n_floats)
@@ -701,7 +741,7 @@ def main():
         # beside begin / end of the weight-gradient tail — a piece that finishes long after tail_ms[1] is what the step
         # waits for; (b) the tail's weight-gradient GEMM time with the exchange running beside it (here) and without
         # (roofline.kernel_ms_per_step, measured after the communicator is gone): RCCL-vs-GEMM CU contention.
-        if True:   # traced in the overlapped form whichever form the calibration kept for the timed steps
+        if args.full:   # traced in the overlapped form whichever form the calibration kept for the timed steps
             eng.set_grad_overlap(True)
             eng.comm_trace(True)
             run_steps(3)
@@ -731,7 +771,7 @@ def main():
 
     # ---- the same K steps with a fresh batch staged every step (H2D inside the timed region) -------------------
     staged = None
-    if not args.no_staged and not args.num_tokens and not shared:  # (ranks sharing a device: rehearsal of the launch only)
+    if args.full and not args.no_staged and not args.num_tokens and not shared:  # (ranks sharing a device: rehearsal of the launch only)
         feeder = StagedFeeder(trainer, min(args.steps, 16), B, S, 99 + rank, torch)
         # pinned-buffer creation leaves the process slow for some tens of steps (as communicator creation does): settle
         # untimed; tools/staged_probe.py shows the staged and the resident loop level once settled
@@ -744,7 +784,7 @@ def main():
                          "the timed region"}
 
     # ---- all-reduce cost: serial collective timed by events; step time with the exchange skipped ---------------
-    if trainer.comm == "rccl" and world >= 1:
+    if args.full and trainer.comm == "rccl" and world >= 1:
         eng.set_grad_overlap(False)
         run_steps(2)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -783,7 +823,7 @@ def main():
         trainer.reducer.active = False
         trainer.world = 1
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         _lib.profile_enable(True)
         for _ in range(args.steps):
             trainer.step(batch)
@@ -850,11 +890,11 @@ def main():
         roofline.pop("_algo_bytes", None)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.num_tokens:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.num_tokens:
         note("cpu_baseline")
         cpu = cpu_baseline(args.cpu_seconds)
     secondary = None
-    if (rank == 0 and world == 1 and not dist.is_initialized() and not args.no_secondary and args.model == "base"
+    if (args.full and rank == 0 and world == 1 and not dist.is_initialized() and not args.no_secondary and args.model == "base"
             and args.dtype == "bf16" and not args.num_tokens and args.batch == 32 and args.seq == 512):
         secondary = secondary_lines()
         if not args.no_pipeline:
@@ -898,6 +938,8 @@ def main():
         os.dup2(real_stdout, 1)
         print(json.dumps(out), flush=True)
         os.dup2(2, 1)
+    if trainer.comm == "rccl":   # a plain run keeps its communicator to the end (--full has destroyed it above)
+        eng.comm_destroy()
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -242,7 +242,7 @@ def capture_model(tag, cfg_kwargs, num_phonemes, num_tokens, batch, seed, full, 
         out["probe_logits"] = pred.numpy()[pb, ps, :]
         out["probe_hidden"] = hidden.numpy()[pb, ps, :]
         out["logit_row_sums"] = pred.numpy().sum(-1)
-    np.savez_compressed(os.path.join(OUT, f"{tag}.npz"), **out, allow_pickle=True)
+    save_fixture(tag, out)
     print(tag, "written; loss", out.get("loss"), "sdpa delta", out["sdpa_max_abs_delta_valid_rows"])
 
 
@@ -319,8 +319,23 @@ def capture_dualloss(tag, cfg_kwargs, num_phonemes, num_tokens, batch, seed, n_s
         out["probe_b"], out["probe_s"] = pb, ps
         out["probe_logits"] = ph0.numpy()[pb, ps, :]
         out["probe_token_logits"] = tk0.numpy()[pb, ps, :]
-    np.savez_compressed(os.path.join(OUT, f"{tag}.npz"), **out, allow_pickle=True)
+    save_fixture(tag, out)
     print(tag, "written; losses", losses, "parts", parts[0])
+
+
+MAX_FILE = 1 << 20   # the limit for a committed file
+
+
+def save_fixture(tag, out):
+    """tests/golden/<tag>.npz; a fixture above MAX_FILE keeps its post-update weights (final/*) in <tag>.final.npz
+    (tests/conftest.py: load_golden gathers the parts)."""
+    path, part = os.path.join(OUT, f"{tag}.npz"), os.path.join(OUT, f"{tag}.final.npz")
+    if os.path.exists(part):
+        os.remove(part)
+    np.savez_compressed(path, **out, allow_pickle=True)
+    if os.path.getsize(path) > MAX_FILE:
+        np.savez_compressed(path, **{k: v for k, v in out.items() if not k.startswith("final/")}, allow_pickle=True)
+        np.savez_compressed(part, **{k: v for k, v in out.items() if k.startswith("final/")}, allow_pickle=True)
 
 
 def main():

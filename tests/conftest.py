@@ -14,8 +14,22 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+class _Golden(dict):
+    """The arrays of one fixture, gathered from ``<name>.npz`` and its parts ``<name>.<part>.npz``: a fixture above the
+    1 MiB limit for a committed file is stored in pieces (oracle/gen_golden.py: save_fixture)."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=True)
+    import glob
+    g = _Golden()
+    for path in [os.path.join(GOLDEN, name + ".npz"), *sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".*.npz")))]:
+        with np.load(path, allow_pickle=True) as z:
+            g.update((k, z[k]) for k in z.files)
+    return g
 
 
 def golden_cfg(g):

@@ -283,6 +283,34 @@ def test_bench_maps_profiler_classes_to_rocprof_kernel_names():
     assert bench._in_class("attn_bwd_dkv", "(anonymous namespace)::attn_bwd_dkv_kernel(PlbAttn)")
 
 
+def test_bench_dump_outputs_stays_within_its_budget(tmp_path):
+    """bench.py --dump-outputs writes float32 .npy files; parameters + gradients above DUMP_BYTES are written as the same
+    fixed sample of positions on every run, in ascending order."""
+    import importlib
+    import types
+
+    import torch
+
+    bench = importlib.import_module("bench")
+
+    def eng(n):
+        p = torch.arange(n, dtype=torch.float32)
+        return types.SimpleNamespace(params=p, grads=-p, loss_parts=torch.tensor([1.5, 0.25]))
+
+    assert bench.dump_outputs(str(tmp_path / "s"), eng(1000), torch.tensor([2.5]), True) == ["grads", "loss", "loss_parts", "params"]
+    s = {n: np.load(tmp_path / "s" / f"{n}.npy") for n in ("grads", "loss", "loss_parts", "params")}
+    assert all(v.dtype == np.float32 for v in s.values())
+    assert np.array_equal(s["params"], np.arange(1000)) and np.array_equal(s["grads"], -s["params"])
+    assert s["loss"].tolist() == [2.5] and s["loss_parts"].tolist() == [1.5, 0.25]
+    big = eng(bench.DUMP_BYTES // 4)   # params + grads: twice the budget
+    for d in ("b1", "b2"):
+        assert bench.dump_outputs(str(tmp_path / d), big, torch.tensor([2.5]), False) == ["grads", "loss", "params"]
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_BYTES
+    p1, g1 = np.load(tmp_path / "b1" / "params.npy"), np.load(tmp_path / "b1" / "grads.npy")
+    assert np.array_equal(p1, np.load(tmp_path / "b2" / "params.npy")) and np.array_equal(g1, -p1)
+    assert (np.diff(p1) > 0).all() and p1.size > bench.DUMP_BYTES // 16
+
+
 def test_bench_parent_spawns_ranks_without_touching_the_gpu(monkeypatch, capsys):
     """`python bench.py --gpus N` as typed: the parent must start N ranks through torch.distributed.run on
     127.0.0.1 BEFORE importing torch / making any GPU call, and relay rank 0's single JSON line."""

@@ -314,7 +314,8 @@ def test_bench_at_world_2_through_the_engines_own_exchange(fake_lib, ranks):
     env = dict(os.environ, PYTHONPATH=ROOT, PLBERT_RCCL_LIB=fake_lib, FAKE_RCCL_TIMEOUT_S="120")
     env.pop("MASTER_PORT", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--comm", "rccl", "--steps", "4",
-                        "--warmup", "2", "--batch", "4", "--seq", "128", "--no-cpu-baseline", "--no-traffic", "--no-roofline"],
+                        "--warmup", "2", "--batch", "4", "--seq", "128", "--full", "--no-cpu-baseline", "--no-traffic",
+                        "--no-roofline"],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -109,8 +109,31 @@ def test_bench_gpus_2_as_typed_self_launches_its_ranks():
     assert out["value"] > 0 and np.isfinite(out["step_loss"])
 
 
+def test_bench_plain_run_dumps_its_last_timed_step(tmp_path):
+    """A plain run (no --full) reports the headline alone and, with --dump-outputs, writes what its last timed step
+    computed: the loss, the parameters after that step's update and the gradients it applied, in float32. The same
+    arguments start from the same weights and batch, so a second run writes the same arrays (no float atomics in the
+    engine: bit for bit)."""
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = _bench("--dump-outputs", str(d))
+        runs.append({n: np.load(d / f"{n}.npy") for n in ("loss", "params", "grads")})
+        assert sum(f.stat().st_size for f in d.iterdir()) < 64e6
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    for k in ("loss_parity", "staged", "roofline", "cpu_baseline"):
+        assert out[k] is None, k
+    assert "secondary" not in out
+    a, b = runs
+    assert all(v.dtype == np.float32 for v in a.values()) and a["loss"].shape == (1,)
+    assert abs(float(a["loss"][0]) - out["step_loss"]) <= 1e-5
+    assert a["params"].shape == a["grads"].shape and np.isfinite(a["params"]).all() and np.abs(a["grads"]).max() > 0
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+
+
 def test_bench_rccl_rehearsal_at_world_1_reports_exchange_cost():
-    out = _bench("--force-dist", "--no-roofline")
+    out = _bench("--force-dist", "--no-roofline", "--full")   # the exchange cost and the staged re-run are --full's
     assert out["n_gpus"] == 1 and out["ranks_seen"] == 1
     c = out["comm"]
     assert c["mode"] == "rccl" and c["rccl_version"] >= 20000

@@ -7,7 +7,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_fp8.py tests/test_gpu_engine.p
 [ $rc -eq 124 ] && exit 1
 fi
 run() { name=$1; shift
-  timeout -k 10 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-traffic --no-staged --no-secondary "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $name failed"; tail -5 $O/bench_$name.err; exit 1; }
+  timeout -k 10 300 python bench.py --steps 40 --warmup 8 --full --no-cpu-baseline --no-traffic --no-staged --no-secondary "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $name failed"; tail -5 $O/bench_$name.err; exit 1; }
   python - $O/bench_$name.json $name <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

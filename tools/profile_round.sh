@@ -9,7 +9,7 @@ R=$PWD
 O=$R/gpurun_out/prof_$tag
 mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 600 python bench.py "$@" > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 B="--steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-traffic --no-staged --no-secondary"
 cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 $R/bench.py $B "$@" > $O/stats.log 2>&1; echo "stats rc=$?"
 for ctr in FETCH_SIZE WRITE_SIZE; do

@@ -25,7 +25,7 @@ def main():
             for kv in [e for e in envs.split(",") if e]:
                 k, _, val = kv.partition("=")
                 env[k] = os.path.abspath(os.path.join(ROOT, val)) if k == "PLBERT_HIP_LIB" else val
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "10", "--no-cpu-baseline",
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "10", "--full", "--no-cpu-baseline",
                    "--no-traffic", "--no-staged", "--no-secondary"] + a.args.split()
             out = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=600)
             line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
