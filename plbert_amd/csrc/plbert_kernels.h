@@ -149,7 +149,8 @@ typedef struct {
 // n consecutive sites. |x| maximum of a bf16 / fp32 buffer into a site (atomic max; zero it first),
 // scale update (delayed scaling: scale = fmax / amax, deq = 1 / scale, amax reset), quantisation of a bf16 / fp32 matrix
 int plb_launch_amax(const void* x, int is_bf16, size_t rows, int cols, int ld, float* amax, hipStream_t stream);
-// group: runs of `group` consecutive sites share one scale (from the largest maximum of the run); 1 = every site its own
+// group: runs of `group` consecutive sites share one scale (from the largest maximum of the run); 1 = every site its own.
+// A group whose maximum is 0 (nothing seen) or +inf keeps its scale, deq and stats; its slots are cleared either way.
 int plb_launch_fp8_scales(float* amax, float* scale, float* deq, int n, float fmax, int group, hipStream_t stream);
 // the same with a second target for entries [n2, n) (n2 a multiple of group). stats (or null): 8 floats per group — a
 // four-call history of the group's maxima (groups from hist_from on take their scale from its largest entry), the number

@@ -446,3 +446,47 @@ def test_fp8_mfmas_stay_in_their_hand_placed_slots(tmp_path):
         else:
             run = 0
     assert total == 64 and best == 1, (total, best)   # two K-tiles of 32 MFMAs, each alone in its slot
+
+
+# Launchers of csrc/plbert_kernels.h that no test calls by name, each with the test that reaches it through a public entry
+# point: (test module, a name that module must contain, why the launcher is not called directly).
+LAUNCHERS_REACHED_THROUGH_ENTRY_POINTS = {
+    "plb_launch_adamw": ("test_gpu_adamw_kernel.py", "adamw_step",
+                         "plb_adamw_step is a thin wrapper; pinned there against torch.optim.AdamW"),
+    "plb_launch_mask": ("test_gpu_device_mask.py", "device_mask_batch",
+                        "plb_mask_batch launches it alone; its statistics and CSR output are tested there"),
+    "plb_launch_apply_mask": ("test_gpu_apply_mask.py", "apply_mask",
+                              "plb_apply_mask launches it alone; compared bit for bit with the host masking there"),
+    "plb_launch_step_status": ("test_gpu_handoff_fault.py", "poll_status",
+                               "the end-of-call status word; its effect (NaN loss, skipped update) is what those tests assert"),
+    "plb_launch_status_export": ("test_gpu_comm_fake_rccl.py", "plb_debug_ln_fault",
+                                 "the word the ranks all-reduce: a fault on rank 1 only must stop the update on both ranks"),
+    "plb_launch_add_scalar": ("test_gpu_dual_head.py", "loss_fwd_bwd_dual",
+                              "the dual-head loss is phoneme + token loss; tested as that sum"),
+}
+
+
+def test_every_kernel_launcher_is_named_by_a_test():
+    """Every `int plb_launch_*(` of csrc/plbert_kernels.h is CALLED (`plb_launch_x(`) in tests/ (gpu_util.py included;
+    naming it in a table of signatures does not count) or is listed above with the test that reaches it: a launcher added
+    without a test fails here."""
+    hdr = open(os.path.join(ROOT, "plbert_amd", "csrc", "plbert_kernels.h")).read()
+    launchers = sorted(set(re.findall(r"\bint\s+(plb_launch_[a-z0-9_]+)\s*\(", hdr)))
+    assert len(launchers) >= 40, launchers
+    tests_dir = os.path.join(ROOT, "tests")
+    texts = {}
+    for name in os.listdir(tests_dir):
+        if name.endswith(".py") and name != os.path.basename(__file__):
+            texts[name] = open(os.path.join(tests_dir, name)).read()
+    untested = []
+    for fn in launchers:
+        if any(re.search(r"\b%s\s*\(" % fn, t) for t in texts.values()):
+            continue
+        if fn in LAUNCHERS_REACHED_THROUGH_ENTRY_POINTS:
+            mod, token, reason = LAUNCHERS_REACHED_THROUGH_ENTRY_POINTS[fn]
+            assert mod in texts and token in texts[mod] and reason, (fn, mod, token)
+            continue
+        untested.append(fn)
+    assert not untested, f"launchers named by no test and not exempted: {untested}"
+    stale = [fn for fn in LAUNCHERS_REACHED_THROUGH_ENTRY_POINTS if fn not in launchers]
+    assert not stale, stale

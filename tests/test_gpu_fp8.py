@@ -18,7 +18,7 @@ import pytest
 import torch
 
 from conftest import golden_cfg, load_golden
-from gpu_util import rel_l2, stream
+from gpu_util import assert_fp8_image, rel_l2, site_max, stream
 import plbert_amd
 from plbert_amd import _lib
 from plbert_amd.engine import HipEngine
@@ -49,7 +49,7 @@ def test_fp8_gemm_against_fp32_on_the_same_quantised_operands(M, N, K, act, bf8)
     aux = (torch.randn(M, N, device=DEV, generator=g)).to(torch.bfloat16)
     Cb = torch.zeros(M, N, dtype=torch.bfloat16, device=DEV)
     C2 = torch.zeros_like(Cb)
-    C8 = torch.zeros(M, N, dtype=torch.uint8, device=DEV)
+    C8 = torch.full((M, N), 0x55, dtype=torch.uint8, device=DEV)
     deq = torch.tensor([1.0 / sa, 1.0 / sw], device=DEV)
     qs = torch.tensor([3.0], device=DEV)
     amax = torch.zeros(64 * 16, device=DEV)  # one site: 64 slots on separate 64-byte lines
@@ -83,6 +83,7 @@ def test_fp8_gemm_against_fp32_on_the_same_quantised_operands(M, N, K, act, bf8)
         q8 = C8.view(torch.float8_e4m3fn).float() / 3.0                     # the fp8 image of gelu as stored
         assert rel_l2(q8[rows], C2[rows].float()) < 4e-2                     # 3 mantissa bits
         assert abs(float(amax.max()) - float(C2[rows].float().abs().max())) < 1e-6
+        assert_fp8_image(C8, C2, qs, 0, rows, amax_site=amax, sentinel=0x55)      # bit for bit, stored rows only
     else:
         x = aux.float()
         k = 0.7978845608028654
@@ -92,6 +93,7 @@ def test_fp8_gemm_against_fp32_on_the_same_quantised_operands(M, N, K, act, bf8)
         assert rel_l2(Cb[rows].float(), want[rows]) < 6e-3
         q8 = C8.view(torch.float8_e5m2).float() / 3.0
         assert rel_l2(q8[rows], Cb[rows].float()) < 8e-2                     # 2 mantissa bits
+        assert_fp8_image(C8, Cb, qs, 1, rows, amax_site=amax, sentinel=0x55)
         assert rel_l2(colp.sum(0), Cb[rows].float().sum(0)) < 1e-4           # bias-gradient partials of the stored values
 
 
@@ -238,6 +240,7 @@ def test_fp8_layernorm_forward_form_against_the_bf16_form(M, N, K):
     assert (q[rows] - y1[rows].float()).abs().max() <= 2.0 ** -4 * float(y1[rows].float().abs().max()) + 1e-6
     assert (img[M - 5:] == 0x55).all() and (y1[M - 5:] == 0).all()           # rows >= Mstore: untouched
     assert abs(float(t.amax.max()) - float(y1[rows].float().abs().max())) < 1e-6
+    assert_fp8_image(img, y1, t.qs, 0, rows, amax_site=t.amax, sentinel=0x55)
     assert int(t.err[0].item()) == 0 and int(t.xchg.abs().sum().item()) == 0
 
 
@@ -273,6 +276,7 @@ def test_fp8_layernorm_backward_form_against_the_bf16_form(M, N, K):
     assert rel_l2(q[rows], dx1[rows].float()) < 8e-2                         # 2 mantissa bits
     assert (img[M - 5:] == 0x55).all()
     assert abs(float(t.amax.max()) - float(dx1[rows].float().abs().max())) < 1e-6
+    assert_fp8_image(img, dx1, t.qs, 1, rows, amax_site=t.amax, sentinel=0x55)
     assert int(t.err[0].item()) == 0 and int(t.xchg.abs().sum().item()) == 0
 
 
@@ -289,7 +293,8 @@ def test_fp8_gelu_stash_forms_forward_then_backward(M, N, K, with16):
     deq = torch.tensor([1.0 / sa, 1.0 / sw], device=DEV)
     stash = torch.zeros(M, N, dtype=torch.bfloat16, device=DEV)
     gl = torch.full((M, N), 7.0, dtype=torch.bfloat16, device=DEV)
-    g8 = torch.zeros(M, N, dtype=torch.uint8, device=DEV)
+    g8buf = torch.full((M + 2, N), 0x55, dtype=torch.uint8, device=DEV)   # two rows past the output: must stay untouched
+    g8 = g8buf[:M]
     qs = torch.tensor([16.0], device=DEV)
     amax = torch.zeros(64 * 16, device=DEV)
     p = _lib.PlbGemmNT()
@@ -310,15 +315,25 @@ def test_fp8_gelu_stash_forms_forward_then_backward(M, N, K, with16):
         assert rel_l2(gl.float(), ref_g.detach()) < 4e-3
         assert rel_l2(q, gl.float()) < 4e-2
         assert abs(float(amax.max()) - float(gl.float().abs().max())) < 1e-6
+        assert_fp8_image(g8buf, gl, qs, 0, slice(0, M), amax_site=amax, sentinel=0x55)
     else:
         assert (gl == 7.0).all()                                             # no bf16 image was written
+        # the image-only launch writes the same bytes as a launch that also stores gelu(u) — the image of those values
+        g8b = torch.full((M + 2, N), 0x55, dtype=torch.uint8, device=DEV)
+        amax_b = torch.zeros(64 * 16, device=DEV)
+        p.C2, p.ldc2, p.C8, p.q_amax = gl.data_ptr(), N, g8b.data_ptr(), amax_b.data_ptr()
+        assert L.plb_launch_gemm_nt_fp8_gelud(C.byref(p), 0, 0, stream()) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(g8b[:M], g8) and site_max(amax_b) == site_max(amax)
+        assert_fp8_image(g8b, gl, qs, 0, slice(0, M), amax_site=amax_b, sentinel=0x55)
     # backward: dU = (dY·W2ᵀ) ∘ gelu'(u) with a gradient operand in e5m2
     K2 = 768 if K == 768 else 1024
     D8, Dd, sd = _q2(torch.randn(M, K2, device=DEV, generator=g) * 0.01, True)
     V8, Vd, sv = _q2(torch.randn(N, K2, device=DEV, generator=g) * K2 ** -0.5, False)
     deq2 = torch.tensor([1.0 / sd, 1.0 / sv], device=DEV)
     du = torch.full((M, N), 7.0, dtype=torch.bfloat16, device=DEV)
-    du8 = torch.zeros(M, N, dtype=torch.uint8, device=DEV)
+    du8buf = torch.full((M + 2, N), 0x55, dtype=torch.uint8, device=DEV)
+    du8 = du8buf[:M]
     colp = torch.zeros(2 * (M // 128), N, device=DEV)
     qs2 = torch.tensor([2.0 ** 16], device=DEV)
     amax2 = torch.zeros(64 * 16, device=DEV)
@@ -341,9 +356,17 @@ def test_fp8_gelu_stash_forms_forward_then_backward(M, N, K, with16):
         assert rel_l2(du.float(), want) < 8e-3                              # the derivative went through one bf16 rounding
         assert rel_l2(colp.sum(0), du.float().sum(0)) < 1e-4
         assert abs(float(amax2.max()) - float(du.float().abs().max())) < 1e-9
+        assert_fp8_image(du8buf, du, qs2, 1, slice(0, M), amax_site=amax2, sentinel=0x55)
     else:
         assert (du == 7.0).all()
         assert rel_l2(colp.sum(0), want.sum(0)) < 2e-2
+        du8b = torch.full((M + 2, N), 0x55, dtype=torch.uint8, device=DEV)
+        amax_b2 = torch.zeros(64 * 16, device=DEV)
+        p2.C, p2.ldc, p2.C8, p2.q_amax = du.data_ptr(), N, du8b.data_ptr(), amax_b2.data_ptr()
+        assert L.plb_launch_gemm_nt_fp8_gelud(C.byref(p2), 1, 1, stream()) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(du8b[:M], du8) and site_max(amax_b2) == site_max(amax2)
+        assert_fp8_image(du8b, du, qs2, 1, slice(0, M), amax_site=amax_b2, sentinel=0x55)
 
 
 @pytest.mark.parametrize("Mtot,N,K,splits", [(8192, 768, 768, 28), (8192, 2304, 768, 9), (12288, 768, 2048, 10),
