@@ -773,9 +773,44 @@ static int check_shape(const PlbEngine* e, int B, int S, const char* who) {
   return 0;
 }
 
+// ---- launch descriptors -----------------------------------------------------------------------------------------------
+// C[M, N] = A[M, K] · B[N, K]^T on packed operands (lda = ldb = K), every row stored: the callers add bias, residual and
+// outputs
+static PlbGemmNT nt_desc(const bf16_t* A, const bf16_t* B, int64_t M, int N, int K) {
+  PlbGemmNT g;
+  memset(&g, 0, sizeof(g));
+  g.A = A; g.lda = K; g.B = B; g.ldb = K; g.M = (int)M; g.N = N; g.K = K; g.Mstore = (int)M;
+  return g;
+}
+
+// One fp8 operand site of one application: the delayed scale its images are written with, the running maximum the writing
+// launch records, the dequantisation factor its readers apply
+struct F8Site {
+  float* scale = nullptr;
+  float* amax = nullptr;
+  float* deq = nullptr;
+  F8Site() = default;
+  F8Site(const PlbEngine* e, int kind, int l) {
+    const int i = f8_site(e, kind, l);
+    scale = f8_scale(e, i); amax = f8_amax(e, i); deq = f8_deq(e, i);
+  }
+};
+// The e4m3 copy of a weight (fp8_quantize_weights) and its dequantisation factor
+struct F8Weight {
+  const uint8_t* img;
+  const float* deq;
+  F8Weight(const PlbEngine* e, int w) {
+    static const int64_t PlbEngine::*const kImage[F8W_N] = {&PlbEngine::o_wq8, &PlbEngine::o_wd8, &PlbEngine::o_w18,
+                                                             &PlbEngine::o_w28, &PlbEngine::o_w2T8, &PlbEngine::o_w1T8,
+                                                             &PlbEngine::o_wqT8, &PlbEngine::o_wdT8};
+    img = e->at<uint8_t>(e->*kImage[w]); deq = f8_deq(e, f8_w(e, w));
+  }
+};
+
 // One NT GEMM of the fp8 set: the fp8 launch when the call runs in fp8 mode (A8 / B8 images, their dequantisation
 // factors), else the bf16 launch on A / B. g carries everything else (shapes, bias, residual, outputs).
 struct F8Op { const uint8_t* A8; const uint8_t* B8; const float* deq_a; const float* deq_b; int a_bf8; };
+static F8Op f8_op(const uint8_t* a8, const F8Site& a, const F8Weight& w, int a_bf8) { return F8Op{a8, w.img, a.deq, w.deq, a_bf8}; }
 static PlbGemmNT f8_operands(const PlbGemmNT* g, const F8Op* f8) {
   PlbGemmNT q = *g;
   q.A = reinterpret_cast<const bf16_t*>(f8->A8); q.B = reinterpret_cast<const bf16_t*>(f8->B8);
@@ -798,11 +833,55 @@ static int gemm_nt_gelud_any(PlbGemmNT* g, int backward, const F8Op* f8, hipStre
   PlbGemmNT q = f8_operands(g, f8);
   return plb_launch_gemm_nt_fp8_gelud(&q, backward, f8->a_bf8, s);
 }
-// the 1-byte image + running maximum a launch writes beside its output (site i: scale in, maxima out)
-static void f8_out(const PlbEngine* e, PlbGemmNT* g, uint8_t* img, int ld, int site, int bf8) {
-  g->C8 = img; g->ldc8 = ld; g->q_scale = f8_scale(e, site); g->q_amax = f8_amax(e, site); g->c8_bf8 = bf8;
+// the 1-byte image + running maximum a launch writes beside its output (scale in, maxima out)
+static void f8_out(PlbGemmNT* g, uint8_t* img, int ld, const F8Site& q, int bf8) {
+  g->C8 = img; g->ldc8 = ld; g->q_scale = q.scale; g->q_amax = q.amax; g->c8_bf8 = bf8;
 }
 
+// ---- stash slots of one application -----------------------------------------------------------------------------------
+// Slot l of a stacked buffer starts at l · Tp · width: the slots of a call are packed with the call's own padded token
+// count, not the capacity, so the token-major weight-gradient GEMMs read L · Tp contiguous rows. Per-application blocks
+// with other strides: lse B·NH·S floats, the LayerNorm-backward partials prows·3H, the Q/K/V bias partial rows
+// qkvcol_rows(B, S)·3H (the call's, not the capacity PlbEngine::qkvcol_rows), the ffn.bias partial rows du_rows·I.
+// stash (training): L+1 slots of x (the input of application l+1 is the output of l) and L of everything else;
+// otherwise one slot of everything and two ping-pong slots of x.
+struct Slots {
+  bf16_t *x, *y;                                    // the application's input and output
+  bf16_t *qkv, *ctx, *pre1, *a, *u, *g, *pre2;      // activations
+  float *mean1, *rstd1, *mean2, *rstd2, *lse;       // LayerNorm statistics, attention log-sum-exp
+  uint8_t *x8, *x8n, *c8, *a8, *g8;                 // 1-byte images (x8n: the next application's input image)
+  // stash only: the gradients that feed the weight-gradient GEMMs, their images, the partial-row blocks
+  bf16_t *dqkv, *dpre1, *du, *dpre2;
+  uint8_t *dp8, *du8, *dp18, *dq8;
+  float *part1, *part2, *qkvcol, *ducol;
+};
+// partial rows per application of the Q/K/V bias gradient that the attention backward stores in a call of B x S
+static int qkvcol_rows(int B, int S) { return B * ((S + 127) / 128) * 4; }
+static Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int prows = 0, int du_rows = 0) {
+  const int64_t H = e->H, I = e->I, sl = stash ? l : 0;
+  auto bf = [&](int64_t off, int64_t width) { return e->at<bf16_t>(off) + sl * Tp * width; };
+  auto u8 = [&](int64_t off, int64_t width) { return e->at<uint8_t>(off) + sl * Tp * width; };
+  auto f32 = [&](int64_t off, int64_t per_layer) { return e->at<float>(off) + sl * per_layer; };
+  Slots v;
+  memset(&v, 0, sizeof(v));
+  v.x = e->at<bf16_t>(e->o_x) + (int64_t)(stash ? l : l & 1) * Tp * H;
+  v.y = e->at<bf16_t>(e->o_x) + (int64_t)(stash ? l + 1 : (l + 1) & 1) * Tp * H;
+  v.qkv = bf(e->o_qkv, 3 * H); v.ctx = bf(e->o_ctx, H); v.pre1 = bf(e->o_pre1, H); v.a = bf(e->o_a, H);
+  v.u = bf(e->o_u, I); v.g = bf(e->o_g, I); v.pre2 = bf(e->o_pre2, H);
+  v.mean1 = f32(e->o_mean1, Tp); v.rstd1 = f32(e->o_rstd1, Tp); v.mean2 = f32(e->o_mean2, Tp); v.rstd2 = f32(e->o_rstd2, Tp);
+  v.lse = f32(e->o_lse, (int64_t)B * e->NH * S);
+  v.x8 = u8(e->o_x8, H); v.c8 = u8(e->o_c8, H); v.a8 = u8(e->o_a8, H); v.g8 = u8(e->o_g8, I);
+  v.x8n = e->at<uint8_t>(e->o_x8) + (stash ? l + 1 : 0) * Tp * H;   // (one slot: consumed before it is rewritten)
+  if (stash) {
+    v.dqkv = bf(e->o_dqkv, 3 * H); v.dpre1 = bf(e->o_dpre1, H); v.du = bf(e->o_du, I); v.dpre2 = bf(e->o_dpre2, H);
+    v.dp8 = u8(e->o_dp8, H); v.du8 = u8(e->o_du8, I); v.dp18 = u8(e->o_dp18, H); v.dq8 = u8(e->o_dq8, 3 * H);
+    v.part1 = f32(e->o_part1, (int64_t)prows * 3 * H); v.part2 = f32(e->o_part2, (int64_t)prows * 3 * H);
+    v.qkvcol = f32(e->o_qkvcol, (int64_t)qkvcol_rows(B, S) * 3 * H); v.ducol = f32(e->o_ducol, (int64_t)du_rows * I);
+  }
+  return v;
+}
+
+// ---- LayerNorm: in the producing GEMM's epilogue or standalone ----------------------------------------------------------
 // LayerNorm in the epilogue of the GEMM that produces its input (gemm_ln.hip, gemm_fp8_ln.hip): the shapes it exists for,
 // in bf16 and in fp8 calls alike (the fp8 forms write the 1-byte images the standalone LayerNorm kernels used to write);
 // an fp8 CALIBRATION call computes in bf16 (it must equal the bf16 path bit for bit: tests/test_gpu_fp8.py).
@@ -820,6 +899,63 @@ static bool gelu_dstash(PlbEngine* e, int64_t Tp, bool f8_call) {
 static void ln_fields(const PlbEngine* e, PlbGemmNT* g, const float* gamma, const float* beta, float* mean, float* rstd) {
   g->ln_gamma = gamma; g->ln_beta = beta; g->ln_mean = mean; g->ln_rstd = rstd; g->ln_eps = e->c.layer_norm_eps;
   g->ln_xchg = e->at<unsigned long long>(e->o_lnx); g->ln_err = e->at<unsigned int>(e->o_lnerr);
+}
+// One LayerNorm of one application: affine parameters, its input (kept by the forward, read by the backward), statistics
+// and backward partial rows
+struct LnSlot { const float* gamma; const float* beta; const bf16_t* pre; float* mean; float* rstd; float* partials; };
+static LnSlot ln1_slot(const PlbEngine* e, const Slots& v) {
+  return LnSlot{e->par(PLB_LN1_W), e->par(PLB_LN1_B), v.pre1, v.mean1, v.rstd1, v.part1};
+}
+static LnSlot ln2_slot(const PlbEngine* e, const Slots& v) {
+  return LnSlot{e->par(PLB_LN2_W), e->par(PLB_LN2_B), v.pre2, v.mean2, v.rstd2, v.part2};
+}
+// g (C = the LayerNorm's input, + bias / residual) and y = LayerNorm(C) on rows [0, T): the fused form 5 (GEMM + residual +
+// LayerNorm in one launch) or the GEMM and the standalone kernel. y8 (or null): y's e4m3 image under site q.
+static int gemm_ln_fwd(PlbEngine* e, PlbGemmNT* g, const F8Op* f8, bool fused, const LnSlot& ln, bf16_t* y, int T,
+                       uint8_t* y8, const F8Site& q, hipStream_t s) {
+  const int H = e->H;
+  if (fused) {
+    g->C2 = y; g->ldc2 = H;
+    ln_fields(e, g, ln.gamma, ln.beta, ln.mean, ln.rstd);
+    if (y8) f8_out(g, y8, H, q, 0);
+    TRY(gemm_nt_ln_any(g, 5, f8, s));
+    return 0;
+  }
+  TRY(gemm_nt_any(g, 0, f8, s));
+  PlbLayerNorm p;
+  memset(&p, 0, sizeof(p));
+  p.x = g->C; p.ldx = H; p.gamma = ln.gamma; p.beta = ln.beta; p.eps = e->c.layer_norm_eps;
+  p.y = y; p.ldy = H; p.T = T; p.H = H; p.mean = ln.mean; p.rstd = ln.rstd;
+  if (y8) { p.out8 = y8; p.ld8 = H; p.q_scale = q.scale; p.q_amax = q.amax; }
+  TRY(plb_launch_ln_fwd(&p, s));
+  return 0;
+}
+// standalone LayerNorm backward: dx = LN'(dy) on rows [0, T), zeros in [T, Tzero), nblocks rows of dgamma | dbeta | column
+// sums of dx; dx8 (or null): dx's e5m2 image under site q
+static int ln_bwd(PlbEngine* e, const LnSlot& ln, int nblocks, const bf16_t* dy, bf16_t* dx, int T, int Tzero, uint8_t* dx8,
+                  const F8Site& q, hipStream_t s) {
+  const int H = e->H;
+  PlbLayerNorm p;
+  memset(&p, 0, sizeof(p));
+  p.x = ln.pre; p.ldx = H; p.gamma = ln.gamma; p.T = T; p.H = H; p.Tzero = Tzero; p.mean = ln.mean; p.rstd = ln.rstd;
+  p.dy = dy; p.lddy = H; p.dx = dx; p.lddx = H; p.partials = ln.partials; p.nblocks = nblocks;
+  if (dx8) { p.out8 = dx8; p.ld8 = H; p.q_scale = q.scale; p.q_amax = q.amax; }
+  TRY(plb_launch_ln_bwd(&p, s));
+  return 0;
+}
+// g (C = the gradient of the LayerNorm's OUTPUT, + residual) and that LayerNorm's backward: the fused form 6 (the output
+// gradient is never stored: the epilogue writes dx and the partial rows) or the GEMM into C and ln_bwd
+static int gemm_ln_bwd(PlbEngine* e, PlbGemmNT* g, const F8Op* f8, bool fused, const LnSlot& ln, int nblocks, bf16_t* dx, int T,
+                       int Tzero, uint8_t* dx8, const F8Site& q, hipStream_t s) {
+  if (fused) {
+    g->C = dx; g->aux = ln.pre; g->ldaux = e->H; g->colpart = ln.partials;
+    ln_fields(e, g, ln.gamma, nullptr, ln.mean, ln.rstd);
+    if (dx8) f8_out(g, dx8, e->H, q, 1);
+    TRY(gemm_nt_ln_any(g, 6, f8, s));
+    return 0;
+  }
+  TRY(gemm_nt_any(g, 0, f8, s));
+  return ln_bwd(e, ln, nblocks, g->C, dx, T, Tzero, dx8, q, s);
 }
 
 // Embeddings + L applications of the shared layer. stash: keep every layer's activations (training)
@@ -856,64 +992,42 @@ static bool prune_enabled() {
   return g_prune_last < 0 ? v : g_prune_last != 0;
 }
 // post-attention part of application L-1 on the compact rows; leaves the final hidden rows in o_hm ([Mc][H]: the head's
-// operand) and, in a training call, the compact activations at the START of application L-1's stash slots — the stacked
-// weight-gradient operands then simply end Tp - Mc rows earlier
-static int last_application_fwd_pruned(PlbEngine* e, const Prune* pr, bool stash, bool calib, bool tn8, const bf16_t* x,
-                                       const bf16_t* ctx_att, int64_t Tp, hipStream_t s) {
+// operand) and, in a training call, the compact activations at the START of application L-1's stash slots (sl) — the
+// stacked weight-gradient operands then simply end Tp - Mc rows earlier
+static int last_application_fwd_pruned(PlbEngine* e, const Prune* pr, bool stash, bool calib, bool tn8, const Slots& sl,
+                                       const bf16_t* ctx_att, hipStream_t s) {
   const int H = e->H, I = e->I, L = e->L, Mc = pr->Mc, n = pr->n;
-  const int64_t sl = stash ? L - 1 : 0;
-  const int64_t Tcap = Tp;   // slots of a call are packed with the call's own padded token count
-  bf16_t* ctx_s = e->at<bf16_t>(e->o_ctx) + sl * Tcap * H;
-  bf16_t* pre1_s = e->at<bf16_t>(e->o_pre1) + sl * Tcap * H;
-  bf16_t* a_s = e->at<bf16_t>(e->o_a) + sl * Tcap * H;
-  bf16_t* u = e->at<bf16_t>(e->o_u) + sl * Tcap * I;
-  bf16_t* gl = e->at<bf16_t>(e->o_g) + sl * Tcap * I;
-  bf16_t* pre2 = e->at<bf16_t>(e->o_pre2) + sl * Tcap * H;
+  const F8Site sA(e, F8_A, L - 1), sG(e, F8_G, L - 1), sC(e, F8_C, L - 1);
   // training: compact tensors in their own slots (the backward and the weight gradients read them), the gathered
   // residual rows in a backward temporary; forward-only: the one set of slots, rotated so that nothing is read and
   // written by the same launch (ctx_att = the ctx slot: gathered into the pre1 slot, whose sum then goes to the ctx slot)
-  bf16_t* ctxc = stash ? ctx_s : pre1_s;
-  bf16_t* xc = stash ? e->at<bf16_t>(e->o_da) : a_s;
-  bf16_t* pre1c = stash ? pre1_s : ctx_s;
-  bf16_t* ac = stash ? a_s : pre1_s;
-  bf16_t* hm = e->at<bf16_t>(e->o_hm);
+  bf16_t* ctxc = stash ? sl.ctx : sl.pre1;
+  bf16_t* xc = stash ? e->at<bf16_t>(e->o_da) : sl.a;
+  bf16_t* pre1c = stash ? sl.pre1 : sl.ctx;
+  bf16_t* ac = stash ? sl.a : sl.pre1;
   TRY(plb_launch_gather_rows(ctx_att, H, pr->rows, n, Mc, H, ctxc, H, s));
-  TRY(plb_launch_gather_rows(x, H, pr->rows, n, Mc, H, xc, H, s));
-  PlbGemmNT g;
-  memset(&g, 0, sizeof(g));
-  g.A = ctxc; g.lda = H; g.B = e->wbf(PLB_DENSE_W); g.ldb = H; g.M = Mc; g.N = H; g.K = H; g.Mstore = Mc;
+  TRY(plb_launch_gather_rows(sl.x, H, pr->rows, n, Mc, H, xc, H, s));
+  PlbGemmNT g = nt_desc(ctxc, e->wbf(PLB_DENSE_W), Mc, H, H);
   g.bias = e->par(PLB_DENSE_B); g.res = xc; g.ldr = H; g.C = pre1c; g.ldc = H;
-  TRY(plb_launch_gemm_nt(&g, 0, 0, s));
-  PlbLayerNorm ln;
-  memset(&ln, 0, sizeof(ln));
-  ln.x = pre1c; ln.ldx = H; ln.gamma = e->par(PLB_LN1_W); ln.beta = e->par(PLB_LN1_B); ln.eps = e->c.layer_norm_eps;
-  ln.y = ac; ln.ldy = H; ln.T = Mc; ln.H = H;
-  ln.mean = e->at<float>(e->o_mean1) + sl * Tcap; ln.rstd = e->at<float>(e->o_rstd1) + sl * Tcap;
-  TRY(plb_launch_ln_fwd(&ln, s));
-  if (calib) TRY(plb_launch_amax(ac, 1, (size_t)n, H, H, f8_amax(e, f8_site(e, F8_A, L - 1)), s));
-  memset(&g, 0, sizeof(g));
-  g.A = ac; g.lda = H; g.B = e->wbf(PLB_FFN_W); g.ldb = H; g.M = Mc; g.N = I; g.K = H; g.Mstore = Mc;
-  g.bias = e->par(PLB_FFN_B); g.C = u; g.ldc = I; g.C2 = gl; g.ldc2 = I;
+  const LnSlot ln1 = {e->par(PLB_LN1_W), e->par(PLB_LN1_B), pre1c, sl.mean1, sl.rstd1, nullptr};
+  if (gemm_ln_fwd(e, &g, nullptr, false, ln1, ac, Mc, nullptr, F8Site(), s)) return 1;
+  if (calib) TRY(plb_launch_amax(ac, 1, (size_t)n, H, H, sA.amax, s));
+  g = nt_desc(ac, e->wbf(PLB_FFN_W), Mc, I, H);
+  g.bias = e->par(PLB_FFN_B); g.C = sl.u; g.ldc = I; g.C2 = sl.g; g.ldc2 = I;
   TRY(plb_launch_gemm_nt(&g, 1, 0, s));
-  if (calib) TRY(plb_launch_amax(gl, 1, (size_t)n, I, I, f8_amax(e, f8_site(e, F8_G, L - 1)), s));
-  memset(&g, 0, sizeof(g));
-  g.A = gl; g.lda = I; g.B = e->wbf(PLB_FFNO_W); g.ldb = I; g.M = Mc; g.N = H; g.K = I; g.Mstore = Mc;
-  g.bias = e->par(PLB_FFNO_B); g.res = ac; g.ldr = H; g.C = pre2; g.ldc = H;
-  TRY(plb_launch_gemm_nt(&g, 0, 0, s));
-  memset(&ln, 0, sizeof(ln));
-  ln.x = pre2; ln.ldx = H; ln.gamma = e->par(PLB_LN2_W); ln.beta = e->par(PLB_LN2_B); ln.eps = e->c.layer_norm_eps;
-  ln.y = hm; ln.ldy = H; ln.T = Mc; ln.H = H;
-  ln.mean = e->at<float>(e->o_mean2) + sl * Tcap; ln.rstd = e->at<float>(e->o_rstd2) + sl * Tcap;
-  TRY(plb_launch_ln_fwd(&ln, s));
+  if (calib) TRY(plb_launch_amax(sl.g, 1, (size_t)n, I, I, sG.amax, s));
+  g = nt_desc(sl.g, e->wbf(PLB_FFNO_W), Mc, H, I);
+  g.bias = e->par(PLB_FFNO_B); g.res = ac; g.ldr = H; g.C = sl.pre2; g.ldc = H;
+  if (gemm_ln_fwd(e, &g, nullptr, false, ln2_slot(e, sl), e->at<bf16_t>(e->o_hm), Mc, nullptr, F8Site(), s)) return 1;
   if (tn8) {
     // fp8 training call: this part itself runs in bf16 (2,000 rows: nothing to gain from fp8 operands), but the stacked
     // weight-gradient GEMMs read 1-byte images of EVERY application: the compact context / a / gelu(u) rows as e4m3 images
     // at the start of this application's image slots, under the sites' scales, their maxima reported like any other's
-    const void* src[3] = {ctxc, ac, gl}; const int fl[3] = {1, 1, 1};
+    const void* src[3] = {ctxc, ac, sl.g}; const int fl[3] = {1, 1, 1};
     const size_t nel[3] = {(size_t)Mc * H, (size_t)Mc * H, (size_t)Mc * I};
-    const float* sc[3] = {f8_scale(e, f8_site(e, F8_C, L - 1)), f8_scale(e, f8_site(e, F8_A, L - 1)), f8_scale(e, f8_site(e, F8_G, L - 1))};
-    uint8_t* dst[3] = {e->at<uint8_t>(e->o_c8) + sl * Tcap * H, e->at<uint8_t>(e->o_a8) + sl * Tcap * H, e->at<uint8_t>(e->o_g8) + sl * Tcap * I};
-    float* am[3] = {f8_amax(e, f8_site(e, F8_C, L - 1)), f8_amax(e, f8_site(e, F8_A, L - 1)), f8_amax(e, f8_site(e, F8_G, L - 1))};
+    const float* sc[3] = {sC.scale, sA.scale, sG.scale};
+    uint8_t* dst[3] = {sl.c8, sl.a8, sl.g8};
+    float* am[3] = {sC.amax, sA.amax, sG.amax};
     TRY(plb_launch_quantize_multi(3, src, fl, nel, sc, dst, am, s));
   }
   return 0;
@@ -935,17 +1049,15 @@ static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
   em.out = e->at<bf16_t>(e->o_e); em.ldo = E;
   TRY(plb_launch_embed_fwd(&em, s));
 
-  bf16_t* xall = e->at<bf16_t>(e->o_x);
-  PlbGemmNT g;
-  memset(&g, 0, sizeof(g));
-  g.A = em.out; g.lda = E; g.B = e->wbf(PLB_MAP_W); g.ldb = E; g.M = (int)Tp; g.N = H; g.K = E; g.Mstore = (int)Tp;
-  g.bias = e->par(PLB_MAP_B); g.C = xall; g.ldc = H;
+  const Slots first = slots(e, Tp, B, S, 0, stash);
+  PlbGemmNT g = nt_desc(em.out, e->wbf(PLB_MAP_W), Tp, H, E);
+  g.bias = e->par(PLB_MAP_B); g.C = first.x; g.ldc = H;
   TRY(plb_launch_gemm_nt(&g, 0, 0, s));
   if (f8) {  // layer 0 reads the map-in output, which no LayerNorm produced: one quantisation pass
     // (image and the site's maximum in one pass: the rows are contiguous)
-    const void* src1[1] = {xall}; const int bf1[1] = {1}; const size_t n1[1] = {(size_t)T * H};
-    const float* sc1[1] = {f8_scale(e, f8_site(e, F8_X, 0))}; uint8_t* dst1[1] = {e->at<uint8_t>(e->o_x8)};
-    float* am1[1] = {f8_amax(e, f8_site(e, F8_X, 0))};
+    const F8Site sX(e, F8_X, 0);
+    const void* src1[1] = {first.x}; const int bf1[1] = {1}; const size_t n1[1] = {(size_t)T * H};
+    const float* sc1[1] = {sX.scale}; uint8_t* dst1[1] = {first.x8}; float* am1[1] = {sX.amax};
     TRY(plb_launch_quantize_multi(1, src1, bf1, n1, sc1, dst1, am1, s));
   }
   const bool fuse_f = ln_fusable(e, Tp, 1);
@@ -956,76 +1068,43 @@ static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
   const bool tn8 = stash && e->tn8_call;
 
   for (int l = 0; l < L; ++l) {
-    const int64_t sl = stash ? l : 0;
-    bf16_t* x = stash ? xall + (int64_t)l * Tp * H : xall + (int64_t)(l & 1) * Tp * H;
-    bf16_t* y = stash ? xall + (int64_t)(l + 1) * Tp * H : xall + (int64_t)((l + 1) & 1) * Tp * H;
-    bf16_t* qkv = e->at<bf16_t>(e->o_qkv) + sl * Tp * 3 * H;
-    bf16_t* ctx = e->at<bf16_t>(e->o_ctx) + sl * Tp * H;
-    bf16_t* pre1 = e->at<bf16_t>(e->o_pre1) + sl * Tp * H;
-    bf16_t* a = e->at<bf16_t>(e->o_a) + sl * Tp * H;
-    bf16_t* u = e->at<bf16_t>(e->o_u) + sl * Tp * I;
-    bf16_t* gl = e->at<bf16_t>(e->o_g) + sl * Tp * I;
-    bf16_t* pre2 = e->at<bf16_t>(e->o_pre2) + sl * Tp * H;
-    // this layer's 1-byte images; the next layer's input image (inference: the one slot, consumed before it is rewritten)
-    uint8_t* x8 = e->at<uint8_t>(e->o_x8) + sl * Tp * H;
-    uint8_t* x8n = e->at<uint8_t>(e->o_x8) + (stash ? (int64_t)(l + 1) : 0) * Tp * H;
-    uint8_t* c8 = e->at<uint8_t>(e->o_c8) + sl * Tp * H;
-    uint8_t* a8 = e->at<uint8_t>(e->o_a8) + sl * Tp * H;
-    uint8_t* g8 = e->at<uint8_t>(e->o_g8) + sl * Tp * I;
-    const int sX = f8_site(e, F8_X, l), sA = f8_site(e, F8_A, l), sG = f8_site(e, F8_G, l), sC = f8_site(e, F8_C, l);
-    if (calib) TRY(plb_launch_amax(x, 1, (size_t)T, H, H, f8_amax(e, sX), s));
+    const Slots sl = slots(e, Tp, B, S, l, stash);
+    const F8Site sX(e, F8_X, l), sA(e, F8_A, l), sG(e, F8_G, l), sC(e, F8_C, l);
+    if (calib) TRY(plb_launch_amax(sl.x, 1, (size_t)T, H, H, sX.amax, s));
     // fused QKV projection
-    memset(&g, 0, sizeof(g));
-    g.A = x; g.lda = H; g.B = e->wbf(PLB_Q_W); g.ldb = H; g.M = (int)Tp; g.N = 3 * H; g.K = H; g.Mstore = (int)Tp;
-    g.bias = e->par(PLB_Q_B); g.C = qkv; g.ldc = 3 * H;
-    F8Op oq = {x8, e->at<uint8_t>(e->o_wq8), f8_deq(e, sX), f8_deq(e, f8_w(e, F8W_QKV)), 0};
+    g = nt_desc(sl.x, e->wbf(PLB_Q_W), Tp, 3 * H, H);
+    g.bias = e->par(PLB_Q_B); g.C = sl.qkv; g.ldc = 3 * H;
+    const F8Op oq = f8_op(sl.x8, sX, F8Weight(e, F8W_QKV), 0);
     TRY(gemm_nt_any(&g, 0, f8 ? &oq : nullptr, s));
     PlbAttn at;
     memset(&at, 0, sizeof(at));
-    at.qkv = qkv; at.ldqkv = 3 * H; at.lengths = lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H;
+    at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H;
     // pruned last application: the attention output of ALL rows goes to a buffer of its own (training: a backward temporary
     // that the attention backward of this application reads again — its slot holds the compact rows), then only the masked
     // rows continue
     const bool pruned_layer = pr != nullptr && l == L - 1;
-    bf16_t* const ctx_att = (pruned_layer && stash) ? e->at<bf16_t>(e->o_dy1) : ctx;
-    at.scale = 0.125f; at.ctx = ctx_att; at.ldctx = H;
-    at.lse = e->at<float>(e->o_lse) + sl * (int64_t)B * e->NH * S;
+    bf16_t* const ctx_att = (pruned_layer && stash) ? e->at<bf16_t>(e->o_dy1) : sl.ctx;
+    at.scale = 0.125f; at.ctx = ctx_att; at.ldctx = H; at.lse = sl.lse;
     // (pruned: nobody reads the context's image of all rows — the compact rows' image is made with the others, below)
-    if (f8 && !pruned_layer) { at.ctx8 = c8; at.ldctx8 = H; at.ctx_scale = f8_scale(e, sC); at.ctx_amax = f8_amax(e, sC); }
+    if (f8 && !pruned_layer) { at.ctx8 = sl.c8; at.ldctx8 = H; at.ctx_scale = sC.scale; at.ctx_amax = sC.amax; }
     TRY(plb_launch_attn_fwd(&at, s));
-    if (calib) TRY(plb_launch_amax(ctx_att, 1, (size_t)T, H, H, f8_amax(e, sC), s));
+    if (calib) TRY(plb_launch_amax(ctx_att, 1, (size_t)T, H, H, sC.amax, s));
     if (pruned_layer) {
-      if (last_application_fwd_pruned(e, pr, stash, calib, tn8, x, ctx_att, Tp, s)) return 1;
+      if (last_application_fwd_pruned(e, pr, stash, calib, tn8, sl, ctx_att, s)) return 1;
       *xout = e->at<bf16_t>(e->o_hm);
       break;
     }
-    // dense + residual, LayerNorm
-    memset(&g, 0, sizeof(g));
-    g.A = ctx; g.lda = H; g.B = e->wbf(PLB_DENSE_W); g.ldb = H; g.M = (int)Tp; g.N = H; g.K = H; g.Mstore = (int)Tp;
-    g.bias = e->par(PLB_DENSE_B); g.res = x; g.ldr = H; g.C = pre1; g.ldc = H;
-    F8Op od = {c8, e->at<uint8_t>(e->o_wd8), f8_deq(e, sC), f8_deq(e, f8_w(e, F8W_D)), 0};
-    PlbLayerNorm ln;
-    if (fuse_f) {  // dense + residual + LayerNorm in one launch
-      g.C2 = a; g.ldc2 = H;
-      ln_fields(e, &g, e->par(PLB_LN1_W), e->par(PLB_LN1_B), e->at<float>(e->o_mean1) + sl * Tp, e->at<float>(e->o_rstd1) + sl * Tp);
-      if (f8) f8_out(e, &g, a8, H, sA, 0);
-      TRY(gemm_nt_ln_any(&g, 5, f8 ? &od : nullptr, s));
-    } else {
-      TRY(gemm_nt_any(&g, 0, f8 ? &od : nullptr, s));
-      memset(&ln, 0, sizeof(ln));
-      ln.x = pre1; ln.ldx = H; ln.gamma = e->par(PLB_LN1_W); ln.beta = e->par(PLB_LN1_B); ln.eps = e->c.layer_norm_eps;
-      ln.y = a; ln.ldy = H; ln.T = T; ln.H = H;
-      ln.mean = e->at<float>(e->o_mean1) + sl * Tp; ln.rstd = e->at<float>(e->o_rstd1) + sl * Tp;
-      if (f8) { ln.out8 = a8; ln.ld8 = H; ln.q_scale = f8_scale(e, sA); ln.q_amax = f8_amax(e, sA); }
-      TRY(plb_launch_ln_fwd(&ln, s));
-    }
-    if (calib) TRY(plb_launch_amax(a, 1, (size_t)T, H, H, f8_amax(e, sA), s));
+    // dense + residual, LayerNorm 1
+    g = nt_desc(sl.ctx, e->wbf(PLB_DENSE_W), Tp, H, H);
+    g.bias = e->par(PLB_DENSE_B); g.res = sl.x; g.ldr = H; g.C = sl.pre1; g.ldc = H;
+    const F8Op od = f8_op(sl.c8, sC, F8Weight(e, F8W_D), 0);
+    if (gemm_ln_fwd(e, &g, f8 ? &od : nullptr, fuse_f, ln1_slot(e, sl), sl.a, T, f8 ? sl.a8 : nullptr, sA, s)) return 1;
+    if (calib) TRY(plb_launch_amax(sl.a, 1, (size_t)T, H, H, sA.amax, s));
     // FFN: u = a W1^T + b1, g = gelu_new(u); pre2 = g W2^T + b2 + a
-    memset(&g, 0, sizeof(g));
-    g.A = a; g.lda = H; g.B = e->wbf(PLB_FFN_W); g.ldb = H; g.M = (int)Tp; g.N = I; g.K = H; g.Mstore = (int)Tp;
-    g.bias = e->par(PLB_FFN_B); g.C = u; g.ldc = I; g.C2 = gl; g.ldc2 = I;
-    if (f8) f8_out(e, &g, g8, I, sG, 0);
-    F8Op o1 = {a8, e->at<uint8_t>(e->o_w18), f8_deq(e, sA), f8_deq(e, f8_w(e, F8W_1)), 0};
+    g = nt_desc(sl.a, e->wbf(PLB_FFN_W), Tp, I, H);
+    g.bias = e->par(PLB_FFN_B); g.C = sl.u; g.ldc = I; g.C2 = sl.g; g.ldc2 = I;
+    if (f8) f8_out(&g, sl.g8, I, sG, 0);
+    const F8Op o1 = f8_op(sl.a8, sA, F8Weight(e, F8W_1), 0);
     // calls on tile multiples stash gelu_new'(u) in the "u" slot (gelu_dstash): the forward's sigmoid serves the
     // activation and its derivative, and the backward epilogue multiplies instead of evaluating the derivative. In an
     // fp8 call gelu(u) itself leaves as its e4m3 image ALONE: nothing reads it in bf16 (FFN output GEMM and weight
@@ -1036,30 +1115,16 @@ static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
     } else {
       TRY(gemm_nt_any(&g, 1, f8 ? &o1 : nullptr, s));
     }
-    if (calib) TRY(plb_launch_amax(gl, 1, (size_t)T, I, I, f8_amax(e, sG), s));
-    memset(&g, 0, sizeof(g));
-    g.A = gl; g.lda = I; g.B = e->wbf(PLB_FFNO_W); g.ldb = I; g.M = (int)Tp; g.N = H; g.K = I; g.Mstore = (int)Tp;
-    g.bias = e->par(PLB_FFNO_B); g.res = a; g.ldr = H; g.C = pre2; g.ldc = H;
-    F8Op o2 = {g8, e->at<uint8_t>(e->o_w28), f8_deq(e, sG), f8_deq(e, f8_w(e, F8W_2)), 0};
-    const bool next8 = f8 && l + 1 < L;   // the next application's input image
-    if (fuse_f) {  // FFN output + residual + LayerNorm in one launch
-      g.C2 = y; g.ldc2 = H;
-      ln_fields(e, &g, e->par(PLB_LN2_W), e->par(PLB_LN2_B), e->at<float>(e->o_mean2) + sl * Tp, e->at<float>(e->o_rstd2) + sl * Tp);
-      if (next8) f8_out(e, &g, x8n, H, f8_site(e, F8_X, l + 1), 0);
-      TRY(gemm_nt_ln_any(&g, 5, f8 ? &o2 : nullptr, s));
-    } else {
-      TRY(gemm_nt_any(&g, 0, f8 ? &o2 : nullptr, s));
-      memset(&ln, 0, sizeof(ln));
-      ln.x = pre2; ln.ldx = H; ln.gamma = e->par(PLB_LN2_W); ln.beta = e->par(PLB_LN2_B); ln.eps = e->c.layer_norm_eps;
-      ln.y = y; ln.ldy = H; ln.T = T; ln.H = H;
-      ln.mean = e->at<float>(e->o_mean2) + sl * Tp; ln.rstd = e->at<float>(e->o_rstd2) + sl * Tp;
-      if (next8) {
-        const int sN = f8_site(e, F8_X, l + 1);
-        ln.out8 = x8n; ln.ld8 = H; ln.q_scale = f8_scale(e, sN); ln.q_amax = f8_amax(e, sN);
-      }
-      TRY(plb_launch_ln_fwd(&ln, s));
-    }
-    *xout = y;
+    if (calib) TRY(plb_launch_amax(sl.g, 1, (size_t)T, I, I, sG.amax, s));
+    // FFN output + residual, LayerNorm 2 (+ the next application's input image)
+    g = nt_desc(sl.g, e->wbf(PLB_FFNO_W), Tp, H, I);
+    g.bias = e->par(PLB_FFNO_B); g.res = sl.a; g.ldr = H; g.C = sl.pre2; g.ldc = H;
+    const F8Op o2 = f8_op(sl.g8, sG, F8Weight(e, F8W_2), 0);
+    const bool next8 = f8 && l + 1 < L;
+    if (gemm_ln_fwd(e, &g, f8 ? &o2 : nullptr, fuse_f, ln2_slot(e, sl), sl.y, T, next8 ? sl.x8n : nullptr,
+                    next8 ? F8Site(e, F8_X, l + 1) : F8Site(), s))
+      return 1;
+    *xout = sl.y;
   }
   return 0;
 }
@@ -1075,17 +1140,14 @@ extern "C" int plb_forward(PlbEngine* e, const int64_t* ids, const int32_t* leng
   bf16_t* x = nullptr;
   if (run_encoder(e, ids, lengths, B, S, false, &x, s)) return 1;
   if (hidden) TRY(plb_launch_bf16_to_f32(x, H, hidden, H, T, H, s));
-  PlbGemmNT g;
   if (phoneme_logits) {
-    memset(&g, 0, sizeof(g));
-    g.A = x; g.lda = H; g.B = e->wbf(PLB_HEAD_W); g.ldb = H; g.M = (int)Tp; g.N = e->NP; g.K = H; g.Mstore = T;
-    g.bias = e->par(PLB_HEAD_B); g.Cf = phoneme_logits; g.ldcf = e->NP;
+    PlbGemmNT g = nt_desc(x, e->wbf(PLB_HEAD_W), Tp, e->NP, H);
+    g.Mstore = T; g.bias = e->par(PLB_HEAD_B); g.Cf = phoneme_logits; g.ldcf = e->NP;
     TRY(plb_launch_gemm_nt(&g, 0, 1, s));
   }
   if (token_logits) {
-    memset(&g, 0, sizeof(g));
-    g.A = x; g.lda = H; g.B = e->wbf(PLB_TOK_W); g.ldb = H; g.M = (int)Tp; g.N = e->NT; g.K = H; g.Mstore = T;
-    g.bias = e->par(PLB_TOK_B); g.Cf = token_logits; g.ldcf = e->NT;
+    PlbGemmNT g = nt_desc(x, e->wbf(PLB_TOK_W), Tp, e->NT, H);
+    g.Mstore = T; g.bias = e->par(PLB_TOK_B); g.Cf = token_logits; g.ldcf = e->NT;
     TRY(plb_launch_gemm_nt(&g, 0, 1, s));
   }
   if (e->fp8_on) {
@@ -1202,6 +1264,29 @@ static int pieces_done(PlbEngine* e) {
   e->grads_reduced = true;
   return 0;
 }
+// The pieces of the overlapped exchange, in issue order, as [begin, end) parameter boundaries of the flat gradient buffer
+// (PLB_HEAD_B + 1: the end of the trainable range). A collective sequence must be the same on every rank: the regular call
+// (the phoneme head, then the tail) and a rank without masked phonemes (zero_loss_call) both issue exactly this list. The
+// token head's piece of a dual-head call is not in it: a dual-head call never takes the zero-loss path.
+struct PieceRange { int begin, end; };
+static const PieceRange kPieces[] = {
+    {PLB_HEAD_W, PLB_HEAD_B + 1},   // the phoneme head: final before the layer loop (the status word travels behind it)
+    {PLB_Q_W, PLB_Q_B},             // the weights, each as soon as its weight-gradient GEMM has written it ...
+    {PLB_FFN_W, PLB_FFN_B},
+    // ... the small tensors between them in the flat order, from the side stream
+    {PLB_WORD_EMB, PLB_Q_W}, {PLB_Q_B, PLB_DENSE_W}, {PLB_DENSE_B, PLB_FFN_W}, {PLB_FFN_B, PLB_FFNO_W}, {PLB_FFNO_B, PLB_HEAD_W},
+    {PLB_FFNO_W, PLB_FFNO_B},
+    {PLB_DENSE_W, PLB_DENSE_B}};   // the smallest weight goes last
+enum { kPieceHead = 0, kPieceQkvW, kPieceFfnW, kPieceSmall, kPieceFfnoW = kPieceSmall + 5, kPieceDenseW, kNPieces };
+static_assert(sizeof(kPieces) / sizeof(kPieces[0]) == kNPieces, "piece table");
+static int64_t piece_begin(const PlbEngine* e, int i) { return e->poff[kPieces[i].begin]; }
+static int64_t piece_end(const PlbEngine* e, int i) { return e->poff[kPieces[i].end]; }
+// kPieces[from, to), each ordered after everything enqueued on `after` so far
+static int reduce_pieces(PlbEngine* e, int from, int to, hipStream_t after) {
+  for (int i = from; i < to; ++i)
+    if (reduce_piece(e, piece_begin(e, i), piece_end(e, i), after)) return 1;
+  return 0;
+}
 
 // ---- the step's health word, agreed between the ranks -----------------------------------------------------------
 // A fused LayerNorm hand-off that times out (never observed) raises the error word of THE RANK IT HAPPENED ON; that
@@ -1243,6 +1328,322 @@ static int status_finish(PlbEngine* e, float* loss, hipStream_t s) {
   return 0;
 }
 
+// ---- stages of a loss call ----------------------------------------------------------------------------------------------
+// Bookkeeping at the start of a training call.
+static int begin_training_call(PlbEngine* e, bool dual, hipStream_t s) {
+  // All-reduce pieces of a PREVIOUS backward that nobody joined (two plb_loss_fwd_bwd calls with no plb_allreduce_grads /
+  // plb_adamw_step between them: gradient probing, a caller that skips a step on a bad loss) still read and write the
+  // gradient buffer on the communication stream: this call's kernels must not touch it before they have finished.
+  if (e->comm && e->comm_pending) HIPTRY(ev_wait(e, s, e->ev_comm_done));
+  e->tok_grads_live = dual;
+  e->comm_pending = false;
+  e->grads_reduced = false;
+  e->piece_floats = 0;
+  e->piece_count = 0;
+  e->status_collectives = 0;
+  if (e->hb.on) {
+    // this call's first launches on the caller's stream may touch any byte of the workspace and the gradient buffer:
+    // whatever the previous call left running on the side / communication stream must be ordered before them
+    HB_W(s, e->ws, e->ws_bytes, "start of a loss call (whole workspace)");
+    HB_W(s, e->grads, e->ptotal * 4, "start of a loss call (gradient buffer)");
+    if (e->hb.violations) return fail("happens-before audit: %s", e->hb.first.c_str());
+    e->hb.new_call();
+  }
+  for (auto& t : e->trace) { e->trace_pool.push_back(t.released); e->trace_pool.push_back(t.done); }
+  e->trace.clear();
+  if (e->trace_on) {
+    if (!e->tr_call0) { (void)hipEventCreate(&e->tr_call0); (void)hipEventCreate(&e->tr_tail0); (void)hipEventCreate(&e->tr_tail1); }
+    (void)hipEventRecord(e->tr_call0, s);
+    e->tr_tail_valid = false;
+  }
+  return 0;
+}
+
+// A phoneme-only call without masked positions (train.py:129): zero loss, nothing to back-propagate.
+static int zero_loss_call(PlbEngine* e, bool backward, float* loss, hipStream_t s) {
+  HIPTRY(hipMemsetAsync(loss, 0, sizeof(float), s));
+  if (!backward) return 0;
+  HIPTRY(hipMemsetAsync(e->grads, 0, (size_t)e->ptrain * 4, s));
+  if (overlapping(e)) {
+    // The other ranks still contribute theirs — and they issue the pieces of a regular step: a collective
+    // sequence must be the same on every rank, so this rank issues the very same ranges in the very same order
+    // (its zeros), not one all-reduce of the whole buffer.
+    for (int i = 0; i < kNPieces; ++i) {
+      HB_W(s, e->grads + piece_begin(e, i), (piece_end(e, i) - piece_begin(e, i)) * 4, "zero gradients of a rank without masked phonemes");
+      if (reduce_pieces(e, i, i + 1, s)) return 1;
+      if (i == kPieceHead && status_exchange(e, s)) return 1;   // where a regular step issues it: behind the head piece
+    }
+    if (pieces_done(e)) return 1;
+  } else if (status_exchange(e, s)) {
+    return 1;
+  }
+  return status_finish(e, loss, s);
+}
+
+// The masked rows: head GEMM, cross-entropy, and in a training call the head's gradients and its rows of dy (the output
+// gradient of the last application; pruned: the compact rows o_dhm are that gradient).
+static int phoneme_head(PlbEngine* e, bool backward, bool prune, const bf16_t* xL, int n_masked, int64_t Tp, bf16_t* dy,
+                        float* loss, hipStream_t s) {
+  const int H = e->H, NP = e->NP;
+  const int NM = (int)rup(n_masked, 128);
+  int32_t* rows = e->at<int32_t>(e->o_rows);
+  bf16_t* hm = e->at<bf16_t>(e->o_hm);
+  float* logm = e->at<float>(e->o_logm);
+  float* lrows = e->at<float>(e->o_lrows);
+  bf16_t* dlog = e->at<bf16_t>(e->o_dlog);
+  bf16_t* dhm = e->at<bf16_t>(e->o_dhm);
+  if (backward && !prune) HIPTRY(hipMemsetAsync(dy, 0, (size_t)Tp * H * 2, s));
+  if (n_masked > 0) {
+    if (!prune) TRY(plb_launch_gather_rows(xL, H, rows, n_masked, NM, H, hm, H, s));   // (pruned: xL IS hm, the compact rows)
+    PlbGemmNT g = nt_desc(hm, e->wbf(PLB_HEAD_W), NM, NP, H);
+    g.bias = e->par(PLB_HEAD_B); g.Cf = logm; g.ldcf = 256;
+    TRY(plb_launch_gemm_nt(&g, 0, 1, s));
+    TRY(plb_launch_ce_fwd_bwd(logm, 256, NP, e->at<int32_t>(e->o_tgt), e->at<float>(e->o_w), n_masked, NM, lrows, dlog, 256, s));
+    TRY(plb_launch_sum_rows(lrows, n_masked, loss, s));
+    if (backward) {
+      if (weight_grad(e, dlog, 256, 256, hm, H, NM, NP, H, e->grd(PLB_HEAD_W), s)) return 1;
+      TRY(plb_launch_colsum(dlog, 1, (size_t)NM, 256, 256, e->grd(PLB_HEAD_B), NP, 0, e->at<float>(e->o_scratch), 8, s));
+      g = nt_desc(dlog, e->at<bf16_t>(e->o_wpT), NM, H, 256);
+      g.C = dhm; g.ldc = H;
+      TRY(plb_launch_gemm_nt(&g, 0, 0, s));
+      // (pruned: the compact gradient rows dhm ARE the output gradient of the last application's compact part)
+      if (!prune) TRY(plb_launch_scatter_rows(dhm, H, rows, n_masked, H, dy, H, s));
+    }
+  } else {  // dual-head step on a batch without masked phonemes: phoneme loss 0, its head gets zero gradients
+    HIPTRY(hipMemsetAsync(loss, 0, sizeof(float), s));
+    if (backward)
+      HIPTRY(hipMemsetAsync(e->grd(PLB_HEAD_W), 0, (size_t)(e->psize[PLB_HEAD_W] + e->psize[PLB_HEAD_B]) * 4, s));
+  }
+  if (!backward) return 0;
+  // the phoneme head's gradients are final: their all-reduce runs beside the whole backward
+  HB_W(s, e->grd(PLB_HEAD_W), (e->ptrain - e->poff[PLB_HEAD_W]) * 4, "phoneme head gradients (weight-gradient GEMM, bias column sums)");
+  if (overlapping(e) && reduce_pieces(e, kPieceHead, kPieceHead + 1, s)) return 1;
+  return 0;
+}
+
+// ---- token (grapheme) head over every valid position: fused GEMM + cross-entropy, head gradients, dH ------------
+// The fp32 logits are never stored. Pass 1 computes them tile by tile and keeps, per row and 256-column tile, the
+// maximum and the sum of exponentials (+ the target logit); a small kernel merges those into the row's
+// log-sum-exp, weight and loss; pass 2 recomputes the logits and writes the gradient (softmax - onehot) * w in
+// bf16 [Tp][NTp] (2.1 GB at 16384 x 64000), the operand of dWt = dlogits^T · H and dH = dlogits · Wt, and the
+// column-sum partials that give the bias gradient.
+static int token_head(PlbEngine* e, bool backward, const bf16_t* xL, const int64_t* token_targets, const int32_t* lengths,
+                      int B, int S, bf16_t* dy, float* loss, float* loss_parts, hipStream_t s) {
+  const int H = e->H, NT = e->NT, NTp = e->NTp, T = B * S;
+  const int64_t Tp = rup(T, 128);
+  const int tile = (Tp % 256 == 0) ? 256 : 1256;          // 256x256 or 128x256: both 256 columns wide
+  const int ntile = NTp / 256, cprows = tile == 256 ? 2 * (int)(Tp / 256) : 2 * (int)(Tp / 128);
+  float* tlrows = e->at<float>(e->o_tlrows);
+  float* tloss = e->at<float>(e->o_tloss);
+  int64_t* ttgt = e->at<int64_t>(e->o_ttgt);
+  HIPTRY(hipMemcpyAsync(ttgt, token_targets, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
+  if (Tp > T) HIPTRY(hipMemsetAsync(ttgt + T, 0, (size_t)(Tp - T) * 8, s));
+  PlbGemmNT g = nt_desc(xL, e->wbf(PLB_TOK_W), Tp, NTp, H);
+  g.bias = e->at<float>(e->o_bt);
+  g.ce_cols = NT; g.ce_tgt = ttgt;
+  g.ce_pmax = e->at<float>(e->o_tpmax); g.ce_psum = e->at<float>(e->o_tpsum); g.ce_tlogit = e->at<float>(e->o_ttl);
+  const double ce_flops = 2.0 * (double)Tp * NTp * H;
+  int tok = plb_prof_begin(PLB_K_GEMM_NT_CE, s, ce_flops, 0.0);
+  TRY(plb_launch_gemm_nt_big(&g, tile, 3, 0, s));
+  plb_prof_end(tok, s);
+  TRY(plb_launch_token_ce_combine(g.ce_pmax, g.ce_psum, ntile, g.ce_tlogit, lengths, B, S, (int)Tp,
+                                  e->at<float>(e->o_tlse), e->at<float>(e->o_tw), tlrows, s));
+  TRY(plb_launch_sum_rows(tlrows, T, tloss, s));
+  TRY(plb_launch_add_scalar(loss, loss, tloss, s));
+  if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts + 1, tloss, sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (!backward) return 0;
+  bf16_t* tdl = e->at<bf16_t>(e->o_tdl);
+  g.ce_lse = e->at<float>(e->o_tlse); g.ce_w = e->at<float>(e->o_tw);
+  g.C = tdl; g.ldc = NTp; g.colpart = e->at<float>(e->o_tcolp);
+  tok = plb_prof_begin(PLB_K_GEMM_NT_CE, s, ce_flops, 0.0);
+  TRY(plb_launch_gemm_nt_big(&g, tile, 4, 0, s));
+  plb_prof_end(tok, s);
+  TRY(plb_launch_colsum(g.colpart, 0, (size_t)cprows, NTp, NTp, e->grd(PLB_TOK_B), NT, 0, e->at<float>(e->o_tscr), 1, s));
+  float* gw = NTp == NT ? e->grd(PLB_TOK_W) : e->at<float>(e->o_tgrad);
+  if (weight_grad(e, tdl, NTp, NTp, xL, H, Tp, NTp, H, gw, s)) return 1;
+  if (NTp != NT) HIPTRY(hipMemcpyAsync(e->grd(PLB_TOK_W), gw, (size_t)NT * H * 4, hipMemcpyDeviceToDevice, s));
+  HB_W(s, e->grd(PLB_TOK_W), (e->ptotal - e->poff[PLB_TOK_W]) * 4, "token head gradients");
+  if (overlapping(e) && reduce_piece(e, e->poff[PLB_TOK_W], e->ptotal, s)) return 1;
+  // dH += dlogits · Wt, on top of the scattered phoneme-head rows (in place: a tile reads its residual
+  // before its own stores)
+  g = nt_desc(tdl, e->at<bf16_t>(e->o_wtT), Tp, H, NTp);
+  g.res = dy; g.ldr = H; g.C = dy; g.ldc = H;
+  TRY(plb_launch_gemm_nt(&g, 0, 0, s));
+  return 0;
+}
+
+// ---- layers in reverse --------------------------------------------------------------------------------------------------
+// What the backward stages of one call share: its shape, its precision mode, the partial-row layout of its layer loop.
+struct Bwd {
+  const int32_t* lengths;
+  int B, S, T;
+  int64_t Tp;
+  bool f8, calib;   // fp8 operands | an fp8-mode call that only records the maxima
+  bool fuse_b;      // LayerNorm backward in the epilogue of the dX GEMM that produces its output gradient
+  int prows;        // LayerNorm-backward partial rows per application
+  int du_rows;      // ffn.bias partial rows per application (0: the tail sums dU itself)
+  hipStream_t s;
+};
+
+// LayerNorm 2, FFN, LayerNorm 1 and dense of application l on all rows, down to dCtx (o_dctx). dy: the application's output
+// gradient (read by the LayerNorm-2 backward of the last application only: for the others, the dX GEMM of application l+1
+// ran it — attention_bwd_dx).
+static int post_attention_bwd(PlbEngine* e, const Bwd& c, int l, const Slots& sl, const bf16_t* dy) {
+  const int H = e->H, I = e->I, T = c.T, Tp = (int)c.Tp;
+  hipStream_t s = c.s;
+  const F8Site sDP(e, F8_DP, l), sDU(e, F8_DU, l), sDP1(e, F8_DP1, l);
+  if (l == e->L - 1 && ln_bwd(e, ln2_slot(e, sl), c.prows, dy, sl.dpre2, T, Tp, c.f8 ? sl.dp8 : nullptr, sDP, s)) return 1;
+  if (c.calib) TRY(plb_launch_amax(sl.dpre2, 1, (size_t)T, H, H, sDP.amax, s));
+  // dU = (dpre2 · W2) ∘ gelu'(u)
+  PlbGemmNT g = nt_desc(sl.dpre2, e->at<bf16_t>(e->o_w2T), Tp, I, H);
+  g.aux = sl.u; g.ldaux = I; g.C = sl.du; g.ldc = I;
+  if (c.du_rows > 0) g.colpart = sl.ducol;
+  if (c.f8) f8_out(&g, sl.du8, I, sDU, 1);
+  const F8Op ou = f8_op(sl.dp8, sDP, F8Weight(e, F8W_2T), 1);
+  if (e->u_is_derivative) {   // what the forward of THIS call stashed; fp8: dU leaves as its e5m2 image alone
+    if (e->tn8_call) g.C = nullptr;
+    TRY(gemm_nt_gelud_any(&g, 1, c.f8 ? &ou : nullptr, s));
+  } else {
+    TRY(gemm_nt_any(&g, 2, c.f8 ? &ou : nullptr, s));
+  }
+  if (c.calib) TRY(plb_launch_amax(sl.du, 1, (size_t)T, I, I, sDU.amax, s));
+  // dA = dU · W1 + dpre2 is the gradient of LayerNorm 1's output. Fused: its backward runs in this GEMM's epilogue and dA
+  // is never stored (dpre1 = the gradient of the LayerNorm's input, + the dgamma | dbeta | bias-gradient partials)
+  g = nt_desc(sl.du, e->at<bf16_t>(e->o_w1T), Tp, H, I);
+  g.res = sl.dpre2; g.ldr = H; g.C = e->at<bf16_t>(e->o_da); g.ldc = H;
+  const F8Op oa = f8_op(sl.du8, sDU, F8Weight(e, F8W_1T), 1);
+  if (gemm_ln_bwd(e, &g, c.f8 ? &oa : nullptr, c.fuse_b, ln1_slot(e, sl), c.prows, sl.dpre1, T, Tp, c.f8 ? sl.dp18 : nullptr,
+                  sDP1, s))
+    return 1;
+  if (c.calib) TRY(plb_launch_amax(sl.dpre1, 1, (size_t)T, H, H, sDP1.amax, s));
+  // dCtx = dpre1 · Wd
+  g = nt_desc(sl.dpre1, e->at<bf16_t>(e->o_wdT), Tp, H, H);
+  g.C = e->at<bf16_t>(e->o_dctx); g.ldc = H;
+  const F8Op oc = f8_op(sl.dp18, sDP1, F8Weight(e, F8W_DT), 1);
+  TRY(gemm_nt_any(&g, 0, c.f8 ? &oc : nullptr, s));
+  return 0;
+}
+
+// ---- backward of the pruned last application: the compact part (LayerNorm 2, FFN, LayerNorm 1, dense) on the Mc
+// masked rows — small-shape launches, the forward's compact activations at the start of this application's slots —
+// then its gradients are scattered back to token rows (zeros elsewhere: that is what the full evaluation computes
+// there) for the attention backward and the dX GEMM, which run on all rows: dCtx into o_dctx, dpre1 into o_da.
+static int last_application_bwd_pruned(PlbEngine* e, const Bwd& c, const Slots& sl, const Prune* pr) {
+  const int H = e->H, I = e->I, L = e->L, Mc = pr->Mc, n = pr->n;
+  hipStream_t s = c.s;
+  const F8Site sDP(e, F8_DP, L - 1), sDU(e, F8_DU, L - 1), sDP1(e, F8_DP1, L - 1);
+  bf16_t* const dac = e->at<bf16_t>(e->o_da);       // dA of the compact rows, then (full) dpre1 scattered to token rows
+  bf16_t* const dctxc = e->at<bf16_t>(e->o_dy0);    // dCtx of the compact rows (dy is not used by this application)
+  bf16_t* const dctx = e->at<bf16_t>(e->o_dctx);
+  if (ln_bwd(e, ln2_slot(e, sl), c.prows, e->at<bf16_t>(e->o_dhm), sl.dpre2, Mc, Mc, nullptr, F8Site(), s)) return 1;
+  if (c.calib) TRY(plb_launch_amax(sl.dpre2, 1, (size_t)n, H, H, sDP.amax, s));
+  PlbGemmNT g = nt_desc(sl.dpre2, e->at<bf16_t>(e->o_w2T), Mc, I, H);
+  g.aux = sl.u; g.ldaux = I; g.C = sl.du; g.ldc = I;
+  TRY(plb_launch_gemm_nt(&g, 2, 0, s));   // (the forward of this part kept u itself: act 1)
+  if (c.calib) TRY(plb_launch_amax(sl.du, 1, (size_t)n, I, I, sDU.amax, s));
+  if (c.du_rows > 0) {   // this application's block of ffn.bias partial rows: its column sums in row 0, zeros below
+    TRY(plb_launch_colsum(sl.du, 1, (size_t)Mc, I, I, sl.ducol, I, 0, e->at<float>(e->o_scratch), 16, s));
+    if (c.du_rows > 1) HIPTRY(hipMemsetAsync(sl.ducol + I, 0, (size_t)(c.du_rows - 1) * I * 4, s));
+  }
+  g = nt_desc(sl.du, e->at<bf16_t>(e->o_w1T), Mc, H, I);
+  g.res = sl.dpre2; g.ldr = H; g.C = dac; g.ldc = H;
+  if (gemm_ln_bwd(e, &g, nullptr, false, ln1_slot(e, sl), c.prows, sl.dpre1, Mc, Mc, nullptr, F8Site(), s)) return 1;
+  if (c.calib) TRY(plb_launch_amax(sl.dpre1, 1, (size_t)n, H, H, sDP1.amax, s));
+  if (e->tn8_call) {   // fp8 call: the compact gradient rows as e5m2 images for the stacked weight-gradient GEMMs
+    const void* src[3] = {sl.dpre2, sl.du, sl.dpre1}; const int fl[3] = {3, 3, 3};
+    const size_t nel[3] = {(size_t)Mc * H, (size_t)Mc * I, (size_t)Mc * H};
+    const float* sc[3] = {sDP.scale, sDU.scale, sDP1.scale};
+    uint8_t* dst[3] = {sl.dp8, sl.du8, sl.dp18};
+    float* am[3] = {sDP.amax, sDU.amax, sDP1.amax};
+    TRY(plb_launch_quantize_multi(3, src, fl, nel, sc, dst, am, s));
+  }
+  g = nt_desc(sl.dpre1, e->at<bf16_t>(e->o_wdT), Mc, H, H);
+  g.C = dctxc; g.ldc = H;
+  TRY(plb_launch_gemm_nt(&g, 0, 0, s));
+  // back to token rows: dCtx and dpre1 are zero wherever no masked position sits
+  HIPTRY(hipMemsetAsync(dctx, 0, (size_t)c.Tp * H * 2, s));
+  TRY(plb_launch_scatter_rows(dctxc, H, pr->rows, n, H, dctx, H, s));
+  HIPTRY(hipMemsetAsync(dac, 0, (size_t)c.Tp * H * 2, s));   // (dA has been consumed by the LayerNorm backward above)
+  TRY(plb_launch_scatter_rows(sl.dpre1, H, pr->rows, n, H, dac, H, s));
+  return 0;
+}
+
+// End of application l's backward, on all rows: the attention backward of dCtx (o_dctx; ctx = the forward's attention
+// output), then dX = dQKV · Wqkv + res into dx — the gradient of LayerNorm 2's output of application l-1, whose backward
+// follows (in the GEMM's epilogue where fused) and writes dpre2 of application l-1.
+static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, bf16_t* ctx, const bf16_t* res,
+                            bf16_t* dx) {
+  const int H = e->H, T = c.T;
+  hipStream_t s = c.s;
+  const F8Site sDQ(e, F8_DQ, l);
+  PlbAttn at;
+  memset(&at, 0, sizeof(at));
+  at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = c.lengths; at.B = c.B; at.S = c.S; at.NH = e->NH; at.H = H; at.scale = 0.125f;
+  at.ctx = ctx; at.ldctx = H; at.lse = sl.lse;
+  at.dctx = e->at<bf16_t>(e->o_dctx); at.lddctx = H; at.delta = e->at<float>(e->o_delta); at.dqkv = sl.dqkv; at.lddqkv = 3 * H;
+  at.colpart = sl.qkvcol; at.colpart_accumulate = 0;
+  if (c.f8) {   // dQKV leaves as its e5m2 image (alone, once the weight gradient reads images too)
+    at.dqkv8 = sl.dq8; at.lddqkv8 = 3 * H; at.dqkv_scale = sDQ.scale; at.dqkv_amax = sDQ.amax;
+    if (e->tn8_call) at.dqkv = nullptr;
+  }
+  TRY(plb_launch_attn_bwd(&at, s));
+  if (c.Tp > T) {
+    if (at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv + (int64_t)T * 3 * H, 0, (size_t)(c.Tp - T) * 3 * H * 2, s));
+    if (c.f8) HIPTRY(hipMemsetAsync(sl.dq8 + (int64_t)T * 3 * H, 0, (size_t)(c.Tp - T) * 3 * H, s));
+  }
+  if (c.calib) TRY(plb_launch_amax(sl.dqkv, 1, (size_t)T, 3 * H, 3 * H, sDQ.amax, s));
+  PlbGemmNT g = nt_desc(sl.dqkv, e->at<bf16_t>(e->o_wqkvT), c.Tp, H, 3 * H);
+  g.res = res; g.ldr = H; g.C = dx; g.ldc = H;
+  const F8Op ox = f8_op(sl.dq8, sDQ, F8Weight(e, F8W_QKVT), 1);
+  if (l == 0) {   // the gradient of the embeddings' map-in output: the tail takes it
+    TRY(gemm_nt_any(&g, 0, c.f8 ? &ox : nullptr, s));
+    return 0;
+  }
+  const Slots below = slots(e, c.Tp, c.B, c.S, l - 1, true, c.prows, c.du_rows);
+  return gemm_ln_bwd(e, &g, c.f8 ? &ox : nullptr, c.fuse_b, ln2_slot(e, below), c.prows, below.dpre2, T, (int)c.Tp,
+                     c.f8 ? below.dp8 : nullptr, F8Site(e, F8_DP, l - 1), s);
+}
+
+// The layer loop of the backward. dy: in, the output gradient of the last application; out, the gradient of the map-in
+// output. *du_rows: the ffn.bias partial rows per application it left for the tail.
+// fp8 mode: every dX GEMM reads e5m2 images of its gradient operand — dU = dpre2·W2 and dA = dU·W1 (+ LayerNorm 1
+// backward), dCtx = dpre1·Wd, dX = dQKV·Wqkv (+ LayerNorm 2 backward of the layer below) — written by the launch that
+// produces the gradient (fused LayerNorm-backward / gelu-backward epilogues, the attention-backward kernels, the
+// standalone LayerNorm backward), one image per layer for the weight-gradient GEMMs at the end.
+static int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, int S, bf16_t** dy, int* du_rows,
+                       hipStream_t s) {
+  const int I = e->I, L = e->L;
+  Bwd c;
+  c.lengths = lengths; c.B = B; c.S = S; c.T = B * S; c.Tp = rup(c.T, 128); c.s = s;
+  const int Tp = (int)c.Tp;
+  c.f8 = f8_call(e, Tp, true);
+  c.calib = e->fp8_on && !c.f8;
+  // ffn.bias gradient from the dU GEMM's epilogue: 2 partial rows per row tile of the kernel that runs it
+  c.du_rows = e->u_is_derivative ? (c.f8 ? 2 * (Tp / plb_gemm_nt_fp8_gelud_tile_rows(Tp)) : 2 * (Tp / 256))
+                                 : (c.f8 ? 2 * (Tp / 128) : plb_gemm_nt_colpart_rows(Tp, I, e->H));
+  // LayerNorm backward inside the dX GEMM that produces its output gradient (gemm_ln.hip). Rows of partials per layer:
+  // 2 per 128-row tile in the fused form (the one standalone launch left — LayerNorm 2 of the last application, whose
+  // output gradient comes from the head — then uses as many blocks), else the LayerNorm kernel's block count.
+  c.fuse_b = ln_fusable(e, Tp, 2);
+  c.prows = c.fuse_b ? 2 * Tp / 128 : e->ln_blocks;
+  e->part_rows_used = c.prows;
+  bf16_t* dx = e->at<bf16_t>(e->o_dy1);
+  for (int l = L - 1; l >= 0; --l) {
+    const Slots sl = slots(e, c.Tp, B, S, l, true, c.prows, c.du_rows);
+    if (pr && l == L - 1) {
+      // the attention output of all rows is the backward temporary o_dy1 (the ctx slot holds the compact rows)
+      if (last_application_bwd_pruned(e, c, sl, pr)) return 1;
+      if (attention_bwd_dx(e, c, l, sl, e->at<bf16_t>(e->o_dy1), e->at<bf16_t>(e->o_da), dx)) return 1;
+    } else {
+      if (post_attention_bwd(e, c, l, sl, *dy)) return 1;
+      if (attention_bwd_dx(e, c, l, sl, sl.ctx, sl.dpre1, dx)) return 1;
+    }
+    bf16_t* tmp = *dy; *dy = dx; dx = tmp;
+  }
+  *du_rows = c.du_rows;
+  return 0;
+}
+
 // token_targets == NULL: the reference's phoneme-only step. Otherwise dual-head: loss = phoneme loss + token loss.
 // backward == false: validate() — forward and loss only, one layer of activations, the gradient buffer untouched.
 static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, const int64_t* labels,
@@ -1257,68 +1658,15 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   if (n_masked < 0 || n_masked > e->NMcap) return fail("%s: n_masked %d out of range", who, n_masked);
   if (token_targets && !e->NT) return fail("%s: the engine has no token head (num_tokens = 0)", who);
   hipStream_t s = (hipStream_t)stream;
-  const int H = e->H, I = e->I, L = e->L, NP = e->NP;
-  const int T = B * S;
-  const int64_t Tp = rup(T, 128);
-  if (backward) {
-    // All-reduce pieces of a PREVIOUS backward that nobody joined (two plb_loss_fwd_bwd calls with no plb_allreduce_grads /
-    // plb_adamw_step between them: gradient probing, a caller that skips a step on a bad loss) still read and write the
-    // gradient buffer on the communication stream: this call's kernels must not touch it before they have finished.
-    if (e->comm && e->comm_pending) HIPTRY(ev_wait(e, s, e->ev_comm_done));
-    e->tok_grads_live = token_targets != nullptr;
-    e->comm_pending = false;
-    e->grads_reduced = false;
-    e->piece_floats = 0;
-    e->piece_count = 0;
-    e->status_collectives = 0;
-    if (e->hb.on) {
-      // this call's first launches on the caller's stream may touch any byte of the workspace and the gradient buffer:
-      // whatever the previous call left running on the side / communication stream must be ordered before them
-      HB_W(s, e->ws, e->ws_bytes, "start of a loss call (whole workspace)");
-      HB_W(s, e->grads, e->ptotal * 4, "start of a loss call (gradient buffer)");
-      if (e->hb.violations) return fail("happens-before audit: %s", e->hb.first.c_str());
-      e->hb.new_call();
-    }
-    for (auto& t : e->trace) { e->trace_pool.push_back(t.released); e->trace_pool.push_back(t.done); }
-    e->trace.clear();
-    if (e->trace_on) {
-      if (!e->tr_call0) { (void)hipEventCreate(&e->tr_call0); (void)hipEventCreate(&e->tr_tail0); (void)hipEventCreate(&e->tr_tail1); }
-      (void)hipEventRecord(e->tr_call0, s);
-      e->tr_tail_valid = false;
-    }
-  }
-  if (n_masked == 0 && !token_targets) {  // train.py:129 — zero loss, nothing to back-propagate
-    HIPTRY(hipMemsetAsync(loss, 0, sizeof(float), s));
-    if (backward) {
-      HIPTRY(hipMemsetAsync(e->grads, 0, (size_t)e->ptrain * 4, s));
-      if (overlapping(e)) {
-        // The other ranks still contribute theirs — and they issue the pieces of a regular step: a collective
-        // sequence must be the same on every rank, so this rank issues the very same ranges in the very same order
-        // (its zeros), not one all-reduce of the whole buffer.
-        const int64_t* o = e->poff;
-        const int64_t ranges[10][2] = {{o[PLB_HEAD_W], e->ptrain}, {o[PLB_Q_W], o[PLB_Q_B]}, {o[PLB_FFN_W], o[PLB_FFN_B]},
-                                       {0, o[PLB_Q_W]}, {o[PLB_Q_B], o[PLB_DENSE_W]}, {o[PLB_DENSE_B], o[PLB_FFN_W]},
-                                       {o[PLB_FFN_B], o[PLB_FFNO_W]}, {o[PLB_FFNO_B], o[PLB_HEAD_W]}, {o[PLB_FFNO_W], o[PLB_FFNO_B]},
-                                       {o[PLB_DENSE_W], o[PLB_DENSE_B]}};
-        for (int i = 0; i < 10; ++i) {
-          HB_W(s, e->grads + ranges[i][0], (ranges[i][1] - ranges[i][0]) * 4, "zero gradients of a rank without masked phonemes");
-          if (reduce_piece(e, ranges[i][0], ranges[i][1], s)) return 1;
-          if (i == 0 && status_exchange(e, s)) return 1;   // where a regular step issues it: behind the head piece
-        }
-        if (pieces_done(e)) return 1;
-      } else if (status_exchange(e, s)) {
-        return 1;
-      }
-      if (status_finish(e, loss, s)) return 1;
-    }
-    return 0;
-  }
-  // ---- masked rows: head GEMM, cross-entropy, head gradients ----------------------------------------
-  const int NM = (int)rup(n_masked, 128);
+  const int64_t Tp = rup(B * S, 128);
+  if (backward && begin_training_call(e, token_targets != nullptr, s)) return 1;
+  if (n_masked == 0 && !token_targets) return zero_loss_call(e, backward, loss, s);
+
   // the row list first: a phoneme-only call runs the post-attention part of its LAST application on these rows alone
   // (last_application_fwd_pruned) when that is less than half of the batch; dual-head calls run every row
+  const int NM = (int)rup(n_masked, 128);
   Prune pr = {e->at<int32_t>(e->o_rows), n_masked, NM};
-  const bool prune = prune_enabled() && n_masked > 0 && !token_targets && L >= 2 && 2 * (int64_t)NM <= Tp;
+  const bool prune = prune_enabled() && n_masked > 0 && !token_targets && e->L >= 2 && 2 * (int64_t)NM <= Tp;
   if (n_masked > 0)
     TRY(plb_launch_ce_prepare(idx_offsets, idx_flat, labels, B, S, e->at<int32_t>(e->o_rows), e->at<int32_t>(e->o_tgt),
                               e->at<float>(e->o_w), s));
@@ -1326,98 +1674,10 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   e->last_call_rows[0] = prune ? NM : Tp; e->last_call_rows[1] = Tp;
   bf16_t* xL = nullptr;
   if (run_encoder(e, masked_ids, lengths, B, S, backward, &xL, s, prune ? &pr : nullptr)) return 1;
-
-  int32_t* rows = e->at<int32_t>(e->o_rows);
-  int32_t* tgt = e->at<int32_t>(e->o_tgt);
-  float* w = e->at<float>(e->o_w);
-  float* lrows = e->at<float>(e->o_lrows);
-  bf16_t* hm = e->at<bf16_t>(e->o_hm);
-  float* logm = e->at<float>(e->o_logm);
-  bf16_t* dlog = e->at<bf16_t>(e->o_dlog);
-  bf16_t* dhm = backward ? e->at<bf16_t>(e->o_dhm) : nullptr;
-  float* scratch = backward ? e->at<float>(e->o_scratch) : nullptr;
   bf16_t* dy = backward ? e->at<bf16_t>(e->o_dy0) : nullptr;
-  bf16_t* dy_other = backward ? e->at<bf16_t>(e->o_dy1) : nullptr;
-  PlbGemmNT g;
-  if (backward && !prune) HIPTRY(hipMemsetAsync(dy, 0, (size_t)Tp * H * 2, s));
-  if (n_masked > 0) {
-    if (!prune) TRY(plb_launch_gather_rows(xL, H, rows, n_masked, NM, H, hm, H, s));   // (pruned: xL IS hm, the compact rows)
-    memset(&g, 0, sizeof(g));
-    g.A = hm; g.lda = H; g.B = e->wbf(PLB_HEAD_W); g.ldb = H; g.M = NM; g.N = NP; g.K = H; g.Mstore = NM;
-    g.bias = e->par(PLB_HEAD_B); g.Cf = logm; g.ldcf = 256;
-    TRY(plb_launch_gemm_nt(&g, 0, 1, s));
-    TRY(plb_launch_ce_fwd_bwd(logm, 256, NP, tgt, w, n_masked, NM, lrows, dlog, 256, s));
-    TRY(plb_launch_sum_rows(lrows, n_masked, loss, s));
-    if (backward) {
-      if (weight_grad(e, dlog, 256, 256, hm, H, NM, NP, H, e->grd(PLB_HEAD_W), s)) return 1;
-      TRY(plb_launch_colsum(dlog, 1, (size_t)NM, 256, 256, e->grd(PLB_HEAD_B), NP, 0, scratch, 8, s));
-      memset(&g, 0, sizeof(g));
-      g.A = dlog; g.lda = 256; g.B = e->at<bf16_t>(e->o_wpT); g.ldb = 256; g.M = NM; g.N = H; g.K = 256; g.Mstore = NM;
-      g.C = dhm; g.ldc = H;
-      TRY(plb_launch_gemm_nt(&g, 0, 0, s));
-      // (pruned: the compact gradient rows dhm ARE the output gradient of the last application's compact part)
-      if (!prune) TRY(plb_launch_scatter_rows(dhm, H, rows, n_masked, H, dy, H, s));
-    }
-  } else {  // dual-head step on a batch without masked phonemes: phoneme loss 0, its head gets zero gradients
-    HIPTRY(hipMemsetAsync(loss, 0, sizeof(float), s));
-    if (backward)
-      HIPTRY(hipMemsetAsync(e->grd(PLB_HEAD_W), 0, (size_t)(e->psize[PLB_HEAD_W] + e->psize[PLB_HEAD_B]) * 4, s));
-  }
-  // the phoneme head's gradients are final: their all-reduce runs beside the whole backward
-  if (backward) HB_W(s, e->grd(PLB_HEAD_W), (e->ptrain - e->poff[PLB_HEAD_W]) * 4, "phoneme head gradients (weight-gradient GEMM, bias column sums)");
-  if (backward && overlapping(e) && reduce_piece(e, e->poff[PLB_HEAD_W], e->ptrain, s)) return 1;
+  if (phoneme_head(e, backward, prune, xL, n_masked, Tp, dy, loss, s)) return 1;
   if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts, loss, sizeof(float), hipMemcpyDeviceToDevice, s));
-
-  // ---- token (grapheme) head over every valid position: fused GEMM + cross-entropy, head gradients, dH ------------
-  // The fp32 logits are never stored. Pass 1 computes them tile by tile and keeps, per row and 256-column tile, the
-  // maximum and the sum of exponentials (+ the target logit); a small kernel merges those into the row's
-  // log-sum-exp, weight and loss; pass 2 recomputes the logits and writes the gradient (softmax - onehot) * w in
-  // bf16 [Tp][NTp] (2.1 GB at 16384 x 64000), the operand of dWt = dlogits^T · H and dH = dlogits · Wt, and the
-  // column-sum partials that give the bias gradient.
-  if (token_targets) {
-    const int NT = e->NT, NTp = e->NTp;
-    const int tile = (Tp % 256 == 0) ? 256 : 1256;          // 256x256 or 128x256: both 256 columns wide
-    const int ntile = NTp / 256, cprows = tile == 256 ? 2 * (int)(Tp / 256) : 2 * (int)(Tp / 128);
-    float* tlrows = e->at<float>(e->o_tlrows);
-    float* tloss = e->at<float>(e->o_tloss);
-    int64_t* ttgt = e->at<int64_t>(e->o_ttgt);
-    HIPTRY(hipMemcpyAsync(ttgt, token_targets, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
-    if (Tp > T) HIPTRY(hipMemsetAsync(ttgt + T, 0, (size_t)(Tp - T) * 8, s));
-    memset(&g, 0, sizeof(g));
-    g.A = xL; g.lda = H; g.B = e->wbf(PLB_TOK_W); g.ldb = H; g.M = (int)Tp; g.N = NTp; g.K = H; g.Mstore = (int)Tp;
-    g.bias = e->at<float>(e->o_bt);
-    g.ce_cols = NT; g.ce_tgt = ttgt;
-    g.ce_pmax = e->at<float>(e->o_tpmax); g.ce_psum = e->at<float>(e->o_tpsum); g.ce_tlogit = e->at<float>(e->o_ttl);
-    const double ce_flops = 2.0 * (double)Tp * NTp * H;
-    int tok = plb_prof_begin(PLB_K_GEMM_NT_CE, s, ce_flops, 0.0);
-    TRY(plb_launch_gemm_nt_big(&g, tile, 3, 0, s));
-    plb_prof_end(tok, s);
-    TRY(plb_launch_token_ce_combine(g.ce_pmax, g.ce_psum, ntile, g.ce_tlogit, lengths, B, S, (int)Tp,
-                                    e->at<float>(e->o_tlse), e->at<float>(e->o_tw), tlrows, s));
-    TRY(plb_launch_sum_rows(tlrows, T, tloss, s));
-    TRY(plb_launch_add_scalar(loss, loss, tloss, s));
-    if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts + 1, tloss, sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (backward) {
-      bf16_t* tdl = e->at<bf16_t>(e->o_tdl);
-      g.ce_lse = e->at<float>(e->o_tlse); g.ce_w = e->at<float>(e->o_tw);
-      g.C = tdl; g.ldc = NTp; g.colpart = e->at<float>(e->o_tcolp);
-      tok = plb_prof_begin(PLB_K_GEMM_NT_CE, s, ce_flops, 0.0);
-      TRY(plb_launch_gemm_nt_big(&g, tile, 4, 0, s));
-      plb_prof_end(tok, s);
-      TRY(plb_launch_colsum(g.colpart, 0, (size_t)cprows, NTp, NTp, e->grd(PLB_TOK_B), NT, 0, e->at<float>(e->o_tscr), 1, s));
-      float* gw = NTp == NT ? e->grd(PLB_TOK_W) : e->at<float>(e->o_tgrad);
-      if (weight_grad(e, tdl, NTp, NTp, xL, H, Tp, NTp, H, gw, s)) return 1;
-      if (NTp != NT) HIPTRY(hipMemcpyAsync(e->grd(PLB_TOK_W), gw, (size_t)NT * H * 4, hipMemcpyDeviceToDevice, s));
-      HB_W(s, e->grd(PLB_TOK_W), (e->ptotal - e->poff[PLB_TOK_W]) * 4, "token head gradients");
-      if (overlapping(e) && reduce_piece(e, e->poff[PLB_TOK_W], e->ptotal, s)) return 1;
-      // dH += dlogits · Wt, on top of the scattered phoneme-head rows (in place: a tile reads its residual
-      // before its own stores)
-      memset(&g, 0, sizeof(g));
-      g.A = tdl; g.lda = NTp; g.B = e->at<bf16_t>(e->o_wtT); g.ldb = NTp; g.M = (int)Tp; g.N = H; g.K = NTp; g.Mstore = (int)Tp;
-      g.res = dy; g.ldr = H; g.C = dy; g.ldc = H;
-      TRY(plb_launch_gemm_nt(&g, 0, 0, s));
-    }
-  }
+  if (token_targets && token_head(e, backward, xL, token_targets, lengths, B, S, dy, loss, loss_parts, s)) return 1;
   if (!backward) {
     if (e->fp8_on) {  // forward-only call in fp8 mode: activation sites only (gradient sites saw nothing and keep theirs)
       TRY(fp8_update_scales(e, s));
@@ -1430,217 +1690,8 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
     return 0;
   }
 
-  // ---- layers in reverse --------------------------------------------------------------------------------
-  // fp8 mode: every dX GEMM reads e5m2 images of its gradient operand — dU = dpre2·W2 and dA = dU·W1 (+ LayerNorm 1
-  // backward), dCtx = dpre1·Wd, dX = dQKV·Wqkv (+ LayerNorm 2 backward of the layer below) — written by the launch that
-  // produces the gradient (fused LayerNorm-backward / gelu-backward epilogues, the attention-backward kernels, the one
-  // standalone LayerNorm backward), one image per layer for the weight-gradient GEMMs at the end.
-  const bool f8 = f8_call(e, Tp, true);
-  const bool calib = e->fp8_on && !f8;
-  // ffn.bias gradient from the dU GEMM's epilogue: 2 partial rows per row tile of the kernel that runs it
-  const int du_rows = e->u_is_derivative ? (f8 ? 2 * (int)(Tp / plb_gemm_nt_fp8_gelud_tile_rows((int)Tp)) : 2 * (int)(Tp / 256))
-                                         : (f8 ? 2 * (int)(Tp / 128) : plb_gemm_nt_colpart_rows((int)Tp, I, H));
-  bf16_t* da = e->at<bf16_t>(e->o_da);
-  bf16_t* dctx = e->at<bf16_t>(e->o_dctx);
-  // LayerNorm backward inside the dX GEMM that produces its output gradient (gemm_ln.hip). Rows of partials per layer:
-  // 2 per 128-row tile in the fused form (the one standalone launch left — LayerNorm 2 of the last application, whose
-  // output gradient comes from the head — then uses as many blocks), else the LayerNorm kernel's block count.
-  const bool fuse_b = ln_fusable(e, Tp, 2);
-  const int prows = fuse_b ? (int)(2 * Tp / 128) : e->ln_blocks;
-  e->part_rows_used = prows;
-  for (int l = L - 1; l >= 0; --l) {
-    bf16_t* qkv = e->at<bf16_t>(e->o_qkv) + (int64_t)l * Tp * 3 * H;
-    bf16_t* ctx = e->at<bf16_t>(e->o_ctx) + (int64_t)l * Tp * H;
-    bf16_t* pre1 = e->at<bf16_t>(e->o_pre1) + (int64_t)l * Tp * H;
-    bf16_t* u = e->at<bf16_t>(e->o_u) + (int64_t)l * Tp * I;
-    bf16_t* pre2 = e->at<bf16_t>(e->o_pre2) + (int64_t)l * Tp * H;
-    bf16_t* dqkv = e->at<bf16_t>(e->o_dqkv) + (int64_t)l * Tp * 3 * H;
-    bf16_t* dpre1 = e->at<bf16_t>(e->o_dpre1) + (int64_t)l * Tp * H;
-    bf16_t* du = e->at<bf16_t>(e->o_du) + (int64_t)l * Tp * I;
-    bf16_t* dpre2 = e->at<bf16_t>(e->o_dpre2) + (int64_t)l * Tp * H;
-    uint8_t* dp8 = e->at<uint8_t>(e->o_dp8) + (int64_t)l * Tp * H;
-    uint8_t* du8 = e->at<uint8_t>(e->o_du8) + (int64_t)l * Tp * I;
-    uint8_t* dp18 = e->at<uint8_t>(e->o_dp18) + (int64_t)l * Tp * H;
-    uint8_t* dq8 = e->at<uint8_t>(e->o_dq8) + (int64_t)l * Tp * 3 * H;
-    const int sDP = f8_site(e, F8_DP, l), sDU = f8_site(e, F8_DU, l), sDP1 = f8_site(e, F8_DP1, l), sDQ = f8_site(e, F8_DQ, l);
-    PlbLayerNorm ln;
-    if (prune && l == L - 1) {
-      // ---- backward of the pruned last application: the compact part (LayerNorm 2, FFN, LayerNorm 1, dense) on the Mc
-      // masked rows — small-shape launches, the forward's compact activations at the start of this application's slots —
-      // then its gradients are scattered back to token rows (zeros elsewhere: that is what the full evaluation computes
-      // there) for the attention backward and the dX GEMM, which run on all rows
-      const int Mc = NM;
-      bf16_t* const dac = e->at<bf16_t>(e->o_da);       // dA of the compact rows, then (full) dpre1 scattered to token rows
-      bf16_t* const dctxc = e->at<bf16_t>(e->o_dy0);    // dCtx of the compact rows (dy is not used by this application)
-      bf16_t* const ctx_att = e->at<bf16_t>(e->o_dy1);  // the forward's attention output of all rows
-      memset(&ln, 0, sizeof(ln));
-      ln.x = pre2; ln.ldx = H; ln.gamma = e->par(PLB_LN2_W); ln.T = Mc; ln.H = H; ln.Tzero = Mc;
-      ln.mean = e->at<float>(e->o_mean2) + (int64_t)l * Tp; ln.rstd = e->at<float>(e->o_rstd2) + (int64_t)l * Tp;
-      ln.dy = dhm; ln.lddy = H; ln.dx = dpre2; ln.lddx = H;
-      ln.partials = e->at<float>(e->o_part2) + (int64_t)l * prows * 3 * H; ln.nblocks = prows;
-      TRY(plb_launch_ln_bwd(&ln, s));
-      if (calib) TRY(plb_launch_amax(dpre2, 1, (size_t)n_masked, H, H, f8_amax(e, sDP), s));
-      memset(&g, 0, sizeof(g));
-      g.A = dpre2; g.lda = H; g.B = e->at<bf16_t>(e->o_w2T); g.ldb = H; g.M = Mc; g.N = I; g.K = H; g.Mstore = Mc;
-      g.aux = u; g.ldaux = I; g.C = du; g.ldc = I;
-      TRY(plb_launch_gemm_nt(&g, 2, 0, s));   // (the forward of this part kept u itself: act 1)
-      if (calib) TRY(plb_launch_amax(du, 1, (size_t)n_masked, I, I, f8_amax(e, sDU), s));
-      if (du_rows > 0) {   // this application's block of ffn.bias partial rows: its column sums in row 0, zeros below
-        float* blk = e->at<float>(e->o_ducol) + (int64_t)l * du_rows * I;
-        TRY(plb_launch_colsum(du, 1, (size_t)Mc, I, I, blk, I, 0, scratch, 16, s));
-        if (du_rows > 1) HIPTRY(hipMemsetAsync(blk + I, 0, (size_t)(du_rows - 1) * I * 4, s));
-      }
-      memset(&g, 0, sizeof(g));
-      g.A = du; g.lda = I; g.B = e->at<bf16_t>(e->o_w1T); g.ldb = I; g.M = Mc; g.N = H; g.K = I; g.Mstore = Mc;
-      g.res = dpre2; g.ldr = H; g.C = dac; g.ldc = H;
-      TRY(plb_launch_gemm_nt(&g, 0, 0, s));
-      memset(&ln, 0, sizeof(ln));
-      ln.x = pre1; ln.ldx = H; ln.gamma = e->par(PLB_LN1_W); ln.T = Mc; ln.H = H; ln.Tzero = Mc;
-      ln.mean = e->at<float>(e->o_mean1) + (int64_t)l * Tp; ln.rstd = e->at<float>(e->o_rstd1) + (int64_t)l * Tp;
-      ln.dy = dac; ln.lddy = H; ln.dx = dpre1; ln.lddx = H;
-      ln.partials = e->at<float>(e->o_part1) + (int64_t)l * prows * 3 * H; ln.nblocks = prows;
-      TRY(plb_launch_ln_bwd(&ln, s));
-      if (calib) TRY(plb_launch_amax(dpre1, 1, (size_t)n_masked, H, H, f8_amax(e, sDP1), s));
-      if (e->tn8_call) {   // fp8 call: the compact gradient rows as e5m2 images for the stacked weight-gradient GEMMs
-        const void* src[3] = {dpre2, du, dpre1}; const int fl[3] = {3, 3, 3};
-        const size_t nel[3] = {(size_t)Mc * H, (size_t)Mc * I, (size_t)Mc * H};
-        const float* sc[3] = {f8_scale(e, sDP), f8_scale(e, sDU), f8_scale(e, sDP1)};
-        uint8_t* dst[3] = {dp8, du8, dp18};
-        float* am[3] = {f8_amax(e, sDP), f8_amax(e, sDU), f8_amax(e, sDP1)};
-        TRY(plb_launch_quantize_multi(3, src, fl, nel, sc, dst, am, s));
-      }
-      memset(&g, 0, sizeof(g));
-      g.A = dpre1; g.lda = H; g.B = e->at<bf16_t>(e->o_wdT); g.ldb = H; g.M = Mc; g.N = H; g.K = H; g.Mstore = Mc;
-      g.C = dctxc; g.ldc = H;
-      TRY(plb_launch_gemm_nt(&g, 0, 0, s));
-      // back to token rows: dCtx and dpre1 are zero wherever no masked position sits
-      HIPTRY(hipMemsetAsync(dctx, 0, (size_t)Tp * H * 2, s));
-      TRY(plb_launch_scatter_rows(dctxc, H, rows, n_masked, H, dctx, H, s));
-      HIPTRY(hipMemsetAsync(dac, 0, (size_t)Tp * H * 2, s));   // (dA has been consumed by the LayerNorm backward above)
-      TRY(plb_launch_scatter_rows(dpre1, H, rows, n_masked, H, dac, H, s));
-      PlbAttn at;
-      memset(&at, 0, sizeof(at));
-      at.qkv = qkv; at.ldqkv = 3 * H; at.lengths = lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H; at.scale = 0.125f;
-      at.ctx = ctx_att; at.ldctx = H; at.lse = e->at<float>(e->o_lse) + (int64_t)l * B * e->NH * S;
-      at.dctx = dctx; at.lddctx = H; at.delta = e->at<float>(e->o_delta); at.dqkv = dqkv; at.lddqkv = 3 * H;
-      at.colpart = e->at<float>(e->o_qkvcol) + (int64_t)l * (B * ((S + 127) / 128) * 4) * 3 * H; at.colpart_accumulate = 0;
-      if (f8) {   // as in the full evaluation: dQKV's e5m2 image for the fp8 dX GEMM (alone, once the weight gradient reads images too)
-        at.dqkv8 = dq8; at.lddqkv8 = 3 * H; at.dqkv_scale = f8_scale(e, sDQ); at.dqkv_amax = f8_amax(e, sDQ);
-        if (e->tn8_call) at.dqkv = nullptr;
-      }
-      TRY(plb_launch_attn_bwd(&at, s));
-      if (Tp > T) {
-        if (at.dqkv) HIPTRY(hipMemsetAsync(dqkv + (int64_t)T * 3 * H, 0, (size_t)(Tp - T) * 3 * H * 2, s));
-        if (f8) HIPTRY(hipMemsetAsync(dq8 + (int64_t)T * 3 * H, 0, (size_t)(Tp - T) * 3 * H, s));
-      }
-      if (calib) TRY(plb_launch_amax(dqkv, 1, (size_t)T, 3 * H, 3 * H, f8_amax(e, sDQ), s));
-      // dX = dQKV · Wqkv + dpre1 (token rows), with the LayerNorm-2 backward of application L-2 in the epilogue where fused
-      memset(&g, 0, sizeof(g));
-      g.A = dqkv; g.lda = 3 * H; g.B = e->at<bf16_t>(e->o_wqkvT); g.ldb = 3 * H; g.M = (int)Tp; g.N = H; g.K = 3 * H;
-      g.Mstore = (int)Tp; g.res = dac; g.ldr = H; g.C = dy_other; g.ldc = H;
-      F8Op oxp = {dq8, e->at<uint8_t>(e->o_wqT8), f8_deq(e, sDQ), f8_deq(e, f8_w(e, F8W_QKVT)), 1};
-      if (fuse_b) {
-        g.C = e->at<bf16_t>(e->o_dpre2) + (int64_t)(l - 1) * Tp * H;
-        g.aux = e->at<bf16_t>(e->o_pre2) + (int64_t)(l - 1) * Tp * H; g.ldaux = H;
-        g.colpart = e->at<float>(e->o_part2) + (int64_t)(l - 1) * prows * 3 * H;
-        ln_fields(e, &g, e->par(PLB_LN2_W), nullptr, e->at<float>(e->o_mean2) + (int64_t)(l - 1) * Tp, e->at<float>(e->o_rstd2) + (int64_t)(l - 1) * Tp);
-        if (f8) f8_out(e, &g, e->at<uint8_t>(e->o_dp8) + (int64_t)(l - 1) * Tp * H, H, f8_site(e, F8_DP, l - 1), 1);
-        TRY(gemm_nt_ln_any(&g, 6, f8 ? &oxp : nullptr, s));
-      } else {
-        TRY(gemm_nt_any(&g, 0, f8 ? &oxp : nullptr, s));
-      }
-      bf16_t* tmp = dy; dy = dy_other; dy_other = tmp;
-      continue;
-    }
-    if (!(fuse_b && l != L - 1)) {  // fused form: the dX GEMM of application l+1 wrote dpre2 of this one (see below)
-      memset(&ln, 0, sizeof(ln));
-      ln.x = pre2; ln.ldx = H; ln.gamma = e->par(PLB_LN2_W); ln.T = T; ln.H = H; ln.Tzero = (int)Tp;
-      ln.mean = e->at<float>(e->o_mean2) + (int64_t)l * Tp; ln.rstd = e->at<float>(e->o_rstd2) + (int64_t)l * Tp;
-      ln.dy = dy; ln.lddy = H; ln.dx = dpre2; ln.lddx = H;
-      ln.partials = e->at<float>(e->o_part2) + (int64_t)l * prows * 3 * H; ln.nblocks = prows;
-      if (f8) { ln.out8 = dp8; ln.ld8 = H; ln.q_scale = f8_scale(e, sDP); ln.q_amax = f8_amax(e, sDP); }
-      TRY(plb_launch_ln_bwd(&ln, s));
-    }
-    if (calib) TRY(plb_launch_amax(dpre2, 1, (size_t)T, H, H, f8_amax(e, sDP), s));
-    // dU = (dpre2 · W2) ∘ gelu'(u)
-    memset(&g, 0, sizeof(g));
-    g.A = dpre2; g.lda = H; g.B = e->at<bf16_t>(e->o_w2T); g.ldb = H; g.M = (int)Tp; g.N = I; g.K = H; g.Mstore = (int)Tp;
-    g.aux = u; g.ldaux = I; g.C = du; g.ldc = I;
-    if (du_rows > 0) g.colpart = e->at<float>(e->o_ducol) + (int64_t)l * du_rows * I;
-    if (f8) f8_out(e, &g, du8, I, sDU, 1);
-    F8Op ou = {dp8, e->at<uint8_t>(e->o_w2T8), f8_deq(e, sDP), f8_deq(e, f8_w(e, F8W_2T)), 1};
-    if (e->u_is_derivative) {   // what the forward of THIS call stashed; fp8: dU leaves as its e5m2 image alone
-      if (e->tn8_call) g.C = nullptr;
-      TRY(gemm_nt_gelud_any(&g, 1, f8 ? &ou : nullptr, s));
-    } else {
-      TRY(gemm_nt_any(&g, 2, f8 ? &ou : nullptr, s));
-    }
-    if (calib) TRY(plb_launch_amax(du, 1, (size_t)T, I, I, f8_amax(e, sDU), s));
-    // dA = dU · W1 + dpre2
-    memset(&g, 0, sizeof(g));
-    g.A = du; g.lda = I; g.B = e->at<bf16_t>(e->o_w1T); g.ldb = I; g.M = (int)Tp; g.N = H; g.K = I; g.Mstore = (int)Tp;
-    g.res = dpre2; g.ldr = H; g.C = da; g.ldc = H;
-    F8Op oa = {du8, e->at<uint8_t>(e->o_w1T8), f8_deq(e, sDU), f8_deq(e, f8_w(e, F8W_1T)), 1};
-    if (fuse_b) {
-      // dA = dU · W1 + dpre2 is the gradient of LayerNorm 1's output: its backward runs in this GEMM's epilogue and dA
-      // is never stored (dpre1 = the gradient of the LayerNorm's input, + the dgamma | dbeta | bias-gradient partials)
-      g.C = dpre1; g.aux = pre1; g.ldaux = H;
-      g.colpart = e->at<float>(e->o_part1) + (int64_t)l * prows * 3 * H;
-      ln_fields(e, &g, e->par(PLB_LN1_W), nullptr, e->at<float>(e->o_mean1) + (int64_t)l * Tp, e->at<float>(e->o_rstd1) + (int64_t)l * Tp);
-      if (f8) f8_out(e, &g, dp18, H, sDP1, 1);
-      TRY(gemm_nt_ln_any(&g, 6, f8 ? &oa : nullptr, s));
-    } else {
-      TRY(gemm_nt_any(&g, 0, f8 ? &oa : nullptr, s));
-      memset(&ln, 0, sizeof(ln));
-      ln.x = pre1; ln.ldx = H; ln.gamma = e->par(PLB_LN1_W); ln.T = T; ln.H = H; ln.Tzero = (int)Tp;
-      ln.mean = e->at<float>(e->o_mean1) + (int64_t)l * Tp; ln.rstd = e->at<float>(e->o_rstd1) + (int64_t)l * Tp;
-      ln.dy = da; ln.lddy = H; ln.dx = dpre1; ln.lddx = H;
-      ln.partials = e->at<float>(e->o_part1) + (int64_t)l * prows * 3 * H; ln.nblocks = prows;
-      if (f8) { ln.out8 = dp18; ln.ld8 = H; ln.q_scale = f8_scale(e, sDP1); ln.q_amax = f8_amax(e, sDP1); }
-      TRY(plb_launch_ln_bwd(&ln, s));
-    }
-    if (calib) TRY(plb_launch_amax(dpre1, 1, (size_t)T, H, H, f8_amax(e, sDP1), s));
-    // dCtx = dpre1 · Wd
-    memset(&g, 0, sizeof(g));
-    g.A = dpre1; g.lda = H; g.B = e->at<bf16_t>(e->o_wdT); g.ldb = H; g.M = (int)Tp; g.N = H; g.K = H; g.Mstore = (int)Tp;
-    g.C = dctx; g.ldc = H;
-    F8Op oc = {dp18, e->at<uint8_t>(e->o_wdT8), f8_deq(e, sDP1), f8_deq(e, f8_w(e, F8W_DT)), 1};
-    TRY(gemm_nt_any(&g, 0, f8 ? &oc : nullptr, s));
-    PlbAttn at;
-    memset(&at, 0, sizeof(at));
-    at.qkv = qkv; at.ldqkv = 3 * H; at.lengths = lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H; at.scale = 0.125f;
-    at.ctx = ctx; at.ldctx = H; at.lse = e->at<float>(e->o_lse) + (int64_t)l * B * e->NH * S;
-    at.dctx = dctx; at.lddctx = H; at.delta = e->at<float>(e->o_delta); at.dqkv = dqkv; at.lddqkv = 3 * H;
-    at.colpart = e->at<float>(e->o_qkvcol) + (int64_t)l * (B * ((S + 127) / 128) * 4) * 3 * H; at.colpart_accumulate = 0;
-    if (f8) {   // dQKV leaves as its e5m2 image (alone, once the weight gradient reads images too)
-      at.dqkv8 = dq8; at.lddqkv8 = 3 * H; at.dqkv_scale = f8_scale(e, sDQ); at.dqkv_amax = f8_amax(e, sDQ);
-      if (e->tn8_call) at.dqkv = nullptr;
-    }
-    TRY(plb_launch_attn_bwd(&at, s));
-    if (Tp > T) {
-      if (at.dqkv) HIPTRY(hipMemsetAsync(dqkv + (int64_t)T * 3 * H, 0, (size_t)(Tp - T) * 3 * H * 2, s));
-      if (f8) HIPTRY(hipMemsetAsync(dq8 + (int64_t)T * 3 * H, 0, (size_t)(Tp - T) * 3 * H, s));
-    }
-    if (calib) TRY(plb_launch_amax(dqkv, 1, (size_t)T, 3 * H, 3 * H, f8_amax(e, sDQ), s));
-    // dX = dQKV · Wqkv + dpre1
-    memset(&g, 0, sizeof(g));
-    g.A = dqkv; g.lda = 3 * H; g.B = e->at<bf16_t>(e->o_wqkvT); g.ldb = 3 * H; g.M = (int)Tp; g.N = H; g.K = 3 * H;
-    g.Mstore = (int)Tp; g.res = dpre1; g.ldr = H; g.C = dy_other; g.ldc = H;
-    F8Op ox = {dq8, e->at<uint8_t>(e->o_wqT8), f8_deq(e, sDQ), f8_deq(e, f8_w(e, F8W_QKVT)), 1};
-    if (fuse_b && l > 0) {
-      // the gradient of this application's input is the gradient of LayerNorm 2's output of application l-1: that
-      // LayerNorm's backward runs here and writes dpre2 of application l-1 directly
-      g.C = e->at<bf16_t>(e->o_dpre2) + (int64_t)(l - 1) * Tp * H;
-      g.aux = e->at<bf16_t>(e->o_pre2) + (int64_t)(l - 1) * Tp * H; g.ldaux = H;
-      g.colpart = e->at<float>(e->o_part2) + (int64_t)(l - 1) * prows * 3 * H;
-      ln_fields(e, &g, e->par(PLB_LN2_W), nullptr, e->at<float>(e->o_mean2) + (int64_t)(l - 1) * Tp, e->at<float>(e->o_rstd2) + (int64_t)(l - 1) * Tp);
-      if (f8) f8_out(e, &g, e->at<uint8_t>(e->o_dp8) + (int64_t)(l - 1) * Tp * H, H, f8_site(e, F8_DP, l - 1), 1);
-      TRY(gemm_nt_ln_any(&g, 6, f8 ? &ox : nullptr, s));
-    } else {
-      TRY(gemm_nt_any(&g, 0, f8 ? &ox : nullptr, s));
-    }
-    bf16_t* tmp = dy; dy = dy_other; dy_other = tmp;
-  }
+  int du_rows = 0;
+  if (encoder_bwd(e, prune ? &pr : nullptr, lengths, B, S, &dy, &du_rows, s)) return 1;
   // the last launch that can raise the hand-off error word is behind us: the word travels now (beside the tail)
   if (status_exchange(e, s)) return 1;
   if (backward_tail(e, masked_ids, dy, B, S, du_rows, s)) return 1;
@@ -1674,15 +1725,16 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, bf16_t
   // stacked rows of the operands whose last application ran on its masked rows only (ffn.weight, ffn_output.weight,
   // dense.weight: their slots of application L-1 hold Mc compact rows); the Q/K/V weights' operands are always full
   const int64_t Mtot_c = e->pruned_rows ? (int64_t)(L - 1) * Tp + e->pruned_rows : Mtot;
-  PlbGemmNT g;
+  // the stacks the layer loop wrote: application 0's slots, L blocks of partial rows behind them
+  const Slots st = slots(e, Tp, B, S, 0, true, e->part_rows_used, du_rows);
+  const int64_t qkvcol_all = (int64_t)L * qkvcol_rows(B, S);
   // side stream -------------------------------------------------------------------------------------------------------
   // (HB_R / HB_W: the happens-before audit's view of each launch — what it reads that another stream wrote, what it
   // writes that another stream reads. The stash operands of the GEMMs are only ever written in the layer loop, which the
   // fork orders before both streams: they are covered by the whole-workspace entry at the fork.)
   bf16_t* evec = e->at<bf16_t>(e->o_e);
   bf16_t* de = e->at<bf16_t>(e->o_de);
-  memset(&g, 0, sizeof(g));
-  g.A = dy; g.lda = H; g.B = e->at<bf16_t>(e->o_winT); g.ldb = H; g.M = (int)Tp; g.N = E; g.K = H; g.Mstore = (int)Tp;
+  PlbGemmNT g = nt_desc(dy, e->at<bf16_t>(e->o_winT), Tp, E, H);
   g.C = de; g.ldc = E;
   HB_R(s2, dy, Tp * H * 2, "dX of application 0"); HB_W(s2, de, Tp * E * 2, "dE (map-in backward)");
   TRY(plb_launch_gemm_nt(&g, 0, 0, s2));
@@ -1711,17 +1763,16 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, bf16_t
   TRY(plb_launch_colsum(e->grd(PLB_POS_EMB), 0, (size_t)e->P, E, E, e->grd(PLB_TYPE_EMB), E, 0, scratch2, 1, s2));
   // Q/K/V biases: the attention-backward kernels left the column sums of every 32-row patch they stored, per application
   // ([L][B*QT*4][3H])
-  HB_R(s2, e->at<float>(e->o_qkvcol), (int64_t)L * (B * ((S + 127) / 128) * 4) * 3 * H * 4, "Q/K/V bias partial rows");
+  HB_R(s2, st.qkvcol, qkvcol_all * 3 * H * 4, "Q/K/V bias partial rows");
   HB_W(s2, e->grd(PLB_Q_B), 3 * H * 4, "Q/K/V bias gradients");
-  TRY(plb_launch_colsum(e->at<float>(e->o_qkvcol), 0, (size_t)L * (size_t)(B * ((S + 127) / 128) * 4), 3 * H, 3 * H, e->grd(PLB_Q_B),
-                        3 * H, 0, scratch2, 64, s2));
+  TRY(plb_launch_colsum(st.qkvcol, 0, (size_t)qkvcol_all, 3 * H, 3 * H, e->grd(PLB_Q_B), 3 * H, 0, scratch2, 64, s2));
   HB_W(s2, e->grd(PLB_FFN_B), I * 4, "ffn.bias gradient");
   if (du_rows > 0) {
-    HB_R(s2, e->at<float>(e->o_ducol), (int64_t)L * du_rows * I * 4, "dU column-sum partial rows");
-    TRY(plb_launch_colsum(e->at<float>(e->o_ducol), 0, (size_t)L * du_rows, I, I, e->grd(PLB_FFN_B), I, 0, scratch2, 16, s2));
+    HB_R(s2, st.ducol, (int64_t)L * du_rows * I * 4, "dU column-sum partial rows");
+    TRY(plb_launch_colsum(st.ducol, 0, (size_t)L * du_rows, I, I, e->grd(PLB_FFN_B), I, 0, scratch2, 16, s2));
   } else {
-    HB_R(s2, e->at<bf16_t>(e->o_du), Mtot_c * I * 2, "dU of every application");
-    TRY(plb_launch_colsum(e->at<bf16_t>(e->o_du), 1, (size_t)Mtot_c, I, I, e->grd(PLB_FFN_B), I, 0, scratch2, 64, s2));
+    HB_R(s2, st.du, Mtot_c * I * 2, "dU of every application");
+    TRY(plb_launch_colsum(st.du, 1, (size_t)Mtot_c, I, I, e->grd(PLB_FFN_B), I, 0, scratch2, 64, s2));
   }
   // LayerNorm-backward partials [L*blocks][3H]: dgamma | dbeta | column sums of dx. (Summing the L applications into
   // one image inside the kernel — PlbLayerNorm.accumulate — was measured: the read-modify-write costs the main stream
@@ -1729,13 +1780,13 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, bf16_t
   // gradient of the Linear that produced the LayerNorm's input (dense.bias = colsum(dpre1), ffn_output.bias =
   // colsum(dpre2)): no pass over the stacked gradients.
   const size_t prow = (size_t)L * e->part_rows_used;
-  HB_R(s2, e->at<float>(e->o_part1), (int64_t)L * e->part_rows * 3 * H * 4, "LayerNorm-1 backward partial rows");
+  HB_R(s2, st.part1, (int64_t)L * e->part_rows * 3 * H * 4, "LayerNorm-1 backward partial rows");
   HB_W(s2, e->grd(PLB_DENSE_B), 3 * H * 4, "dense.bias + LayerNorm-1 affine gradients");
-  TRY(plb_launch_colsum(e->at<float>(e->o_part1), 0, prow, 3 * H, 3 * H, e->grd(PLB_LN1_W), 2 * H, 0, scratch2, 64, s2));
+  TRY(plb_launch_colsum(st.part1, 0, prow, 3 * H, 3 * H, e->grd(PLB_LN1_W), 2 * H, 0, scratch2, 64, s2));
   TRY(plb_launch_copy_cols(scratch2, 64, 3 * H, 2 * H, H, e->grd(PLB_DENSE_B), s2));
-  HB_R(s2, e->at<float>(e->o_part2), (int64_t)L * e->part_rows * 3 * H * 4, "LayerNorm-2 backward partial rows");
+  HB_R(s2, st.part2, (int64_t)L * e->part_rows * 3 * H * 4, "LayerNorm-2 backward partial rows");
   HB_W(s2, e->grd(PLB_LN2_W), 2 * H * 4, "LayerNorm-2 affine gradients"); HB_W(s2, e->grd(PLB_FFNO_B), H * 4, "ffn_output.bias gradient");
-  TRY(plb_launch_colsum(e->at<float>(e->o_part2), 0, prow, 3 * H, 3 * H, e->grd(PLB_LN2_W), 2 * H, 0, scratch2, 64, s2));
+  TRY(plb_launch_colsum(st.part2, 0, prow, 3 * H, 3 * H, e->grd(PLB_LN2_W), 2 * H, 0, scratch2, 64, s2));
   TRY(plb_launch_copy_cols(scratch2, 64, 3 * H, 2 * H, H, e->grd(PLB_FFNO_B), s2));
   if (s2 != s) HIPTRY(ev_record(e, e->ev_join, s2));
   // main stream: shared-layer weight gradients, one token-major GEMM per weight over all L applications ------------
@@ -1746,13 +1797,13 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, bf16_t
   const bool t8 = e->tn8_call;   // fp8 call: gradient (e5m2) x activation (e4m3) images of all L applications
   float* const slab = e->at<float>(e->o_slab);
   HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_Q_W), 3 * H * H * 4, "Q/K/V weight gradients");
-  if (t8 ? weight_grad8(e, e->at<uint8_t>(e->o_dq8), e->at<uint8_t>(e->o_x8), Mtot, 3 * H, H, F8_DQ, F8_X, e->grd(PLB_Q_W), s)
-         : weight_grad(e, e->at<bf16_t>(e->o_dqkv), 3 * H, 3 * H, e->at<bf16_t>(e->o_x), H, Mtot, 3 * H, H, e->grd(PLB_Q_W), s)) return 1;
-  if (ov && reduce_piece(e, e->poff[PLB_Q_W], e->poff[PLB_Q_B], s)) return 1;
+  if (t8 ? weight_grad8(e, st.dq8, st.x8, Mtot, 3 * H, H, F8_DQ, F8_X, e->grd(PLB_Q_W), s)
+         : weight_grad(e, st.dqkv, 3 * H, 3 * H, st.x, H, Mtot, 3 * H, H, e->grd(PLB_Q_W), s)) return 1;
+  if (ov && reduce_pieces(e, kPieceQkvW, kPieceFfnW, s)) return 1;
   HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_FFN_W), (int64_t)I * H * 4, "ffn.weight gradient");
-  if (t8 ? weight_grad8(e, e->at<uint8_t>(e->o_du8), e->at<uint8_t>(e->o_a8), Mtot_c, I, H, F8_DU, F8_A, e->grd(PLB_FFN_W), s)
-         : weight_grad(e, e->at<bf16_t>(e->o_du), I, I, e->at<bf16_t>(e->o_a), H, Mtot_c, I, H, e->grd(PLB_FFN_W), s)) return 1;
-  if (ov && reduce_piece(e, e->poff[PLB_FFN_W], e->poff[PLB_FFN_B], s)) return 1;
+  if (t8 ? weight_grad8(e, st.du8, st.a8, Mtot_c, I, H, F8_DU, F8_A, e->grd(PLB_FFN_W), s)
+         : weight_grad(e, st.du, I, I, st.a, H, Mtot_c, I, H, e->grd(PLB_FFN_W), s)) return 1;
+  if (ov && reduce_pieces(e, kPieceFfnW, kPieceSmall, s)) return 1;
   if (ov) {
     // The small tensors between the weights in the flat order (embeddings + map-in + LayerNorm 2 | Q/K/V biases | dense.bias +
     // LayerNorm 1 | ffn.bias | ffn_output.bias) all come from the side stream, which is done after about three of the four
@@ -1761,21 +1812,16 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, bf16_t
     // GEMMs it runs beside, ends between GEMM 2 and GEMM 3: piece_trace) — five latency-bound all-reduces that
     // travel beside the remaining GEMMs instead of after the last one (they were the step's exposed tail at world > 1:
     // four collectives in a row behind the join). The main stream joins the side stream at the end of the tail as before.
-    const int64_t* o = e->poff;
-    if (reduce_piece(e, 0, o[PLB_Q_W], s2)) return 1;
-    if (reduce_piece(e, o[PLB_Q_B], o[PLB_DENSE_W], s2)) return 1;
-    if (reduce_piece(e, o[PLB_DENSE_B], o[PLB_FFN_W], s2)) return 1;
-    if (reduce_piece(e, o[PLB_FFN_B], o[PLB_FFNO_W], s2)) return 1;
-    if (reduce_piece(e, o[PLB_FFNO_B], o[PLB_HEAD_W], s2)) return 1;
+    if (reduce_pieces(e, kPieceSmall, kPieceFfnoW, s2)) return 1;
   }
   HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_FFNO_W), (int64_t)I * H * 4, "ffn_output.weight gradient");
-  if (t8 ? weight_grad8(e, e->at<uint8_t>(e->o_dp8), e->at<uint8_t>(e->o_g8), Mtot_c, H, I, F8_DP, F8_G, e->grd(PLB_FFNO_W), s)
-         : weight_grad(e, e->at<bf16_t>(e->o_dpre2), H, H, e->at<bf16_t>(e->o_g), I, Mtot_c, H, I, e->grd(PLB_FFNO_W), s)) return 1;
-  if (ov && reduce_piece(e, e->poff[PLB_FFNO_W], e->poff[PLB_FFNO_B], s)) return 1;
+  if (t8 ? weight_grad8(e, st.dp8, st.g8, Mtot_c, H, I, F8_DP, F8_G, e->grd(PLB_FFNO_W), s)
+         : weight_grad(e, st.dpre2, H, H, st.g, I, Mtot_c, H, I, e->grd(PLB_FFNO_W), s)) return 1;
+  if (ov && reduce_pieces(e, kPieceFfnoW, kPieceDenseW, s)) return 1;
   HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_DENSE_W), (int64_t)H * H * 4, "dense.weight gradient");
-  if (t8 ? weight_grad8(e, e->at<uint8_t>(e->o_dp18), e->at<uint8_t>(e->o_c8), Mtot_c, H, H, F8_DP1, F8_C, e->grd(PLB_DENSE_W), s)
-         : weight_grad(e, e->at<bf16_t>(e->o_dpre1), H, H, e->at<bf16_t>(e->o_ctx), H, Mtot_c, H, H, e->grd(PLB_DENSE_W), s)) return 1;
-  if (ov && reduce_piece(e, e->poff[PLB_DENSE_W], e->poff[PLB_DENSE_B], s)) return 1;   // the smallest weight goes last
+  if (t8 ? weight_grad8(e, st.dp18, st.c8, Mtot_c, H, H, F8_DP1, F8_C, e->grd(PLB_DENSE_W), s)
+         : weight_grad(e, st.dpre1, H, H, st.ctx, H, Mtot_c, H, H, e->grd(PLB_DENSE_W), s)) return 1;
+  if (ov && reduce_pieces(e, kPieceDenseW, kNPieces, s)) return 1;   // the smallest weight goes last
   return 0;
 }
 
