@@ -231,6 +231,45 @@ int plb_status_import(PlbEngine* e, const float* summed, void* stream);
  * (padded to 128), of = the call's padded token count (rows == of: every row — a dual-head call, an fp8 call, more than
  * half of the positions masked, or PLBERT_PRUNE_LAST=0). */
 int plb_last_application_rows(const PlbEngine* e, int64_t* rows, int64_t* of);
+/* ---- token-packed execution of ragged batches (opt-in) ----
+ * The reference collater zero-pads every sample to the batch maximum (dataloader.py:276-297) and the loss slices the pads
+ * away again (train.py:107-131); a padded call of B x S runs every projection, FFN, LayerNorm and weight-gradient row for the
+ * pads too. A packed call runs on a dense token axis instead: sample b owns rows [row_start[b], row_start[b] + lengths[b])
+ * of every activation buffer, in a slot of ceil(lengths[b] / 128) * 128 rows (the attention kernels' row tile: a sample's
+ * tiles are those of the padded call). ids / labels / index lists / outputs keep the padded [B,S] layout of the caller.
+ * plb_packing_plan (host only, no device access): lengths int32 [B] on the HOST -> row_start int32 [B+1] (host; the caller
+ *   copies it to the device with the batch), *used = row_start[B] = rows covered by the slots, *rows = the rows the call
+ *   executes = used rounded up to the coarsest of 1024 (LayerNorm in the GEMM epilogues) / 256 (gelu' stash) / 128 that
+ *   still leaves fewer rows than the padded call's ceil128(B*S). When nothing is saved (every length == S, or the slots
+ *   alone reach ceil128(B*S)) the plan is the padded layout itself: row_start[b] = b*S, rows = ceil128(B*S).
+ * The *_packed entry points are their namesakes with a plan (packing == NULL or packing->row_start == NULL: exactly the
+ * namesake). row_start is a DEVICE pointer; a plan must come from plb_packing_plan for the same lengths, B and S (the
+ * engine checks what it can see on the host: rows, used). Nothing in a packed call synchronises with the host: for a fixed
+ * plan it is graph-capturable like the padded call. Same results as the padded call up to bf16 summation order in the
+ * weight gradients (each valid row's arithmetic is unchanged). A call runs PADDED, with the padded call's results bit for
+ * bit, when the plan is the padded layout, when lengths == NULL, for dual-head calls (token_ids / token_logits given) and
+ * while fp8 mode is on. plb_forward_packed: hidden / phoneme_logits at pad positions (s >= lengths[b]) are ZEROS (the padded
+ * path leaves values there that nothing reads). plb_pooler takes the [B,S,H] output as before.
+ * Rows of the packed axis that hold no token are given defined values in every call (zeros from the embeddings, computed
+ * like padded rows inside a slot, a zeroed attention output and zero gradients in the tail), so a packed call does not
+ * depend on what an earlier call left in the workspace.
+ * plb_last_call_rows: rows = token rows the last plb_forward / plb_loss_* call executed, of = the B*S it stood for
+ * (rows == of: the call ran padded). */
+typedef struct {
+  const int32_t* row_start;   /* device, int32 [B+1], from plb_packing_plan */
+  int32_t rows;               /* rows the call executes (plb_packing_plan's *rows) */
+  int32_t used;               /* rows covered by the samples' slots (plb_packing_plan's *used) */
+} PlbPacking;
+int plb_packing_plan(const int32_t* lengths, int32_t B, int32_t S, int32_t* row_start, int32_t* rows, int32_t* used);
+int plb_forward_packed(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                       const PlbPacking* packing, float* hidden, float* phoneme_logits, float* token_logits, void* stream);
+int plb_loss_fwd_bwd_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int32_t* lengths,
+                            const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked, int32_t B, int32_t S,
+                            const PlbPacking* packing, float* loss, void* stream);
+int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int64_t* token_ids,
+                        const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked,
+                        int32_t B, int32_t S, const PlbPacking* packing, float* loss, float* loss_parts, void* stream);
+int plb_last_call_rows(const PlbEngine* e, int64_t* rows, int64_t* of);
 /* What the last training step exchanged: the number of collectives it issued (10 pieces for the reference's phoneme-only
  * step with overlap on, 1 with overlap off; one more after a dual-head step) and the floats they covered. The reference
  * has no counterpart (DDP's bucket count is internal to torch, train.py:218-221); a caller logs it to see which form of

@@ -54,7 +54,8 @@ PUBLIC_SYMBOLS = [
     "plb_last_error", "plb_create", "plb_destroy", "plb_param_layout", "plb_workspace_bytes", "plb_bind",
     "plb_sync_weights", "plb_forward", "plb_pooler", "plb_loss_fwd_bwd", "plb_loss_fwd", "plb_loss_fwd_bwd_dual", "plb_adamw_step",
     "plb_set_fp8", "plb_fp8_state", "plb_fp8_stats", "plb_token_head_steps", "plb_set_token_head_steps", "plb_comm_unique_id", "plb_comm_init", "plb_comm_destroy",
-    "plb_comm_info", "plb_comm_pieces", "plb_last_application_rows", "plb_status", "plb_status_ex", "plb_poll_status", "plb_status_export", "plb_status_import", "plb_broadcast_params", "plb_set_grad_overlap", "plb_allreduce_grads", "plb_apply_mask",
+    "plb_comm_info", "plb_comm_pieces", "plb_last_application_rows", "plb_last_call_rows",
+    "plb_packing_plan", "plb_forward_packed", "plb_loss_fwd_bwd_packed", "plb_loss_fwd_packed", "plb_status", "plb_status_ex", "plb_poll_status", "plb_status_export", "plb_status_import", "plb_broadcast_params", "plb_set_grad_overlap", "plb_allreduce_grads", "plb_apply_mask",
     "plb_mask_batch", "plb_profile_enable", "plb_profile_num_classes", "plb_profile_class_name", "plb_profile_read",
     # test / tuning hooks (documented as such at the end of the header)
     "plb_debug_skip_piece", "plb_debug_ln_fault", "plb_debug_hb_audit", "plb_debug_hb_report", "plb_comm_trace", "plb_comm_trace_read",
@@ -108,6 +109,7 @@ class PlbAttn(C.Structure):
         ("dqkv8", C.c_void_p), ("lddqkv8", C.c_int), ("dqkv_scale", C.c_void_p), ("dqkv_amax", C.c_void_p),
         ("qoff", C.c_void_p), ("q", C.c_void_p), ("ldq", C.c_int), ("nq_total", C.c_int), ("dq", C.c_void_p), ("lddq", C.c_int),
         ("dq8", C.c_void_p), ("lddq8", C.c_int),
+        ("row_start", C.c_void_p),
     ]
 
 
@@ -117,7 +119,13 @@ class PlbEmbed(C.Structure):
         ("word", C.c_void_p), ("pos", C.c_void_p), ("type0", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
         ("eps", C.c_float), ("out", C.c_void_p), ("ldo", C.c_int), ("dout", C.c_void_p), ("lddo", C.c_int),
         ("dx", C.c_void_p), ("dword", C.c_void_p), ("dpos", C.c_void_p), ("partials", C.c_void_p), ("nblocks", C.c_int),
+        ("row_start", C.c_void_p), ("lengths", C.c_void_p), ("B", C.c_int),
     ]
+
+
+class PlbPacking(C.Structure):
+    """include/plbert.h: the plan of a token-packed call (row_start: device int32 [B+1])."""
+    _fields_ = [("row_start", C.c_void_p), ("rows", C.c_int32), ("used", C.c_int32)]
 
 
 class PlbLayerNorm(C.Structure):
@@ -202,6 +210,22 @@ def lib():
     L.plb_fp8_stats.argtypes = [vp, C.POINTER(f32), C.POINTER(f32), vp]
     L.plb_last_application_rows.restype = C.c_int
     L.plb_last_application_rows.argtypes = [vp, i64p, i64p]
+    if hasattr(L, "plb_packing_plan"):   # (PLBERT_HIP_LIB may name an A/B build that predates token-packed execution)
+        pk = C.POINTER(PlbPacking)
+        L.plb_last_call_rows.restype = C.c_int
+        L.plb_last_call_rows.argtypes = [vp, i64p, i64p]
+        L.plb_packing_plan.restype = C.c_int
+        L.plb_packing_plan.argtypes = [vp, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
+        L.plb_forward_packed.restype = C.c_int
+        L.plb_forward_packed.argtypes = [vp, vp, vp, i32, i32, pk, vp, vp, vp, vp]
+        L.plb_loss_fwd_bwd_packed.restype = C.c_int
+        L.plb_loss_fwd_bwd_packed.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, pk, vp, vp]
+        L.plb_loss_fwd_packed.restype = C.c_int
+        L.plb_loss_fwd_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, pk, vp, vp, vp]
+        L.plb_launch_ce_prepare_packed.restype = C.c_int
+        L.plb_launch_ce_prepare_packed.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+        L.plb_launch_unpack_rows.restype = C.c_int
+        L.plb_launch_unpack_rows.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.plb_status_export.restype = C.c_int
     L.plb_status_export.argtypes = [vp, vp, vp]
     L.plb_status_import.restype = C.c_int
@@ -281,6 +305,8 @@ def lib():
     L.plb_launch_ln_bwd.argtypes = [C.POINTER(PlbLayerNorm), vp]
     L.plb_launch_embed_scatter.restype = C.c_int
     L.plb_launch_embed_scatter.argtypes = [C.POINTER(PlbEmbed), C.c_int, vp]
+    L.plb_launch_ce_prepare.restype = C.c_int
+    L.plb_launch_ce_prepare.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.plb_launch_colsum.restype = C.c_int
     L.plb_launch_colsum.argtypes = [vp, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]
     _lib = L

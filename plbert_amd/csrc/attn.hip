@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256, FWD_WAVES) void attn_fwd_kernel(PlbAttn p) {
   int len = p.lengths ? p.lengths[b] : S;
   len = len < 1 ? 1 : (len > S ? S : len);
   const int q0 = bx * 128 + wave * 32;
-  const size_t tok0 = (size_t)b * S;
+  const size_t tok0 = p.row_start ? (size_t)p.row_start[b] : (size_t)b * S;   // (token-packed rows: PlbAttn.row_start)
   const bf16_t* kbase = p.qkv + H + hd * 64;
   const bf16_t* vbase = p.qkv + 2 * H + hd * 64;
   const int ld = p.ldqkv;
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256, FWD_WAVES) void attn_fwd_kernel(PlbAttn p) {
   const bool cq = p.qoff != nullptr;
   const int qlo = cq ? p.qoff[b] : 0;
   const int Sq = cq ? p.qoff[b + 1] - qlo : S;
-  if (bx * 128 >= Sq) return;   // (wave-uniform, before any barrier: a q tile without a query)
+  if (bx * 128 >= Sq || (p.row_start && bx * 128 >= len)) return;   // (wave-uniform, before any barrier: a q tile without a query)
   const size_t qrow0 = cq ? (size_t)qlo : tok0;   // first query row of the sample in q / ctx
   const int ldq = cq ? p.ldq : ld;
 
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(PlbAttn p) {
   int len = p.lengths ? p.lengths[b] : S;
   len = len < 1 ? 1 : (len > S ? S : len);
   const int q0 = bx * 128 + wave * 32;
-  const size_t tok0 = (size_t)b * S;
+  const size_t tok0 = p.row_start ? (size_t)p.row_start[b] : (size_t)b * S;   // (token-packed rows: PlbAttn.row_start)
   const bf16_t* kbase = p.qkv + H + hd * 64;
   const bf16_t* vbase = p.qkv + 2 * H + hd * 64;
   const int ld = p.ldqkv;
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(PlbAttn p) {
   const bool cq = p.qoff != nullptr;
   const int qlo = cq ? p.qoff[b] : 0;
   const int Sq = cq ? p.qoff[b + 1] - qlo : S;
-  if (bx * 128 >= Sq) {   // a q tile without a query (compact mode only): its bias-gradient partial rows are zeros
+  if (bx * 128 >= Sq || (p.row_start && bx * 128 >= len)) {   // a q tile without a query (compact mode, packed rows): its bias-gradient partial rows are zeros
     if (p.colpart && !p.colpart_accumulate) p.colpart[((size_t)(b * QT + bx) * 4 + wave) * (3 * H) + hd * 64 + lane] = 0.f;
     return;
   }
@@ -354,10 +354,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(PlbAttn p) {
   int len = p.lengths ? p.lengths[b] : S;
   len = len < 1 ? 1 : (len > S ? S : len);
   const int key0 = bx * 128 + wave * 32;
-  const size_t tok0 = (size_t)b * S;
+  const size_t tok0 = p.row_start ? (size_t)p.row_start[b] : (size_t)b * S;   // (token-packed rows: PlbAttn.row_start)
   const int ld = p.ldqkv, ldo = p.lddctx;
   const int lk = lane & 31, h = lane >> 5;
   const int mykey = key0 + lk;
+  if (p.row_start && bx * 128 >= len) {   // token-packed rows: the sample's slot ends before this key tile (nothing to store)
+    if (p.colpart && !p.colpart_accumulate) {
+      float* z = p.colpart + ((size_t)(b * QT + bx) * 4 + wave) * (3 * H) + hd * 64;
+      z[H + lane] = 0.f;
+      z[2 * H + lane] = 0.f;
+    }
+    return;
+  }
 
   bf16x8 kf[4], vf[4];
   {
@@ -539,6 +547,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(PlbAttn p) {
 
 static int check_attn(const PlbAttn* p) {
   if (p->H != p->NH * 64 || p->S < 1 || p->B < 1) return 1;
+  if (p->row_start && !p->lengths) return 1;   // token-packed rows are defined by the lengths
   if (p->ldqkv % 8 || p->ldctx % 8) return 1;
   return 0;
 }
@@ -597,6 +606,10 @@ static PlbAttn attn_samples(const PlbAttn* p, int b0, int nb) {
   q.lse = p->lse + (size_t)b0 * p->NH * p->S;
   if (p->delta) q.delta = p->delta + (size_t)b0 * p->NH * p->S;
   if (p->colpart) q.colpart = p->colpart + (size_t)b0 * ((p->S + 127) / 128) * 4 * (3 * p->H);
+  if (p->row_start) {   // token-packed rows: the table holds absolute rows, so the row pointers stay where they are
+    q.row_start = p->row_start + b0;
+    q.qkv = p->qkv; q.ctx = p->ctx; q.dctx = p->dctx; q.dqkv = p->dqkv; q.dqkv8 = p->dqkv8;
+  }
   return q;
 }
 

@@ -69,15 +69,18 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused_kernel(PlbAttn p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hd = blockIdx.x % p.NH, b = blockIdx.x / p.NH;
-  const int S = p.S, H = p.H;
-  int len = p.lengths ? p.lengths[b] : S;
-  len = len < 1 ? 1 : (len > S ? S : len);
-  const size_t tok0 = (size_t)b * S;
+  const int Sfull = p.S, H = p.H;
+  int len = p.lengths ? p.lengths[b] : Sfull;
+  len = len < 1 ? 1 : (len > Sfull ? Sfull : len);
+  // token-packed rows (PlbAttn.row_start): the sample owns ceil(len / 128) * 128 rows from row_start[b]; every row index
+  // below is clamped to that extent instead of S (rows past the length only ever meet P = 0, as in the padded call)
+  const int S = p.row_start ? min(Sfull, (len + 127) & ~127) : Sfull;
+  const size_t tok0 = p.row_start ? (size_t)p.row_start[b] : (size_t)b * Sfull;
   const int ld = p.ldqkv, ldo = p.lddctx;
   const int lk = lane & 31, h = lane >> 5;
   const float sl2 = p.scale * LOG2E;
   const uint32_t lds_base = LDS_ADDR(smem);
-  const int QT = (S + 127) >> 7;
+  const int QT = (Sfull + 127) >> 7;
 
   // ---- K image: wave w fills the rows of its own keys (every row below 32*ceil(len/32) is read by the dQ phase; rows past
   // S repeat row S-1: finite values that only ever meet dS = 0)
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused_kernel(PlbAttn p) {
   // (wave-uniform bases + 32-bit lane offsets: one address register per load instead of a 64-bit pointer per tensor)
   const bf16_t* const g_do = p.dctx + hd * 64 + tok0 * ldo;
   const bf16_t* const g_o = p.ctx + hd * 64 + tok0 * p.ldctx;
-  const float* const g_lse = p.lse + ((size_t)b * p.NH + hd) * S;
+  const float* const g_lse = p.lse + ((size_t)b * p.NH + hd) * Sfull;
   uint4 sv_do, sv_o;
   float sv_lse = 0.f;
 #define F_STAT_LOAD(qb_)                                                                              \
@@ -496,6 +499,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused_kernel(PlbAttn p) {
 // S <= 512: the single-kernel form. p->delta is not written (the kernel keeps delta in LDS).
 extern "C" int plb_launch_attn_bwd_fused(const PlbAttn* p, hipStream_t stream) {
   if (p->H != p->NH * 64 || p->S < 1 || p->S > 512 || p->B < 1) return 1;
+  if (p->row_start && !p->lengths) return 1;
   if (p->ldqkv % 8 || p->ldctx % 8 || p->lddctx % 8 || p->lddqkv % 8) return 1;
   if ((!p->dqkv && !p->dqkv8) || (p->dqkv8 && (!p->dqkv_scale || p->lddqkv8 % 8))) return 1;
   dim3 grid(p->NH * p->B), block(256);

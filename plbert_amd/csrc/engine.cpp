@@ -260,7 +260,8 @@ struct PlbEngine {
   // states reaches the loss, so behind the attention of application L-1 only those rows are computed): decided by the
   // forward of a call, read by its backward. pruned_rows = the compact row count (a multiple of 128), 0 = the call was full.
   int pruned_rows = 0;
-  int64_t last_call_rows[2] = {0, 0};   // token rows the last loss call ran the post-attention part of its last application on | of
+  int64_t last_app_rows[2] = {0, 0};   // token rows the last loss call ran the post-attention part of its last application on | of
+  int64_t last_exec_rows[2] = {0, 0};   // token rows the last forward / loss call executed | the B*S it stood for (plb_last_call_rows)
   int tok_steps = 0;            // AdamW steps the token head has taken (its own bias correction)
   // data-parallel exchange (plb_comm_*): RCCL communicator, its stream, and the join event of the pieces in flight
   RcclComm comm = nullptr;
@@ -773,6 +774,33 @@ static int check_shape(const PlbEngine* e, int B, int S, const char* who) {
   return 0;
 }
 
+// ---- token-packed calls (include/plbert.h: PlbPacking) ------------------------------------------------------------------
+// The rows of one call. Padded: sample b at rows b*S.., T = B*S real rows, Tp = T rounded up to 128. Packed: sample b at
+// rows row_start[b].. (128-aligned slots holding its valid tokens only), T = the rows the slots cover, Tp = the plan's row
+// count. Everything between the embeddings and the loss rows sees only T and Tp; rows [T, Tp) are the tail the padded path
+// has always had when B*S is no multiple of 128 (no attention workgroup writes them, their gradients are kept at zero).
+struct Rows {
+  const int32_t* row_start;   // device, or null: padded
+  int T; int64_t Tp;
+};
+static Rows padded_rows(int B, int S) { return Rows{nullptr, B * S, rup(B * S, 128)}; }
+// Does this call run packed? It runs padded — same results as without a plan — when the plan saves nothing (every
+// sample full, or slots that add up to the padded rows), for dual-head calls and while fp8 mode is on.
+static int pick_rows(PlbEngine* e, const PlbPacking* pk, const int32_t* lengths, bool dual, int B, int S, const char* who,
+                     Rows* out) {
+  *out = padded_rows(B, S);
+  e->last_exec_rows[0] = e->last_exec_rows[1] = (int64_t)B * S;
+  if (!pk || !pk->row_start) return 0;
+  if (pk->rows < 128 || pk->rows % 128 || pk->used < 1 || pk->used > pk->rows)
+    return fail("%s: packing plan of %d rows (%d used) is not one plb_packing_plan made", who, pk->rows, pk->used);
+  if (pk->rows > out->Tp) return fail("%s: packing plan of %d rows exceeds the call's %lld", who, pk->rows, (long long)out->Tp);
+  if (!lengths || dual || e->fp8_on || pk->rows == out->Tp) return 0;   // (rows == Tp: the plan is the padded layout)
+  if (pk->used % 128) return fail("%s: packing plan with %d used rows: slots are multiples of 128", who, pk->used);
+  *out = Rows{pk->row_start, pk->used, pk->rows};
+  e->last_exec_rows[0] = pk->rows;
+  return 0;
+}
+
 // ---- launch descriptors -----------------------------------------------------------------------------------------------
 // C[M, N] = A[M, K] · B[N, K]^T on packed operands (lda = ldb = K), every row stored: the callers add bias, residual and
 // outputs
@@ -1033,11 +1061,11 @@ static int last_application_fwd_pruned(PlbEngine* e, const Prune* pr, bool stash
   return 0;
 }
 
-static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B, int S, bool stash, bf16_t** xout,
-                       hipStream_t s, const Prune* pr = nullptr) {
+static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B, int S, const Rows& rw, bool stash,
+                       bf16_t** xout, hipStream_t s, const Prune* pr = nullptr) {
   const int E = e->E, H = e->H, I = e->I, L = e->L;
-  const int T = B * S;
-  const int64_t Tp = rup(T, 128);
+  const int T = rw.T;
+  const int64_t Tp = rw.Tp;
   const bool f8 = f8_call(e, Tp, stash);
   const bool calib = e->fp8_on && !f8;
   if (e->fp8_on && e->fp8_wstale) TRY(fp8_quantize_weights(e, s));
@@ -1047,6 +1075,9 @@ static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
   em.word = e->par(PLB_WORD_EMB); em.pos = e->par(PLB_POS_EMB); em.type0 = e->par(PLB_TYPE_EMB);
   em.gamma = e->par(PLB_EMB_LN_W); em.beta = e->par(PLB_EMB_LN_B); em.eps = e->c.layer_norm_eps;
   em.out = e->at<bf16_t>(e->o_e); em.ldo = E;
+  if (rw.row_start) {   // packed: every row of the call gets a value (zeros where no token sits), the tail included
+    em.row_start = rw.row_start; em.lengths = lengths; em.B = B; em.T = (int)Tp;
+  }
   TRY(plb_launch_embed_fwd(&em, s));
 
   const Slots first = slots(e, Tp, B, S, 0, stash);
@@ -1079,6 +1110,7 @@ static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
     PlbAttn at;
     memset(&at, 0, sizeof(at));
     at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H;
+    at.row_start = rw.row_start;
     // pruned last application: the attention output of ALL rows goes to a buffer of its own (training: a backward temporary
     // that the attention backward of this application reads again — its slot holds the compact rows), then only the masked
     // rows continue
@@ -1088,6 +1120,9 @@ static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
     // (pruned: nobody reads the context's image of all rows — the compact rows' image is made with the others, below)
     if (f8 && !pruned_layer) { at.ctx8 = sl.c8; at.ldctx8 = H; at.ctx_scale = sC.scale; at.ctx_amax = sC.amax; }
     TRY(plb_launch_attn_fwd(&at, s));
+    // packed: the tail behind the last slot (up to 1,023 rows) is written by no attention workgroup, and what sits there
+    // goes through dense / LayerNorm / FFN into the stash the weight-gradient GEMMs read: zeros, not whatever was there
+    if (rw.row_start && Tp > T) HIPTRY(hipMemsetAsync(ctx_att + (int64_t)T * H, 0, (size_t)(Tp - T) * H * 2, s));
     if (calib) TRY(plb_launch_amax(ctx_att, 1, (size_t)T, H, H, sC.amax, s));
     if (pruned_layer) {
       if (last_application_fwd_pruned(e, pr, stash, calib, tn8, sl, ctx_att, s)) return 1;
@@ -1129,21 +1164,39 @@ static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
   return 0;
 }
 
-extern "C" int plb_forward(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, float* hidden,
-                           float* phoneme_logits, float* token_logits, void* stream) {
+static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                        const PlbPacking* pk, float* hidden, float* phoneme_logits, float* token_logits, void* stream) {
   if (check_shape(e, B, S, "plb_forward")) return 1;
   if (!ids) return fail("plb_forward: ids is null");
   if (token_logits && !e->NT) return fail("plb_forward: token_logits requested but num_tokens = 0");
   hipStream_t s = (hipStream_t)stream;
-  const int H = e->H, T = B * S;
-  const int64_t Tp = rup(T, 128);
+  const int H = e->H;
+  Rows rw;
+  // (token logits: the dual-head model runs padded. Phoneme logits of a packed call pass, as [Tp][NP] fp32, through a slot
+  // of the forward-only call that is free once the encoder is done: QKV (6H bytes per row) or the FFN's u (2I))
+  const int64_t lg_off = 4 * e->NP <= 6 * H ? e->o_qkv : 4 * e->NP <= 2 * e->I ? e->o_u : -1;
+  if (pick_rows(e, pk, lengths, token_logits != nullptr || lg_off < 0, B, S, "plb_forward", &rw)) return 1;
+  const int T = rw.T;
+  const int64_t Tp = rw.Tp;
   bf16_t* x = nullptr;
-  if (run_encoder(e, ids, lengths, B, S, false, &x, s)) return 1;
+  if (run_encoder(e, ids, lengths, B, S, rw, false, &x, s)) return 1;
+  if (rw.row_start) {
+    // back to the caller's [B,S,*] layout, zeros at the pad positions
+    if (hidden) TRY(plb_launch_unpack_rows(x, 1, H, rw.row_start, lengths, B, S, H, hidden, s));
+    if (phoneme_logits) {
+      float* lg = e->at<float>(lg_off);
+      PlbGemmNT g = nt_desc(x, e->wbf(PLB_HEAD_W), Tp, e->NP, H);
+      g.Mstore = T; g.bias = e->par(PLB_HEAD_B); g.Cf = lg; g.ldcf = e->NP;
+      TRY(plb_launch_gemm_nt(&g, 0, 1, s));
+      TRY(plb_launch_unpack_rows(lg, 0, e->NP, rw.row_start, lengths, B, S, e->NP, phoneme_logits, s));
+    }
+  } else {
   if (hidden) TRY(plb_launch_bf16_to_f32(x, H, hidden, H, T, H, s));
   if (phoneme_logits) {
     PlbGemmNT g = nt_desc(x, e->wbf(PLB_HEAD_W), Tp, e->NP, H);
     g.Mstore = T; g.bias = e->par(PLB_HEAD_B); g.Cf = phoneme_logits; g.ldcf = e->NP;
     TRY(plb_launch_gemm_nt(&g, 0, 1, s));
+  }
   }
   if (token_logits) {
     PlbGemmNT g = nt_desc(x, e->wbf(PLB_TOK_W), Tp, e->NT, H);
@@ -1156,6 +1209,15 @@ extern "C" int plb_forward(PlbEngine* e, const int64_t* ids, const int32_t* leng
   }
   TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), nullptr, e->host_err_dev, nullptr, s));
   return 0;
+}
+extern "C" int plb_forward(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, float* hidden,
+                           float* phoneme_logits, float* token_logits, void* stream) {
+  return forward_impl(e, ids, lengths, B, S, nullptr, hidden, phoneme_logits, token_logits, stream);
+}
+extern "C" int plb_forward_packed(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                                  const PlbPacking* packing, float* hidden, float* phoneme_logits, float* token_logits,
+                                  void* stream) {
+  return forward_impl(e, ids, lengths, B, S, packing, hidden, phoneme_logits, token_logits, stream);
 }
 
 extern "C" int plb_pooler(PlbEngine* e, const float* hidden, int32_t B, int32_t S, float* pooled, void* stream) {
@@ -1210,7 +1272,8 @@ static bool tn8_ok(const PlbEngine* e, int64_t Mtot) {
   return Mtot % 128 == 0 && e->H % 256 == 0 && e->I % 256 == 0 && Mtot >= 8192;
 }
 
-static int backward_tail(PlbEngine* e, const int64_t* masked_ids, bf16_t* dy, int B, int S, int du_rows, hipStream_t s);
+static int backward_tail(PlbEngine* e, const int64_t* masked_ids, const int32_t* lengths, bf16_t* dy, int B, int S,
+                         const Rows& rw, int du_rows, hipStream_t s);
 
 // ---- gradient exchange pieces ---------------------------------------------------------------------------------
 // One sum all-reduce of grads[a, b) on the communication stream, ordered after everything enqueued on `after` so far.
@@ -1476,6 +1539,7 @@ static int token_head(PlbEngine* e, bool backward, const bf16_t* xL, const int64
 // What the backward stages of one call share: its shape, its precision mode, the partial-row layout of its layer loop.
 struct Bwd {
   const int32_t* lengths;
+  const int32_t* row_start;   // token-packed call (Rows), or null
   int B, S, T;
   int64_t Tp;
   bool f8, calib;   // fp8 operands | an fp8-mode call that only records the maxima
@@ -1579,6 +1643,7 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
   PlbAttn at;
   memset(&at, 0, sizeof(at));
   at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = c.lengths; at.B = c.B; at.S = c.S; at.NH = e->NH; at.H = H; at.scale = 0.125f;
+  at.row_start = c.row_start;
   at.ctx = ctx; at.ldctx = H; at.lse = sl.lse;
   at.dctx = e->at<bf16_t>(e->o_dctx); at.lddctx = H; at.delta = e->at<float>(e->o_delta); at.dqkv = sl.dqkv; at.lddqkv = 3 * H;
   at.colpart = sl.qkvcol; at.colpart_accumulate = 0;
@@ -1610,11 +1675,11 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
 // backward), dCtx = dpre1·Wd, dX = dQKV·Wqkv (+ LayerNorm 2 backward of the layer below) — written by the launch that
 // produces the gradient (fused LayerNorm-backward / gelu-backward epilogues, the attention-backward kernels, the
 // standalone LayerNorm backward), one image per layer for the weight-gradient GEMMs at the end.
-static int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, int S, bf16_t** dy, int* du_rows,
-                       hipStream_t s) {
+static int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, int S, const Rows& rw, bf16_t** dy,
+                       int* du_rows, hipStream_t s) {
   const int I = e->I, L = e->L;
   Bwd c;
-  c.lengths = lengths; c.B = B; c.S = S; c.T = B * S; c.Tp = rup(c.T, 128); c.s = s;
+  c.lengths = lengths; c.row_start = rw.row_start; c.B = B; c.S = S; c.T = rw.T; c.Tp = rw.Tp; c.s = s;
   const int Tp = (int)c.Tp;
   c.f8 = f8_call(e, Tp, true);
   c.calib = e->fp8_on && !c.f8;
@@ -1648,8 +1713,8 @@ static int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, in
 // backward == false: validate() — forward and loss only, one layer of activations, the gradient buffer untouched.
 static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, const int64_t* labels,
                      const int64_t* token_targets, const int32_t* lengths, const int32_t* idx_offsets,
-                     const int32_t* idx_flat, int32_t n_masked, int32_t B, int32_t S, float* loss, float* loss_parts,
-                     void* stream) {
+                     const int32_t* idx_flat, int32_t n_masked, int32_t B, int32_t S, const PlbPacking* pk, float* loss,
+                     float* loss_parts, void* stream) {
   const char* who = backward ? "plb_loss_fwd_bwd" : "plb_loss_fwd";
   if (check_shape(e, B, S, who)) return 1;
   if (backward && e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1)", who);
@@ -1658,7 +1723,9 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   if (n_masked < 0 || n_masked > e->NMcap) return fail("%s: n_masked %d out of range", who, n_masked);
   if (token_targets && !e->NT) return fail("%s: the engine has no token head (num_tokens = 0)", who);
   hipStream_t s = (hipStream_t)stream;
-  const int64_t Tp = rup(B * S, 128);
+  Rows rw;
+  if (pick_rows(e, pk, lengths, token_targets != nullptr, B, S, who, &rw)) return 1;
+  const int64_t Tp = rw.Tp;
   if (backward && begin_training_call(e, token_targets != nullptr, s)) return 1;
   if (n_masked == 0 && !token_targets) return zero_loss_call(e, backward, loss, s);
 
@@ -1667,13 +1734,18 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   const int NM = (int)rup(n_masked, 128);
   Prune pr = {e->at<int32_t>(e->o_rows), n_masked, NM};
   const bool prune = prune_enabled() && n_masked > 0 && !token_targets && e->L >= 2 && 2 * (int64_t)NM <= Tp;
-  if (n_masked > 0)
-    TRY(plb_launch_ce_prepare(idx_offsets, idx_flat, labels, B, S, e->at<int32_t>(e->o_rows), e->at<int32_t>(e->o_tgt),
-                              e->at<float>(e->o_w), s));
+  if (n_masked > 0) {
+    if (rw.row_start)
+      TRY(plb_launch_ce_prepare_packed(idx_offsets, idx_flat, labels, B, S, rw.row_start, e->at<int32_t>(e->o_rows),
+                                       e->at<int32_t>(e->o_tgt), e->at<float>(e->o_w), s));
+    else
+      TRY(plb_launch_ce_prepare(idx_offsets, idx_flat, labels, B, S, e->at<int32_t>(e->o_rows), e->at<int32_t>(e->o_tgt),
+                                e->at<float>(e->o_w), s));
+  }
   if (backward) e->pruned_rows = prune ? NM : 0;
-  e->last_call_rows[0] = prune ? NM : Tp; e->last_call_rows[1] = Tp;
+  e->last_app_rows[0] = prune ? NM : Tp; e->last_app_rows[1] = Tp;
   bf16_t* xL = nullptr;
-  if (run_encoder(e, masked_ids, lengths, B, S, backward, &xL, s, prune ? &pr : nullptr)) return 1;
+  if (run_encoder(e, masked_ids, lengths, B, S, rw, backward, &xL, s, prune ? &pr : nullptr)) return 1;
   bf16_t* dy = backward ? e->at<bf16_t>(e->o_dy0) : nullptr;
   if (phoneme_head(e, backward, prune, xL, n_masked, Tp, dy, loss, s)) return 1;
   if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts, loss, sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1691,10 +1763,10 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   }
 
   int du_rows = 0;
-  if (encoder_bwd(e, prune ? &pr : nullptr, lengths, B, S, &dy, &du_rows, s)) return 1;
+  if (encoder_bwd(e, prune ? &pr : nullptr, lengths, B, S, rw, &dy, &du_rows, s)) return 1;
   // the last launch that can raise the hand-off error word is behind us: the word travels now (beside the tail)
   if (status_exchange(e, s)) return 1;
-  if (backward_tail(e, masked_ids, dy, B, S, du_rows, s)) return 1;
+  if (backward_tail(e, masked_ids, lengths, dy, B, S, rw, du_rows, s)) return 1;
   if (e->fp8_on) {
     // This call's maxima become the next call's scales; a calibration call arms the fp8 path. AFTER the tail: the weight-
     // gradient GEMMs dequantise this call's images with the scales they were written with (updated before the tail, a
@@ -1716,11 +1788,11 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
 //  side: everything else that only needs finished gradients — embedding chain, bias and LayerNorm-affine column sums
 //        (HBM-bound) — with its own slab / scratch so nothing is shared; joined before the first piece that holds
 //        any of its outputs.
-static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, bf16_t* dy, int B, int S, int du_rows,
-                                 hipStream_t s, hipStream_t s2, float* scratch2) {
+static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const int32_t* lengths, bf16_t* dy, int B, int S,
+                                 const Rows& rw, int du_rows, hipStream_t s, hipStream_t s2, float* scratch2) {
   const int E = e->E, H = e->H, I = e->I, L = e->L;
-  const int T = B * S;
-  const int64_t Tp = rup(T, 128);
+  const int T = rw.T;
+  const int64_t Tp = rw.Tp;
   const int64_t Mtot = (int64_t)L * Tp;
   // stacked rows of the operands whose last application ran on its masked rows only (ffn.weight, ffn_output.weight,
   // dense.weight: their slots of application L-1 hold Mc compact rows); the Q/K/V weights' operands are always full
@@ -1754,6 +1826,7 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, bf16_t
   em.dout = de; em.lddo = E; em.dword = e->grd(PLB_WORD_EMB); em.dpos = e->grd(PLB_POS_EMB);
   em.dx = e->at<float>(e->o_dxe);
   em.partials = e->at<float>(e->o_parte); em.nblocks = e->emb_blocks;
+  if (rw.row_start) { em.row_start = rw.row_start; em.lengths = lengths; em.B = B; }
   HB_W(s2, em.dx, Tp * E * 4, "embedding LayerNorm backward rows"); HB_W(s2, em.partials, (int64_t)e->emb_blocks * 2 * E * 4, "embedding LayerNorm partials");
   HB_W(s2, e->grd(PLB_WORD_EMB), (e->poff[PLB_MAP_W] - e->poff[PLB_WORD_EMB]) * 4, "embedding tables' and embedding LayerNorm's gradients");
   TRY(plb_launch_embed_bwd(&em, s2));
@@ -1825,7 +1898,8 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, bf16_t
   return 0;
 }
 
-static int backward_tail(PlbEngine* e, const int64_t* masked_ids, bf16_t* dy, int B, int S, int du_rows, hipStream_t s) {
+static int backward_tail(PlbEngine* e, const int64_t* masked_ids, const int32_t* lengths, bf16_t* dy, int B, int S,
+                         const Rows& rw, int du_rows, hipStream_t s) {
   hipStream_t s2 = s;
   float* scratch2 = e->at<float>(e->o_scratch);
   // the layer loop (all of it on the caller's stream) has written the stash, the partial-row tables, dX: one entry
@@ -1837,7 +1911,7 @@ static int backward_tail(PlbEngine* e, const int64_t* masked_ids, bf16_t* dy, in
     HIPTRY(ev_record(e, e->ev_fork, s));
     HIPTRY(ev_wait(e, s2, e->ev_fork));
   }
-  const int rc = backward_tail_streams(e, masked_ids, dy, B, S, du_rows, s, s2, scratch2);
+  const int rc = backward_tail_streams(e, masked_ids, lengths, dy, B, S, rw, du_rows, s, s2, scratch2);
   // Whatever happened above, the caller's stream must not run ahead of the side stream's work (also on an error
   // path: the side stream may hold launches that read buffers the caller is about to reuse).
   if (s2 != s) {
@@ -1855,7 +1929,14 @@ static int backward_tail(PlbEngine* e, const int64_t* masked_ids, bf16_t* dy, in
 extern "C" int plb_loss_fwd_bwd(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int32_t* lengths,
                                 const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked, int32_t B,
                                 int32_t S, float* loss, void* stream) {
-  return loss_impl(e, true, masked_ids, labels, nullptr, lengths, idx_offsets, idx_flat, n_masked, B, S, loss, nullptr, stream);
+  return loss_impl(e, true, masked_ids, labels, nullptr, lengths, idx_offsets, idx_flat, n_masked, B, S, nullptr, loss, nullptr,
+                   stream);
+}
+extern "C" int plb_loss_fwd_bwd_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int32_t* lengths,
+                                       const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked, int32_t B,
+                                       int32_t S, const PlbPacking* packing, float* loss, void* stream) {
+  return loss_impl(e, true, masked_ids, labels, nullptr, lengths, idx_offsets, idx_flat, n_masked, B, S, packing, loss, nullptr,
+                   stream);
 }
 
 extern "C" int plb_loss_fwd_bwd_dual(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels,
@@ -1863,15 +1944,59 @@ extern "C" int plb_loss_fwd_bwd_dual(PlbEngine* e, const int64_t* masked_ids, co
                                      const int32_t* idx_flat, int32_t n_masked, int32_t B, int32_t S, float* loss,
                                      float* loss_parts, void* stream) {
   if (!token_ids) return fail("plb_loss_fwd_bwd_dual: token_ids is null");
-  return loss_impl(e, true, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, loss, loss_parts,
-                   stream);
+  return loss_impl(e, true, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, nullptr, loss,
+                   loss_parts, stream);
 }
 
 extern "C" int plb_loss_fwd(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int64_t* token_ids,
                             const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked,
                             int32_t B, int32_t S, float* loss, float* loss_parts, void* stream) {
-  return loss_impl(e, false, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, loss, loss_parts,
-                   stream);
+  return loss_impl(e, false, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, nullptr, loss,
+                   loss_parts, stream);
+}
+extern "C" int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int64_t* token_ids,
+                                   const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat,
+                                   int32_t n_masked, int32_t B, int32_t S, const PlbPacking* packing, float* loss,
+                                   float* loss_parts, void* stream) {
+  return loss_impl(e, false, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, packing, loss,
+                   loss_parts, stream);
+}
+
+// The plan of a token-packed call, on the host (include/plbert.h). Slots start on multiples of 128 — the row tile of the
+// attention kernels, so a sample's tiles are those of the padded call — and the row count is rounded up to the coarsest of
+// 1024 (LayerNorm in the GEMM epilogues) / 256 (gelu' stash) / 128 that still leaves fewer rows than the padded call.
+#ifndef PLB_PACK_GRAN_MAX
+#define PLB_PACK_GRAN_MAX 1024   // A/B builds: 256 / 128 leave out the coarser roundings
+#endif
+extern "C" int plb_packing_plan(const int32_t* lengths, int32_t B, int32_t S, int32_t* row_start, int32_t* rows,
+                                int32_t* used) {
+  if (!lengths || !row_start || !rows || !used) return fail("plb_packing_plan: null argument");
+  if (B < 1 || S < 1 || (int64_t)B * S > (int64_t)1 << 30) return fail("plb_packing_plan: bad shape %d x %d", B, S);
+  const int64_t padded = rup((int64_t)B * S, 128);
+  int64_t at = 0;
+  bool full = true;
+  for (int b = 0; b < B; ++b) {
+    const int len = lengths[b] < 1 ? 1 : (lengths[b] > S ? S : lengths[b]);
+    full = full && len == S;
+    at += rup(len, 128);
+  }
+  const int64_t gran = (PLB_PACK_GRAN_MAX >= 1024 && rup(at, 1024) < padded) ? 1024
+                       : (PLB_PACK_GRAN_MAX >= 256 && rup(at, 256) < padded) ? 256 : 128;
+  if (full || rup(at, gran) >= padded) {   // nothing to gain: the plan IS the padded layout, the engine runs the padded path
+    for (int b = 0; b <= B; ++b) row_start[b] = b * S;
+    *rows = (int32_t)padded; *used = B * S;
+    return 0;
+  }
+  at = 0;
+  for (int b = 0; b < B; ++b) {
+    const int len = lengths[b] < 1 ? 1 : (lengths[b] > S ? S : lengths[b]);
+    row_start[b] = (int32_t)at;
+    at += rup(len, 128);
+  }
+  row_start[B] = (int32_t)at;
+  *used = (int32_t)at;
+  *rows = (int32_t)rup(at, gran);
+  return 0;
 }
 
 // ---- data-parallel exchange -------------------------------------------------------------------------------------
@@ -2026,8 +2151,15 @@ extern "C" int plb_comm_trace_read(PlbEngine* e, int32_t max_pieces, int32_t* n,
 
 extern "C" int plb_last_application_rows(const PlbEngine* e, int64_t* rows, int64_t* of) {
   if (!e) return fail("plb_last_application_rows: null engine");
-  if (rows) *rows = e->last_call_rows[0];
-  if (of) *of = e->last_call_rows[1];
+  if (rows) *rows = e->last_app_rows[0];
+  if (of) *of = e->last_app_rows[1];
+  return 0;
+}
+
+extern "C" int plb_last_call_rows(const PlbEngine* e, int64_t* rows, int64_t* of) {
+  if (!e) return fail("plb_last_call_rows: null engine");
+  if (rows) *rows = e->last_exec_rows[0];
+  if (of) *of = e->last_exec_rows[1];
   return 0;
 }
 

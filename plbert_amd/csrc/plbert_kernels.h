@@ -121,6 +121,11 @@ typedef struct {
   float *dword, *dpos;          // fp32 [V,E], [P,E]: written by embed_scatter (every row, no atomics)
   float* partials;              // [nblocks][2E] : dgamma | dbeta partial sums
   int nblocks;
+  // Token-packed rows (row_start != NULL; include/plbert.h PlbPacking): ids stays the padded [B,S] input, T counts PACKED
+  // rows and out / dout / dx are indexed by packed row: sample b's position s < lengths[b] is row row_start[b] + s, its
+  // position embedding is pos[s]. Rows that belong to no sample (the rest of a sample's 128-aligned slot, the tail behind
+  // row_start[B]) are written as zeros by the forward and the backward and add nothing to partials / dword / dpos.
+  const int32_t* row_start; const int32_t* lengths; int B;
 } PlbEmbed;
 int plb_launch_embed_fwd(const PlbEmbed* p, hipStream_t stream);
 int plb_launch_embed_bwd(const PlbEmbed* p, hipStream_t stream);  // grid = p->nblocks; writes dx + partials
@@ -203,6 +208,12 @@ typedef struct {
   // and dQ goes to dq ([Nq, lddq]; + its e5m2 image dq8 in fp8 mode) instead of dqkv's Q block; dqkv's K and V blocks
   // (and colpart, row (b * ceil(S/128) + q tile) * 4 + wave as always) are written as in the full form.
   const int32_t* qoff; const bf16_t* q; int ldq; int nq_total; bf16_t* dq; int lddq; uint8_t* dq8; int lddq8;
+  // Token-packed rows (row_start != NULL, [B] entries, multiples of 128; needs lengths): sample b's tokens are rows
+  // row_start[b].. of qkv / ctx / dctx / dqkv instead of b*S.., in a slot of ceil(lengths[b] / 128) * 128 rows. The 128-row
+  // tiles of a sample are those of the padded call, so every valid row is computed exactly as there; tiles that start
+  // at or past the length return before any barrier (their colpart rows are zeroed unless accumulating) and nothing
+  // outside the slot is read or written. lse / delta / colpart keep their (b, S) indexing.
+  const int32_t* row_start;
 } PlbAttn;
 int plb_launch_attn_fwd(const PlbAttn* p, hipStream_t stream);
 // Default: the two-kernel form, dq (+delta) then dk,dv. plb_set_attn_bwd_fused(1) / PLBERT_ATTN_BWD=fused: ONE kernel for
@@ -227,6 +238,13 @@ int plb_launch_scatter_rows(const bf16_t* src, int lds_, const int32_t* rows, in
 // From the CSR index lists: rows[j] = b*S + idx, tgt[j] = labels[b,idx], w[j] = 1/(n_b * count)
 int plb_launch_ce_prepare(const int32_t* offsets, const int32_t* flat, const int64_t* labels, int B, int S,
                           int32_t* rows, int32_t* tgt, float* w, hipStream_t stream);
+// the same for token-packed rows: rows[j] = row_start[b] + idx (labels stay the padded [B,S] input)
+int plb_launch_ce_prepare_packed(const int32_t* offsets, const int32_t* flat, const int64_t* labels, int B, int S,
+                                 const int32_t* row_start, int32_t* rows, int32_t* tgt, float* w, hipStream_t stream);
+// Token-packed rows back to the padded layout: dst[b, s, 0..C) (fp32, [B,S,C] contiguous) = src[row_start[b] + s, 0..C)
+// for s < lengths[b], zeros at the pad positions. src is bf16 (src_is_bf16) or fp32 with row stride lds_ elements.
+int plb_launch_unpack_rows(const void* src, int src_is_bf16, int lds_, const int32_t* row_start, const int32_t* lengths,
+                           int B, int S, int C, float* dst, hipStream_t stream);
 // per row: loss_rows[j] = w*(lse - z[tgt]); dlogits[j,:] = w*(softmax - onehot) (bf16, zero padded to ldd cols)
 int plb_launch_ce_fwd_bwd(const float* logits, int ldl, int V, const int32_t* tgt, const float* w, int n, int npad,
                           float* loss_rows, bf16_t* dlogits, int ldd, hipStream_t stream);

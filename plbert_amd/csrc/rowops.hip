@@ -10,6 +10,21 @@ namespace {
 
 // ------------------------------------------------------------------------- embeddings (A4 / A11)
 // AlbertEmbeddings.forward (modeling_albert.py:67-106): LN_E(word[id] + type[0] + pos[s]); E <= 256.
+// Token-packed rows (PlbEmbed.row_start / PlbAttn.row_start): the sample that owns packed row r and r's position in it.
+// Returns false for a row that belongs to no sample (behind a sample's length inside its slot, or behind row_start[B]).
+__device__ __forceinline__ bool packed_locate(const int32_t* row_start, const int32_t* lengths, int B, int S, int r, int* b_out,
+                                              int* s_out) {
+  int lo = 0, hi = B;   // the last b with row_start[b] <= r (row_start is non-decreasing, row_start[0] = 0)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (row_start[mid] <= r) lo = mid; else hi = mid;
+  }
+  int len = lengths[lo];
+  len = len < 1 ? 1 : (len > S ? S : len);
+  *b_out = lo; *s_out = r - row_start[lo];
+  return *s_out < len;
+}
+
 template <bool BWD>
 __global__ __launch_bounds__(256) void embed_kernel(PlbEmbed p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -25,9 +40,22 @@ __global__ __launch_bounds__(256) void embed_kernel(PlbEmbed p) {
   float dg[4] = {0, 0, 0, 0}, db[4] = {0, 0, 0, 0};
   const float invE = 1.0f / (float)E;
   for (int t = blockIdx.x * 4 + wave; t < p.T; t += gridDim.x * 4) {
-    long long id = p.ids[t];
+    int src = t, s = 0;
+    if (p.row_start) {   // packed row t -> token (b, s) of the padded ids (wave-uniform: one row per wave)
+      int b;
+      if (!packed_locate(p.row_start, p.lengths, p.B, p.S, t, &b, &s)) {
+        if (act) {
+          if (!BWD) *(uint2*)(p.out + (size_t)t * p.ldo + c) = make_uint2(0u, 0u);
+          else *(float4*)(p.dx + (size_t)t * E + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        continue;
+      }
+      src = b * p.S + s;
+    } else {
+      s = t % p.S;
+    }
+    long long id = p.ids[src];
     if (id < 0 || id >= p.V) id = 0;  // host validates; never index out of the table
-    const int s = t % p.S;
     float x[4] = {0, 0, 0, 0};
     if (act) {
       float4 w = *(const float4*)(p.word + (size_t)id * E + c);
@@ -89,11 +117,15 @@ __global__ __launch_bounds__(256) void embed_kernel(PlbEmbed p) {
 // The token range is walked in chunks of EMB_CHUNK tokens so the list fits LDS for any T (configs/config.yml:16
 // is 96 x 512 = 49,152 tokens on one GPU).
 constexpr int EMB_CHUNK = 32768;
+// PACKED (PlbEmbed.row_start): the ids are still walked in the padded [B,S] order — the lists, and with them the order of
+// every sum, are those of the padded call — and only the row of dx a token is read from comes from the plan; pad
+// positions (exact zeros in the padded call) are left out.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void embed_scatter_kernel(PlbEmbed p, int P) {
   extern __shared__ int list[];  // 4 per-wave segments of matching token indices
   __shared__ int wcnt[4];
   __shared__ float4 part[256];
-  const int E = p.E, T = p.T;
+  const int E = p.E, T = PACKED ? p.B * p.S : p.T;
   const int row = blockIdx.x;
   const int EQ = E >> 2;                                   // float4 columns per row
   const int q = threadIdx.x % EQ, grp = threadIdx.x / EQ, ngrp = 256 / EQ;  // E = 128: 32 x 8
@@ -113,9 +145,15 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(PlbEmbed p, int P) {
       int cnt = 0;
       for (int t0 = c0 + w * 64; t0 < c1; t0 += 256) {
         const int t = t0 + lane;
-        const bool hit = t < c1 && p.ids[t] == row;
+        bool hit = t < c1 && p.ids[t] == row;
+        int trow = t;   // the row of dx that holds token t
+        if (PACKED && hit) {
+          const int b = t / p.S, sp = t - b * p.S;
+          hit = sp < max(p.lengths[b], 1);   // (lengths are clamped to [1, S] everywhere: packed_locate; sp < S always)
+          trow = p.row_start[b] + sp;
+        }
         const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-        if (hit) list[w * cap + cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = t;
+        if (hit) list[w * cap + cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = trow;
         cnt += __builtin_popcountll(m);
       }
       if (lane == 0) wcnt[w] = cnt;
@@ -147,8 +185,14 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(PlbEmbed p, int P) {
     }
   } else {
     const int sidx = row - p.V;  // position row: sum over the batch
-    if (sidx < p.S)
-      for (int t = sidx + grp * p.S; t < T; t += ngrp * p.S) add(t);
+    if (sidx < p.S) {
+      if (PACKED) {
+        for (int b = grp; b < p.B; b += ngrp)
+          if (sidx < max(p.lengths[b], 1)) add(p.row_start[b] + sidx);
+      } else {
+        for (int t = sidx + grp * p.S; t < T; t += ngrp * p.S) add(t);
+      }
+    }
   }
   part[threadIdx.x] = s;
   __syncthreads();
@@ -731,7 +775,7 @@ __global__ void scatter_rows_kernel(const bf16_t* src, int lds_, const int32_t* 
 // calculate_phoneme_loss (train.py:107-131): per-sample mean over its masked indices, then mean over
 // the samples that have any. One thread per sample.
 __global__ void ce_prepare_kernel(const int32_t* offsets, const int32_t* flat, const int64_t* labels, int B, int S,
-                                  int32_t* rows, int32_t* tgt, float* w) {
+                                  const int32_t* row_start, int32_t* rows, int32_t* tgt, float* w) {
   // one block per sample; every block counts the non-empty samples itself (B is small)
   __shared__ int cnt[4];
   int c = 0;
@@ -745,9 +789,26 @@ __global__ void ce_prepare_kernel(const int32_t* offsets, const int32_t* flat, c
   const float wb = (j1 > j0) ? 1.0f / ((float)(j1 - j0) * (float)count) : 0.f;
   for (int j = j0 + threadIdx.x; j < j1; j += blockDim.x) {
     const int idx = flat[j];
-    rows[j] = b * S + idx;
+    rows[j] = row_start ? row_start[b] + idx : b * S + idx;
     tgt[j] = (int32_t)labels[(size_t)b * S + idx];
     w[j] = wb;
+  }
+}
+// token-packed rows back to [B,S,C] fp32 with zeros at the pad positions: one block per (b, s)
+template <typename T>
+__global__ __launch_bounds__(256) void unpack_rows_kernel(const T* src, int lds_, const int32_t* row_start, const int32_t* lengths,
+                                                          int S, int C, float* dst) {
+  const int b = blockIdx.x / S, s = blockIdx.x - b * S;
+  int len = lengths[b];
+  len = len < 1 ? 1 : (len > S ? S : len);
+  float* d = dst + (size_t)blockIdx.x * C;
+  if (s >= len) {
+    for (int c = threadIdx.x; c < C; c += 256) d[c] = 0.f;
+    return;
+  }
+  const T* r = src + (size_t)(row_start[b] + s) * lds_;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    if constexpr (sizeof(T) == 2) d[c] = bf2f(r[c]); else d[c] = r[c];
   }
 }
 // nn.CrossEntropyLoss on one row per wave: V <= 256 classes, 4 per lane.
@@ -1080,6 +1141,7 @@ struct ProfScope {  // brackets every launch made while it is alive with one pai
 
 extern "C" int plb_launch_embed_fwd(const PlbEmbed* p, hipStream_t stream) {
   if (p->E % 4 || p->E > 256 || p->T <= 0) return 1;
+  if (p->row_start && (!p->lengths || p->B < 1)) return 1;
   int blocks = (p->T + 3) / 4; if (blocks > 2048) blocks = 2048;
   ProfScope ps(PLB_K_EMBED_FWD, stream, 0, (double)p->T * (8 + 2.0 * p->E));
   hipLaunchKernelGGL((embed_kernel<false>), dim3(blocks), dim3(256), 0, stream, *p);
@@ -1088,12 +1150,17 @@ extern "C" int plb_launch_embed_fwd(const PlbEmbed* p, hipStream_t stream) {
 extern "C" int plb_launch_embed_scatter(const PlbEmbed* p, int P, hipStream_t stream) {
   if ((p->E != 64 && p->E != 128 && p->E != 256) || p->T <= 0) return 1;
   ProfScope ps(PLB_K_EMBED_BWD, stream, 0, (double)p->T * p->E * 8.0);
-  const int chunk = p->T < EMB_CHUNK ? p->T : EMB_CHUNK;
-  hipLaunchKernelGGL(embed_scatter_kernel, dim3(p->V + P), dim3(256), (size_t)(((chunk + 3) / 4 + 64) * 4) * 4, stream, *p, P);
+  if (p->row_start && (!p->lengths || p->B < 1)) return 1;
+  const int Tscan = p->row_start ? p->B * p->S : p->T;   // packed: the padded ids are what is scanned
+  const int chunk = Tscan < EMB_CHUNK ? Tscan : EMB_CHUNK;
+  const size_t lds_bytes = (size_t)(((chunk + 3) / 4 + 64) * 4) * 4;
+  if (p->row_start) hipLaunchKernelGGL(embed_scatter_kernel<true>, dim3(p->V + P), dim3(256), lds_bytes, stream, *p, P);
+  else hipLaunchKernelGGL(embed_scatter_kernel<false>, dim3(p->V + P), dim3(256), lds_bytes, stream, *p, P);
   return LAUNCH_OK();
 }
 extern "C" int plb_launch_embed_bwd(const PlbEmbed* p, hipStream_t stream) {
   if (p->E % 4 || p->E > 256 || p->T <= 0 || p->nblocks <= 0) return 1;
+  if (p->row_start && (!p->lengths || p->B < 1)) return 1;
   ProfScope ps(PLB_K_EMBED_BWD, stream, 0, (double)p->T * (8 + 2.0 * p->E + 8.0 * p->E));
   hipLaunchKernelGGL((embed_kernel<true>), dim3(p->nblocks), dim3(256), 0, stream, *p);
   return LAUNCH_OK();
@@ -1188,7 +1255,26 @@ extern "C" int plb_launch_scatter_rows(const bf16_t* src, int lds_, const int32_
 }
 extern "C" int plb_launch_ce_prepare(const int32_t* offsets, const int32_t* flat, const int64_t* labels, int B, int S,
                                      int32_t* rows, int32_t* tgt, float* w, hipStream_t stream) {
-  hipLaunchKernelGGL(ce_prepare_kernel, dim3(B), dim3(256), 0, stream, offsets, flat, labels, B, S, rows, tgt, w);
+  hipLaunchKernelGGL(ce_prepare_kernel, dim3(B), dim3(256), 0, stream, offsets, flat, labels, B, S, nullptr, rows, tgt, w);
+  return LAUNCH_OK();
+}
+extern "C" int plb_launch_ce_prepare_packed(const int32_t* offsets, const int32_t* flat, const int64_t* labels, int B, int S,
+                                            const int32_t* row_start, int32_t* rows, int32_t* tgt, float* w,
+                                            hipStream_t stream) {
+  if (!row_start || B < 1 || S < 1) return 1;
+  hipLaunchKernelGGL(ce_prepare_kernel, dim3(B), dim3(256), 0, stream, offsets, flat, labels, B, S, row_start, rows, tgt, w);
+  return LAUNCH_OK();
+}
+extern "C" int plb_launch_unpack_rows(const void* src, int src_is_bf16, int lds_, const int32_t* row_start,
+                                      const int32_t* lengths, int B, int S, int C, float* dst, hipStream_t stream) {
+  if (!src || !row_start || !lengths || !dst || B < 1 || S < 1 || C < 1 || lds_ < C) return 1;
+  ProfScope ps(PLB_K_CAST, stream, 0, (double)B * S * C * 6.0);
+  if (src_is_bf16)
+    hipLaunchKernelGGL(unpack_rows_kernel<bf16_t>, dim3((unsigned)(B * S)), dim3(256), 0, stream, (const bf16_t*)src, lds_,
+                       row_start, lengths, S, C, dst);
+  else
+    hipLaunchKernelGGL(unpack_rows_kernel<float>, dim3((unsigned)(B * S)), dim3(256), 0, stream, (const float*)src, lds_,
+                       row_start, lengths, S, C, dst);
   return LAUNCH_OK();
 }
 extern "C" int plb_launch_ce_fwd_bwd(const float* logits, int ldl, int V, const int32_t* tgt, const float* w, int n,

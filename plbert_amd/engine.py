@@ -23,6 +23,59 @@ class HandoffTimeout(RuntimeError):
     (exchange buffer and error word zeroed): the caller may simply run the step again."""
 
 
+class PackingPlan:
+    """Plan of a token-packed call (include/plbert.h: PlbPacking), made on the host from the host's lengths: sample b's
+    valid tokens are rows [row_start[b], row_start[b] + lengths[b]) of the call's dense token axis, ``rows`` rows are
+    executed instead of B*S. ``packed`` is False when the plan is the padded layout itself (nothing to gain): calls that
+    are given such a plan run the padded path. ``to(device)`` uploads the table once; the plan can be reused for every
+    call with the same lengths (a captured graph included)."""
+
+    def __init__(self, lengths, S):
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).reshape(-1))
+        self.B, self.S = int(lens.shape[0]), int(S)
+        self.lengths = lens
+        self.row_start_host = np.zeros(self.B + 1, dtype=np.int32)
+        rows, used = C.c_int32(), C.c_int32()
+        _lib.check(_lib.lib().plb_packing_plan(lens.ctypes.data, self.B, self.S, self.row_start_host.ctypes.data,
+                                               C.byref(rows), C.byref(used)), "plb_packing_plan")
+        self.rows, self.used = int(rows.value), int(used.value)
+        self.row_start = None   # device int32 [B+1] after to()
+
+    @property
+    def packed(self):
+        return self.rows < (self.B * self.S + 127) // 128 * 128
+
+    @property
+    def valid_tokens(self):
+        return int(np.clip(self.lengths, 1, self.S).sum())
+
+    def to(self, device, non_blocking=True, pinned=None, out=None):
+        """Upload the row table. ``pinned`` / ``out`` (int32, at least B+1 entries): a caller's own pinned staging
+        buffer and device tensor (pipeline.DeviceFeeder keeps one pair per slot), so that nothing is allocated here."""
+        n = self.B + 1
+        if pinned is not None and out is not None:
+            pinned[:n].copy_(torch.from_numpy(self.row_start_host))
+            out[:n].copy_(pinned[:n], non_blocking=True)
+            self.row_start = out[:n]
+            return self
+        t = torch.from_numpy(self.row_start_host)
+        if non_blocking and torch.cuda.is_available():
+            t = t.pin_memory()
+        self.row_start = t.to(device, non_blocking=non_blocking)
+        self._pinned = t   # keeps the staging buffer alive until the copy has run
+        return self
+
+    def c_struct(self, device):
+        if self.row_start is None or self.row_start.device != torch.device(device):
+            self.to(device)
+        return _lib.PlbPacking(self.row_start.data_ptr(), self.rows, self.used)
+
+
+def packing_plan(lengths, S):
+    """Host-only: the PackingPlan of a batch with these per-sample lengths padded to S (plb_packing_plan)."""
+    return PackingPlan(lengths, S)
+
+
 class HipEngine:
     def __init__(self, cfg, num_phonemes, num_tokens=0, max_batch=32, max_seq=512, device=None, train=True):
         """``train=False``: inference / validation engine (README.md:91, train.py:288-304) — no gradient, moment or
@@ -260,6 +313,20 @@ class HipEngine:
         _lib.check(self.L.plb_last_application_rows(self.handle, C.byref(r), C.byref(o)), "plb_last_application_rows")
         return int(r.value), int(o.value)
 
+    def last_call_rows(self):
+        """(rows, of): token rows the last forward / loss call executed and the B*S it stood for (plb_last_call_rows);
+        rows < of: the call ran token-packed."""
+        r, o = C.c_int64(), C.c_int64()
+        _lib.check(self.L.plb_last_call_rows(self.handle, C.byref(r), C.byref(o)), "plb_last_call_rows")
+        return int(r.value), int(o.value)
+
+    def _packing(self, packing, B, S):
+        if packing is None:
+            return None
+        if packing.B != B or packing.S != S:
+            raise ValueError(f"packing plan made for {packing.B} x {packing.S}, the batch is {B} x {S}")
+        return packing.c_struct(self.device)
+
     def comm_pieces(self):
         """(collectives, floats) of the last step's gradient exchange."""
         n, f = C.c_int32(), C.c_int64()
@@ -327,9 +394,10 @@ class HipEngine:
             t = t.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous()
         return t
 
-    def forward(self, ids, lengths=None, want_hidden=False, want_phoneme=True, want_token=False):
+    def forward(self, ids, lengths=None, want_hidden=False, want_phoneme=True, want_token=False, packing=None):
         """ids int64 [B,S]; lengths per-sample valid-token counts (None = no padding).
-        Returns (hidden | None, phoneme_logits | None, token_logits | None), fp32 on the device."""
+        Returns (hidden | None, phoneme_logits | None, token_logits | None), fp32 on the device.
+        ``packing`` (PackingPlan of these lengths): token-packed execution; pad positions of the outputs are zeros."""
         self._ensure_synced()
         ids = self._dev_i64(ids)
         B, S = ids.shape
@@ -339,8 +407,13 @@ class HipEngine:
             ph = torch.empty((B, S, self.num_phonemes), dtype=torch.float32, device=self.device) if want_phoneme else None
             tk = torch.empty((B, S, self.num_tokens), dtype=torch.float32, device=self.device) if want_token else None
             p = lambda t: None if t is None else t.data_ptr()
-            _lib.check(self.L.plb_forward(self.handle, ids.data_ptr(), p(lens), B, S, p(hid), p(ph), p(tk), self._stream()),
-                       "plb_forward")
+            pk = self._packing(packing, B, S)
+            if pk is None:
+                _lib.check(self.L.plb_forward(self.handle, ids.data_ptr(), p(lens), B, S, p(hid), p(ph), p(tk), self._stream()),
+                           "plb_forward")
+            else:
+                _lib.check(self.L.plb_forward_packed(self.handle, ids.data_ptr(), p(lens), B, S, C.byref(pk), p(hid), p(ph),
+                                                     p(tk), self._stream()), "plb_forward_packed")
         return hid, ph, tk
 
     def pooler(self, hidden):
@@ -352,20 +425,22 @@ class HipEngine:
             _lib.check(self.L.plb_pooler(self.handle, hidden.data_ptr(), B, S, out.data_ptr(), self._stream()), "plb_pooler")
         return out
 
-    def loss_fwd(self, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids=None):
+    def loss_fwd(self, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids=None, packing=None):
         """Loss of one batch WITHOUT the backward (validate(), train.py:288-304; process_batch under no_grad):
         plb_loss_fwd — the gradient buffer is not touched. Returns the 1-element device loss tensor."""
-        return self._loss_call(False, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids)
+        return self._loss_call(False, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids, packing)
 
-    def loss_fwd_bwd(self, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids=None):
+    def loss_fwd_bwd(self, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids=None, packing=None):
         """Loss of one batch + gradients of every trainable parameter into ``self.grads``.
         Returns the 1-element device tensor holding the loss (no host sync).
         With ``token_ids`` (int64 [B,S], the 4-tuple Collater's first element) the step is dual-head:
         loss = phoneme loss + token loss, ``self.loss_parts`` holds the two terms and the token head's
-        gradients are produced too."""
-        return self._loss_call(True, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids)
+        gradients are produced too.
+        ``packing`` (PackingPlan of these lengths, loss_fwd too): the call runs on the valid tokens only
+        (include/plbert.h: plb_loss_fwd_bwd_packed); dual-head and fp8 calls run padded all the same."""
+        return self._loss_call(True, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids, packing)
 
-    def _loss_call(self, backward, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids):
+    def _loss_call(self, backward, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids, packing=None):
         if backward and not self.train_mode:
             raise RuntimeError("this HipEngine was built with train=False (inference / validation only)")
         self.raise_if_failed()   # a step that completed since the last call and timed out: never train on top of it
@@ -386,7 +461,18 @@ class HipEngine:
         p = lambda t: None if t is None else t.data_ptr()
         flat_p = flat.data_ptr() if n_masked else None
         with torch.cuda.device(self.device):
-            if not backward:
+            pk = self._packing(packing, B, S)
+            if pk is not None and not backward:
+                _lib.check(self.L.plb_loss_fwd_packed(self.handle, masked_ids.data_ptr(), labels.data_ptr(), p(tok), p(lens),
+                                                      offs.data_ptr(), flat_p, int(n_masked), B, S, C.byref(pk),
+                                                      self._loss.data_ptr(),
+                                                      self._loss_parts.data_ptr() if tok is not None else None,
+                                                      self._stream()), "plb_loss_fwd_packed")
+            elif pk is not None and tok is None:
+                _lib.check(self.L.plb_loss_fwd_bwd_packed(self.handle, masked_ids.data_ptr(), labels.data_ptr(), p(lens),
+                                                          offs.data_ptr(), flat_p, int(n_masked), B, S, C.byref(pk),
+                                                          self._loss.data_ptr(), self._stream()), "plb_loss_fwd_bwd_packed")
+            elif not backward:
                 _lib.check(self.L.plb_loss_fwd(self.handle, masked_ids.data_ptr(), labels.data_ptr(), p(tok), p(lens),
                                                offs.data_ptr(), flat_p, int(n_masked), B, S, self._loss.data_ptr(),
                                                self._loss_parts.data_ptr() if tok is not None else None, self._stream()),

@@ -18,6 +18,7 @@ are plain tensors; training goes through ``loss_and_grads`` / ``plbert_amd.train
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 
 import torch
@@ -46,6 +47,18 @@ class _Leaf(nn.Module):
         self.weight = nn.Parameter(weight, requires_grad=True)
         if bias is not None:
             self.bias = nn.Parameter(bias, requires_grad=True)
+
+
+def _packing_from_lengths(module, lengths, ids):
+    """Token-packed forward (include/plbert.h: plb_forward_packed) when the module's ``packed`` attribute — default:
+    PLBERT_PACKED=1 — is set and the mask pads anything: the plan is made on the host from the mask's lengths (one small
+    read-back here; a caller that has the lengths on the host passes ``packing`` to HipEngine.forward itself). Outputs
+    at pad positions are then zeros."""
+    from .train import make_packing
+    packed = getattr(module, "packed", None)
+    if lengths is None or not (packed if packed is not None else os.environ.get("PLBERT_PACKED", "0") == "1"):
+        return None
+    return make_packing(lengths.cpu().numpy(), ids.shape[1], module.engine.device, True)
 
 
 def _lengths_from_mask(attention_mask, strict=True):
@@ -132,7 +145,8 @@ class AlbertModel(nn.Module):
         if token_type_ids is not None or position_ids is not None:
             raise ValueError("the HIP path implements the reference's implicit token_type_ids=0 / position_ids=arange")
         lengths = _lengths_from_mask(attention_mask)
-        hid, _, _ = self._engine.forward(input_ids, lengths, want_hidden=True, want_phoneme=False)
+        hid, _, _ = self._engine.forward(input_ids, lengths, want_hidden=True, want_phoneme=False,
+                                         packing=_packing_from_lengths(self, lengths, input_ids))
         # pooler (modeling_albert.py:403): computed for API completeness (plb_pooler), never used by the loss
         return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid))
 
@@ -168,7 +182,8 @@ class PhonemeOnlyModel(_HeadModel):
         super().__init__(model, num_phonemes, 0, hidden_size)
 
     def forward(self, phonemes, attention_mask=None):
-        _, ph, _ = self._engine.forward(phonemes, _lengths_from_mask(attention_mask))
+        lengths = _lengths_from_mask(attention_mask)
+        _, ph, _ = self._engine.forward(phonemes, lengths, packing=_packing_from_lengths(self, lengths, phonemes))
         return ph
 
 

@@ -59,12 +59,17 @@ class DeviceFeeder:
     pinned buffers, device slots and copy stream persist."""
 
     def __init__(self, loader, device=None, depth=2, vocab_size=None, validate=True, word_separator=None, prefetch=4,
-                 draw_budget=None, mask_on_copy_stream=True):
+                 draw_budget=None, mask_on_copy_stream=True, packed=None):
         self.loader = loader
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.depth = max(2, int(depth))
         self.vocab_size, self.validate, self.word_separator = vocab_size, validate, word_separator
         self.copy_stream = torch.cuda.Stream(device=self.device)
+        # token-packed execution (train.make_packing): the plan of a ragged batch is made where the batch is staged, its
+        # row table goes through one pinned buffer and one device tensor per slot (nothing allocated per batch)
+        from .train import packed_default
+        self.packed = packed_default() if packed is None else bool(packed)
+        self._plan_bufs = {}
         self.prefetch = prefetch
         self._slots = [None] * self.depth          # device uint8 buffers
         self._pinned = [None] * self.depth
@@ -228,8 +233,26 @@ class DeviceFeeder:
                 info["_slot"] = k
                 batch = self._stage(kind, meta, info, dev)
                 batch._slot = k
+                if self.packed and batch.lengths is not None:
+                    batch.packing = self._plan(k, batch.lengths_host, info["S"])
                 self._prev = batch
                 yield batch
+
+    def _plan(self, k, lengths, S):
+        from .engine import PackingPlan
+        plan = PackingPlan(lengths, S)
+        if not plan.packed:
+            return None
+        bufs = self._plan_bufs.get(k)
+        if bufs is None or bufs[0].numel() < plan.B + 1:
+            n = max(plan.B + 1, 64)
+            bufs = self._plan_bufs[k] = (torch.empty(n, dtype=torch.int32).pin_memory(),
+                                         torch.empty(n, dtype=torch.int32, device=self.device), torch.cuda.Event())
+        else:
+            bufs[2].synchronize()   # the slot's previous upload (depth batches ago) has left the pinned buffer
+        plan.to(self.device, pinned=bufs[0], out=bufs[1])
+        bufs[2].record(torch.cuda.current_stream(self.device))
+        return plan
 
     def _stage(self, kind, meta, info, dev):
         B, S, lengths = info["B"], info["S"], info["lengths"]
@@ -238,7 +261,7 @@ class DeviceFeeder:
             tok = self._view(dev, meta, "token_ids") if "token_ids" in meta else None
             return StagedBatch(self._view(dev, meta, "masked"), self._view(dev, meta, "labels"), lens_t,
                                self._view(dev, meta, "offsets"), self._view(dev, meta, "flat"), info["n_masked"],
-                               int(sum(lengths)), tok)
+                               int(sum(lengths)), tok, lengths_host=np.asarray(lengths, dtype=np.int32))
         # decisions: the masking is applied on the device (plb_apply_mask)
         k = info["_slot"]
         if not self.mask_on_copy_stream:
@@ -249,7 +272,7 @@ class DeviceFeeder:
         v = lambda name: o[name][: B * S].view(B, S)
         lens_t = None if all(x == S for x in lengths) else o["lens"][:B]
         return StagedBatch(v("masked"), v("labels"), lens_t, o["offsets"][: B + 1], o["flat"][:n], n, int(sum(lengths)),
-                           v("tokens") if "word_token" in meta else None)
+                           v("tokens") if "word_token" in meta else None, lengths_host=np.asarray(lengths, dtype=np.int32))
 
     def _apply_mask(self, k, meta, info, dev, stream):
         """plb_apply_mask of slot k's decision records on ``stream`` (behind the upload), outputs into the slot's own

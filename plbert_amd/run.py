@@ -171,7 +171,8 @@ def _feeder(loader, trainer, word_separator, budget=None):
     f = cache.get(loader)
     if f is None:
         f = cache[loader] = DeviceFeeder(loader, device=trainer.engine.device, vocab_size=trainer.engine.cfg.vocab_size,
-                                         word_separator=word_separator, draw_budget=budget)
+                                         word_separator=word_separator, draw_budget=budget,
+                                         packed=getattr(trainer, "packed", None))
     return f
 
 
@@ -245,7 +246,7 @@ def validate(trainer, val_loader, device_masking=False, word_separator=None):
     """Mean of the per-batch losses, forward only (train.py:288-304; masks are re-drawn each pass, as there)."""
     total, n = 0.0, 0
     for b in _batches(val_loader, trainer, device_masking, word_separator):
-        total += _checked(trainer, lambda: trainer.engine.loss_fwd(b.masked, b.labels, b.lengths, b.offsets, b.flat, b.n_masked))
+        total += _checked(trainer, lambda: trainer.loss_only(b))
         n += 1
     return total / max(n, 1)
 

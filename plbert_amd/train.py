@@ -18,7 +18,7 @@ import torch
 
 from .data import masked_indices_to_csr
 from .dist import GradReducer
-from .engine import HipEngine
+from .engine import HipEngine, PackingPlan
 from .init import reference_init_state_dict
 
 
@@ -33,6 +33,22 @@ class StagedBatch:
     n_masked: int
     n_tokens: int
     token_ids: torch.Tensor | None = None  # int64 [B,S]: grapheme-token targets of the 4-tuple Collater (dual-head)
+    packing: PackingPlan | None = None     # token-packed execution: the plan of these lengths (engine.PackingPlan), or None
+    lengths_host: np.ndarray | None = None  # the collater's lengths as it returned them (host): a plan can be made later
+
+
+def packed_default():
+    """PLBERT_PACKED=1: ragged batches run token-packed (include/plbert.h: PlbPacking) wherever ``packed`` is left open."""
+    return os.environ.get("PLBERT_PACKED", "0") == "1"
+
+
+def make_packing(lengths, S, device, packed=None):
+    """The PackingPlan of a batch when packing is on (``packed``; None = PLBERT_PACKED) and saves rows, else None. Host
+    arithmetic plus one small asynchronous upload of the row table: nothing is read back from the device."""
+    if not (packed_default() if packed is None else packed) or lengths is None:
+        return None
+    plan = PackingPlan(lengths, S)
+    return plan.to(device) if plan.packed else None
 
 
 def validate_token_ids(token_ids, shape, lengths, num_tokens):
@@ -88,8 +104,10 @@ class PLBertTrainer:
 
     def __init__(self, cfg, num_phonemes, max_batch=32, max_seq=512, lr=7e-5, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.01, device=None, seed=0, state_dict=None, process_group=None, force_collectives=False,
-                 num_tokens=0, comm="auto", overlap=True):
-        """``comm``: how the gradient exchange of a data-parallel run travels.
+                 num_tokens=0, comm="auto", overlap=True, packed=None):
+        """``packed``: ragged batches run on their valid tokens only (token-packed execution, include/plbert.h PlbPacking);
+        None = PLBERT_PACKED=1. Dual-head and fp8 steps run padded all the same.
+        ``comm``: how the gradient exchange of a data-parallel run travels.
         "rccl"  — the engine's own RCCL communicator behind the C ABI (plb_comm_init / plb_allreduce_grads): the
                   all-reduce is issued by plb_loss_fwd_bwd itself, piece by piece on the engine's communication
                   stream while the remaining weight-gradient GEMMs run (``overlap``); torch.distributed only
@@ -101,6 +119,7 @@ class PLBertTrainer:
         self.engine = HipEngine(cfg, num_phonemes, num_tokens, max_batch=max_batch, max_seq=max_seq, device=device)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.step_count = 0
+        self.packed = packed_default() if packed is None else bool(packed)
         self.reducer = GradReducer(process_group, device=self.engine.device, force=force_collectives)
         self.world = self.reducer.world
         sd = state_dict if state_dict is not None else reference_init_state_dict(cfg, num_phonemes, num_tokens, seed=seed)
@@ -124,7 +143,13 @@ class PLBertTrainer:
                 raise ValueError(f"comm must be 'auto', 'rccl' or 'torch', not {comm!r}")
             self.comm = comm
 
-    def stage_batch(self, labels, masked, lengths, masked_indices, validate=True, token_ids=None):
+    def packing_of(self, batch):
+        """The batch's packing plan: the one it was staged with, else (packing on) one made now from its host lengths."""
+        if batch.packing is None and self.packed and batch.lengths is not None and batch.lengths_host is not None:
+            batch.packing = make_packing(batch.lengths_host, batch.masked.shape[1], self.engine.device, True)
+        return batch.packing if self.packed else None
+
+    def stage_batch(self, labels, masked, lengths, masked_indices, validate=True, token_ids=None, packed=None):
         if validate:
             validate_batch(labels, masked, lengths, masked_indices, self.engine.cfg.vocab_size)
             if token_ids is not None:
@@ -137,12 +162,18 @@ class PLBertTrainer:
         lengths_t = None if (lens == S).all() else torch.from_numpy(lens).to(dev)
         off, flat = masked_indices_to_csr(masked_indices)
         tok_t = None if token_ids is None else torch.as_tensor(np.asarray(token_ids), dtype=torch.int64).to(dev)
+        plan = None if lengths_t is None else make_packing(lens, S, dev, self.packed if packed is None else packed)
         return StagedBatch(masked_t, labels_t, lengths_t, torch.from_numpy(off).to(dev), torch.from_numpy(flat).to(dev),
-                           int(off[-1]), int(lens.sum()), tok_t)
+                           int(off[-1]), int(lens.sum()), tok_t, plan, lens)
 
     def loss_and_grads(self, batch: StagedBatch):
         return self.engine.loss_fwd_bwd(batch.masked, batch.labels, batch.lengths, batch.offsets, batch.flat,
-                                        batch.n_masked, token_ids=batch.token_ids)
+                                        batch.n_masked, token_ids=batch.token_ids, packing=self.packing_of(batch))
+
+    def loss_only(self, batch: StagedBatch):
+        """validate() (train.py:288-304): the batch's loss without the backward."""
+        return self.engine.loss_fwd(batch.masked, batch.labels, batch.lengths, batch.offsets, batch.flat, batch.n_masked,
+                                    token_ids=batch.token_ids, packing=self.packing_of(batch))
 
     def all_reduce_grads(self, dual=False):
         """Sum the trainable gradient range over ranks (RCCL over xGMI, one collective in the step's stream:
@@ -223,7 +254,7 @@ class _FusedLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, engine, names, batch, *params):
         loss = engine.loss_fwd_bwd(batch.masked, batch.labels, batch.lengths, batch.offsets, batch.flat, batch.n_masked,
-                                   token_ids=batch.token_ids)
+                                   token_ids=batch.token_ids, packing=batch.packing)
         ctx.engine, ctx.names, ctx.dual = engine, names, batch.token_ids is not None
         return loss[0].clone()
 
@@ -244,9 +275,10 @@ class _FusedLoss(torch.autograd.Function):
         return (None, None, None, *grads)
 
 
-def stage_reference_batch(engine, batch, validate=True):
+def stage_reference_batch(engine, batch, validate=True, packed=None):
     """(labels, masked, lengths, masked_indices) as PhonemeOnlyCollater returns it, or the 5-tuple
-    (token_ids, labels, masked, lengths, masked_indices) of Collater (dataloader.py:200-223) -> StagedBatch."""
+    (token_ids, labels, masked, lengths, masked_indices) of Collater (dataloader.py:200-223) -> StagedBatch.
+    ``packed`` (None = PLBERT_PACKED): the same padded tensors plus the packing plan of a ragged batch."""
     token_ids = None
     if len(batch) == 5:
         token_ids, *batch = batch
@@ -263,8 +295,9 @@ def stage_reference_batch(engine, batch, validate=True):
     lengths_t = None if (lens == S).all() else torch.from_numpy(lens).to(dev)
     off, flat = masked_indices_to_csr(idx)
     tok_t = None if token_ids is None else torch.as_tensor(np.asarray(token_ids), dtype=torch.int64).to(dev)
+    plan = None if lengths_t is None else make_packing(lens, S, dev, packed)
     return StagedBatch(masked_t, labels_t, lengths_t, torch.from_numpy(off).to(dev), torch.from_numpy(flat).to(dev),
-                       int(off[-1]), int(lens.sum()), tok_t)
+                       int(off[-1]), int(lens.sum()), tok_t, plan, lens)
 
 
 def device_mask_batch(labels, lengths=None, seed=1, step=0, word_pred_prob=0.15, phoneme_mask_prob=0.8, replace_prob=0.1,
@@ -365,7 +398,7 @@ def process_batch(model, batch, criterion=None, accelerator=None):
         return _FusedLoss.apply(engine, names, staged, *params)
     # validate() (train.py:288-304): forward + loss only; the gradient buffer is left alone
     return engine.loss_fwd(staged.masked, staged.labels, staged.lengths, staged.offsets, staged.flat,
-                           staged.n_masked, token_ids=staged.token_ids)[0].clone()
+                           staged.n_masked, token_ids=staged.token_ids, packing=staged.packing)[0].clone()
 
 
 class AdamW:

@@ -1,0 +1,125 @@
+"""Padded against token-packed training steps on a RAGGED batch, on ONE box (bench.py measures the resident full-length
+batch, where packing has nothing to remove). The batch is the reference-captured fixture tests/golden/real_s512_b32_ragged
+(32 x 512, lengths 512 .. 74: 10,271 valid tokens of 16,384 rows) at config A (768 / 12 layers / 12 heads / FFN 2048), one
+training step = loss + backward + AdamW on the resident batch; a full-length 32 x 512 batch is the control (a plan of
+full lengths is the padded layout: that leg shows what the packed entry point costs when it has nothing to do, and the
+box's run-to-run spread).
+Every measurement is a fresh child process under its own time limit, variants round-robin; the parent never opens the
+GPU.
+   python tools/ragged_bench.py [--reps 3] [--steps 30] [--warmup 10] [--timeout 300] label[:ENV=VAL[,ENV=VAL...]] ...
+e.g. python tools/ragged_bench.py parent:PLBERT_HIP_LIB=plbert_amd/build/ab/lib_parent.so,PACKED=0 padded:PACKED=0 packed
+PACKED=0 in a variant's list: padded calls only (a library built before the packed entry points existed has no others);
+the default variant runs both legs, packed and padded.  Prints one JSON line per child and a summary with ms/step and
+VALID tokens/s (the batch's real tokens per second: the figure that packing can move)."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def child(a):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+    import torch
+    from conftest import golden_cfg, load_golden
+    import plbert_amd
+    from plbert_amd.train import PLBertTrainer
+
+    g = load_golden("real_s512_b32_ragged")
+    _, pcfg, sd = golden_cfg(g)
+    B, S = g["labels"].shape
+    legs = {}
+    if a.batch == "ragged":
+        labels, masked = g["labels"], g["masked"]
+        lengths, idx = [int(x) for x in g["lengths"]], [list(map(int, x)) for x in g["index"]]
+    else:
+        labels, masked, lengths, idx = plbert_amd.synthetic_batch(B, S, seed=1234)
+        lengths = [S] * B
+    valid = int(np.sum(lengths))
+    for packed in ([False, True] if a.packed else [False]):
+        kw = {"packed": True} if packed else {}
+        tr = PLBertTrainer(pcfg, int(g["num_phonemes"]), max_batch=B, max_seq=S, lr=7e-5, device="cuda:0", state_dict=sd, **kw)
+        batch = tr.stage_batch(labels, masked, lengths, idx, **kw)
+        for _ in range(a.warmup):
+            tr.step(batch)
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+        ev[0].record()
+        for i in range(a.steps):
+            loss = tr.step(batch)
+            ev[i + 1].record()
+        torch.cuda.synchronize()
+        ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(a.steps))
+        med = ms[len(ms) // 2]
+        rows = tr.engine.last_call_rows() if packed else (B * S, B * S)
+        legs["packed" if packed else "padded"] = {
+            "ms_per_step": round(med, 4), "ms_min": round(ms[0], 4), "ms_p90": round(ms[int(0.9 * (len(ms) - 1))], 4),
+            "valid_tokens_per_s": round(valid / med * 1e3, 1), "rows": int(rows[0]), "of": int(rows[1]),
+            "loss": float(loss.item()), "timeouts": tr.engine.status()["ln_exchange_timeouts"]}
+        del tr
+    print(json.dumps({"batch": a.batch, "valid_tokens": valid, "legs": legs}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--child", action="store_true")
+    ap.add_argument("--batch", choices=["ragged", "full"], default="ragged")
+    ap.add_argument("--packed", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--timeout", type=int, default=300, help="seconds, per child process")
+    ap.add_argument("variants", nargs="*", default=["here"])
+    a = ap.parse_args()
+    if a.child:
+        return child(a)
+    res = {}
+    for rep in range(a.reps):
+        for batch in ("ragged", "full"):
+            for v in a.variants:
+                label, _, envs = v.partition(":")
+                env, packed = dict(os.environ), 1
+                env.pop("PLBERT_PACKED", None)
+                for kv in [e for e in envs.split(",") if e]:
+                    k, _, val = kv.partition("=")
+                    if k == "PACKED":
+                        packed = int(val)
+                    else:
+                        env[k] = os.path.abspath(os.path.join(ROOT, val)) if k == "PLBERT_HIP_LIB" else val
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", "--batch", batch, "--packed", str(packed),
+                       "--steps", str(a.steps), "--warmup", str(a.warmup)]
+                try:
+                    out = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=a.timeout)
+                except subprocess.TimeoutExpired:
+                    print(f"{label} {batch}: no result within {a.timeout} s; stopping", flush=True)
+                    return 1
+                line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+                if out.returncode != 0 or not line:   # nothing more is started on a GPU that has just failed a run
+                    print(f"{label} {batch}: FAILED (exit {out.returncode})\n{out.stderr[-800:]}", flush=True)
+                    return 1
+                d = json.loads(line[-1])
+                print(json.dumps({"variant": label, "rep": rep, **d}), flush=True)
+                for leg, r in d["legs"].items():
+                    res.setdefault((batch, label, leg), []).append(r)
+    print("--- median over the runs: ms/step (all runs) | valid tokens/s | rows executed")
+    med = {}
+    for (batch, label, leg), rs in res.items():
+        ms = [r["ms_per_step"] for r in rs]
+        med[(batch, label, leg)] = statistics.median(ms)
+        print(f"{batch:7s} {label:10s} {leg:7s} {statistics.median(ms):8.3f} ({', '.join(f'{x:.3f}' for x in ms)}) | "
+              f"{statistics.median(r['valid_tokens_per_s'] for r in rs):10.0f} | {rs[0]['rows']} of {rs[0]['of']}")
+    base = a.variants[0].partition(":")[0]
+    for (batch, label, leg), m in med.items():
+        ref = med.get((batch, base, "padded"))
+        if ref and (label, leg) != (base, "padded"):
+            print(f"{batch:7s} {label}/{leg} against {base}/padded: x{ref / m:.3f}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
