@@ -270,6 +270,40 @@ int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* 
                         const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked,
                         int32_t B, int32_t S, const PlbPacking* packing, float* loss, float* loss_parts, void* stream);
 int plb_last_call_rows(const PlbEngine* e, int64_t* rows, int64_t* of);
+/* ---- differentiable encoder: fine-tuning a checkpoint inside a downstream model ----
+ * Stands in for the reference README's "Finetuning" use (README.md:36-119):
+ *   bert_dur = model.bert(texts, attention_mask=(~text_mask).int()).last_hidden_state   -> plb_encode
+ *   ... the caller's own model and loss, its backward down to d(loss)/d(last_hidden_state) ...
+ *   loss.backward()                                                                     -> plb_encode_bwd
+ *   optimizer.step('bert')                                                              -> plb_adamw_step
+ * plb_encode: the forward of a TRAINING engine that keeps every application's activations (nothing is pruned). hidden fp32
+ *   [B,S,H] = .last_hidden_state: at valid positions bit-equal to what plb_forward[_packed] returns on the same engine; at
+ *   pad positions (s >= lengths[b]) ZEROS, in the padded and the packed layout alike. This deviates from HuggingFace (and
+ *   from the padded plb_forward), whose pad query rows hold values: a differentiable output must not hand a downstream
+ *   model numbers that carry no gradient. packing may be NULL. Fails on an inference-only engine, and while fp8 mode is
+ *   on: the gradient sites' delayed-scale history belongs to the pre-training loss and must not be mixed with the
+ *   magnitudes of a foreign gradient (fp8 fine-tuning is out of scope; plb_set_fp8(e, 0, ...) first).
+ * plb_encode_bwd: d_hidden fp32 [B,S,H] = d(loss)/d(hidden) from the caller; values at pad positions are ignored (never
+ *   read: treated as zero). ids / lengths / B / S / packing as given to the plb_encode call whose stash is LIVE: the stash
+ *   stops being live after any call that writes the workspace or moves the weights — plb_forward*, plb_loss_*, plb_encode,
+ *   plb_encode_bwd itself (one backward per forward), plb_adamw_step, plb_sync_weights, plb_set_fp8,
+ *   plb_broadcast_params. Without a live stash, or with another B, S or plan, the call fails with a text that says which,
+ *   launches nothing and leaves the gradient buffer alone.
+ *   Gradient buffer: the encoder range [0, offset of PLB_HEAD_W) is overwritten (not accumulated) as by a loss call; the
+ *   phoneme head's range is written as ZEROS and the head — like the token head and the pooler after a phoneme-only call —
+ *   is marked as having no gradient: the plb_adamw_step that follows updates [0, PLB_HEAD_W) only and leaves the head's
+ *   parameters, both moments and bf16 copies bit-unchanged, as torch skips a parameter whose .grad is None. The head does
+ *   NOT get a step count of its own: it keeps sharing the engine's (`step` of plb_adamw_step), so after k fine-tuning steps
+ *   its next pre-training update is bias-corrected for step + k. The next plb_loss_fwd_bwd makes the head live again.
+ *   Data-parallel runs: with a communicator and overlap on, the call issues the ten pieces of a regular step in the same
+ *   order (the head piece carries its zeros, the status all-reduce sits behind it); overlap off: plb_allreduce_grads as
+ *   before. plb_comm_pieces and plb_last_call_rows report for these calls too.
+ *   A host that steps the parameters with an optimizer of its own (torch.optim.AdamW over the views) must check
+ *   plb_poll_status itself: the device-side skip of a poisoned step lives in plb_adamw_step only. */
+int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing,
+               float* hidden, void* stream);
+int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing,
+                   const float* d_hidden, void* stream);
 /* What the last training step exchanged: the number of collectives it issued (10 pieces for the reference's phoneme-only
  * step with overlap on, 1 with overlap off; one more after a dual-head step) and the floats they covered. The reference
  * has no counterpart (DDP's bucket count is internal to torch, train.py:218-221); a caller logs it to see which form of

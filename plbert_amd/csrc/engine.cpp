@@ -226,6 +226,14 @@ struct PlbEngine {
   int64_t o_tpmax = 0, o_tpsum = 0, o_ttl = 0, o_tlse = 0, o_tw = 0, o_ttgt = 0, o_tcolp = 0;
   bool tok_pad_zeroed = false;  // pad columns of the transposed copy are zeroed once
   bool tok_grads_live = false;  // the last loss call produced token-head gradients (AdamW then steps them)
+  bool head_grads_live = true;  // ... phoneme-head gradients (false after plb_encode_bwd: AdamW then stops at PLB_HEAD_W)
+  // plb_encode / plb_encode_bwd: the stash of a differentiable forward is live until a call writes the workspace or moves
+  // the weights (stash_dead_by: which one — the text plb_encode_bwd fails with)
+  bool stash_live = false;
+  const char* stash_dead_by = "no plb_encode has run on this engine";
+  int stash_B = 0, stash_S = 0;
+  int64_t stash_rows = 0, stash_used = 0;       // Tp and T of the plb_encode call
+  const int32_t* stash_row_start = nullptr;     // its plan's table (null: it ran padded)
   // side stream: the tail of the backward (embedding chain, bias / LayerNorm column sums) runs beside the
   // four large weight-gradient GEMMs
   hipStream_t side = nullptr;
@@ -621,6 +629,11 @@ static hipError_t ev_wait(PlbEngine* e, hipStream_t s, hipEvent_t ev) {
 #define HB_R(stream, ptr, bytes, what) do { if (e->hb.on) e->hb.access(hb_idx(e, stream), (ptr), (size_t)(bytes), false, what); } while (0)
 #define HB_W(stream, ptr, bytes, what) do { if (e->hb.on) e->hb.access(hb_idx(e, stream), (ptr), (size_t)(bytes), true, what); } while (0)
 
+// Every call that writes the workspace or moves the weights ends the life of a plb_encode stash.
+static void drop_stash(PlbEngine* e, const char* by) {
+  if (e && e->stash_live) { e->stash_live = false; e->stash_dead_by = by; }
+}
+
 // ---- fp8 mode ---------------------------------------------------------------------------------------------------------
 // Sites: activations X (layer input), A (attention block output), G (gelu output) in e4m3; gradients DP (dpre2) and DU
 // in e5m2 (their range within a tensor is what e5m2's five exponent bits are for); weights W* in e4m3.
@@ -725,6 +738,7 @@ static int sync_transposes(PlbEngine* e, hipStream_t s, bool exact_fp8 = true) {
 
 extern "C" int plb_set_fp8(PlbEngine* e, int32_t on, void* stream) {
   if (!e || !e->ws) return fail("plb_set_fp8: engine not bound");
+  drop_stash(e, "plb_set_fp8 was called since");
   if (on && !(e->H == 768 || e->H == 1024)) return fail("plb_set_fp8: the fp8 path needs hidden_size 768 or 1024");
   if (on && !e->fp8_on) {  // the first call afterwards runs in bf16 and calibrates the scales
     hipStream_t s = (hipStream_t)stream;
@@ -762,6 +776,7 @@ extern "C" int plb_fp8_stats(PlbEngine* e, float clamped_calls[8], float worst_o
 
 extern "C" int plb_sync_weights(PlbEngine* e, void* stream) {
   if (!e || !e->ws) return fail("plb_sync_weights: engine not bound");
+  drop_stash(e, "plb_sync_weights refreshed the compute copies since");
   hipStream_t s = (hipStream_t)stream;
   TRY(plb_launch_cast_bf16(e->params, e->at<bf16_t>(e->o_wbf), (size_t)e->ptotal, s));
   return sync_transposes(e, s);
@@ -1167,6 +1182,7 @@ static int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
 static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                         const PlbPacking* pk, float* hidden, float* phoneme_logits, float* token_logits, void* stream) {
   if (check_shape(e, B, S, "plb_forward")) return 1;
+  drop_stash(e, "plb_forward rewrote the workspace since");
   if (!ids) return fail("plb_forward: ids is null");
   if (token_logits && !e->NT) return fail("plb_forward: token_logits requested but num_tokens = 0");
   hipStream_t s = (hipStream_t)stream;
@@ -1399,6 +1415,7 @@ static int begin_training_call(PlbEngine* e, bool dual, hipStream_t s) {
   // gradient buffer on the communication stream: this call's kernels must not touch it before they have finished.
   if (e->comm && e->comm_pending) HIPTRY(ev_wait(e, s, e->ev_comm_done));
   e->tok_grads_live = dual;
+  e->head_grads_live = true;
   e->comm_pending = false;
   e->grads_reduced = false;
   e->piece_floats = 0;
@@ -1651,6 +1668,10 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
     at.dqkv8 = sl.dq8; at.lddqkv8 = 3 * H; at.dqkv_scale = sDQ.scale; at.dqkv_amax = sDQ.amax;
     if (e->tn8_call) at.dqkv = nullptr;
   }
+  // packed, S no multiple of 128: the backward kernels store no row of a sample at or past position S, and the slot of a
+  // full-length sample runs on to the next multiple of 128 — rows no launch of this call writes, which the weight-gradient
+  // GEMMs read: zeros (their true value: no token sits there), not what an earlier call left
+  if (c.row_start && c.S % 128 && at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv, 0, (size_t)T * 3 * H * 2, s));
   TRY(plb_launch_attn_bwd(&at, s));
   if (c.Tp > T) {
     if (at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv + (int64_t)T * 3 * H, 0, (size_t)(c.Tp - T) * 3 * H * 2, s));
@@ -1717,6 +1738,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
                      float* loss_parts, void* stream) {
   const char* who = backward ? "plb_loss_fwd_bwd" : "plb_loss_fwd";
   if (check_shape(e, B, S, who)) return 1;
+  drop_stash(e, "a plb_loss_* call rewrote the workspace since");
   if (backward && e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1)", who);
   if (backward && !e->grads) return fail("%s: no gradient buffer bound", who);
   if (!masked_ids || !labels || !idx_offsets || !loss) return fail("%s: null argument", who);
@@ -1962,6 +1984,80 @@ extern "C" int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, cons
                    loss_parts, stream);
 }
 
+// ---- differentiable encoder: forward now, backward from a caller's gradient later (include/plbert.h) --------------------
+// plb_encode is run_encoder with the stash on and nothing pruned; the stash then waits, marked live, while the caller's
+// downstream model runs. plb_encode_bwd turns the caller's d(last_hidden_state) into the output gradient of the last
+// application (plb_launch_seed_dy) and runs the stages of a loss call's backward behind it. The phoneme head takes no
+// part: its gradient range is written as zeros (and still travels as the first piece of the exchange, as in
+// zero_loss_call: the collective sequence of a step is the same whatever the step computes).
+extern "C" int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                          const PlbPacking* pk, float* hidden, void* stream) {
+  if (check_shape(e, B, S, "plb_encode")) return 1;
+  if (e->infer) return fail("plb_encode: inference-only engine (PlbConfig.inference_only = 1): a differentiable forward keeps every application's activations");
+  if (!e->grads) return fail("plb_encode: no gradient buffer bound");
+  if (e->fp8_on) return fail("plb_encode: fp8 mode is on (the gradient sites' delayed scales belong to the pre-training loss); call plb_set_fp8(e, 0, stream) first");
+  if (!ids || !hidden) return fail("plb_encode: %s is null", !ids ? "ids" : "hidden");
+  hipStream_t s = (hipStream_t)stream;
+  Rows rw;
+  if (pick_rows(e, pk, lengths, false, B, S, "plb_encode", &rw)) return 1;
+  drop_stash(e, "a plb_encode call that failed rewrote the workspace since");
+  // (whatever an earlier call left on the side / communication stream was joined by that call's tail; audit on: checked)
+  HB_W(s, e->ws, e->ws_bytes, "plb_encode (whole workspace)");
+  e->last_app_rows[0] = e->last_app_rows[1] = rw.Tp;
+  bf16_t* x = nullptr;
+  if (run_encoder(e, ids, lengths, B, S, rw, true, &x, s)) return 1;
+  // .last_hidden_state in the caller's [B,S,H] layout, ZEROS at the pad positions in both layouts: a downstream model must
+  // not be handed numbers that carry no gradient
+  if (lengths) TRY(plb_launch_unpack_rows(x, 1, e->H, rw.row_start, lengths, B, S, e->H, hidden, s));
+  else TRY(plb_launch_bf16_to_f32(x, e->H, hidden, e->H, rw.T, e->H, s));
+  TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), nullptr, e->host_err_dev, nullptr, s));
+  e->stash_live = true;
+  e->stash_B = B; e->stash_S = S; e->stash_rows = rw.Tp; e->stash_used = rw.T; e->stash_row_start = rw.row_start;
+  return 0;
+}
+
+extern "C" int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                              const PlbPacking* pk, const float* d_hidden, void* stream) {
+  if (check_shape(e, B, S, "plb_encode_bwd")) return 1;
+  if (e->infer) return fail("plb_encode_bwd: inference-only engine (PlbConfig.inference_only = 1)");
+  if (!e->grads) return fail("plb_encode_bwd: no gradient buffer bound");
+  if (!ids || !d_hidden) return fail("plb_encode_bwd: %s is null", !ids ? "ids" : "d_hidden");
+  if (!e->stash_live) return fail("plb_encode_bwd: no live plb_encode stash: %s", e->stash_dead_by);
+  if (B != e->stash_B || S != e->stash_S)
+    return fail("plb_encode_bwd: batch %d x seq %d differs from the plb_encode call's %d x %d", B, S, e->stash_B, e->stash_S);
+  hipStream_t s = (hipStream_t)stream;
+  Rows rw;
+  // (a call that fails launches nothing and leaves what plb_last_call_rows reports alone)
+  const int64_t exec_rows[2] = {e->last_exec_rows[0], e->last_exec_rows[1]};
+  const bool plan_ok = pick_rows(e, pk, lengths, false, B, S, "plb_encode_bwd", &rw) == 0;   // (its own text names the plan)
+  const bool same = plan_ok && rw.Tp == e->stash_rows && rw.T == e->stash_used && rw.row_start == e->stash_row_start;
+  if (!same) {
+    e->last_exec_rows[0] = exec_rows[0]; e->last_exec_rows[1] = exec_rows[1];
+    if (!plan_ok) return 1;
+    return fail("plb_encode_bwd: packing plan differs from the plb_encode call's (%lld rows, %lld used, %s; that call: %lld rows, %lld used, %s)",
+                (long long)rw.Tp, (long long)rw.T, rw.row_start ? "packed" : "padded", (long long)e->stash_rows,
+                (long long)e->stash_used, e->stash_row_start ? "packed" : "padded");
+  }
+  if (begin_training_call(e, false, s)) return 1;
+  e->stash_live = false;
+  e->stash_dead_by = "plb_encode_bwd has consumed it (one backward per plb_encode)";
+  e->head_grads_live = false;
+  e->pruned_rows = 0;
+  const int64_t Tp = rw.Tp;
+  bf16_t* dy = e->at<bf16_t>(e->o_dy0);
+  HB_W(s, dy, Tp * e->H * 2, "output gradient of the last application, seeded from d_hidden");
+  TRY(plb_launch_seed_dy(d_hidden, lengths, rw.row_start, B, S, e->H, (int)Tp, dy, s));
+  // the phoneme head took no part: zeros, final before the layer loop — its piece travels where a regular step's does
+  HB_W(s, e->grd(PLB_HEAD_W), (e->ptrain - e->poff[PLB_HEAD_W]) * 4, "phoneme head gradients (zeros: plb_encode_bwd)");
+  HIPTRY(hipMemsetAsync(e->grd(PLB_HEAD_W), 0, (size_t)(e->ptrain - e->poff[PLB_HEAD_W]) * 4, s));
+  if (overlapping(e) && reduce_pieces(e, kPieceHead, kPieceHead + 1, s)) return 1;
+  int du_rows = 0;
+  if (encoder_bwd(e, nullptr, lengths, B, S, rw, &dy, &du_rows, s)) return 1;
+  if (status_exchange(e, s)) return 1;
+  if (backward_tail(e, ids, lengths, dy, B, S, rw, du_rows, s)) return 1;
+  return status_finish(e, nullptr, s);
+}
+
 // The plan of a token-packed call, on the host (include/plbert.h). Slots start on multiples of 128 — the row tile of the
 // attention kernels, so a sample's tiles are those of the padded call — and the row count is rounded up to the coarsest of
 // 1024 (LayerNorm in the GEMM epilogues) / 256 (gelu' stash) / 128 that still leaves fewer rows than the padded call.
@@ -2178,6 +2274,7 @@ extern "C" int plb_set_grad_overlap(PlbEngine* e, int32_t overlap) {
 
 extern "C" int plb_broadcast_params(PlbEngine* e, int32_t root, void* stream) {
   if (!e || !e->ws) return fail("plb_broadcast_params: engine not bound");
+  drop_stash(e, "plb_broadcast_params moved the weights since");
   if (!e->comm) return 0;
   hipStream_t s = (hipStream_t)stream;
   const int rc = g_rccl.Broadcast(e->params, e->params, (size_t)e->ptotal, kNcclFloat32, root, e->comm, s);
@@ -2260,13 +2357,17 @@ extern "C" int plb_adamw_step(PlbEngine* e, double lr, double beta1, double beta
   if (!e || !e->ws || !e->grads || !e->m || !e->v) return fail("plb_adamw_step: optimizer buffers not bound");
   if (e->infer) return fail("plb_adamw_step: inference-only engine");
   if (step < 1) return fail("plb_adamw_step: step counts from 1");
+  drop_stash(e, "plb_adamw_step moved the weights since");
   hipStream_t s = (hipStream_t)stream;
   if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
     HIPTRY(ev_wait(e, s, e->ev_comm_done));
     e->comm_pending = false;
   }
   HB_R(s, e->grads, e->ptotal * 4, "AdamW (reads the gradient buffer)");
-  TRY(plb_launch_adamw(e->params, e->grads, e->m, e->v, e->at<bf16_t>(e->o_wbf), (size_t)e->ptrain, lr, beta1, beta2, eps,
+  // after plb_encode_bwd the phoneme head has no gradient: no update, as torch skips a parameter whose .grad is None
+  // (parameters, both moments and the bf16 copy of the head stay as they are; the rule of the token head and the pooler)
+  const int64_t nstep = e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W];
+  TRY(plb_launch_adamw(e->params, e->grads, e->m, e->v, e->at<bf16_t>(e->o_wbf), (size_t)nstep, lr, beta1, beta2, eps,
                        weight_decay, step, grad_scale, e->at<unsigned int>(e->o_lnerr), 1, s));
   if (e->tok_grads_live) {
     // token head: trained only by dual-head steps (no gradient, no update — as the pooler), with its OWN step count:

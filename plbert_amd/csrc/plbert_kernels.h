@@ -243,8 +243,17 @@ int plb_launch_ce_prepare_packed(const int32_t* offsets, const int32_t* flat, co
                                  const int32_t* row_start, int32_t* rows, int32_t* tgt, float* w, hipStream_t stream);
 // Token-packed rows back to the padded layout: dst[b, s, 0..C) (fp32, [B,S,C] contiguous) = src[row_start[b] + s, 0..C)
 // for s < lengths[b], zeros at the pad positions. src is bf16 (src_is_bf16) or fp32 with row stride lds_ elements.
+// row_start == NULL: src is in the padded order already (row b*S + s) — the conversion pass of plb_encode, which hands out
+// zeros at the pad positions in either layout.
 int plb_launch_unpack_rows(const void* src, int src_is_bf16, int lds_, const int32_t* row_start, const int32_t* lengths,
                            int B, int S, int C, float* dst, hipStream_t stream);
+// The output gradient of the last application from an upstream fp32 gradient (plb_encode_bwd): every one of the Tp rows of
+// dy [Tp,H] is written exactly once — bf16(d_hidden[b,s,:]), rounded to nearest even, on row row_start[b] + s (row_start
+// == NULL: b*S + s) for s < lengths[b] (lengths == NULL, padded only: every position), zeros on every other row: pad
+// positions, the rest of a 128-row slot, the tail up to Tp. d_hidden (fp32 [B,S,H], 16-byte aligned) is not read at pad
+// positions. H a multiple of 4.
+int plb_launch_seed_dy(const float* d_hidden, const int32_t* lengths, const int32_t* row_start, int B, int S, int H, int Tp,
+                       bf16_t* dy, hipStream_t stream);
 // per row: loss_rows[j] = w*(lse - z[tgt]); dlogits[j,:] = w*(softmax - onehot) (bf16, zero padded to ldd cols)
 int plb_launch_ce_fwd_bwd(const float* logits, int ldl, int V, const int32_t* tgt, const float* w, int n, int npad,
                           float* loss_rows, bf16_t* dlogits, int ldd, hipStream_t stream);

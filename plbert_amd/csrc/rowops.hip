@@ -794,7 +794,8 @@ __global__ void ce_prepare_kernel(const int32_t* offsets, const int32_t* flat, c
     w[j] = wb;
   }
 }
-// token-packed rows back to [B,S,C] fp32 with zeros at the pad positions: one block per (b, s)
+// token-packed rows (row_start == null: rows already in the padded b*S + s order) to [B,S,C] fp32 with zeros at the pad
+// positions: one block per (b, s)
 template <typename T>
 __global__ __launch_bounds__(256) void unpack_rows_kernel(const T* src, int lds_, const int32_t* row_start, const int32_t* lengths,
                                                           int S, int C, float* dst) {
@@ -806,9 +807,36 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const T* src, int lds_
     for (int c = threadIdx.x; c < C; c += 256) d[c] = 0.f;
     return;
   }
-  const T* r = src + (size_t)(row_start[b] + s) * lds_;
+  const T* r = src + (size_t)(row_start ? row_start[b] + s : blockIdx.x) * lds_;
   for (int c = threadIdx.x; c < C; c += 256) {
     if constexpr (sizeof(T) == 2) d[c] = bf2f(r[c]); else d[c] = r[c];
+  }
+}
+// Output gradient of the last application from a caller's fp32 [B,S,H] gradient (plb_encode_bwd): ONE pass writes every
+// one of the Tp rows of dy exactly once — bf16(d_hidden[b,s,:]) (round to nearest even, as cast_bf16_kernel) on the row that
+// holds token (b, s < lengths[b]), zeros on every other row (pad positions, the rest of a packed slot, the tail up to Tp) —
+// so nothing has to clear dy first, and d_hidden is never read at a pad position (it may hold anything there). One lane per
+// four columns: a 16-byte load, an 8-byte store, 6 bytes of traffic per element. row_start (or null: padded rows b*S + s):
+// the sample of a packed row is found by searching the plan, as the packed embedding kernel does.
+__global__ __launch_bounds__(256) void seed_dy_kernel(const float* d_hidden, const int32_t* lengths, const int32_t* row_start, int B,
+                                                      int S, int H4, unsigned int total, bf16_t* dy) {
+  for (unsigned int i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const int r = (int)(i / (unsigned int)H4), c = (int)(i - (unsigned int)r * (unsigned int)H4);
+    int b = 0, s = 0;
+    bool live;
+    if (row_start) {
+      live = packed_locate(row_start, lengths, B, S, r, &b, &s);
+    } else {
+      b = r / S; s = r - b * S;
+      live = b < B;
+      if (live && lengths) { int len = lengths[b]; len = len < 1 ? 1 : (len > S ? S : len); live = s < len; }
+    }
+    uint2 o = make_uint2(0u, 0u);
+    if (live) {
+      const float4 v = *(const float4*)(d_hidden + ((size_t)b * S + s) * ((size_t)H4 * 4) + (size_t)c * 4);
+      o.x = pack_bf2(v.x, v.y); o.y = pack_bf2(v.z, v.w);
+    }
+    *(uint2*)(dy + (size_t)i * 4) = o;
   }
 }
 // nn.CrossEntropyLoss on one row per wave: V <= 256 classes, 4 per lane.
@@ -1267,7 +1295,7 @@ extern "C" int plb_launch_ce_prepare_packed(const int32_t* offsets, const int32_
 }
 extern "C" int plb_launch_unpack_rows(const void* src, int src_is_bf16, int lds_, const int32_t* row_start,
                                       const int32_t* lengths, int B, int S, int C, float* dst, hipStream_t stream) {
-  if (!src || !row_start || !lengths || !dst || B < 1 || S < 1 || C < 1 || lds_ < C) return 1;
+  if (!src || !lengths || !dst || B < 1 || S < 1 || C < 1 || lds_ < C) return 1;
   ProfScope ps(PLB_K_CAST, stream, 0, (double)B * S * C * 6.0);
   if (src_is_bf16)
     hipLaunchKernelGGL(unpack_rows_kernel<bf16_t>, dim3((unsigned)(B * S)), dim3(256), 0, stream, (const bf16_t*)src, lds_,
@@ -1275,6 +1303,19 @@ extern "C" int plb_launch_unpack_rows(const void* src, int src_is_bf16, int lds_
   else
     hipLaunchKernelGGL(unpack_rows_kernel<float>, dim3((unsigned)(B * S)), dim3(256), 0, stream, (const float*)src, lds_,
                        row_start, lengths, S, C, dst);
+  return LAUNCH_OK();
+}
+extern "C" int plb_launch_seed_dy(const float* d_hidden, const int32_t* lengths, const int32_t* row_start, int B, int S, int H,
+                                  int Tp, bf16_t* dy, hipStream_t stream) {
+  if (!d_hidden || !dy || B < 1 || S < 1 || H < 4 || H % 4 || Tp < 1) return 1;
+  if (row_start ? !lengths : (int64_t)Tp < (int64_t)B * S) return 1;   // (packed: the plan's rows; padded: at least B*S of them)
+  if (((uintptr_t)d_hidden & 15) || ((uintptr_t)dy & 7)) return 1;
+  const int64_t total = (int64_t)Tp * (H / 4);
+  if (total >= ((int64_t)1 << 31)) return 1;
+  const int64_t blocks = (total + 255) / 256;
+  ProfScope ps(PLB_K_CAST, stream, 0, (double)Tp * H * 6.0);
+  hipLaunchKernelGGL(seed_dy_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, stream, d_hidden, lengths,
+                     row_start, B, S, H / 4, (unsigned int)total, dy);
   return LAUNCH_OK();
 }
 extern "C" int plb_launch_ce_fwd_bwd(const float* logits, int ldl, int V, const int32_t* tgt, const float* w, int n,

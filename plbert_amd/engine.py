@@ -416,6 +416,49 @@ class HipEngine:
                                                      p(tk), self._stream()), "plb_forward_packed")
         return hid, ph, tk
 
+    def encode(self, ids, lengths=None, packing=None):
+        """Differentiable forward (include/plbert.h: plb_encode): ``.last_hidden_state`` fp32 [B,S,H] with every
+        application's activations kept for ``encode_bwd``; ZEROS at pad positions. Training engines only, not in fp8
+        mode. The ids, lengths and plan are remembered for the backward; any other computing call on this engine in
+        between (forward, a loss call, another encode, an optimizer step) ends the life of the kept activations."""
+        if not self.train_mode:
+            raise RuntimeError("this HipEngine was built with train=False (inference / validation only): encode() keeps "
+                               "the activations of every layer for a backward")
+        self.raise_if_failed()
+        self._ensure_synced()
+        ids = self._dev_i64(ids)
+        B, S = ids.shape
+        lens = self._dev_i32(lengths)
+        self._live_encode = None
+        with torch.cuda.device(self.device):
+            hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device)
+            pk = self._packing(packing, B, S)
+            _lib.check(self.L.plb_encode(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
+                                         None if pk is None else C.byref(pk), hid.data_ptr(), self._stream()), "plb_encode")
+        self._encode_serial = getattr(self, "_encode_serial", 0) + 1
+        self._live_encode = (ids, lens, packing, B, S)   # (holds the tensors the backward reads again)
+        return hid
+
+    def encode_bwd(self, d_hidden):
+        """Backward of the live ``encode`` from ``d_hidden`` = d(loss)/d(hidden), fp32 [B,S,H] (values at pad positions
+        are ignored): the encoder range of ``self.grads`` is overwritten, the phoneme head's is zeroed and the next
+        ``adamw_step`` leaves the head alone (plb_encode_bwd)."""
+        live = getattr(self, "_live_encode", None)
+        if live is None:
+            raise RuntimeError("encode_bwd: no live encode() on this engine (one backward per encode)")
+        ids, lens, packing, B, S = live
+        d = torch.as_tensor(d_hidden)
+        if d.dtype != torch.float32 or d.device != self.device or not d.is_contiguous():
+            d = d.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(d.shape) != (B, S, self.cfg.hidden_size):
+            raise ValueError(f"d_hidden must be [{B}, {S}, {self.cfg.hidden_size}], got {tuple(d.shape)}")
+        self._live_encode = None
+        with torch.cuda.device(self.device):
+            pk = self._packing(packing, B, S)
+            _lib.check(self.L.plb_encode_bwd(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
+                                             None if pk is None else C.byref(pk), d.data_ptr(), self._stream()),
+                       "plb_encode_bwd")
+
     def pooler(self, hidden):
         """tanh(pooler(hidden[:, 0])) (modeling_albert.py:403), fp32 [B,H]; ``hidden`` fp32 [B,S,H] on the device."""
         self._ensure_synced()

@@ -15,6 +15,14 @@ The modules are real ``torch.nn.Module`` trees whose Parameters are VIEWS into t
 buffer, so ``load_state_dict``/``state_dict``/``torch.save`` behave as usual while the kernels see
 one contiguous allocation.  Forward runs entirely in libplbert_hip.so (no autograd graph: outputs
 are plain tensors; training goes through ``loss_and_grads`` / ``plbert_amd.train``).
+
+Fine-tuning inside a downstream model (the reference README's "Finetuning" section) is the one place
+where a forward joins torch's autograd graph: an encoder whose ``differentiable`` attribute is set
+(``AlbertModel(config, finetune=True)``, or ``model.encoder.differentiable = True`` on a wrapped one)
+returns a ``last_hidden_state`` that requires grad while the module is in training mode and grad is
+enabled; ``backward()`` runs plb_encode_bwd and hands every encoder Parameter its slice of the
+engine's gradient buffer.  ``pooler_output`` is returned DETACHED (the pooler gets no gradient), and
+``last_hidden_state`` is zero at pad positions.
 """
 from __future__ import annotations
 
@@ -79,10 +87,48 @@ def _lengths_from_mask(attention_mask, strict=True):
     return lengths
 
 
+class _Encode(torch.autograd.Function):
+    """The differentiable forward as one autograd node: forward = plb_encode, backward = plb_encode_bwd on the upstream
+    gradient; every encoder Parameter receives the view of its slice of ``engine.grads`` (the scheme of train._FusedLoss),
+    the pooler and the heads receive None. The engine keeps ONE forward's activations: the backward of a forward that a
+    later engine call has overwritten raises."""
+
+    @staticmethod
+    def forward(ctx, engine, names, ids, lengths, packing, *params):
+        hid = engine.encode(ids, lengths, packing)
+        ctx.engine, ctx.names, ctx.serial = engine, names, engine._encode_serial
+        return hid
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        eng = ctx.engine
+        gone = "a later engine call overwrote the activations of this forward (the engine keeps one differentiable " \
+               "forward at a time: call backward() before the next forward, loss call or optimizer step)"
+        if eng._live_encode is None or eng._encode_serial != ctx.serial:
+            raise RuntimeError(gone)
+        try:
+            eng.encode_bwd(grad.contiguous().float())
+        except RuntimeError as ex:
+            if "no live plb_encode stash" in str(ex):
+                raise RuntimeError(f"{gone}: {ex}") from ex
+            raise
+        end = eng.layout["phoneme_predictor.weight"][0]   # the encoder range of the flat buffers
+        grads = []
+        for n in ctx.names:
+            off, size, shp = eng.layout[n]
+            grads.append(eng.grads[off:off + size].view(shp) if off + size <= end else None)
+        return (None, None, None, None, None, *grads)
+
+
 class AlbertModel(nn.Module):
     """Drop-in for ``transformers.AlbertModel`` on this path (modeling_albert.py:338-408)."""
 
-    def __init__(self, config, add_pooling_layer=True, max_batch=_DEFAULT_MAX_BATCH, max_seq=None, device=None, seed=0):
+    def __init__(self, config, add_pooling_layer=True, max_batch=_DEFAULT_MAX_BATCH, max_seq=None, device=None, seed=0,
+                 finetune=False):
+        """``finetune=True``: the encoder sits on a TRAINING engine of its own and is ``differentiable`` — the model a TTS
+        training loop fine-tunes (reference README "Finetuning": ``bert(texts, attention_mask=...).last_hidden_state``
+        feeding the caller's layers, ``optimizer.step('bert')``)."""
         super().__init__()
         config.check_supported()
         self.config = config
@@ -95,7 +141,10 @@ class AlbertModel(nn.Module):
         # the parameters and, from the first forward on, one layer of activations (< 1 GB at 32 x 512) — no gradient,
         # moment or per-layer stash. Wrapped by PhonemeOnlyModel / MultiTaskModel its parameters move into the
         # wrapper's training engine before this one has allocated anything but them.
-        self._build(HipEngine(config, 4, 0, max_batch=self._max_batch, max_seq=self._max_seq, device=device, train=False),
+        # finetune: all layers' activations, gradients and AdamW moments (the stand-in head sizes stay: the head is unused)
+        self.differentiable = bool(finetune)
+        self._build(HipEngine(config, 4, 0, max_batch=self._max_batch, max_seq=self._max_seq, device=device,
+                              train=bool(finetune)),
                     reference_init_state_dict(config, 4, 0, seed=seed), prefix="encoder.")
 
     # -- module tree with the reference's parameter names ----------------------------------------------
@@ -145,6 +194,16 @@ class AlbertModel(nn.Module):
         if token_type_ids is not None or position_ids is not None:
             raise ValueError("the HIP path implements the reference's implicit token_type_ids=0 / position_ids=arange")
         lengths = _lengths_from_mask(attention_mask)
+        if getattr(self, "differentiable", False) and self.training and torch.is_grad_enabled():
+            # fine-tuning: the forward joins the autograd graph (_Encode); pad positions of last_hidden_state are zeros and
+            # pooler_output is DETACHED (the pooler receives no gradient, as in every other call of this library)
+            names, params = [], []
+            for n, p in self.named_parameters():
+                names.append("encoder." + n)
+                params.append(p)
+            hid = _Encode.apply(self._engine, names, input_ids, lengths, _packing_from_lengths(self, lengths, input_ids),
+                                *params)
+            return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid.detach()))
         hid, _, _ = self._engine.forward(input_ids, lengths, want_hidden=True, want_phoneme=False,
                                          packing=_packing_from_lengths(self, lengths, input_ids))
         # pooler (modeling_albert.py:403): computed for API completeness (plb_pooler), never used by the loss

@@ -409,15 +409,22 @@ class AdamW:
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, model=None):
         self.param_list = list(params)
         if model is None:
-            raise ValueError("pass model=<PhonemeOnlyModel|MultiTaskModel>: the fused optimizer updates the model's "
+            raise ValueError("pass model=<PhonemeOnlyModel|MultiTaskModel|AlbertModel(finetune=True)>: the fused optimizer updates the model's "
                              "flat parameter buffer")
         self.engine = model.engine
         self.defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.step_count = 0
         self.grad_scale = 1.0
         self.engine._on_handoff_timeout.append(_rewind_steps(self))
-        by_id = {id(p): n for n, p in model.named_parameters()}
+        # (a stand-alone AlbertModel names its parameters without the "encoder." prefix of the engine's layout)
+        by_id = {id(p): (n if n in self.engine.layout else "encoder." + n) for n, p in model.named_parameters()}
         self._names = [by_id[id(p)] for p in self.param_list]
+
+    @property
+    def param_groups(self):
+        """One group, and its dict IS the live ``defaults``: ``for g in optimizer.param_groups: g['lr'] = ...`` (the
+        reference README's fine-tuning set-up) takes effect at the next step."""
+        return [self.defaults]
 
     def zero_grad(self, set_to_none=True):
         for p in self.param_list:
