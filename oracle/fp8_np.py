@@ -6,7 +6,7 @@ The reference has no fp8 path (it trains under fp16 autocast, configs/config.yml
 reference beyond what ``albert_np.py`` already pins: with ``amax=None`` this module computes EXACTLY the arithmetic of
 ``albert_np.loss_and_grads`` (tests/test_oracle_fp8.py asserts equality) and records the per-site maxima; with maxima
 given it repeats the call with the operands of the layer's large GEMMs rounded to OCP fp8 at the sites, in the formats
-and under the scales the HIP path uses (plbert_amd/csrc/engine.cpp "fp8 mode"):
+and under the scales the HIP path uses (plbert_amd/csrc/engine_fp8.cpp, "fp8 mode" in csrc/engine_internal.h):
 
   site   tensor (per application l)                 format   consumers
   X      layer input x_l                            e4m3     QKV GEMM, dW_qkv
@@ -27,7 +27,7 @@ row-minimum fall-back: weight gradients from the un-rounded tensors.
 
 ``bf16=True`` additionally rounds to bfloat16 wherever the device STORES a tensor in bfloat16 (every GEMM / LayerNorm /
 attention output, the bf16 weight copies, the gelu-derivative stash, the probabilities and dS fed to the attention
-products) — csrc/engine.cpp run_encoder / backward; the fused LayerNorm epilogues round their input "as a bf16 store
+products) — csrc/engine_layers.cpp run_encoder / encoder_bwd; the fused LayerNorm epilogues round their input "as a bf16 store
 would leave it" (gemm_nt_pipeline.h), so fused and unfused calls share these semantics.  The 1-byte images are taken
 from the bf16 values (attn_common.h store_transposed, gemm_nt_pipeline.h "the values as stored"), so with the stores
 restated the images — and with them the rounding decisions of every later site — coincide with the device's almost
@@ -102,7 +102,7 @@ class _Sites:
     def weights(self, w):
         """(copy the forward GEMM reads, copy the backward GEMM reads) of one weight tensor.  fp8 call: the forward copy
         is quantised from the fp32 master, the backward (transposed) copy from its bf16 transpose — each under its own
-        maximum (engine.cpp fp8_quantize_weights).  bf16 call: the bf16 copy both ways."""
+        maximum (engine_fp8.cpp fp8_quantize_weights).  bf16 call: the bf16 copy both ways."""
         w16 = round_bf16(w) if self.bf16 else w
         if self.use is None:
             return w16, w16
@@ -114,7 +114,7 @@ def loss_and_grads_fp8(cfg, P, masked_ids, labels, lengths, masked_indices, amax
     """One loss call: (loss, phoneme_pred, grads-by-name, maxima recorded per site).
 
     prune_last: restates the device's evaluation of the LAST application's post-attention part on the masked rows only
-    (csrc/engine.cpp last_application_fwd_pruned; a phoneme-only call with at most half of the positions masked). That part
+    (csrc/engine_layers.cpp last_application_fwd_pruned; a phoneme-only call with at most half of the positions masked). That part
     runs in bf16 even inside an fp8 call — dense, FFN and their dX GEMMs on the bf16 weight copies and un-rounded operands,
     the pre-activation u stored in bf16 with gelu / gelu' taken from the stored value — while the stacked weight-gradient
     GEMMs still read 1-byte images of its (compact) rows. Rows without a masked position carry an exactly zero gradient

@@ -8,8 +8,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libplbert_hip.so")
-SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_fp8.hip", "gemm_fp8_ln.hip", "gemm_tn_fp8.hip", "gemm_ln.hip", "attn.hip", "attn_bwd_fused.hip", "rowops.hip", "mask.hip", "engine.cpp"]
-HEADERS = ["common.h", "plbert_kernels.h", "gemm_epilogue.h", "gemm_nt_pipeline.h", "attn_common.h", os.path.join("..", "..", "include", "plbert.h")]
+SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_fp8.hip", "gemm_fp8_ln.hip", "gemm_tn_fp8.hip", "gemm_ln.hip", "attn.hip", "attn_bwd_fused.hip", "rowops.hip", "mask.hip",
+           "engine.cpp", "engine_prof.cpp", "engine_comm.cpp", "engine_fp8.cpp", "engine_layers.cpp", "engine_calls.cpp"]
+# what a rebuild depends on beside the sources: the headers and the linker version script
+HEADERS = ["exports.map", "common.h", "plbert_kernels.h", "gemm_epilogue.h", "gemm_nt_pipeline.h", "attn_common.h", "engine_internal.h", os.path.join("..", "..", "include", "plbert.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # Per-source flags. attn_bwd_fused.hip is a one-wave-per-SIMD kernel with the whole 512-entry register file: by default
 # hipcc then selects the AGPR form for EVERY MFMA, so the S / dP tiles that the softmax arithmetic consumes land in
@@ -129,7 +131,8 @@ def build(force=False, verbose=True):
         if verbose and out.strip():
             print(out, file=sys.stderr)
         objs.append(obj)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs]
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"),
+           "-o", LIB, *objs]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("link failed:\n" + r.stdout)

@@ -1,0 +1,565 @@
+// Call-level stages of the engine: row selection of a padded or token-packed call, the heads, the stages of a loss call and
+// the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd. Only
+// writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
+// last_exec_rows, tok_grads_live and head_grads_live.
+#include "engine_internal.h"
+
+// Every call that writes the workspace or moves the weights ends the life of a plb_encode stash.
+void drop_stash(PlbEngine* e, const char* by) {
+  if (e && e->stash_live) { e->stash_live = false; e->stash_dead_by = by; }
+}
+
+static int check_shape(const PlbEngine* e, int B, int S, const char* who) {
+  if (!e || !e->ws) return fail("%s: engine not bound", who);
+  if (B < 1 || S < 1 || B > e->c.max_batch || S > e->c.max_seq || (int64_t)B * S > (int64_t)e->c.max_batch * e->c.max_seq)
+    return fail("%s: batch %d x seq %d exceeds the engine capacity %d x %d", who, B, S, e->c.max_batch, e->c.max_seq);
+  return 0;
+}
+
+static Rows padded_rows(int B, int S) { return Rows{nullptr, B * S, rup(B * S, 128)}; }
+// Does this call run packed? It runs padded — same results as without a plan — when the plan saves nothing (every
+// sample full, or slots that add up to the padded rows), for dual-head calls and while fp8 mode is on.
+static int pick_rows(PlbEngine* e, const PlbPacking* pk, const int32_t* lengths, bool dual, int B, int S, const char* who,
+                     Rows* out) {
+  *out = padded_rows(B, S);
+  e->last_exec_rows[0] = e->last_exec_rows[1] = (int64_t)B * S;
+  if (!pk || !pk->row_start) return 0;
+  if (pk->rows < 128 || pk->rows % 128 || pk->used < 1 || pk->used > pk->rows)
+    return fail("%s: packing plan of %d rows (%d used) is not one plb_packing_plan made", who, pk->rows, pk->used);
+  if (pk->rows > out->Tp) return fail("%s: packing plan of %d rows exceeds the call's %lld", who, pk->rows, (long long)out->Tp);
+  if (!lengths || dual || e->fp8_on || pk->rows == out->Tp) return 0;   // (rows == Tp: the plan is the padded layout)
+  if (pk->used % 128) return fail("%s: packing plan with %d used rows: slots are multiples of 128", who, pk->used);
+  *out = Rows{pk->row_start, pk->used, pk->rows};
+  e->last_exec_rows[0] = pk->rows;
+  return 0;
+}
+
+static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                        const PlbPacking* pk, float* hidden, float* phoneme_logits, float* token_logits, void* stream) {
+  if (check_shape(e, B, S, "plb_forward")) return 1;
+  drop_stash(e, "plb_forward rewrote the workspace since");
+  if (!ids) return fail("plb_forward: ids is null");
+  if (token_logits && !e->NT) return fail("plb_forward: token_logits requested but num_tokens = 0");
+  hipStream_t s = (hipStream_t)stream;
+  const int H = e->H;
+  Rows rw;
+  // (token logits: the dual-head model runs padded. Phoneme logits of a packed call pass, as [Tp][NP] fp32, through a slot
+  // of the forward-only call that is free once the encoder is done: QKV (6H bytes per row) or the FFN's u (2I))
+  const int64_t lg_off = 4 * e->NP <= 6 * H ? e->o_qkv : 4 * e->NP <= 2 * e->I ? e->o_u : -1;
+  if (pick_rows(e, pk, lengths, token_logits != nullptr || lg_off < 0, B, S, "plb_forward", &rw)) return 1;
+  const int T = rw.T;
+  const int64_t Tp = rw.Tp;
+  bf16_t* x = nullptr;
+  if (run_encoder(e, ids, lengths, B, S, rw, false, &x, s)) return 1;
+  if (rw.row_start) {
+    // back to the caller's [B,S,*] layout, zeros at the pad positions
+    if (hidden) TRY(plb_launch_unpack_rows(x, 1, H, rw.row_start, lengths, B, S, H, hidden, s));
+    if (phoneme_logits) {
+      float* lg = e->at<float>(lg_off);
+      PlbGemmNT g = nt_desc(x, e->wbf(PLB_HEAD_W), Tp, e->NP, H);
+      g.Mstore = T; g.bias = e->par(PLB_HEAD_B); g.Cf = lg; g.ldcf = e->NP;
+      TRY(plb_launch_gemm_nt(&g, 0, 1, s));
+      TRY(plb_launch_unpack_rows(lg, 0, e->NP, rw.row_start, lengths, B, S, e->NP, phoneme_logits, s));
+    }
+  } else {
+  if (hidden) TRY(plb_launch_bf16_to_f32(x, H, hidden, H, T, H, s));
+  if (phoneme_logits) {
+    PlbGemmNT g = nt_desc(x, e->wbf(PLB_HEAD_W), Tp, e->NP, H);
+    g.Mstore = T; g.bias = e->par(PLB_HEAD_B); g.Cf = phoneme_logits; g.ldcf = e->NP;
+    TRY(plb_launch_gemm_nt(&g, 0, 1, s));
+  }
+  }
+  if (token_logits) {
+    PlbGemmNT g = nt_desc(x, e->wbf(PLB_TOK_W), Tp, e->NT, H);
+    g.Mstore = T; g.bias = e->par(PLB_TOK_B); g.Cf = token_logits; g.ldcf = e->NT;
+    TRY(plb_launch_gemm_nt(&g, 0, 1, s));
+  }
+  if (e->fp8_on) {
+    TRY(fp8_update_scales(e, s));
+    e->fp8_ready = true;
+  }
+  TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), nullptr, e->host_err_dev, nullptr, s));
+  return 0;
+}
+extern "C" int plb_forward(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, float* hidden,
+                           float* phoneme_logits, float* token_logits, void* stream) {
+  return forward_impl(e, ids, lengths, B, S, nullptr, hidden, phoneme_logits, token_logits, stream);
+}
+extern "C" int plb_forward_packed(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                                  const PlbPacking* packing, float* hidden, float* phoneme_logits, float* token_logits,
+                                  void* stream) {
+  return forward_impl(e, ids, lengths, B, S, packing, hidden, phoneme_logits, token_logits, stream);
+}
+
+// ---- stages of a loss call ----------------------------------------------------------------------------------------------
+// Bookkeeping at the start of a training call.
+static int begin_training_call(PlbEngine* e, bool dual, hipStream_t s) {
+  // All-reduce pieces of a PREVIOUS backward that nobody joined (two plb_loss_fwd_bwd calls with no plb_allreduce_grads /
+  // plb_adamw_step between them: gradient probing, a caller that skips a step on a bad loss) still read and write the
+  // gradient buffer on the communication stream: this call's kernels must not touch it before they have finished.
+  if (e->comm && e->comm_pending) HIPTRY(ev_wait(e, s, e->ev_comm_done));
+  e->tok_grads_live = dual;
+  e->head_grads_live = true;
+  e->comm_pending = false;
+  e->grads_reduced = false;
+  e->piece_floats = 0;
+  e->piece_count = 0;
+  e->status_collectives = 0;
+  if (e->hb.on) {
+    // this call's first launches on the caller's stream may touch any byte of the workspace and the gradient buffer:
+    // whatever the previous call left running on the side / communication stream must be ordered before them
+    HB_W(s, e->ws, e->ws_bytes, "start of a loss call (whole workspace)");
+    HB_W(s, e->grads, e->ptotal * 4, "start of a loss call (gradient buffer)");
+    if (e->hb.violations) return fail("happens-before audit: %s", e->hb.first.c_str());
+    e->hb.new_call();
+  }
+  for (auto& t : e->trace) { e->trace_pool.push_back(t.released); e->trace_pool.push_back(t.done); }
+  e->trace.clear();
+  if (e->trace_on) {
+    if (!e->tr_call0) { (void)hipEventCreate(&e->tr_call0); (void)hipEventCreate(&e->tr_tail0); (void)hipEventCreate(&e->tr_tail1); }
+    (void)hipEventRecord(e->tr_call0, s);
+    e->tr_tail_valid = false;
+  }
+  return 0;
+}
+
+// A phoneme-only call without masked positions (train.py:129): zero loss, nothing to back-propagate.
+static int zero_loss_call(PlbEngine* e, bool backward, float* loss, hipStream_t s) {
+  HIPTRY(hipMemsetAsync(loss, 0, sizeof(float), s));
+  if (!backward) return 0;
+  HIPTRY(hipMemsetAsync(e->grads, 0, (size_t)e->ptrain * 4, s));
+  if (overlapping(e)) {
+    // The other ranks still contribute theirs — and they issue the pieces of a regular step: a collective
+    // sequence must be the same on every rank, so this rank issues the very same ranges in the very same order
+    // (its zeros), not one all-reduce of the whole buffer.
+    for (int i = 0; i < kNPieces; ++i) {
+      HB_W(s, e->grads + piece_begin(e, i), (piece_end(e, i) - piece_begin(e, i)) * 4, "zero gradients of a rank without masked phonemes");
+      if (reduce_pieces(e, i, i + 1, s)) return 1;
+      if (i == kPieceHead && status_exchange(e, s)) return 1;   // where a regular step issues it: behind the head piece
+    }
+    if (pieces_done(e)) return 1;
+  } else if (status_exchange(e, s)) {
+    return 1;
+  }
+  return status_finish(e, loss, s);
+}
+
+// The masked rows: head GEMM, cross-entropy, and in a training call the head's gradients and its rows of dy (the output
+// gradient of the last application; pruned: the compact rows o_dhm are that gradient).
+static int phoneme_head(PlbEngine* e, bool backward, bool prune, const bf16_t* xL, int n_masked, int64_t Tp, bf16_t* dy,
+                        float* loss, hipStream_t s) {
+  const int H = e->H, NP = e->NP;
+  const int NM = (int)rup(n_masked, 128);
+  int32_t* rows = e->at<int32_t>(e->o_rows);
+  bf16_t* hm = e->at<bf16_t>(e->o_hm);
+  float* logm = e->at<float>(e->o_logm);
+  float* lrows = e->at<float>(e->o_lrows);
+  bf16_t* dlog = e->at<bf16_t>(e->o_dlog);
+  bf16_t* dhm = e->at<bf16_t>(e->o_dhm);
+  if (backward && !prune) HIPTRY(hipMemsetAsync(dy, 0, (size_t)Tp * H * 2, s));
+  if (n_masked > 0) {
+    if (!prune) TRY(plb_launch_gather_rows(xL, H, rows, n_masked, NM, H, hm, H, s));   // (pruned: xL IS hm, the compact rows)
+    PlbGemmNT g = nt_desc(hm, e->wbf(PLB_HEAD_W), NM, NP, H);
+    g.bias = e->par(PLB_HEAD_B); g.Cf = logm; g.ldcf = 256;
+    TRY(plb_launch_gemm_nt(&g, 0, 1, s));
+    TRY(plb_launch_ce_fwd_bwd(logm, 256, NP, e->at<int32_t>(e->o_tgt), e->at<float>(e->o_w), n_masked, NM, lrows, dlog, 256, s));
+    TRY(plb_launch_sum_rows(lrows, n_masked, loss, s));
+    if (backward) {
+      if (weight_grad(e, dlog, 256, 256, hm, H, NM, NP, H, e->grd(PLB_HEAD_W), s)) return 1;
+      TRY(plb_launch_colsum(dlog, 1, (size_t)NM, 256, 256, e->grd(PLB_HEAD_B), NP, 0, e->at<float>(e->o_scratch), 8, s));
+      g = nt_desc(dlog, e->at<bf16_t>(e->o_wpT), NM, H, 256);
+      g.C = dhm; g.ldc = H;
+      TRY(plb_launch_gemm_nt(&g, 0, 0, s));
+      // (pruned: the compact gradient rows dhm ARE the output gradient of the last application's compact part)
+      if (!prune) TRY(plb_launch_scatter_rows(dhm, H, rows, n_masked, H, dy, H, s));
+    }
+  } else {  // dual-head step on a batch without masked phonemes: phoneme loss 0, its head gets zero gradients
+    HIPTRY(hipMemsetAsync(loss, 0, sizeof(float), s));
+    if (backward)
+      HIPTRY(hipMemsetAsync(e->grd(PLB_HEAD_W), 0, (size_t)(e->psize[PLB_HEAD_W] + e->psize[PLB_HEAD_B]) * 4, s));
+  }
+  if (!backward) return 0;
+  // the phoneme head's gradients are final: their all-reduce runs beside the whole backward
+  HB_W(s, e->grd(PLB_HEAD_W), (e->ptrain - e->poff[PLB_HEAD_W]) * 4, "phoneme head gradients (weight-gradient GEMM, bias column sums)");
+  if (overlapping(e) && reduce_pieces(e, kPieceHead, kPieceHead + 1, s)) return 1;
+  return 0;
+}
+
+// ---- token (grapheme) head over every valid position: fused GEMM + cross-entropy, head gradients, dH ------------
+// The fp32 logits are never stored. Pass 1 computes them tile by tile and keeps, per row and 256-column tile, the
+// maximum and the sum of exponentials (+ the target logit); a small kernel merges those into the row's
+// log-sum-exp, weight and loss; pass 2 recomputes the logits and writes the gradient (softmax - onehot) * w in
+// bf16 [Tp][NTp] (2.1 GB at 16384 x 64000), the operand of dWt = dlogits^T · H and dH = dlogits · Wt, and the
+// column-sum partials that give the bias gradient.
+static int token_head(PlbEngine* e, bool backward, const bf16_t* xL, const int64_t* token_targets, const int32_t* lengths,
+                      int B, int S, bf16_t* dy, float* loss, float* loss_parts, hipStream_t s) {
+  const int H = e->H, NT = e->NT, NTp = e->NTp, T = B * S;
+  const int64_t Tp = rup(T, 128);
+  const int tile = (Tp % 256 == 0) ? 256 : 1256;          // 256x256 or 128x256: both 256 columns wide
+  const int ntile = NTp / 256, cprows = tile == 256 ? 2 * (int)(Tp / 256) : 2 * (int)(Tp / 128);
+  float* tlrows = e->at<float>(e->o_tlrows);
+  float* tloss = e->at<float>(e->o_tloss);
+  int64_t* ttgt = e->at<int64_t>(e->o_ttgt);
+  HIPTRY(hipMemcpyAsync(ttgt, token_targets, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
+  if (Tp > T) HIPTRY(hipMemsetAsync(ttgt + T, 0, (size_t)(Tp - T) * 8, s));
+  PlbGemmNT g = nt_desc(xL, e->wbf(PLB_TOK_W), Tp, NTp, H);
+  g.bias = e->at<float>(e->o_bt);
+  g.ce_cols = NT; g.ce_tgt = ttgt;
+  g.ce_pmax = e->at<float>(e->o_tpmax); g.ce_psum = e->at<float>(e->o_tpsum); g.ce_tlogit = e->at<float>(e->o_ttl);
+  const double ce_flops = 2.0 * (double)Tp * NTp * H;
+  int tok = plb_prof_begin(PLB_K_GEMM_NT_CE, s, ce_flops, 0.0);
+  TRY(plb_launch_gemm_nt_big(&g, tile, 3, 0, s));
+  plb_prof_end(tok, s);
+  TRY(plb_launch_token_ce_combine(g.ce_pmax, g.ce_psum, ntile, g.ce_tlogit, lengths, B, S, (int)Tp,
+                                  e->at<float>(e->o_tlse), e->at<float>(e->o_tw), tlrows, s));
+  TRY(plb_launch_sum_rows(tlrows, T, tloss, s));
+  TRY(plb_launch_add_scalar(loss, loss, tloss, s));
+  if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts + 1, tloss, sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (!backward) return 0;
+  bf16_t* tdl = e->at<bf16_t>(e->o_tdl);
+  g.ce_lse = e->at<float>(e->o_tlse); g.ce_w = e->at<float>(e->o_tw);
+  g.C = tdl; g.ldc = NTp; g.colpart = e->at<float>(e->o_tcolp);
+  tok = plb_prof_begin(PLB_K_GEMM_NT_CE, s, ce_flops, 0.0);
+  TRY(plb_launch_gemm_nt_big(&g, tile, 4, 0, s));
+  plb_prof_end(tok, s);
+  TRY(plb_launch_colsum(g.colpart, 0, (size_t)cprows, NTp, NTp, e->grd(PLB_TOK_B), NT, 0, e->at<float>(e->o_tscr), 1, s));
+  float* gw = NTp == NT ? e->grd(PLB_TOK_W) : e->at<float>(e->o_tgrad);
+  if (weight_grad(e, tdl, NTp, NTp, xL, H, Tp, NTp, H, gw, s)) return 1;
+  if (NTp != NT) HIPTRY(hipMemcpyAsync(e->grd(PLB_TOK_W), gw, (size_t)NT * H * 4, hipMemcpyDeviceToDevice, s));
+  HB_W(s, e->grd(PLB_TOK_W), (e->ptotal - e->poff[PLB_TOK_W]) * 4, "token head gradients");
+  if (overlapping(e) && reduce_piece(e, e->poff[PLB_TOK_W], e->ptotal, s)) return 1;
+  // dH += dlogits · Wt, on top of the scattered phoneme-head rows (in place: a tile reads its residual
+  // before its own stores)
+  g = nt_desc(tdl, e->at<bf16_t>(e->o_wtT), Tp, H, NTp);
+  g.res = dy; g.ldr = H; g.C = dy; g.ldc = H;
+  TRY(plb_launch_gemm_nt(&g, 0, 0, s));
+  return 0;
+}
+
+// Tail of the backward on two streams.
+//  main: the four large token-major weight-gradient GEMMs (MFMA-bound, ~2 ms at config A), each followed — when a
+//        communicator is attached — by the all-reduce of the weight it completed, on the communication stream: weight i
+//        travels over xGMI while GEMM i+1 runs. The smallest GEMM goes last, so only dense.weight and the small
+//        tensors (3.2 MB of 23.4) have nothing left to hide behind.
+//  side: everything else that only needs finished gradients — embedding chain, bias and LayerNorm-affine column sums
+//        (HBM-bound) — with its own slab / scratch so nothing is shared; joined before the first piece that holds
+//        any of its outputs.
+static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const int32_t* lengths, bf16_t* dy, int B, int S,
+                                 const Rows& rw, int du_rows, hipStream_t s, hipStream_t s2, float* scratch2) {
+  const int E = e->E, H = e->H, I = e->I, L = e->L;
+  const int T = rw.T;
+  const int64_t Tp = rw.Tp;
+  const int64_t Mtot = (int64_t)L * Tp;
+  // stacked rows of the operands whose last application ran on its masked rows only (ffn.weight, ffn_output.weight,
+  // dense.weight: their slots of application L-1 hold Mc compact rows); the Q/K/V weights' operands are always full
+  const int64_t Mtot_c = e->pruned_rows ? (int64_t)(L - 1) * Tp + e->pruned_rows : Mtot;
+  // the stacks the layer loop wrote: application 0's slots, L blocks of partial rows behind them
+  const Slots st = slots(e, Tp, B, S, 0, true, e->part_rows_used, du_rows);
+  const int64_t qkvcol_all = (int64_t)L * qkvcol_rows(B, S);
+  // side stream -------------------------------------------------------------------------------------------------------
+  // (HB_R / HB_W: the happens-before audit's view of each launch — what it reads that another stream wrote, what it
+  // writes that another stream reads. The stash operands of the GEMMs are only ever written in the layer loop, which the
+  // fork orders before both streams: they are covered by the whole-workspace entry at the fork.)
+  bf16_t* evec = e->at<bf16_t>(e->o_e);
+  bf16_t* de = e->at<bf16_t>(e->o_de);
+  PlbGemmNT g = nt_desc(dy, e->at<bf16_t>(e->o_winT), Tp, E, H);
+  g.C = de; g.ldc = E;
+  HB_R(s2, dy, Tp * H * 2, "dX of application 0"); HB_W(s2, de, Tp * E * 2, "dE (map-in backward)");
+  TRY(plb_launch_gemm_nt(&g, 0, 0, s2));
+  HB_W(s2, e->at<float>(s2 != s ? e->o_slab2 : e->o_slab), (s2 != s ? e->slab2_floats : e->slab_floats) * 4, "map-in weight-gradient slab");
+  HB_W(s2, e->grd(PLB_MAP_W), e->psize[PLB_MAP_W] * 4, "map-in weight gradient");
+  if (weight_grad(e, dy, H, H, evec, E, Tp, H, E, e->grd(PLB_MAP_W), s2, s2 != s)) return 1;
+  HB_W(s2, scratch2, 512 * (3 * H > I ? 3 * H : I) * 4, "column-sum scratch of the side stream");
+  HB_W(s2, e->grd(PLB_MAP_B), H * 4, "map-in bias gradient");
+  TRY(plb_launch_colsum(dy, 1, (size_t)Tp, H, H, e->grd(PLB_MAP_B), H, 0, scratch2, 128, s2));
+  HB_W(s2, e->grd(PLB_TYPE_EMB), e->psize[PLB_TYPE_EMB] * 4, "token-type embedding gradient");
+  HIPTRY(hipMemsetAsync(e->grd(PLB_TYPE_EMB), 0, (size_t)e->psize[PLB_TYPE_EMB] * 4, s2));
+  PlbEmbed em;
+  memset(&em, 0, sizeof(em));
+  em.ids = masked_ids; em.T = T; em.S = S; em.E = E; em.V = e->V;
+  em.word = e->par(PLB_WORD_EMB); em.pos = e->par(PLB_POS_EMB); em.type0 = e->par(PLB_TYPE_EMB);
+  em.gamma = e->par(PLB_EMB_LN_W); em.beta = e->par(PLB_EMB_LN_B); em.eps = e->c.layer_norm_eps;
+  em.dout = de; em.lddo = E; em.dword = e->grd(PLB_WORD_EMB); em.dpos = e->grd(PLB_POS_EMB);
+  em.dx = e->at<float>(e->o_dxe);
+  em.partials = e->at<float>(e->o_parte); em.nblocks = e->emb_blocks;
+  if (rw.row_start) { em.row_start = rw.row_start; em.lengths = lengths; em.B = B; }
+  HB_W(s2, em.dx, Tp * E * 4, "embedding LayerNorm backward rows"); HB_W(s2, em.partials, (int64_t)e->emb_blocks * 2 * E * 4, "embedding LayerNorm partials");
+  HB_W(s2, e->grd(PLB_WORD_EMB), (e->poff[PLB_MAP_W] - e->poff[PLB_WORD_EMB]) * 4, "embedding tables' and embedding LayerNorm's gradients");
+  TRY(plb_launch_embed_bwd(&em, s2));
+  TRY(plb_launch_embed_scatter(&em, e->P, s2));
+  TRY(plb_launch_colsum(em.partials, 0, (size_t)e->emb_blocks, 2 * E, 2 * E, e->grd(PLB_EMB_LN_W), 2 * E, 0, scratch2, 1, s2));
+  // token_type row 0 receives every token's gradient = the column sums of dpos
+  TRY(plb_launch_colsum(e->grd(PLB_POS_EMB), 0, (size_t)e->P, E, E, e->grd(PLB_TYPE_EMB), E, 0, scratch2, 1, s2));
+  // Q/K/V biases: the attention-backward kernels left the column sums of every 32-row patch they stored, per application
+  // ([L][B*QT*4][3H])
+  HB_R(s2, st.qkvcol, qkvcol_all * 3 * H * 4, "Q/K/V bias partial rows");
+  HB_W(s2, e->grd(PLB_Q_B), 3 * H * 4, "Q/K/V bias gradients");
+  TRY(plb_launch_colsum(st.qkvcol, 0, (size_t)qkvcol_all, 3 * H, 3 * H, e->grd(PLB_Q_B), 3 * H, 0, scratch2, 64, s2));
+  HB_W(s2, e->grd(PLB_FFN_B), I * 4, "ffn.bias gradient");
+  if (du_rows > 0) {
+    HB_R(s2, st.ducol, (int64_t)L * du_rows * I * 4, "dU column-sum partial rows");
+    TRY(plb_launch_colsum(st.ducol, 0, (size_t)L * du_rows, I, I, e->grd(PLB_FFN_B), I, 0, scratch2, 16, s2));
+  } else {
+    HB_R(s2, st.du, Mtot_c * I * 2, "dU of every application");
+    TRY(plb_launch_colsum(st.du, 1, (size_t)Mtot_c, I, I, e->grd(PLB_FFN_B), I, 0, scratch2, 64, s2));
+  }
+  // LayerNorm-backward partials [L*blocks][3H]: dgamma | dbeta | column sums of dx. (Summing the L applications into
+  // one image inside the kernel — PlbLayerNorm.accumulate — was measured: the read-modify-write costs the main stream
+  // 2.5 us per launch to save side-stream traffic that is hidden behind the weight-gradient GEMMs anyway.) The third block is the bias
+  // gradient of the Linear that produced the LayerNorm's input (dense.bias = colsum(dpre1), ffn_output.bias =
+  // colsum(dpre2)): no pass over the stacked gradients.
+  const size_t prow = (size_t)L * e->part_rows_used;
+  HB_R(s2, st.part1, (int64_t)L * e->part_rows * 3 * H * 4, "LayerNorm-1 backward partial rows");
+  HB_W(s2, e->grd(PLB_DENSE_B), 3 * H * 4, "dense.bias + LayerNorm-1 affine gradients");
+  TRY(plb_launch_colsum(st.part1, 0, prow, 3 * H, 3 * H, e->grd(PLB_LN1_W), 2 * H, 0, scratch2, 64, s2));
+  TRY(plb_launch_copy_cols(scratch2, 64, 3 * H, 2 * H, H, e->grd(PLB_DENSE_B), s2));
+  HB_R(s2, st.part2, (int64_t)L * e->part_rows * 3 * H * 4, "LayerNorm-2 backward partial rows");
+  HB_W(s2, e->grd(PLB_LN2_W), 2 * H * 4, "LayerNorm-2 affine gradients"); HB_W(s2, e->grd(PLB_FFNO_B), H * 4, "ffn_output.bias gradient");
+  TRY(plb_launch_colsum(st.part2, 0, prow, 3 * H, 3 * H, e->grd(PLB_LN2_W), 2 * H, 0, scratch2, 64, s2));
+  TRY(plb_launch_copy_cols(scratch2, 64, 3 * H, 2 * H, H, e->grd(PLB_FFNO_B), s2));
+  if (s2 != s) HIPTRY(ev_record(e, e->ev_join, s2));
+  // main stream: shared-layer weight gradients, one token-major GEMM per weight over all L applications ------------
+  // Overlapped exchange: a weight's range travels as soon as its GEMM (+ slab reduction) has written it; the small
+  // tensors between the weights in the flat order (biases, LayerNorm, embeddings) travel behind the SIDE stream's event
+  // (below, after the first weight's piece); the smallest weight goes last.
+  const bool ov = overlapping(e);
+  const bool t8 = e->tn8_call;   // fp8 call: gradient (e5m2) x activation (e4m3) images of all L applications
+  float* const slab = e->at<float>(e->o_slab);
+  HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_Q_W), 3 * H * H * 4, "Q/K/V weight gradients");
+  if (t8 ? weight_grad8(e, st.dq8, st.x8, Mtot, 3 * H, H, F8_DQ, F8_X, e->grd(PLB_Q_W), s)
+         : weight_grad(e, st.dqkv, 3 * H, 3 * H, st.x, H, Mtot, 3 * H, H, e->grd(PLB_Q_W), s)) return 1;
+  if (ov && reduce_pieces(e, kPieceQkvW, kPieceFfnW, s)) return 1;
+  HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_FFN_W), (int64_t)I * H * 4, "ffn.weight gradient");
+  if (t8 ? weight_grad8(e, st.du8, st.a8, Mtot_c, I, H, F8_DU, F8_A, e->grd(PLB_FFN_W), s)
+         : weight_grad(e, st.du, I, I, st.a, H, Mtot_c, I, H, e->grd(PLB_FFN_W), s)) return 1;
+  if (ov && reduce_pieces(e, kPieceFfnW, kPieceSmall, s)) return 1;
+  if (ov) {
+    // The small tensors between the weights in the flat order (embeddings + map-in + LayerNorm 2 | Q/K/V biases | dense.bias +
+    // LayerNorm 1 | ffn.bias | ffn_output.bias) all come from the side stream, which is done after about three of the four
+    // GEMMs: their pieces are released by the SIDE stream's own event (everything it does in this call has been enqueued
+    // above), behind the second weight's piece in the communication stream's queue (the side stream, stretched by the
+    // GEMMs it runs beside, ends between GEMM 2 and GEMM 3: piece_trace) — five latency-bound all-reduces that
+    // travel beside the remaining GEMMs instead of after the last one (they were the step's exposed tail at world > 1:
+    // four collectives in a row behind the join). The main stream joins the side stream at the end of the tail as before.
+    if (reduce_pieces(e, kPieceSmall, kPieceFfnoW, s2)) return 1;
+  }
+  HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_FFNO_W), (int64_t)I * H * 4, "ffn_output.weight gradient");
+  if (t8 ? weight_grad8(e, st.dp8, st.g8, Mtot_c, H, I, F8_DP, F8_G, e->grd(PLB_FFNO_W), s)
+         : weight_grad(e, st.dpre2, H, H, st.g, I, Mtot_c, H, I, e->grd(PLB_FFNO_W), s)) return 1;
+  if (ov && reduce_pieces(e, kPieceFfnoW, kPieceDenseW, s)) return 1;
+  HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_DENSE_W), (int64_t)H * H * 4, "dense.weight gradient");
+  if (t8 ? weight_grad8(e, st.dp18, st.c8, Mtot_c, H, H, F8_DP1, F8_C, e->grd(PLB_DENSE_W), s)
+         : weight_grad(e, st.dpre1, H, H, st.ctx, H, Mtot_c, H, H, e->grd(PLB_DENSE_W), s)) return 1;
+  if (ov && reduce_pieces(e, kPieceDenseW, kNPieces, s)) return 1;   // the smallest weight goes last
+  return 0;
+}
+
+static int backward_tail(PlbEngine* e, const int64_t* masked_ids, const int32_t* lengths, bf16_t* dy, int B, int S,
+                         const Rows& rw, int du_rows, hipStream_t s) {
+  hipStream_t s2 = s;
+  float* scratch2 = e->at<float>(e->o_scratch);
+  // the layer loop (all of it on the caller's stream) has written the stash, the partial-row tables, dX: one entry
+  HB_W(s, e->ws, e->ws_bytes, "layer loop (whole workspace)");
+  if (e->trace_on) (void)hipEventRecord(e->tr_tail0, s);
+  if (e->side) {
+    s2 = e->side;
+    scratch2 = e->at<float>(e->o_scratch2);
+    HIPTRY(ev_record(e, e->ev_fork, s));
+    HIPTRY(ev_wait(e, s2, e->ev_fork));
+  }
+  const int rc = backward_tail_streams(e, masked_ids, lengths, dy, B, S, rw, du_rows, s, s2, scratch2);
+  // Whatever happened above, the caller's stream must not run ahead of the side stream's work (also on an error
+  // path: the side stream may hold launches that read buffers the caller is about to reuse).
+  if (s2 != s) {
+    if (rc) (void)ev_record(e, e->ev_join, s2);
+    const hipError_t je = ev_wait(e, s, e->ev_join);
+    if (!rc && je != hipSuccess) return fail("plb_loss_fwd_bwd: joining the side stream: %s", hipGetErrorString(je));
+  }
+  if (e->trace_on) { (void)hipEventRecord(e->tr_tail1, s); e->tr_tail_valid = true; }
+  if (rc) return rc;
+  // from here on the caller's stream may again touch anything in the workspace (the next call's forward will)
+  HB_W(s, e->ws, e->ws_bytes, "after the side stream's join (whole workspace)");
+  return pieces_done(e);
+}
+
+// token_targets == NULL: the reference's phoneme-only step. Otherwise dual-head: loss = phoneme loss + token loss.
+// backward == false: validate() — forward and loss only, one layer of activations, the gradient buffer untouched.
+static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, const int64_t* labels,
+                     const int64_t* token_targets, const int32_t* lengths, const int32_t* idx_offsets,
+                     const int32_t* idx_flat, int32_t n_masked, int32_t B, int32_t S, const PlbPacking* pk, float* loss,
+                     float* loss_parts, void* stream) {
+  const char* who = backward ? "plb_loss_fwd_bwd" : "plb_loss_fwd";
+  if (check_shape(e, B, S, who)) return 1;
+  drop_stash(e, "a plb_loss_* call rewrote the workspace since");
+  if (backward && e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1)", who);
+  if (backward && !e->grads) return fail("%s: no gradient buffer bound", who);
+  if (!masked_ids || !labels || !idx_offsets || !loss) return fail("%s: null argument", who);
+  if (n_masked < 0 || n_masked > e->NMcap) return fail("%s: n_masked %d out of range", who, n_masked);
+  if (token_targets && !e->NT) return fail("%s: the engine has no token head (num_tokens = 0)", who);
+  hipStream_t s = (hipStream_t)stream;
+  Rows rw;
+  if (pick_rows(e, pk, lengths, token_targets != nullptr, B, S, who, &rw)) return 1;
+  const int64_t Tp = rw.Tp;
+  if (backward && begin_training_call(e, token_targets != nullptr, s)) return 1;
+  if (n_masked == 0 && !token_targets) return zero_loss_call(e, backward, loss, s);
+
+  // the row list first: a phoneme-only call runs the post-attention part of its LAST application on these rows alone
+  // (last_application_fwd_pruned) when that is less than half of the batch; dual-head calls run every row
+  const int NM = (int)rup(n_masked, 128);
+  Prune pr = {e->at<int32_t>(e->o_rows), n_masked, NM};
+  const bool prune = prune_enabled() && n_masked > 0 && !token_targets && e->L >= 2 && 2 * (int64_t)NM <= Tp;
+  if (n_masked > 0) {
+    if (rw.row_start)
+      TRY(plb_launch_ce_prepare_packed(idx_offsets, idx_flat, labels, B, S, rw.row_start, e->at<int32_t>(e->o_rows),
+                                       e->at<int32_t>(e->o_tgt), e->at<float>(e->o_w), s));
+    else
+      TRY(plb_launch_ce_prepare(idx_offsets, idx_flat, labels, B, S, e->at<int32_t>(e->o_rows), e->at<int32_t>(e->o_tgt),
+                                e->at<float>(e->o_w), s));
+  }
+  if (backward) e->pruned_rows = prune ? NM : 0;
+  e->last_app_rows[0] = prune ? NM : Tp; e->last_app_rows[1] = Tp;
+  bf16_t* xL = nullptr;
+  if (run_encoder(e, masked_ids, lengths, B, S, rw, backward, &xL, s, prune ? &pr : nullptr)) return 1;
+  bf16_t* dy = backward ? e->at<bf16_t>(e->o_dy0) : nullptr;
+  if (phoneme_head(e, backward, prune, xL, n_masked, Tp, dy, loss, s)) return 1;
+  if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts, loss, sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (token_targets && token_head(e, backward, xL, token_targets, lengths, B, S, dy, loss, loss_parts, s)) return 1;
+  if (!backward) {
+    if (e->fp8_on) {  // forward-only call in fp8 mode: activation sites only (gradient sites saw nothing and keep theirs)
+      TRY(fp8_update_scales(e, s));
+      e->fp8_ready = true;
+    }
+    // (no collective in a loss-only call: ranks may validate different numbers of batches. A word raised here is sticky
+    // and travels with the next training call's exchange.)
+    e->last_loss = loss;
+    TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), loss, e->host_err_dev, nullptr, s));
+    return 0;
+  }
+
+  int du_rows = 0;
+  if (encoder_bwd(e, prune ? &pr : nullptr, lengths, B, S, rw, &dy, &du_rows, s)) return 1;
+  // the last launch that can raise the hand-off error word is behind us: the word travels now (beside the tail)
+  if (status_exchange(e, s)) return 1;
+  if (backward_tail(e, masked_ids, lengths, dy, B, S, rw, du_rows, s)) return 1;
+  if (e->fp8_on) {
+    // This call's maxima become the next call's scales; a calibration call arms the fp8 path. AFTER the tail: the weight-
+    // gradient GEMMs dequantise this call's images with the scales they were written with (updated before the tail, a
+    // call that follows one with 4x larger gradients came out 2x off: tools/fp8_diag.py).
+    TRY(fp8_update_scales(e, s));
+    e->fp8_ready = true;
+    e->fp8_bwd_ready = true;
+  }
+  // Last launch of the step: a hand-off of the fused LayerNorm launches that timed out — on ANY rank — turns the loss into
+  // NaN and shows in plb_poll_status; plb_adamw_step skips on the same word. No host round trip anywhere.
+  return status_finish(e, loss, s);
+}
+
+extern "C" int plb_loss_fwd_bwd(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int32_t* lengths,
+                                const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked, int32_t B,
+                                int32_t S, float* loss, void* stream) {
+  return loss_impl(e, true, masked_ids, labels, nullptr, lengths, idx_offsets, idx_flat, n_masked, B, S, nullptr, loss, nullptr,
+                   stream);
+}
+extern "C" int plb_loss_fwd_bwd_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int32_t* lengths,
+                                       const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked, int32_t B,
+                                       int32_t S, const PlbPacking* packing, float* loss, void* stream) {
+  return loss_impl(e, true, masked_ids, labels, nullptr, lengths, idx_offsets, idx_flat, n_masked, B, S, packing, loss, nullptr,
+                   stream);
+}
+
+extern "C" int plb_loss_fwd_bwd_dual(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels,
+                                     const int64_t* token_ids, const int32_t* lengths, const int32_t* idx_offsets,
+                                     const int32_t* idx_flat, int32_t n_masked, int32_t B, int32_t S, float* loss,
+                                     float* loss_parts, void* stream) {
+  if (!token_ids) return fail("plb_loss_fwd_bwd_dual: token_ids is null");
+  return loss_impl(e, true, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, nullptr, loss,
+                   loss_parts, stream);
+}
+
+extern "C" int plb_loss_fwd(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int64_t* token_ids,
+                            const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked,
+                            int32_t B, int32_t S, float* loss, float* loss_parts, void* stream) {
+  return loss_impl(e, false, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, nullptr, loss,
+                   loss_parts, stream);
+}
+extern "C" int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int64_t* token_ids,
+                                   const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat,
+                                   int32_t n_masked, int32_t B, int32_t S, const PlbPacking* packing, float* loss,
+                                   float* loss_parts, void* stream) {
+  return loss_impl(e, false, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, packing, loss,
+                   loss_parts, stream);
+}
+
+// ---- differentiable encoder: forward now, backward from a caller's gradient later (include/plbert.h) --------------------
+// plb_encode is run_encoder with the stash on and nothing pruned; the stash then waits, marked live, while the caller's
+// downstream model runs. plb_encode_bwd turns the caller's d(last_hidden_state) into the output gradient of the last
+// application (plb_launch_seed_dy) and runs the stages of a loss call's backward behind it. The phoneme head takes no
+// part: its gradient range is written as zeros (and still travels as the first piece of the exchange, as in
+// zero_loss_call: the collective sequence of a step is the same whatever the step computes).
+extern "C" int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                          const PlbPacking* pk, float* hidden, void* stream) {
+  if (check_shape(e, B, S, "plb_encode")) return 1;
+  if (e->infer) return fail("plb_encode: inference-only engine (PlbConfig.inference_only = 1): a differentiable forward keeps every application's activations");
+  if (!e->grads) return fail("plb_encode: no gradient buffer bound");
+  if (e->fp8_on) return fail("plb_encode: fp8 mode is on (the gradient sites' delayed scales belong to the pre-training loss); call plb_set_fp8(e, 0, stream) first");
+  if (!ids || !hidden) return fail("plb_encode: %s is null", !ids ? "ids" : "hidden");
+  hipStream_t s = (hipStream_t)stream;
+  Rows rw;
+  if (pick_rows(e, pk, lengths, false, B, S, "plb_encode", &rw)) return 1;
+  drop_stash(e, "a plb_encode call that failed rewrote the workspace since");
+  // (whatever an earlier call left on the side / communication stream was joined by that call's tail; audit on: checked)
+  HB_W(s, e->ws, e->ws_bytes, "plb_encode (whole workspace)");
+  e->last_app_rows[0] = e->last_app_rows[1] = rw.Tp;
+  bf16_t* x = nullptr;
+  if (run_encoder(e, ids, lengths, B, S, rw, true, &x, s)) return 1;
+  // .last_hidden_state in the caller's [B,S,H] layout, ZEROS at the pad positions in both layouts: a downstream model must
+  // not be handed numbers that carry no gradient
+  if (lengths) TRY(plb_launch_unpack_rows(x, 1, e->H, rw.row_start, lengths, B, S, e->H, hidden, s));
+  else TRY(plb_launch_bf16_to_f32(x, e->H, hidden, e->H, rw.T, e->H, s));
+  TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), nullptr, e->host_err_dev, nullptr, s));
+  e->stash_live = true;
+  e->stash_B = B; e->stash_S = S; e->stash_rows = rw.Tp; e->stash_used = rw.T; e->stash_row_start = rw.row_start;
+  return 0;
+}
+
+extern "C" int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                              const PlbPacking* pk, const float* d_hidden, void* stream) {
+  if (check_shape(e, B, S, "plb_encode_bwd")) return 1;
+  if (e->infer) return fail("plb_encode_bwd: inference-only engine (PlbConfig.inference_only = 1)");
+  if (!e->grads) return fail("plb_encode_bwd: no gradient buffer bound");
+  if (!ids || !d_hidden) return fail("plb_encode_bwd: %s is null", !ids ? "ids" : "d_hidden");
+  if (!e->stash_live) return fail("plb_encode_bwd: no live plb_encode stash: %s", e->stash_dead_by);
+  if (B != e->stash_B || S != e->stash_S)
+    return fail("plb_encode_bwd: batch %d x seq %d differs from the plb_encode call's %d x %d", B, S, e->stash_B, e->stash_S);
+  hipStream_t s = (hipStream_t)stream;
+  Rows rw;
+  // (a call that fails launches nothing and leaves what plb_last_call_rows reports alone)
+  const int64_t exec_rows[2] = {e->last_exec_rows[0], e->last_exec_rows[1]};
+  const bool plan_ok = pick_rows(e, pk, lengths, false, B, S, "plb_encode_bwd", &rw) == 0;   // (its own text names the plan)
+  const bool same = plan_ok && rw.Tp == e->stash_rows && rw.T == e->stash_used && rw.row_start == e->stash_row_start;
+  if (!same) {
+    e->last_exec_rows[0] = exec_rows[0]; e->last_exec_rows[1] = exec_rows[1];
+    if (!plan_ok) return 1;
+    return fail("plb_encode_bwd: packing plan differs from the plb_encode call's (%lld rows, %lld used, %s; that call: %lld rows, %lld used, %s)",
+                (long long)rw.Tp, (long long)rw.T, rw.row_start ? "packed" : "padded", (long long)e->stash_rows,
+                (long long)e->stash_used, e->stash_row_start ? "packed" : "padded");
+  }
+  if (begin_training_call(e, false, s)) return 1;
+  e->stash_live = false;
+  e->stash_dead_by = "plb_encode_bwd has consumed it (one backward per plb_encode)";
+  e->head_grads_live = false;
+  e->pruned_rows = 0;
+  const int64_t Tp = rw.Tp;
+  bf16_t* dy = e->at<bf16_t>(e->o_dy0);
+  HB_W(s, dy, Tp * e->H * 2, "output gradient of the last application, seeded from d_hidden");
+  TRY(plb_launch_seed_dy(d_hidden, lengths, rw.row_start, B, S, e->H, (int)Tp, dy, s));
+  // the phoneme head took no part: zeros, final before the layer loop — its piece travels where a regular step's does
+  HB_W(s, e->grd(PLB_HEAD_W), (e->ptrain - e->poff[PLB_HEAD_W]) * 4, "phoneme head gradients (zeros: plb_encode_bwd)");
+  HIPTRY(hipMemsetAsync(e->grd(PLB_HEAD_W), 0, (size_t)(e->ptrain - e->poff[PLB_HEAD_W]) * 4, s));
+  if (overlapping(e) && reduce_pieces(e, kPieceHead, kPieceHead + 1, s)) return 1;
+  int du_rows = 0;
+  if (encoder_bwd(e, nullptr, lengths, B, S, rw, &dy, &du_rows, s)) return 1;
+  if (status_exchange(e, s)) return 1;
+  if (backward_tail(e, ids, lengths, dy, B, S, rw, du_rows, s)) return 1;
+  return status_finish(e, nullptr, s);
+}

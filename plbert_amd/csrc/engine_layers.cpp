@@ -1,0 +1,566 @@
+// Launch sequences of the shared layer: embeddings + L applications forward (run_encoder), the layer loop of the backward
+// (encoder_bwd), both with the last application full or pruned to the masked rows, and the token-major weight-gradient
+// GEMMs with their split rule. Only writer of u_is_derivative, tn8_call and part_rows_used, which the forward of a call
+// leaves for its backward.
+#include "engine_internal.h"
+
+// Row splits of a token-major weight-gradient GEMM. Shapes that fit the 256x256 pipeline kernel get
+// one workgroup per CU (tiles x splits <= 256); the rest use the 128x128 kernel at ~3 workgroups per CU.
+static bool tn_big(int64_t Mtot, int Ncols, int K) { return Ncols % 256 == 0 && K % 256 == 0 && Mtot >= 8192; }
+// PLBERT_TN_SPLITS=xcd restores round 1's rule (8 * s splits, s * tiles <= 32: whole splits per XCD, but only 192-216
+// of the 256 CUs busy on the model's shapes); default: as many splits as fit one workgroup per CU.
+static bool tn_fill_chip() {
+  static const bool v = [] { const char* e = getenv("PLBERT_TN_SPLITS"); return !(e && !strcmp(e, "xcd")); }();
+  return v;
+}
+// PLBERT_TN_CUS = n (64..256, default 256): workgroups a big weight-gradient GEMM may occupy. The tail of the backward is
+// where the gradient pieces travel; RCCL's kernels need CUs of their own and the one-workgroup-per-CU grids leave 4-16
+// (dense.weight: 4). Lowering n trades GEMM width for CUs the collective finds free — a knob for the first real N > 1 run
+// (bench.py reports the tail's GEMM time with and without the exchange), read once per process.
+static int tn_cus() {
+  static const int v = [] {
+    const char* e = getenv("PLBERT_TN_CUS");
+    const int n = e ? atoi(e) : 256;
+    return (n >= 64 && n <= 256) ? n : 256;
+  }();
+  return v;
+}
+int tn_splits(int64_t Mtot, int N, int K, int* rows_per_split) {
+  const bool big = tn_big(Mtot, N, K);
+  const int tiles = big ? (N / 256) * (K / 256) : ((N + 127) / 128) * ((K + 127) / 128);
+  int splits = 768 / tiles;
+  if (big) {
+    // One workgroup per CU (128 KiB of LDS each): tiles * splits <= 256 and as close to it as the tile count allows —
+    // 24 tiles (the two FFN weights) -> 10 splits = 240 workgroups, 27 (QKV) -> 9 = 243, 9 (dense) -> 28 = 252. The
+    // kernel deals the (split, tile) pairs to the XCDs in contiguous runs (xcd_remap), so an XCD still streams a
+    // contiguous range of token rows through its L2 (a split may straddle two XCDs).
+    int s = 32 / tiles;
+    if (s < 1) s = 1;
+    splits = tiles >= 256 ? 1 : (tn_fill_chip() ? (tn_cus() / tiles > 0 ? tn_cus() / tiles : 1) : 8 * s);  // a wide output (token head) needs no row splits
+  }
+  const int64_t maxs = Mtot / 64;
+  if (splits > maxs) splits = (int)maxs;
+  if (splits < 1) splits = 1;
+  int64_t rps = rup((Mtot + splits - 1) / splits, 64);
+  splits = (int)((Mtot + rps - 1) / rps);
+  *rows_per_split = (int)rps;
+  return splits;
+}
+
+// ---- launch descriptors -----------------------------------------------------------------------------------------------
+// C[M, N] = A[M, K] · B[N, K]^T on packed operands (lda = ldb = K), every row stored: the callers add bias, residual and
+// outputs
+PlbGemmNT nt_desc(const bf16_t* A, const bf16_t* B, int64_t M, int N, int K) {
+  PlbGemmNT g;
+  memset(&g, 0, sizeof(g));
+  g.A = A; g.lda = K; g.B = B; g.ldb = K; g.M = (int)M; g.N = N; g.K = K; g.Mstore = (int)M;
+  return g;
+}
+
+static F8Op f8_op(const uint8_t* a8, const F8Site& a, const F8Weight& w, int a_bf8) { return F8Op{a8, w.img, a.deq, w.deq, a_bf8}; }
+static PlbGemmNT f8_operands(const PlbGemmNT* g, const F8Op* f8) {
+  PlbGemmNT q = *g;
+  q.A = reinterpret_cast<const bf16_t*>(f8->A8); q.B = reinterpret_cast<const bf16_t*>(f8->B8);
+  q.deq_a = f8->deq_a; q.deq_b = f8->deq_b;
+  return q;
+}
+static int gemm_nt_any(PlbGemmNT* g, int act, const F8Op* f8, hipStream_t s) {
+  if (!f8) return plb_launch_gemm_nt(g, act, 0, s);
+  PlbGemmNT q = f8_operands(g, f8);
+  return plb_launch_gemm_nt_fp8(&q, act, f8->a_bf8, s);
+}
+// the LayerNorm forms (5 / 6) and the gelu-derivative-stash forms, bf16 or fp8 operands
+static int gemm_nt_ln_any(PlbGemmNT* g, int mode, const F8Op* f8, hipStream_t s) {
+  if (!f8) return plb_launch_gemm_nt_ln(g, mode, s);
+  PlbGemmNT q = f8_operands(g, f8);
+  return plb_launch_gemm_nt_fp8_ln(&q, mode, f8->a_bf8, s);
+}
+static int gemm_nt_gelud_any(PlbGemmNT* g, int backward, const F8Op* f8, hipStream_t s) {
+  if (!f8) return plb_launch_gemm_nt_gelud(g, backward, s);
+  PlbGemmNT q = f8_operands(g, f8);
+  return plb_launch_gemm_nt_fp8_gelud(&q, backward, f8->a_bf8, s);
+}
+// the 1-byte image + running maximum a launch writes beside its output (scale in, maxima out)
+static void f8_out(PlbGemmNT* g, uint8_t* img, int ld, const F8Site& q, int bf8) {
+  g->C8 = img; g->ldc8 = ld; g->q_scale = q.scale; g->q_amax = q.amax; g->c8_bf8 = bf8;
+}
+
+// partial rows per application of the Q/K/V bias gradient that the attention backward stores in a call of B x S
+int qkvcol_rows(int B, int S) { return B * ((S + 127) / 128) * 4; }
+Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int prows, int du_rows) {
+  const int64_t H = e->H, I = e->I, sl = stash ? l : 0;
+  auto bf = [&](int64_t off, int64_t width) { return e->at<bf16_t>(off) + sl * Tp * width; };
+  auto u8 = [&](int64_t off, int64_t width) { return e->at<uint8_t>(off) + sl * Tp * width; };
+  auto f32 = [&](int64_t off, int64_t per_layer) { return e->at<float>(off) + sl * per_layer; };
+  Slots v;
+  memset(&v, 0, sizeof(v));
+  v.x = e->at<bf16_t>(e->o_x) + (int64_t)(stash ? l : l & 1) * Tp * H;
+  v.y = e->at<bf16_t>(e->o_x) + (int64_t)(stash ? l + 1 : (l + 1) & 1) * Tp * H;
+  v.qkv = bf(e->o_qkv, 3 * H); v.ctx = bf(e->o_ctx, H); v.pre1 = bf(e->o_pre1, H); v.a = bf(e->o_a, H);
+  v.u = bf(e->o_u, I); v.g = bf(e->o_g, I); v.pre2 = bf(e->o_pre2, H);
+  v.mean1 = f32(e->o_mean1, Tp); v.rstd1 = f32(e->o_rstd1, Tp); v.mean2 = f32(e->o_mean2, Tp); v.rstd2 = f32(e->o_rstd2, Tp);
+  v.lse = f32(e->o_lse, (int64_t)B * e->NH * S);
+  v.x8 = u8(e->o_x8, H); v.c8 = u8(e->o_c8, H); v.a8 = u8(e->o_a8, H); v.g8 = u8(e->o_g8, I);
+  v.x8n = e->at<uint8_t>(e->o_x8) + (stash ? l + 1 : 0) * Tp * H;   // (one slot: consumed before it is rewritten)
+  if (stash) {
+    v.dqkv = bf(e->o_dqkv, 3 * H); v.dpre1 = bf(e->o_dpre1, H); v.du = bf(e->o_du, I); v.dpre2 = bf(e->o_dpre2, H);
+    v.dp8 = u8(e->o_dp8, H); v.du8 = u8(e->o_du8, I); v.dp18 = u8(e->o_dp18, H); v.dq8 = u8(e->o_dq8, 3 * H);
+    v.part1 = f32(e->o_part1, (int64_t)prows * 3 * H); v.part2 = f32(e->o_part2, (int64_t)prows * 3 * H);
+    v.qkvcol = f32(e->o_qkvcol, (int64_t)qkvcol_rows(B, S) * 3 * H); v.ducol = f32(e->o_ducol, (int64_t)du_rows * I);
+  }
+  return v;
+}
+
+// ---- LayerNorm: in the producing GEMM's epilogue or standalone ----------------------------------------------------------
+// LayerNorm in the epilogue of the GEMM that produces its input (gemm_ln.hip, gemm_fp8_ln.hip): the shapes it exists for,
+// in bf16 and in fp8 calls alike (the fp8 forms write the 1-byte images the standalone LayerNorm kernels used to write);
+// an fp8 CALIBRATION call computes in bf16 (it must equal the bf16 path bit for bit: tests/test_gpu_fp8.py).
+static bool ln_fusable(const PlbEngine* e, int64_t Tp, int bit) {
+  const int H = e->H;
+  return (e->ln_fuse & bit) && Tp % 1024 == 0 && (H % 384 == 0 ? H / 384 : H % 256 == 0 ? H / 256 : 99) <= 4;
+}
+// Does the forward of this call stash gelu_new'(u) instead of u (plb_launch_gemm_nt_gelud)? Recorded in the engine: the
+// backward of the same call must read the stash the way the forward wrote it — the stash is in the LANE layout of the
+// tile that wrote it (256x256 in bf16 calls, 128x256 in fp8 calls), so forward and backward of a call run in one mode.
+static bool gelu_dstash(PlbEngine* e, int64_t Tp, bool f8_call) {
+  e->u_is_derivative = e->gelu_dstash_on && (f8_call ? Tp % 128 == 0 : Tp % 256 == 0) && e->I % 256 == 0;
+  return e->u_is_derivative;
+}
+static void ln_fields(const PlbEngine* e, PlbGemmNT* g, const float* gamma, const float* beta, float* mean, float* rstd) {
+  g->ln_gamma = gamma; g->ln_beta = beta; g->ln_mean = mean; g->ln_rstd = rstd; g->ln_eps = e->c.layer_norm_eps;
+  g->ln_xchg = e->at<unsigned long long>(e->o_lnx); g->ln_err = e->at<unsigned int>(e->o_lnerr);
+}
+static LnSlot ln1_slot(const PlbEngine* e, const Slots& v) {
+  return LnSlot{e->par(PLB_LN1_W), e->par(PLB_LN1_B), v.pre1, v.mean1, v.rstd1, v.part1};
+}
+static LnSlot ln2_slot(const PlbEngine* e, const Slots& v) {
+  return LnSlot{e->par(PLB_LN2_W), e->par(PLB_LN2_B), v.pre2, v.mean2, v.rstd2, v.part2};
+}
+// g (C = the LayerNorm's input, + bias / residual) and y = LayerNorm(C) on rows [0, T): the fused form 5 (GEMM + residual +
+// LayerNorm in one launch) or the GEMM and the standalone kernel. y8 (or null): y's e4m3 image under site q.
+static int gemm_ln_fwd(PlbEngine* e, PlbGemmNT* g, const F8Op* f8, bool fused, const LnSlot& ln, bf16_t* y, int T,
+                       uint8_t* y8, const F8Site& q, hipStream_t s) {
+  const int H = e->H;
+  if (fused) {
+    g->C2 = y; g->ldc2 = H;
+    ln_fields(e, g, ln.gamma, ln.beta, ln.mean, ln.rstd);
+    if (y8) f8_out(g, y8, H, q, 0);
+    TRY(gemm_nt_ln_any(g, 5, f8, s));
+    return 0;
+  }
+  TRY(gemm_nt_any(g, 0, f8, s));
+  PlbLayerNorm p;
+  memset(&p, 0, sizeof(p));
+  p.x = g->C; p.ldx = H; p.gamma = ln.gamma; p.beta = ln.beta; p.eps = e->c.layer_norm_eps;
+  p.y = y; p.ldy = H; p.T = T; p.H = H; p.mean = ln.mean; p.rstd = ln.rstd;
+  if (y8) { p.out8 = y8; p.ld8 = H; p.q_scale = q.scale; p.q_amax = q.amax; }
+  TRY(plb_launch_ln_fwd(&p, s));
+  return 0;
+}
+// standalone LayerNorm backward: dx = LN'(dy) on rows [0, T), zeros in [T, Tzero), nblocks rows of dgamma | dbeta | column
+// sums of dx; dx8 (or null): dx's e5m2 image under site q
+static int ln_bwd(PlbEngine* e, const LnSlot& ln, int nblocks, const bf16_t* dy, bf16_t* dx, int T, int Tzero, uint8_t* dx8,
+                  const F8Site& q, hipStream_t s) {
+  const int H = e->H;
+  PlbLayerNorm p;
+  memset(&p, 0, sizeof(p));
+  p.x = ln.pre; p.ldx = H; p.gamma = ln.gamma; p.T = T; p.H = H; p.Tzero = Tzero; p.mean = ln.mean; p.rstd = ln.rstd;
+  p.dy = dy; p.lddy = H; p.dx = dx; p.lddx = H; p.partials = ln.partials; p.nblocks = nblocks;
+  if (dx8) { p.out8 = dx8; p.ld8 = H; p.q_scale = q.scale; p.q_amax = q.amax; }
+  TRY(plb_launch_ln_bwd(&p, s));
+  return 0;
+}
+// g (C = the gradient of the LayerNorm's OUTPUT, + residual) and that LayerNorm's backward: the fused form 6 (the output
+// gradient is never stored: the epilogue writes dx and the partial rows) or the GEMM into C and ln_bwd
+static int gemm_ln_bwd(PlbEngine* e, PlbGemmNT* g, const F8Op* f8, bool fused, const LnSlot& ln, int nblocks, bf16_t* dx, int T,
+                       int Tzero, uint8_t* dx8, const F8Site& q, hipStream_t s) {
+  if (fused) {
+    g->C = dx; g->aux = ln.pre; g->ldaux = e->H; g->colpart = ln.partials;
+    ln_fields(e, g, ln.gamma, nullptr, ln.mean, ln.rstd);
+    if (dx8) f8_out(g, dx8, e->H, q, 1);
+    TRY(gemm_nt_ln_any(g, 6, f8, s));
+    return 0;
+  }
+  TRY(gemm_nt_any(g, 0, f8, s));
+  return ln_bwd(e, ln, nblocks, g->C, dx, T, Tzero, dx8, q, s);
+}
+
+// ---- the last application on the masked rows only --------------------------------------------------------------------
+// The reference evaluates every position of every application and then reads the masked positions of the LAST one
+// (train.py:107-131: pred[b, :len_b][idx_b]). Positions exchange information only inside attention (keys / values), so
+// behind the attention of application L-1 nothing a non-masked row computes reaches the loss — forward or backward, where
+// its output gradient is exactly zero. A phoneme-only loss call therefore runs dense + LayerNorm, the FFN and the second
+// LayerNorm of application L-1 on the ~13 % masked rows alone (gathered, padded to 128), and their backward likewise; Q/K/V
+// projection and attention stay on all rows (every key / value is needed), and so does everything below application L-1.
+// Results are those of the full evaluation (each row's arithmetic is unchanged; the weight gradients lose only exact
+// zeros from their sums). Compact GEMMs of ~2,300 rows do not fill one-tile-per-CU grids, so this part runs on the
+// small-shape launches (GEMM + LayerNorm kernels, gelu by act 1 / 2): 168 -> 75 us forward, 164 -> 86 us backward, and the
+// three weight-gradient GEMMs that stack its rows read (L-1) Tp + Mc rows instead of L Tp (measured: profiles/r05_*).
+// fp8 calls run this part in bf16 too and add the 1-byte images of the compact rows that their stacked weight-gradient
+// GEMMs read. Not taken by dual-head calls (the token loss reads every position), when more than half of the positions
+// are masked, and under PLBERT_PRUNE_LAST=0.
+static int g_prune_last = -1;   // test / tuning hook (plb_set_prune_last): -1 the environment's choice, 0 off, 1 on
+extern "C" void plb_set_prune_last(int on) { g_prune_last = on < 0 ? -1 : (on ? 1 : 0); }
+bool prune_enabled() {
+  static const bool v = [] { const char* e = getenv("PLBERT_PRUNE_LAST"); return !(e && !strcmp(e, "0")); }();
+  return g_prune_last < 0 ? v : g_prune_last != 0;
+}
+// post-attention part of application L-1 on the compact rows; leaves the final hidden rows in o_hm ([Mc][H]: the head's
+// operand) and, in a training call, the compact activations at the START of application L-1's stash slots (sl) — the
+// stacked weight-gradient operands then simply end Tp - Mc rows earlier
+static int last_application_fwd_pruned(PlbEngine* e, const Prune* pr, bool stash, bool calib, bool tn8, const Slots& sl,
+                                       const bf16_t* ctx_att, hipStream_t s) {
+  const int H = e->H, I = e->I, L = e->L, Mc = pr->Mc, n = pr->n;
+  const F8Site sA(e, F8_A, L - 1), sG(e, F8_G, L - 1), sC(e, F8_C, L - 1);
+  // training: compact tensors in their own slots (the backward and the weight gradients read them), the gathered
+  // residual rows in a backward temporary; forward-only: the one set of slots, rotated so that nothing is read and
+  // written by the same launch (ctx_att = the ctx slot: gathered into the pre1 slot, whose sum then goes to the ctx slot)
+  bf16_t* ctxc = stash ? sl.ctx : sl.pre1;
+  bf16_t* xc = stash ? e->at<bf16_t>(e->o_da) : sl.a;
+  bf16_t* pre1c = stash ? sl.pre1 : sl.ctx;
+  bf16_t* ac = stash ? sl.a : sl.pre1;
+  TRY(plb_launch_gather_rows(ctx_att, H, pr->rows, n, Mc, H, ctxc, H, s));
+  TRY(plb_launch_gather_rows(sl.x, H, pr->rows, n, Mc, H, xc, H, s));
+  PlbGemmNT g = nt_desc(ctxc, e->wbf(PLB_DENSE_W), Mc, H, H);
+  g.bias = e->par(PLB_DENSE_B); g.res = xc; g.ldr = H; g.C = pre1c; g.ldc = H;
+  const LnSlot ln1 = {e->par(PLB_LN1_W), e->par(PLB_LN1_B), pre1c, sl.mean1, sl.rstd1, nullptr};
+  if (gemm_ln_fwd(e, &g, nullptr, false, ln1, ac, Mc, nullptr, F8Site(), s)) return 1;
+  if (calib) TRY(plb_launch_amax(ac, 1, (size_t)n, H, H, sA.amax, s));
+  g = nt_desc(ac, e->wbf(PLB_FFN_W), Mc, I, H);
+  g.bias = e->par(PLB_FFN_B); g.C = sl.u; g.ldc = I; g.C2 = sl.g; g.ldc2 = I;
+  TRY(plb_launch_gemm_nt(&g, 1, 0, s));
+  if (calib) TRY(plb_launch_amax(sl.g, 1, (size_t)n, I, I, sG.amax, s));
+  g = nt_desc(sl.g, e->wbf(PLB_FFNO_W), Mc, H, I);
+  g.bias = e->par(PLB_FFNO_B); g.res = ac; g.ldr = H; g.C = sl.pre2; g.ldc = H;
+  if (gemm_ln_fwd(e, &g, nullptr, false, ln2_slot(e, sl), e->at<bf16_t>(e->o_hm), Mc, nullptr, F8Site(), s)) return 1;
+  if (tn8) {
+    // fp8 training call: this part itself runs in bf16 (2,000 rows: nothing to gain from fp8 operands), but the stacked
+    // weight-gradient GEMMs read 1-byte images of EVERY application: the compact context / a / gelu(u) rows as e4m3 images
+    // at the start of this application's image slots, under the sites' scales, their maxima reported like any other's
+    const void* src[3] = {ctxc, ac, sl.g}; const int fl[3] = {1, 1, 1};
+    const size_t nel[3] = {(size_t)Mc * H, (size_t)Mc * H, (size_t)Mc * I};
+    const float* sc[3] = {sC.scale, sA.scale, sG.scale};
+    uint8_t* dst[3] = {sl.c8, sl.a8, sl.g8};
+    float* am[3] = {sC.amax, sA.amax, sG.amax};
+    TRY(plb_launch_quantize_multi(3, src, fl, nel, sc, dst, am, s));
+  }
+  return 0;
+}
+
+// Embeddings + L applications of the shared layer. stash: keep every layer's activations (training)
+// or reuse the layer-0 slots (inference). Returns the final hidden buffer in *xout.
+// fp8 mode: EVERY large GEMM of the layer runs on 1-byte images — QKV, dense (+ LayerNorm 1), FFN up (+ gelu), FFN output
+// (+ LayerNorm 2) on e4m3 images of x, the attention context, a and gelu(u). Each image is written, with the scale its
+// site learnt in the previous call, by the launch that produces the tensor (the fused LayerNorm / gelu epilogues, the
+// attention kernel; the standalone LayerNorm kernels on shapes without a fused form), one image per layer in a training
+// call: the weight-gradient GEMMs read them all at the end of the backward. A calibration call (the first after
+// plb_set_fp8, and a training call whose gradient sites have not been seen yet) runs in bf16 and only records the maxima.
+int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B, int S, const Rows& rw, bool stash,
+                       bf16_t** xout, hipStream_t s, const Prune* pr) {
+  const int E = e->E, H = e->H, I = e->I, L = e->L;
+  const int T = rw.T;
+  const int64_t Tp = rw.Tp;
+  const bool f8 = f8_call(e, Tp, stash);
+  const bool calib = e->fp8_on && !f8;
+  if (e->fp8_on && e->fp8_wstale) TRY(fp8_quantize_weights(e, s));
+  PlbEmbed em;
+  memset(&em, 0, sizeof(em));
+  em.ids = ids; em.T = T; em.S = S; em.E = E; em.V = e->V;
+  em.word = e->par(PLB_WORD_EMB); em.pos = e->par(PLB_POS_EMB); em.type0 = e->par(PLB_TYPE_EMB);
+  em.gamma = e->par(PLB_EMB_LN_W); em.beta = e->par(PLB_EMB_LN_B); em.eps = e->c.layer_norm_eps;
+  em.out = e->at<bf16_t>(e->o_e); em.ldo = E;
+  if (rw.row_start) {   // packed: every row of the call gets a value (zeros where no token sits), the tail included
+    em.row_start = rw.row_start; em.lengths = lengths; em.B = B; em.T = (int)Tp;
+  }
+  TRY(plb_launch_embed_fwd(&em, s));
+
+  const Slots first = slots(e, Tp, B, S, 0, stash);
+  PlbGemmNT g = nt_desc(em.out, e->wbf(PLB_MAP_W), Tp, H, E);
+  g.bias = e->par(PLB_MAP_B); g.C = first.x; g.ldc = H;
+  TRY(plb_launch_gemm_nt(&g, 0, 0, s));
+  if (f8) {  // layer 0 reads the map-in output, which no LayerNorm produced: one quantisation pass
+    // (image and the site's maximum in one pass: the rows are contiguous)
+    const F8Site sX(e, F8_X, 0);
+    const void* src1[1] = {first.x}; const int bf1[1] = {1}; const size_t n1[1] = {(size_t)T * H};
+    const float* sc1[1] = {sX.scale}; uint8_t* dst1[1] = {first.x8}; float* am1[1] = {sX.amax};
+    TRY(plb_launch_quantize_multi(1, src1, bf1, n1, sc1, dst1, am1, s));
+  }
+  const bool fuse_f = ln_fusable(e, Tp, 1);
+  const bool dstash = gelu_dstash(e, Tp, f8);
+  // do the weight-gradient GEMMs of this call read the 1-byte images? Then gelu(u), dU and dQKV leave as images alone.
+  // (Needs the derivative stash: forms 1 / 2 always write their bf16 outputs.)
+  if (stash) e->tn8_call = f8 && e->fp8_tn && dstash && tn8_ok(e, (int64_t)L * Tp);
+  const bool tn8 = stash && e->tn8_call;
+
+  for (int l = 0; l < L; ++l) {
+    const Slots sl = slots(e, Tp, B, S, l, stash);
+    const F8Site sX(e, F8_X, l), sA(e, F8_A, l), sG(e, F8_G, l), sC(e, F8_C, l);
+    if (calib) TRY(plb_launch_amax(sl.x, 1, (size_t)T, H, H, sX.amax, s));
+    // fused QKV projection
+    g = nt_desc(sl.x, e->wbf(PLB_Q_W), Tp, 3 * H, H);
+    g.bias = e->par(PLB_Q_B); g.C = sl.qkv; g.ldc = 3 * H;
+    const F8Op oq = f8_op(sl.x8, sX, F8Weight(e, F8W_QKV), 0);
+    TRY(gemm_nt_any(&g, 0, f8 ? &oq : nullptr, s));
+    PlbAttn at;
+    memset(&at, 0, sizeof(at));
+    at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H;
+    at.row_start = rw.row_start;
+    // pruned last application: the attention output of ALL rows goes to a buffer of its own (training: a backward temporary
+    // that the attention backward of this application reads again — its slot holds the compact rows), then only the masked
+    // rows continue
+    const bool pruned_layer = pr != nullptr && l == L - 1;
+    bf16_t* const ctx_att = (pruned_layer && stash) ? e->at<bf16_t>(e->o_dy1) : sl.ctx;
+    at.scale = 0.125f; at.ctx = ctx_att; at.ldctx = H; at.lse = sl.lse;
+    // (pruned: nobody reads the context's image of all rows — the compact rows' image is made with the others, below)
+    if (f8 && !pruned_layer) { at.ctx8 = sl.c8; at.ldctx8 = H; at.ctx_scale = sC.scale; at.ctx_amax = sC.amax; }
+    TRY(plb_launch_attn_fwd(&at, s));
+    // packed: the tail behind the last slot (up to 1,023 rows) is written by no attention workgroup, and what sits there
+    // goes through dense / LayerNorm / FFN into the stash the weight-gradient GEMMs read: zeros, not whatever was there
+    if (rw.row_start && Tp > T) HIPTRY(hipMemsetAsync(ctx_att + (int64_t)T * H, 0, (size_t)(Tp - T) * H * 2, s));
+    if (calib) TRY(plb_launch_amax(ctx_att, 1, (size_t)T, H, H, sC.amax, s));
+    if (pruned_layer) {
+      if (last_application_fwd_pruned(e, pr, stash, calib, tn8, sl, ctx_att, s)) return 1;
+      *xout = e->at<bf16_t>(e->o_hm);
+      break;
+    }
+    // dense + residual, LayerNorm 1
+    g = nt_desc(sl.ctx, e->wbf(PLB_DENSE_W), Tp, H, H);
+    g.bias = e->par(PLB_DENSE_B); g.res = sl.x; g.ldr = H; g.C = sl.pre1; g.ldc = H;
+    const F8Op od = f8_op(sl.c8, sC, F8Weight(e, F8W_D), 0);
+    if (gemm_ln_fwd(e, &g, f8 ? &od : nullptr, fuse_f, ln1_slot(e, sl), sl.a, T, f8 ? sl.a8 : nullptr, sA, s)) return 1;
+    if (calib) TRY(plb_launch_amax(sl.a, 1, (size_t)T, H, H, sA.amax, s));
+    // FFN: u = a W1^T + b1, g = gelu_new(u); pre2 = g W2^T + b2 + a
+    g = nt_desc(sl.a, e->wbf(PLB_FFN_W), Tp, I, H);
+    g.bias = e->par(PLB_FFN_B); g.C = sl.u; g.ldc = I; g.C2 = sl.g; g.ldc2 = I;
+    if (f8) f8_out(&g, sl.g8, I, sG, 0);
+    const F8Op o1 = f8_op(sl.a8, sA, F8Weight(e, F8W_1), 0);
+    // calls on tile multiples stash gelu_new'(u) in the "u" slot (gelu_dstash): the forward's sigmoid serves the
+    // activation and its derivative, and the backward epilogue multiplies instead of evaluating the derivative. In an
+    // fp8 call gelu(u) itself leaves as its e4m3 image ALONE: nothing reads it in bf16 (FFN output GEMM and weight
+    // gradient take the image)
+    if (dstash) {
+      if (tn8) { g.C2 = nullptr; g.ldc2 = 0; }
+      TRY(gemm_nt_gelud_any(&g, 0, f8 ? &o1 : nullptr, s));
+    } else {
+      TRY(gemm_nt_any(&g, 1, f8 ? &o1 : nullptr, s));
+    }
+    if (calib) TRY(plb_launch_amax(sl.g, 1, (size_t)T, I, I, sG.amax, s));
+    // FFN output + residual, LayerNorm 2 (+ the next application's input image)
+    g = nt_desc(sl.g, e->wbf(PLB_FFNO_W), Tp, H, I);
+    g.bias = e->par(PLB_FFNO_B); g.res = sl.a; g.ldr = H; g.C = sl.pre2; g.ldc = H;
+    const F8Op o2 = f8_op(sl.g8, sG, F8Weight(e, F8W_2), 0);
+    const bool next8 = f8 && l + 1 < L;
+    if (gemm_ln_fwd(e, &g, f8 ? &o2 : nullptr, fuse_f, ln2_slot(e, sl), sl.y, T, next8 ? sl.x8n : nullptr,
+                    next8 ? F8Site(e, F8_X, l + 1) : F8Site(), s))
+      return 1;
+    *xout = sl.y;
+  }
+  return 0;
+}
+
+// dW[N,K] = A^T B over Mtot rows -> grads[which] (overwrite)
+int weight_grad(PlbEngine* e, const bf16_t* A, int lda, int Ncols, const bf16_t* Bm, int ldb, int64_t Mtot, int N,
+                       int K, float* out, hipStream_t s, bool side_slab) {
+  PlbGemmTN t;
+  memset(&t, 0, sizeof(t));
+  t.A = A; t.lda = lda; t.Ncols = Ncols; t.B = Bm; t.ldb = ldb; t.Mtot = (int)Mtot; t.N = N; t.K = K;
+  t.splits = tn_splits(Mtot, N, K, &t.rows_per_split);
+  const bool direct = t.splits == 1 && N == Ncols;  // every element is written exactly once: no slab, no reduce
+  if (!direct && (int64_t)t.splits * N * K > (side_slab ? e->slab2_floats : e->slab_floats)) return fail("weight_grad: slab too small");
+  t.slab = direct ? out : e->at<float>(side_slab ? e->o_slab2 : e->o_slab);
+  if (N == Ncols && tn_big(Mtot, Ncols, K)) {
+    const int tok = plb_prof_begin(PLB_K_GEMM_TN, s, 2.0 * (double)Mtot * N * K, 0.0);
+    TRY(plb_launch_gemm_tn_big(&t, s));
+    plb_prof_end(tok, s);
+  } else {
+    TRY(plb_launch_gemm_tn(&t, s));
+  }
+  if (!direct) TRY(plb_launch_reduce_slabs(t.slab, t.splits, (size_t)N * K, out, 0, s));
+  return 0;
+}
+
+// The same on the per-layer 1-byte images of an fp8 call: A8 = e5m2 gradient image [Mtot, N], B8 = e4m3 activation image
+// [Mtot, K] (row strides = widths in bytes), one dequantisation factor per operand site (shared by the L applications).
+int weight_grad8(PlbEngine* e, const uint8_t* A8, const uint8_t* B8, int64_t Mtot, int N, int K, int site_a, int site_b,
+                        float* out, hipStream_t s) {
+  PlbGemmTN t;
+  memset(&t, 0, sizeof(t));
+  t.A = reinterpret_cast<const bf16_t*>(A8); t.lda = N; t.Ncols = N; t.B = reinterpret_cast<const bf16_t*>(B8); t.ldb = K;
+  t.Mtot = (int)Mtot; t.N = N; t.K = K;
+  t.splits = tn_splits(Mtot, N, K, &t.rows_per_split);
+  t.rows_per_split = (int)rup(t.rows_per_split, 128);   // K-tiles of 128 tokens
+  t.splits = (int)((Mtot + t.rows_per_split - 1) / t.rows_per_split);
+  if ((int64_t)t.splits * N * K > e->slab_floats) return fail("weight_grad8: slab too small");
+  t.slab = e->at<float>(e->o_slab);
+  t.deq_a = f8_deq(e, f8_site(e, site_a, 0)); t.deq_b = f8_deq(e, f8_site(e, site_b, 0));
+  const int tok = plb_prof_begin(PLB_K_GEMM_TN_FP8, s, 2.0 * (double)Mtot * N * K, 0.0);
+  TRY(plb_launch_gemm_tn_fp8(&t, s));
+  plb_prof_end(tok, s);
+  TRY(plb_launch_reduce_slabs(t.slab, t.splits, (size_t)N * K, out, 0, s));
+  return 0;
+}
+
+// ---- layers in reverse --------------------------------------------------------------------------------------------------
+// LayerNorm 2, FFN, LayerNorm 1 and dense of application l on all rows, down to dCtx (o_dctx). dy: the application's output
+// gradient (read by the LayerNorm-2 backward of the last application only: for the others, the dX GEMM of application l+1
+// ran it — attention_bwd_dx).
+static int post_attention_bwd(PlbEngine* e, const Bwd& c, int l, const Slots& sl, const bf16_t* dy) {
+  const int H = e->H, I = e->I, T = c.T, Tp = (int)c.Tp;
+  hipStream_t s = c.s;
+  const F8Site sDP(e, F8_DP, l), sDU(e, F8_DU, l), sDP1(e, F8_DP1, l);
+  if (l == e->L - 1 && ln_bwd(e, ln2_slot(e, sl), c.prows, dy, sl.dpre2, T, Tp, c.f8 ? sl.dp8 : nullptr, sDP, s)) return 1;
+  if (c.calib) TRY(plb_launch_amax(sl.dpre2, 1, (size_t)T, H, H, sDP.amax, s));
+  // dU = (dpre2 · W2) ∘ gelu'(u)
+  PlbGemmNT g = nt_desc(sl.dpre2, e->at<bf16_t>(e->o_w2T), Tp, I, H);
+  g.aux = sl.u; g.ldaux = I; g.C = sl.du; g.ldc = I;
+  if (c.du_rows > 0) g.colpart = sl.ducol;
+  if (c.f8) f8_out(&g, sl.du8, I, sDU, 1);
+  const F8Op ou = f8_op(sl.dp8, sDP, F8Weight(e, F8W_2T), 1);
+  if (e->u_is_derivative) {   // what the forward of THIS call stashed; fp8: dU leaves as its e5m2 image alone
+    if (e->tn8_call) g.C = nullptr;
+    TRY(gemm_nt_gelud_any(&g, 1, c.f8 ? &ou : nullptr, s));
+  } else {
+    TRY(gemm_nt_any(&g, 2, c.f8 ? &ou : nullptr, s));
+  }
+  if (c.calib) TRY(plb_launch_amax(sl.du, 1, (size_t)T, I, I, sDU.amax, s));
+  // dA = dU · W1 + dpre2 is the gradient of LayerNorm 1's output. Fused: its backward runs in this GEMM's epilogue and dA
+  // is never stored (dpre1 = the gradient of the LayerNorm's input, + the dgamma | dbeta | bias-gradient partials)
+  g = nt_desc(sl.du, e->at<bf16_t>(e->o_w1T), Tp, H, I);
+  g.res = sl.dpre2; g.ldr = H; g.C = e->at<bf16_t>(e->o_da); g.ldc = H;
+  const F8Op oa = f8_op(sl.du8, sDU, F8Weight(e, F8W_1T), 1);
+  if (gemm_ln_bwd(e, &g, c.f8 ? &oa : nullptr, c.fuse_b, ln1_slot(e, sl), c.prows, sl.dpre1, T, Tp, c.f8 ? sl.dp18 : nullptr,
+                  sDP1, s))
+    return 1;
+  if (c.calib) TRY(plb_launch_amax(sl.dpre1, 1, (size_t)T, H, H, sDP1.amax, s));
+  // dCtx = dpre1 · Wd
+  g = nt_desc(sl.dpre1, e->at<bf16_t>(e->o_wdT), Tp, H, H);
+  g.C = e->at<bf16_t>(e->o_dctx); g.ldc = H;
+  const F8Op oc = f8_op(sl.dp18, sDP1, F8Weight(e, F8W_DT), 1);
+  TRY(gemm_nt_any(&g, 0, c.f8 ? &oc : nullptr, s));
+  return 0;
+}
+
+// ---- backward of the pruned last application: the compact part (LayerNorm 2, FFN, LayerNorm 1, dense) on the Mc
+// masked rows — small-shape launches, the forward's compact activations at the start of this application's slots —
+// then its gradients are scattered back to token rows (zeros elsewhere: that is what the full evaluation computes
+// there) for the attention backward and the dX GEMM, which run on all rows: dCtx into o_dctx, dpre1 into o_da.
+static int last_application_bwd_pruned(PlbEngine* e, const Bwd& c, const Slots& sl, const Prune* pr) {
+  const int H = e->H, I = e->I, L = e->L, Mc = pr->Mc, n = pr->n;
+  hipStream_t s = c.s;
+  const F8Site sDP(e, F8_DP, L - 1), sDU(e, F8_DU, L - 1), sDP1(e, F8_DP1, L - 1);
+  bf16_t* const dac = e->at<bf16_t>(e->o_da);       // dA of the compact rows, then (full) dpre1 scattered to token rows
+  bf16_t* const dctxc = e->at<bf16_t>(e->o_dy0);    // dCtx of the compact rows (dy is not used by this application)
+  bf16_t* const dctx = e->at<bf16_t>(e->o_dctx);
+  if (ln_bwd(e, ln2_slot(e, sl), c.prows, e->at<bf16_t>(e->o_dhm), sl.dpre2, Mc, Mc, nullptr, F8Site(), s)) return 1;
+  if (c.calib) TRY(plb_launch_amax(sl.dpre2, 1, (size_t)n, H, H, sDP.amax, s));
+  PlbGemmNT g = nt_desc(sl.dpre2, e->at<bf16_t>(e->o_w2T), Mc, I, H);
+  g.aux = sl.u; g.ldaux = I; g.C = sl.du; g.ldc = I;
+  TRY(plb_launch_gemm_nt(&g, 2, 0, s));   // (the forward of this part kept u itself: act 1)
+  if (c.calib) TRY(plb_launch_amax(sl.du, 1, (size_t)n, I, I, sDU.amax, s));
+  if (c.du_rows > 0) {   // this application's block of ffn.bias partial rows: its column sums in row 0, zeros below
+    TRY(plb_launch_colsum(sl.du, 1, (size_t)Mc, I, I, sl.ducol, I, 0, e->at<float>(e->o_scratch), 16, s));
+    if (c.du_rows > 1) HIPTRY(hipMemsetAsync(sl.ducol + I, 0, (size_t)(c.du_rows - 1) * I * 4, s));
+  }
+  g = nt_desc(sl.du, e->at<bf16_t>(e->o_w1T), Mc, H, I);
+  g.res = sl.dpre2; g.ldr = H; g.C = dac; g.ldc = H;
+  if (gemm_ln_bwd(e, &g, nullptr, false, ln1_slot(e, sl), c.prows, sl.dpre1, Mc, Mc, nullptr, F8Site(), s)) return 1;
+  if (c.calib) TRY(plb_launch_amax(sl.dpre1, 1, (size_t)n, H, H, sDP1.amax, s));
+  if (e->tn8_call) {   // fp8 call: the compact gradient rows as e5m2 images for the stacked weight-gradient GEMMs
+    const void* src[3] = {sl.dpre2, sl.du, sl.dpre1}; const int fl[3] = {3, 3, 3};
+    const size_t nel[3] = {(size_t)Mc * H, (size_t)Mc * I, (size_t)Mc * H};
+    const float* sc[3] = {sDP.scale, sDU.scale, sDP1.scale};
+    uint8_t* dst[3] = {sl.dp8, sl.du8, sl.dp18};
+    float* am[3] = {sDP.amax, sDU.amax, sDP1.amax};
+    TRY(plb_launch_quantize_multi(3, src, fl, nel, sc, dst, am, s));
+  }
+  g = nt_desc(sl.dpre1, e->at<bf16_t>(e->o_wdT), Mc, H, H);
+  g.C = dctxc; g.ldc = H;
+  TRY(plb_launch_gemm_nt(&g, 0, 0, s));
+  // back to token rows: dCtx and dpre1 are zero wherever no masked position sits
+  HIPTRY(hipMemsetAsync(dctx, 0, (size_t)c.Tp * H * 2, s));
+  TRY(plb_launch_scatter_rows(dctxc, H, pr->rows, n, H, dctx, H, s));
+  HIPTRY(hipMemsetAsync(dac, 0, (size_t)c.Tp * H * 2, s));   // (dA has been consumed by the LayerNorm backward above)
+  TRY(plb_launch_scatter_rows(sl.dpre1, H, pr->rows, n, H, dac, H, s));
+  return 0;
+}
+
+// End of application l's backward, on all rows: the attention backward of dCtx (o_dctx; ctx = the forward's attention
+// output), then dX = dQKV · Wqkv + res into dx — the gradient of LayerNorm 2's output of application l-1, whose backward
+// follows (in the GEMM's epilogue where fused) and writes dpre2 of application l-1.
+static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, bf16_t* ctx, const bf16_t* res,
+                            bf16_t* dx) {
+  const int H = e->H, T = c.T;
+  hipStream_t s = c.s;
+  const F8Site sDQ(e, F8_DQ, l);
+  PlbAttn at;
+  memset(&at, 0, sizeof(at));
+  at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = c.lengths; at.B = c.B; at.S = c.S; at.NH = e->NH; at.H = H; at.scale = 0.125f;
+  at.row_start = c.row_start;
+  at.ctx = ctx; at.ldctx = H; at.lse = sl.lse;
+  at.dctx = e->at<bf16_t>(e->o_dctx); at.lddctx = H; at.delta = e->at<float>(e->o_delta); at.dqkv = sl.dqkv; at.lddqkv = 3 * H;
+  at.colpart = sl.qkvcol; at.colpart_accumulate = 0;
+  if (c.f8) {   // dQKV leaves as its e5m2 image (alone, once the weight gradient reads images too)
+    at.dqkv8 = sl.dq8; at.lddqkv8 = 3 * H; at.dqkv_scale = sDQ.scale; at.dqkv_amax = sDQ.amax;
+    if (e->tn8_call) at.dqkv = nullptr;
+  }
+  // packed, S no multiple of 128: the backward kernels store no row of a sample at or past position S, and the slot of a
+  // full-length sample runs on to the next multiple of 128 — rows no launch of this call writes, which the weight-gradient
+  // GEMMs read: zeros (their true value: no token sits there), not what an earlier call left
+  if (c.row_start && c.S % 128 && at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv, 0, (size_t)T * 3 * H * 2, s));
+  TRY(plb_launch_attn_bwd(&at, s));
+  if (c.Tp > T) {
+    if (at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv + (int64_t)T * 3 * H, 0, (size_t)(c.Tp - T) * 3 * H * 2, s));
+    if (c.f8) HIPTRY(hipMemsetAsync(sl.dq8 + (int64_t)T * 3 * H, 0, (size_t)(c.Tp - T) * 3 * H, s));
+  }
+  if (c.calib) TRY(plb_launch_amax(sl.dqkv, 1, (size_t)T, 3 * H, 3 * H, sDQ.amax, s));
+  PlbGemmNT g = nt_desc(sl.dqkv, e->at<bf16_t>(e->o_wqkvT), c.Tp, H, 3 * H);
+  g.res = res; g.ldr = H; g.C = dx; g.ldc = H;
+  const F8Op ox = f8_op(sl.dq8, sDQ, F8Weight(e, F8W_QKVT), 1);
+  if (l == 0) {   // the gradient of the embeddings' map-in output: the tail takes it
+    TRY(gemm_nt_any(&g, 0, c.f8 ? &ox : nullptr, s));
+    return 0;
+  }
+  const Slots below = slots(e, c.Tp, c.B, c.S, l - 1, true, c.prows, c.du_rows);
+  return gemm_ln_bwd(e, &g, c.f8 ? &ox : nullptr, c.fuse_b, ln2_slot(e, below), c.prows, below.dpre2, T, (int)c.Tp,
+                     c.f8 ? below.dp8 : nullptr, F8Site(e, F8_DP, l - 1), s);
+}
+
+// The layer loop of the backward. dy: in, the output gradient of the last application; out, the gradient of the map-in
+// output. *du_rows: the ffn.bias partial rows per application it left for the tail.
+// fp8 mode: every dX GEMM reads e5m2 images of its gradient operand — dU = dpre2·W2 and dA = dU·W1 (+ LayerNorm 1
+// backward), dCtx = dpre1·Wd, dX = dQKV·Wqkv (+ LayerNorm 2 backward of the layer below) — written by the launch that
+// produces the gradient (fused LayerNorm-backward / gelu-backward epilogues, the attention-backward kernels, the
+// standalone LayerNorm backward), one image per layer for the weight-gradient GEMMs at the end.
+int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, int S, const Rows& rw, bf16_t** dy,
+                       int* du_rows, hipStream_t s) {
+  const int I = e->I, L = e->L;
+  Bwd c;
+  c.lengths = lengths; c.row_start = rw.row_start; c.B = B; c.S = S; c.T = rw.T; c.Tp = rw.Tp; c.s = s;
+  const int Tp = (int)c.Tp;
+  c.f8 = f8_call(e, Tp, true);
+  c.calib = e->fp8_on && !c.f8;
+  // ffn.bias gradient from the dU GEMM's epilogue: 2 partial rows per row tile of the kernel that runs it
+  c.du_rows = e->u_is_derivative ? (c.f8 ? 2 * (Tp / plb_gemm_nt_fp8_gelud_tile_rows(Tp)) : 2 * (Tp / 256))
+                                 : (c.f8 ? 2 * (Tp / 128) : plb_gemm_nt_colpart_rows(Tp, I, e->H));
+  // LayerNorm backward inside the dX GEMM that produces its output gradient (gemm_ln.hip). Rows of partials per layer:
+  // 2 per 128-row tile in the fused form (the one standalone launch left — LayerNorm 2 of the last application, whose
+  // output gradient comes from the head — then uses as many blocks), else the LayerNorm kernel's block count.
+  c.fuse_b = ln_fusable(e, Tp, 2);
+  c.prows = c.fuse_b ? 2 * Tp / 128 : e->ln_blocks;
+  e->part_rows_used = c.prows;
+  bf16_t* dx = e->at<bf16_t>(e->o_dy1);
+  for (int l = L - 1; l >= 0; --l) {
+    const Slots sl = slots(e, c.Tp, B, S, l, true, c.prows, c.du_rows);
+    if (pr && l == L - 1) {
+      // the attention output of all rows is the backward temporary o_dy1 (the ctx slot holds the compact rows)
+      if (last_application_bwd_pruned(e, c, sl, pr)) return 1;
+      if (attention_bwd_dx(e, c, l, sl, e->at<bf16_t>(e->o_dy1), e->at<bf16_t>(e->o_da), dx)) return 1;
+    } else {
+      if (post_attention_bwd(e, c, l, sl, *dy)) return 1;
+      if (attention_bwd_dx(e, c, l, sl, sl.ctx, sl.dpre1, dx)) return 1;
+    }
+    bf16_t* tmp = *dy; *dy = dx; dx = tmp;
+  }
+  *du_rows = c.du_rows;
+  return 0;
+}

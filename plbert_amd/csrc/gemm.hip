@@ -216,7 +216,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(PlbGemmTN p) {
 
 static int g_nt_tile = 0;  // 0: pick per shape; 128 / 256 / 384: force that tile where the shape allows
 extern "C" void plb_set_gemm_nt_tile(int tile) { g_nt_tile = tile; }
-extern "C" int plb_launch_gemm_nt_big(const PlbGemmNT* p, int tile, int act, int out_f32, hipStream_t stream);
 
 // Tile policy: fill 256 CUs. efficiency = tiles / (rounds * 256) with one workgroup per CU for the
 // big tiles; 128x384 moves 4/3 the operand bytes per flop of 256x256, hence the small handicap.

@@ -83,6 +83,8 @@ int plb_launch_gemm_nt_fp8_gelud(const PlbGemmNT* p, int backward, int a_bf8, hi
 int plb_gemm_nt_fp8_gelud_tile_rows(int M);  // rows of the tile that launcher uses at this M (colpart: 2 rows per row tile)
 int plb_ln_fault_take(void);  // fault injection state shared by the LayerNorm launchers (plb_debug_ln_fault)
 int plb_launch_gemm_nt(const PlbGemmNT* p, int act, int out_f32, hipStream_t stream);
+// the big-tile forms behind it (gemm_big.hip): tile 256 / 384 / 1256 = 128x256; act 3 / 4 = the fused GEMM + cross-entropy passes
+int plb_launch_gemm_nt_big(const PlbGemmNT* p, int tile, int act, int out_f32, hipStream_t stream);
 int plb_gemm_nt_colpart_rows(int M, int N, int K);  // rows of colpart written for this shape (0: unsupported)
 // Tuning / test hooks (not part of include/plbert.h): force a tile (0 = per-shape policy; 128, 256, 384, 1256 =
 // 128x256) or a K-loop form (-1 = per-launch policy, 1 interleaved, 0 staggered) for the launches that follow.

@@ -87,7 +87,7 @@ class GradReducer:
 
     The product exchange is NOT this class: ``plb_loss_fwd_bwd`` issues the all-reduce itself, piecewise, on the
     engine's communication stream, each piece behind the weight-gradient GEMM that completed it
-    (``csrc/engine.cpp: reduce_piece``); ``plb_allreduce_grads`` joins it. This class reduces the whole
+    (``csrc/engine_comm.cpp: reduce_piece``); ``plb_allreduce_grads`` joins it. This class reduces the whole
     buffer after the backward because a host-side collective cannot be ordered between the launches of one C call."""
 
     def __init__(self, group=None, device=None, force=False, side_stream=False):

@@ -1,9 +1,9 @@
 // TEST INFRASTRUCTURE, not product code: a stand-in for librccl.so that lets TWO (or more) processes sharing ONE GPU run
-// the engine's own gradient-exchange protocol (csrc/engine.cpp: plb_comm_* / reduce_piece / pieces_done) at world > 1.
+// the engine's own gradient-exchange protocol (csrc/engine_comm.cpp: plb_comm_* / reduce_piece / pieces_done) at world > 1.
 // RCCL itself refuses two ranks on one device, and the test box has one GPU, so without this the piecewise exchange had
 // only ever executed where ncclAllReduce is the identity (world 1).
 //
-// It exports exactly the seven symbols engine.cpp resolves (ncclGetUniqueId, ncclCommInitRank, ncclCommDestroy,
+// It exports exactly the seven symbols engine_comm.cpp resolves (ncclGetUniqueId, ncclCommInitRank, ncclCommDestroy,
 // ncclAllReduce, ncclBroadcast, ncclGetVersion, ncclGetErrorString) and is selected with PLBERT_RCCL_LIB=<this .so>.
 // Collectives are stream-ordered like the real ones: device -> pinned host copy, a host function on the stream that meets
 // the other ranks in a POSIX shared-memory segment (sum in rank order: deterministic), pinned host -> device copy. Every

@@ -1,5 +1,5 @@
 """The engine's OWN gradient exchange at world size 2 (-m gpu). RCCL refuses two ranks on one device and the test box has
-one GPU, so the piecewise protocol of csrc/engine.cpp (pieces issued inside plb_loss_fwd_bwd on the communication
+one GPU, so the piecewise protocol of csrc/engine_comm.cpp (pieces issued inside plb_loss_fwd_bwd on the communication
 stream, the zero-masked rank that must issue the identical collective sequence, the dual-head token piece, the coverage
 check of pieces_done) had only run where ncclAllReduce is the identity. tests/fake_rccl.cpp is a stand-in library with
 RCCL's seven entry points — stream-ordered collectives over POSIX shared memory between processes that share the GPU —

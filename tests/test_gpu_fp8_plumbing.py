@@ -7,7 +7,7 @@ launch and the delayed-scaling state machine (csrc/rowops.hip), each against a p
  * plb_launch_amax / plb_launch_quantize_multi: the site's maximum EQUALS max |source| (a maximum of the same values: no
    rounding separates them), padding columns and other sites untouched;
  * plb_launch_fp8_scales / plb_launch_fp8_scales2: a Python model written from the contract in csrc/plbert_kernels.h, driven
-   through a dozen calls in the engine's own layout (csrc/engine.cpp: fp8_update_scales), scale / deq / stats / cleared slots
+   through a dozen calls in the engine's own layout (csrc/engine_fp8.cpp: fp8_update_scales), scale / deq / stats / cleared slots
    equal bit for bit.
 NaN inputs are left out: their bytes are not part of the contract."""
 import ctypes as C
@@ -396,7 +396,7 @@ def test_fp8_scales2_cases_one_by_one():
 
 
 def test_fp8_scales_weight_update_group_one():
-    """The weight images' update (csrc/engine.cpp: fp8_quantize_weights): group 1, no stats, target 448."""
+    """The weight images' update (csrc/engine_fp8.cpp: fp8_quantize_weights): group 1, no stats, target 448."""
     Lb = bind()
     n = 8
     g = np.random.default_rng(2)

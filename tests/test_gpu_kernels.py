@@ -349,7 +349,7 @@ def test_attention_bwd_fused_writes_the_fp8_image(with_rows):
                                                 (4, 512, 12, [512, 449, 130, 512], [64, 128, 1, 200])])
 def test_attention_compact_queries(B, S, NH, lens, counts):
     """Compact-query mode (PlbAttn.qoff): the queries of a sample are a LIST of rows (the masked positions of the last
-    application, csrc/engine.cpp) gathered into a compact buffer, keys and values stay all S rows. Forward: the compact
+    application, csrc/engine_layers.cpp) gathered into a compact buffer, keys and values stay all S rows. Forward: the compact
     context rows and statistics equal the full evaluation's rows at those positions BITWISE (a query's arithmetic does not
     depend on which other queries share its tile). Backward with dO given on the compact rows only: dQ of the compact rows,
     dK / dV of all rows and the bias-gradient partial rows against torch autograd of the full attention with dO zero
