@@ -1,6 +1,7 @@
 """Helpers shared by the -m gpu tests: raw launches through the C ABI with torch tensors as buffers."""
 import ctypes as C
 
+import pytest
 import torch
 
 from plbert_amd import _lib
@@ -190,3 +191,176 @@ def assert_fp8_image(img_u8, stored, scale, bf8, rows, amax_site=None, sentinel=
     if amax_site is not None:
         want_max = float(st[smask, :cols].float().abs().max()) if bool(smask.any()) else 0.0
         assert site_max(amax_site) == want_max, (site_max(amax_site), want_max)
+
+
+# ---- the attention row contract (tests/test_gpu_attention_rows.py, tests/test_attention_rows_host.py) ---------------------
+# Every (token row, head) of ctx, dQ, dK and dV is held to the float64 evaluation of the same bf16 inputs, within 4 x the
+# WORST row of a float64 evaluation that rounds only where the kernels round. Nothing below calls a kernel: the helpers run
+# on whatever device the inputs live on, so the host file exercises them on the CPU.
+ATTN_SCALE = 0.125     # head_dim 64 (attn_args)
+ROW_FACTOR = 4.0       # kernel row error <= ROW_FACTOR x the model's worst row (fp32 summation order, hardware exp2, the
+                       # forward's lazy rescale and the scatter of a finite sample's worst row: each second order to a
+                       # bf16 rounding)
+ROW_TINY = 1e-6        # a row whose float64 norm is below this fraction of the output's largest row norm is checked
+ROW_ABS = 1e-5         # absolutely: |got| < ROW_ABS
+
+
+@pytest.fixture
+def bwd_form(request):
+    """Forces the attention backward's form: 0 = dq + dkv kernels, 1 = the single-kernel form (S <= 512); afterwards the
+    per-shape policy (-1) is back."""
+    L = _lib.lib()
+    L.plb_set_attn_bwd_fused(int(request.param))
+    yield int(request.param)
+    L.plb_set_attn_bwd_fused(-1)
+
+
+def _r16(x):
+    return x.to(torch.bfloat16).double()
+
+
+def _attention_eval(qkv, lengths, B, S, NH, q, qoff, rounded):
+    H = NH * 64
+    dev = qkv.device
+    x = qkv.double()
+    heads = lambda t, n: t.reshape(B, n, NH, 64).permute(0, 2, 1, 3)          # [B*n, H] -> [B, NH, n, 64]
+    rows = lambda t, n: t.permute(0, 2, 1, 3).reshape(B, n, H)                # and back, per sample
+    K, V = heads(x[:, H:2 * H], S), heads(x[:, 2 * H:3 * H], S)
+    lens = torch.full((B,), S, dtype=torch.long, device=dev) if lengths is None else lengths.long().clamp(1, S)
+    masked = (torch.arange(S, device=dev)[None, :] >= lens[:, None])[:, None, None, :]   # keys past the length
+    if qoff is None:
+        Sq, Nq, qvalid = S, B * S, None
+        Q = heads(x[:, :H], S)
+    else:  # compact queries: sample b's queries are rows [qoff[b], qoff[b+1]) of q, padded here to the largest count
+        off = qoff.long()
+        counts = off[1:] - off[:-1]
+        Nq, Sq = int(off[-1]), max(int(counts.max()), 1)
+        pos = torch.arange(Sq, device=dev)[None, :]
+        qvalid = pos < counts[:, None]                                        # [B, Sq]
+        Qp = torch.zeros((B, Sq, H), dtype=torch.float64, device=dev)
+        Qp[qvalid] = q.double()[:Nq, :H]                                      # row-major over (b, pos) = compact order
+        Q = heads(Qp, Sq)
+    pack = (lambda t: rows(t, Sq).reshape(B * Sq, H)) if qoff is None else (lambda t: rows(t, Sq)[qvalid])
+    stat = (lambda t: t) if qoff is None else (lambda t: t.permute(1, 0, 2)[:, qvalid])   # [B,NH,S] | [NH,Nq]
+    sraw = Q @ K.transpose(2, 3)                                              # raw scores [B, NH, Sq, S]
+    s = (sraw * ATTN_SCALE).masked_fill(masked, float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    e = torch.exp(s - m)
+    l = e.sum(-1, keepdim=True)
+    lse = (m + torch.log(l)).squeeze(-1)
+    if rounded:
+        # forward: exp(s - reference) leaves the S accumulator as a bf16 MFMA operand (acc_frag), the row sum is taken
+        # from the fp32 values, the division by it happens in fp32 at the end, and the context row is stored as bf16
+        ctx = _r16((_r16(e) @ V) / l)
+    else:
+        ctx = (e / l) @ V
+
+    def grad(dctx, ctx_stored=None):
+        """dctx by (compact) query row -> dq by (compact) query row, dk, dv [B*S, H], delta in the layout of the
+        statistics. delta = -sum(dO * O) over the context rows the kernel stored (ctx_stored) when given."""
+        if qoff is None:
+            dO = heads(dctx.double(), S)
+        else:
+            dOp = torch.zeros((B, Sq, H), dtype=torch.float64, device=dev)
+            dOp[qvalid] = dctx.double()[:Nq]
+            dO = heads(dOp, Sq)
+        if rounded:
+            # the backward recomputes P = exp2(c * S + bias) from the statistic the forward stored: fp32, minus the
+            # log-sum-exp in units of raw scores; delta is the row sum of dO with the context AS STORED (bf16)
+            lse_st = (-lse / ATTN_SCALE).float().double()
+            P = torch.exp((sraw + lse_st[..., None]) * ATTN_SCALE).masked_fill(masked, 0.0)
+        else:
+            P = e / l
+        delta = (dO * ctx).sum(-1, keepdim=True)
+        dS = P * (dO @ V.transpose(2, 3) - delta)
+        if rounded:
+            dS = _r16(dS)                                                     # operand of dS.K and dS^T.Q (all forms)
+        dq = (dS @ K) * ATTN_SCALE
+        dk = (dS.transpose(2, 3) @ Q) * ATTN_SCALE
+        dv = (_r16(P) if rounded else P).transpose(2, 3) @ dO                 # P as a bf16 operand of dV = P^T.dO
+        if rounded:
+            dq, dk, dv = _r16(dq), _r16(dk), _r16(dv)
+        if ctx_stored is None:
+            dl = -stat(delta.squeeze(-1))
+        else:
+            dl = attention_delta_terms(dctx, ctx_stored, B, S, NH, qoff)[0]
+        return pack(dq), rows(dk, S).reshape(B * S, H), rows(dv, S).reshape(B * S, H), dl
+
+    return pack(ctx), stat(lse), grad
+
+
+def attention_fp64(qkv, lengths, B, S, NH, q=None, qoff=None):
+    """float64 attention on the same (bf16-rounded) inputs: ctx [rows, H], lse (natural log, scaled scores) [B, NH, S] and
+    grad(dctx, ctx_stored=None) -> (dq, dk, dv, delta). Compact-query mode follows PlbAttn.qoff: the queries are the rows
+    of q, keys and values come from qkv; ctx, dq by compact row, lse and delta [NH, Nq]."""
+    return _attention_eval(qkv, lengths, B, S, NH, q, qoff, False)
+
+
+def attention_rounded(qkv, lengths, B, S, NH, q=None, qoff=None):
+    """attention_fp64 with the roundings the kernels make (attn.hip, attn_bwd_fused.hip, attn_common.h) and float64 in
+    between — the source of the row tolerance:
+      forward   exp(s - reference) -> bf16 before P.V; the row sum and the final division stay unrounded; ctx -> bf16
+      statistic minus log-sum-exp in raw-score units -> fp32 (PlbAttn.lse); the backward recomputes P from it
+      backward  delta from the bf16 ctx; P -> bf16 before P^T.dO only; dS = P(dP - delta) -> bf16 before dS.K and dS^T.Q;
+                dq, dk, dv -> bf16
+    Both backward forms round at the same points (the single-kernel form feeds ONE bf16 dS to dK and dQ)."""
+    return _attention_eval(qkv, lengths, B, S, NH, q, qoff, True)
+
+
+def attention_delta_terms(dctx, ctx, B, S, NH, qoff=None):
+    """(-sum(dO * O), sum |dO * O|) per (query, head) in float64, in the layout of PlbAttn.delta: [B, NH, S], or [NH, Nq]
+    for compact queries."""
+    n = B * S if qoff is None else int(qoff[-1])
+    t = (dctx.double()[:n] * ctx.double()[:n]).reshape(n, NH, 64)
+    ref, mag = -t.sum(-1), t.abs().sum(-1)
+    if qoff is None:
+        return tuple(v.reshape(B, S, NH).permute(0, 2, 1) for v in (ref, mag))
+    return ref.T, mag.T
+
+
+def check_delta(got, ref, mag, tol=1e-5):
+    """|delta - ref| <= tol x sum |dO * O| per row: 64 fp32 products accumulated in fp32 are within 64 x 2^-24 = 4e-6 of
+    the absolute sum."""
+    err = (got.double() - ref).abs()
+    bad = err > tol * mag
+    if bool(bad.any()):
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"delta{list(i)}: got {float(got[i])!r}, want {float(ref[i])!r}: off by {float(err[i]):.3e} > "
+                             f"{tol:g} x {float(mag[i]):.3e}; {int(bad.sum())} rows over")
+
+
+def check_rows(name, got, ref, model, NH, valid=None, n_abs=0, factor=ROW_FACTOR):
+    """The row contract for one output. got / ref / model [R, NH*64]: the kernel's rows, the float64 reference, the rounding
+    model. valid [R] bool: rows outside it (padded keys / queries) must be exactly 0 in got. Of the valid (row, head)
+    pairs, those whose reference norm is below ROW_TINY of the largest are held to |got| < ROW_ABS, and there must be
+    exactly n_abs of them; every other pair is held to ||got - ref|| / ||ref|| <= factor x the model's worst such pair.
+    Returns {"model": the model's maximum, "got": got's maximum, "bound", "n_abs"}; raises AssertionError naming the row."""
+    R = ref.shape[0]
+    g, f, mo = (t.double()[:R].reshape(R, NH, 64) for t in (got, ref, model))
+    ok = torch.ones(R, dtype=torch.bool, device=ref.device) if valid is None else valid.to(ref.device)
+    if not bool((g[~ok] == 0).all()):
+        r = int((g[~ok] != 0).flatten(1).any(1).nonzero()[0])
+        raise AssertionError(f"{name}: padded row {int((~ok).nonzero()[r])} is not exactly zero")
+    den = f.norm(dim=-1)
+    okh = ok[:, None].expand(R, NH)
+    tiny = okh & (den < ROW_TINY * den[okh].max())
+    rel = okh & ~tiny
+    stats = {"model": 0.0, "got": 0.0, "bound": 0.0, "n_abs": int(tiny.sum())}
+    if stats["n_abs"] != n_abs:
+        raise AssertionError(f"{name}: {stats['n_abs']} (row, head) pairs fall under the absolute check, {n_abs} predicted")
+    if n_abs:
+        worst = g.abs().amax(-1).masked_fill(~tiny, 0.0)
+        if float(worst.max()) >= ROW_ABS:
+            r, h = divmod(int(worst.argmax()), NH)
+            raise AssertionError(f"{name}: row {r} head {h} has a zero reference, got |x| up to {float(worst.max()):.3e}")
+    if bool(rel.any()):
+        eg = ((g - f).norm(dim=-1) / den.clamp_min(1e-300)).masked_fill(~rel, 0.0)
+        em = ((mo - f).norm(dim=-1) / den.clamp_min(1e-300)).masked_fill(~rel, 0.0)
+        stats.update(model=float(em.max()), got=float(eg.max()), bound=factor * float(em.max()))
+        if not (torch.isfinite(eg).all() and stats["got"] <= stats["bound"]):
+            eg = torch.nan_to_num(eg, nan=float("inf"))
+            r, h = divmod(int(eg.argmax()), NH)
+            raise AssertionError(f"{name}: row {r} head {h} is off by {float(eg[r, h]):.3e} of its norm; the bound is "
+                                 f"{factor:g} x the rounding model's worst row {stats['model']:.3e} = {stats['bound']:.3e}; "
+                                 f"{int((eg > stats['bound']).sum())} of {int(rel.sum())} rows over")
+    return stats
