@@ -364,3 +364,72 @@ def check_rows(name, got, ref, model, NH, valid=None, n_abs=0, factor=ROW_FACTOR
                                  f"{factor:g} x the rounding model's worst row {stats['model']:.3e} = {stats['bound']:.3e}; "
                                  f"{int((eg > stats['bound']).sum())} of {int(rel.sum())} rows over")
     return stats
+
+
+# ---- call-history independence (tests/test_call_history_host.py) -----------------------------------------------------------
+# A call on a used engine must leave the gradient buffer a fresh engine's call leaves, bit for bit. When two gradient buffers
+# that should be the same are not, the report names the parameter tensors and the coordinates: that is the way back to the
+# launch that summed a stale row.
+def _bits(t):
+    t = t.detach().reshape(-1)
+    assert t.dtype == torch.float32, t.dtype
+    return t.contiguous().view(torch.int32)
+
+
+def first_difference(engine_like, a, b):
+    """a, b: two flat fp32 buffers laid out as ``engine_like.layout`` says ({name: (offset, size, shape)}, as
+    HipEngine.layout; the buffers may end before the layout does, e.g. grads[:trainable]). Returns [] when they are the
+    same, else one record per differing tensor, in layout order: dict(name, count, index — the first differing element as
+    a coordinate of the tensor's shape —, a, b — the two values there —, a_bits, b_bits). Elements no tensor of the layout
+    covers are reported under the name "(outside the layout)" with a flat index.
+
+    "The same" is equality of BIT PATTERNS, with one exception: a NaN equals a NaN of identical bits (a float == would call
+    them different), a NaN differs from any number and from a NaN of other bits, 1.0 differs from its neighbour. The
+    exception: -0.0 and +0.0 are equal, as for torch.equal — an fp32 sum that started at +0 and added -0, or a product of
+    an exact zero with a stale value of either sign, is not a leak."""
+    ia, ib = _bits(a), _bits(b)
+    if ia.shape != ib.shape:
+        raise ValueError(f"buffers of {ia.numel()} and {ib.numel()} elements")
+    diff = (ia != ib) & (((ia | ib) & 0x7FFFFFFF) != 0)
+    if not bool(diff.any()):
+        return []
+    n = ia.numel()
+    covered = torch.zeros(n, dtype=torch.bool, device=diff.device)
+    out = []
+
+    def record(name, d, base, shape):
+        flat = int(d.nonzero()[0])
+        i = base + flat
+        coord = [] if shape else [flat]
+        for dim in reversed(shape or ()):   # needs only the shape: also given for a tensor that the buffer ends inside
+            flat, c = divmod(flat, dim)
+            coord.insert(0, c)
+        out.append(dict(name=name, count=int(d.sum()), index=[int(c) for c in coord],
+                        a=float(a.reshape(-1)[i]), b=float(b.reshape(-1)[i]),
+                        a_bits=int(ia[i]) & 0xFFFFFFFF, b_bits=int(ib[i]) & 0xFFFFFFFF))
+
+    for name, (off, size, shape) in engine_like.layout.items():
+        lo, hi = min(off, n), min(off + size, n)
+        if hi <= lo:
+            continue
+        covered[lo:hi] = True
+        d = diff[lo:hi]
+        if bool(d.any()):
+            record(name, d, lo, tuple(shape))
+    rest = diff & ~covered
+    if bool(rest.any()):
+        record("(outside the layout)", rest, 0, None)
+    return out
+
+
+def format_difference(records):
+    return "; ".join(f"{r['name']}: {r['count']} element{'s' * (r['count'] != 1)}, first at {r['index']}: "
+                     f"{r['a']!r} (0x{r['a_bits']:08x}) vs {r['b']!r} (0x{r['b_bits']:08x})" for r in records)
+
+
+def assert_same_bits(engine_like, a, b, what):
+    """Raises AssertionError with first_difference's report, e.g. "gradients after H1: ...value.weight: 31 elements, first
+    at [17, 203]: 1.5 (0x3fc00000) vs 1.25 (0x3fa00000)"."""
+    rec = first_difference(engine_like, a, b)
+    if rec:
+        raise AssertionError(f"{what}: {len(rec)} tensor{'s' * (len(rec) != 1)} differ — {format_difference(rec)}")
