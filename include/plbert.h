@@ -247,8 +247,9 @@ int plb_last_application_rows(const PlbEngine* e, int64_t* rows, int64_t* of);
  * engine checks what it can see on the host: rows, used). Nothing in a packed call synchronises with the host: for a fixed
  * plan it is graph-capturable like the padded call. Same results as the padded call up to bf16 summation order in the
  * weight gradients (each valid row's arithmetic is unchanged). A call runs PADDED, with the padded call's results bit for
- * bit, when the plan is the padded layout, when lengths == NULL, for dual-head calls (token_ids / token_logits given) and
- * while fp8 mode is on. plb_forward_packed: hidden / phoneme_logits at pad positions (s >= lengths[b]) are ZEROS (the padded
+ * bit, when the plan is the padded layout (S < 128 included: such a batch has no plan that packs), when lengths == NULL,
+ * while fp8 mode is on, for plb_forward_packed with token_logits (a full [B,S,NT] fp32 output is a debugging output, not a
+ * hot path) and for dual-head loss calls (token_ids given) unless plb_set_packed_dual is on. plb_forward_packed: hidden / phoneme_logits at pad positions (s >= lengths[b]) are ZEROS (the padded
  * path leaves values there that nothing reads). plb_pooler takes the [B,S,H] output as before.
  * Rows of the packed axis that hold no token are given defined values in every call (zeros from the embeddings, computed
  * like padded rows inside a slot, a zeroed attention output and zero gradients in the tail), so a packed call does not
@@ -270,6 +271,23 @@ int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* 
                         const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked,
                         int32_t B, int32_t S, const PlbPacking* packing, float* loss, float* loss_parts, void* stream);
 int plb_last_call_rows(const PlbEngine* e, int64_t* rows, int64_t* of);
+/* Token-packed DUAL-HEAD loss calls (opt-in on top of the plan; off by default, engine state, no device state touched, a
+ * live plb_encode stash stays live). Off: every call with token_ids runs padded, plan or not, as above. On: a dual-head
+ * loss call that is given a plan that packs — plb_loss_fwd_bwd_dual_packed, plb_loss_fwd_packed with token_ids — runs the
+ * encoder AND the token head on the plan's row axis: the head's three rows x num_tokens GEMMs, its weight-gradient GEMM and
+ * the bf16 [rows][num_tokens] logit-gradient image shrink with the executed rows. Same results as the padded call up to
+ * summation order: each valid row's forward arithmetic, token logit statistics and logit-gradient row are unchanged; the
+ * token-loss sum and the weight / bias gradient sums run over another row set (rows that hold no token contribute exact
+ * zeros in both layouts). plb_last_call_rows reports rows < of for such a call; plb_last_application_rows stays rows == of
+ * (a dual-head call prunes nothing). Still padded with the switch on: fp8 mode (the delayed-scale maxima of the padded
+ * call include rows a packed call does not run), S < 128 and plans that are the padded layout, lengths == NULL, and
+ * plb_forward_packed with token_logits.
+ * plb_loss_fwd_bwd_dual_packed: plb_loss_fwd_bwd_dual with a plan; packing == NULL, or the switch off: exactly
+ * plb_loss_fwd_bwd_dual. */
+int plb_set_packed_dual(PlbEngine* e, int32_t on);
+int plb_loss_fwd_bwd_dual_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int64_t* token_ids,
+                                 const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked,
+                                 int32_t B, int32_t S, const PlbPacking* packing, float* loss, float* loss_parts, void* stream);
 /* ---- differentiable encoder: fine-tuning a checkpoint inside a downstream model ----
  * Stands in for the reference README's "Finetuning" use (README.md:36-119):
  *   bert_dur = model.bert(texts, attention_mask=(~text_mask).int()).last_hidden_state   -> plb_encode

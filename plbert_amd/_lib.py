@@ -55,7 +55,8 @@ PUBLIC_SYMBOLS = [
     "plb_sync_weights", "plb_forward", "plb_pooler", "plb_loss_fwd_bwd", "plb_loss_fwd", "plb_loss_fwd_bwd_dual", "plb_adamw_step",
     "plb_set_fp8", "plb_fp8_state", "plb_fp8_stats", "plb_token_head_steps", "plb_set_token_head_steps", "plb_comm_unique_id", "plb_comm_init", "plb_comm_destroy",
     "plb_comm_info", "plb_comm_pieces", "plb_last_application_rows", "plb_last_call_rows",
-    "plb_packing_plan", "plb_forward_packed", "plb_loss_fwd_bwd_packed", "plb_loss_fwd_packed", "plb_encode", "plb_encode_bwd", "plb_status", "plb_status_ex", "plb_poll_status", "plb_status_export", "plb_status_import", "plb_broadcast_params", "plb_set_grad_overlap", "plb_allreduce_grads", "plb_apply_mask",
+    "plb_packing_plan", "plb_forward_packed", "plb_loss_fwd_bwd_packed", "plb_loss_fwd_packed", "plb_set_packed_dual",
+    "plb_loss_fwd_bwd_dual_packed", "plb_encode", "plb_encode_bwd", "plb_status", "plb_status_ex", "plb_poll_status", "plb_status_export", "plb_status_import", "plb_broadcast_params", "plb_set_grad_overlap", "plb_allreduce_grads", "plb_apply_mask",
     "plb_mask_batch", "plb_profile_enable", "plb_profile_num_classes", "plb_profile_class_name", "plb_profile_read",
     # test / tuning hooks (documented as such at the end of the header)
     "plb_debug_skip_piece", "plb_debug_ln_fault", "plb_debug_hb_audit", "plb_debug_hb_report", "plb_comm_trace", "plb_comm_trace_read",
@@ -233,6 +234,15 @@ def lib():
         L.plb_encode_bwd.argtypes = [vp, vp, vp, i32, i32, C.POINTER(PlbPacking), vp, vp]
         L.plb_launch_seed_dy.restype = C.c_int
         L.plb_launch_seed_dy.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    if hasattr(L, "plb_set_packed_dual"):   # (an A/B build named by PLBERT_HIP_LIB may predate packed dual-head calls)
+        L.plb_set_packed_dual.restype = C.c_int
+        L.plb_set_packed_dual.argtypes = [vp, i32]
+        L.plb_loss_fwd_bwd_dual_packed.restype = C.c_int
+        L.plb_loss_fwd_bwd_dual_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(PlbPacking), vp, vp, vp]
+        L.plb_launch_pack_token_targets.restype = C.c_int
+        L.plb_launch_pack_token_targets.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.plb_launch_token_ce_combine_packed.restype = C.c_int
+        L.plb_launch_token_ce_combine_packed.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.plb_status_export.restype = C.c_int
     L.plb_status_export.argtypes = [vp, vp, vp]
     L.plb_status_import.restype = C.c_int

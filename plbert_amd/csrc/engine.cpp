@@ -385,6 +385,13 @@ extern "C" int plb_last_call_rows(const PlbEngine* e, int64_t* rows, int64_t* of
   return 0;
 }
 
+// Host state only: nothing on the device changes and a live plb_encode stash stays live.
+extern "C" int plb_set_packed_dual(PlbEngine* e, int32_t on) {
+  if (!e) return fail("plb_set_packed_dual: null engine");
+  e->packed_dual = on != 0;
+  return 0;
+}
+
 extern "C" int32_t plb_token_head_steps(const PlbEngine* e) { return e ? e->tok_steps : -1; }
 extern "C" int plb_set_token_head_steps(PlbEngine* e, int32_t steps) {
   if (!e || steps < 0) return fail("plb_set_token_head_steps: bad argument");

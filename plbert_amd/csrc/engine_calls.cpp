@@ -1,7 +1,7 @@
 // Call-level stages of the engine: row selection of a padded or token-packed call, the heads, the stages of a loss call and
 // the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd. Only
 // writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
-// last_exec_rows, tok_grads_live and head_grads_live.
+// last_exec_rows, tok_grads_live and head_grads_live. (packed_dual: plb_set_packed_dual, engine.cpp.)
 #include "engine_internal.h"
 
 // Every call that writes the workspace or moves the weights ends the life of a plb_encode stash.
@@ -18,8 +18,9 @@ static int check_shape(const PlbEngine* e, int B, int S, const char* who) {
 
 static Rows padded_rows(int B, int S) { return Rows{nullptr, B * S, rup(B * S, 128)}; }
 // Does this call run packed? It runs padded — same results as without a plan — when the plan saves nothing (every
-// sample full, or slots that add up to the padded rows), for dual-head calls and while fp8 mode is on.
-static int pick_rows(PlbEngine* e, const PlbPacking* pk, const int32_t* lengths, bool dual, int B, int S, const char* who,
+// sample full, or slots that add up to the padded rows), while fp8 mode is on, and when the caller says so (`padded`: a
+// forward call that returns token logits, a dual-head loss call while plb_set_packed_dual is off).
+static int pick_rows(PlbEngine* e, const PlbPacking* pk, const int32_t* lengths, bool padded, int B, int S, const char* who,
                      Rows* out) {
   *out = padded_rows(B, S);
   e->last_exec_rows[0] = e->last_exec_rows[1] = (int64_t)B * S;
@@ -27,7 +28,7 @@ static int pick_rows(PlbEngine* e, const PlbPacking* pk, const int32_t* lengths,
   if (pk->rows < 128 || pk->rows % 128 || pk->used < 1 || pk->used > pk->rows)
     return fail("%s: packing plan of %d rows (%d used) is not one plb_packing_plan made", who, pk->rows, pk->used);
   if (pk->rows > out->Tp) return fail("%s: packing plan of %d rows exceeds the call's %lld", who, pk->rows, (long long)out->Tp);
-  if (!lengths || dual || e->fp8_on || pk->rows == out->Tp) return 0;   // (rows == Tp: the plan is the padded layout)
+  if (!lengths || padded || e->fp8_on || pk->rows == out->Tp) return 0;   // (rows == Tp: the plan is the padded layout)
   if (pk->used % 128) return fail("%s: packing plan with %d used rows: slots are multiples of 128", who, pk->used);
   *out = Rows{pk->row_start, pk->used, pk->rows};
   e->last_exec_rows[0] = pk->rows;
@@ -43,7 +44,8 @@ static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths
   hipStream_t s = (hipStream_t)stream;
   const int H = e->H;
   Rows rw;
-  // (token logits: the dual-head model runs padded. Phoneme logits of a packed call pass, as [Tp][NP] fp32, through a slot
+  // (token logits: a full [B,S,NT] fp32 output is a debugging output and runs padded, whatever plb_set_packed_dual says.
+  // Phoneme logits of a packed call pass, as [Tp][NP] fp32, through a slot
   // of the forward-only call that is free once the encoder is done: QKV (6H bytes per row) or the FFN's u (2I))
   const int64_t lg_off = 4 * e->NP <= 6 * H ? e->o_qkv : 4 * e->NP <= 2 * e->I ? e->o_u : -1;
   if (pick_rows(e, pk, lengths, token_logits != nullptr || lg_off < 0, B, S, "plb_forward", &rw)) return 1;
@@ -191,17 +193,24 @@ static int phoneme_head(PlbEngine* e, bool backward, bool prune, const bf16_t* x
 // log-sum-exp, weight and loss; pass 2 recomputes the logits and writes the gradient (softmax - onehot) * w in
 // bf16 [Tp][NTp] (2.1 GB at 16384 x 64000), the operand of dWt = dlogits^T · H and dH = dlogits · Wt, and the
 // column-sum partials that give the bias gradient.
+// Token-packed call (rw.row_start): the row axis is the plan's — Tp = rw.Tp rows, the targets and the row weights placed by
+// the plan, zeros on the rows that hold no token: pass 2 selects an exact 0 for a row of weight 0, so those rows add nothing
+// to the head's gradients or to dH.
 static int token_head(PlbEngine* e, bool backward, const bf16_t* xL, const int64_t* token_targets, const int32_t* lengths,
-                      int B, int S, bf16_t* dy, float* loss, float* loss_parts, hipStream_t s) {
+                      int B, int S, const Rows& rw, bf16_t* dy, float* loss, float* loss_parts, hipStream_t s) {
   const int H = e->H, NT = e->NT, NTp = e->NTp, T = B * S;
-  const int64_t Tp = rup(T, 128);
+  const int64_t Tp = rw.Tp;
   const int tile = (Tp % 256 == 0) ? 256 : 1256;          // 256x256 or 128x256: both 256 columns wide
   const int ntile = NTp / 256, cprows = tile == 256 ? 2 * (int)(Tp / 256) : 2 * (int)(Tp / 128);
   float* tlrows = e->at<float>(e->o_tlrows);
   float* tloss = e->at<float>(e->o_tloss);
   int64_t* ttgt = e->at<int64_t>(e->o_ttgt);
+  if (rw.row_start) {
+    TRY(plb_launch_pack_token_targets(token_targets, lengths, rw.row_start, B, S, (int)Tp, ttgt, s));
+  } else {
   HIPTRY(hipMemcpyAsync(ttgt, token_targets, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
   if (Tp > T) HIPTRY(hipMemsetAsync(ttgt + T, 0, (size_t)(Tp - T) * 8, s));
+  }
   PlbGemmNT g = nt_desc(xL, e->wbf(PLB_TOK_W), Tp, NTp, H);
   g.bias = e->at<float>(e->o_bt);
   g.ce_cols = NT; g.ce_tgt = ttgt;
@@ -210,9 +219,15 @@ static int token_head(PlbEngine* e, bool backward, const bf16_t* xL, const int64
   int tok = plb_prof_begin(PLB_K_GEMM_NT_CE, s, ce_flops, 0.0);
   TRY(plb_launch_gemm_nt_big(&g, tile, 3, 0, s));
   plb_prof_end(tok, s);
+  if (rw.row_start) {
+    TRY(plb_launch_token_ce_combine_packed(g.ce_pmax, g.ce_psum, ntile, g.ce_tlogit, lengths, rw.row_start, B, S, (int)Tp,
+                                           e->at<float>(e->o_tlse), e->at<float>(e->o_tw), tlrows, s));
+    TRY(plb_launch_sum_rows(tlrows, (int)Tp, tloss, s));
+  } else {
   TRY(plb_launch_token_ce_combine(g.ce_pmax, g.ce_psum, ntile, g.ce_tlogit, lengths, B, S, (int)Tp,
                                   e->at<float>(e->o_tlse), e->at<float>(e->o_tw), tlrows, s));
   TRY(plb_launch_sum_rows(tlrows, T, tloss, s));
+  }
   TRY(plb_launch_add_scalar(loss, loss, tloss, s));
   if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts + 1, tloss, sizeof(float), hipMemcpyDeviceToDevice, s));
   if (!backward) return 0;
@@ -398,7 +413,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   if (token_targets && !e->NT) return fail("%s: the engine has no token head (num_tokens = 0)", who);
   hipStream_t s = (hipStream_t)stream;
   Rows rw;
-  if (pick_rows(e, pk, lengths, token_targets != nullptr, B, S, who, &rw)) return 1;
+  if (pick_rows(e, pk, lengths, token_targets != nullptr && !e->packed_dual, B, S, who, &rw)) return 1;
   const int64_t Tp = rw.Tp;
   if (backward && begin_training_call(e, token_targets != nullptr, s)) return 1;
   if (n_masked == 0 && !token_targets) return zero_loss_call(e, backward, loss, s);
@@ -423,7 +438,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   bf16_t* dy = backward ? e->at<bf16_t>(e->o_dy0) : nullptr;
   if (phoneme_head(e, backward, prune, xL, n_masked, Tp, dy, loss, s)) return 1;
   if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts, loss, sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (token_targets && token_head(e, backward, xL, token_targets, lengths, B, S, dy, loss, loss_parts, s)) return 1;
+  if (token_targets && token_head(e, backward, xL, token_targets, lengths, B, S, rw, dy, loss, loss_parts, s)) return 1;
   if (!backward) {
     if (e->fp8_on) {  // forward-only call in fp8 mode: activation sites only (gradient sites saw nothing and keep theirs)
       TRY(fp8_update_scales(e, s));
@@ -473,6 +488,15 @@ extern "C" int plb_loss_fwd_bwd_dual(PlbEngine* e, const int64_t* masked_ids, co
                                      float* loss_parts, void* stream) {
   if (!token_ids) return fail("plb_loss_fwd_bwd_dual: token_ids is null");
   return loss_impl(e, true, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, nullptr, loss,
+                   loss_parts, stream);
+}
+
+extern "C" int plb_loss_fwd_bwd_dual_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels,
+                                            const int64_t* token_ids, const int32_t* lengths, const int32_t* idx_offsets,
+                                            const int32_t* idx_flat, int32_t n_masked, int32_t B, int32_t S,
+                                            const PlbPacking* packing, float* loss, float* loss_parts, void* stream) {
+  if (!token_ids) return fail("plb_loss_fwd_bwd_dual_packed: token_ids is null");
+  return loss_impl(e, true, masked_ids, labels, token_ids, lengths, idx_offsets, idx_flat, n_masked, B, S, packing, loss,
                    loss_parts, stream);
 }
 

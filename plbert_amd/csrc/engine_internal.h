@@ -95,6 +95,8 @@ struct PlbEngine {
   bool gelu_dstash_on = true;   // PLBERT_GELU_STASH=u restores the pre-activation stash
   bool fp8_tn = true;           // fp8 calls run the weight-gradient GEMMs on the 1-byte images too (PLBERT_FP8_TN=0: bf16 operands)
   int f8n = 0;
+  // ---- caller's switches: engine.cpp ----
+  bool packed_dual = false;     // plb_set_packed_dual: dual-head loss calls follow a plan that packs (off: they run padded)
   // ---- workspace offsets (bytes): engine.cpp (plb_create) ----
   int64_t o_wbf, o_wqkvT, o_wdT, o_w1T, o_w2T, o_wpT, o_winT;
   int64_t o_e, o_x, o_qkv, o_ctx, o_pre1, o_a, o_u, o_g, o_pre2;

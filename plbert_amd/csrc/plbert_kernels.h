@@ -266,6 +266,17 @@ int plb_launch_sum_rows(const float* x, int n, float* out, hipStream_t stream);
 int plb_launch_token_ce_combine(const float* pmax, const float* psum, int ntiles, const float* tlogit,
                                 const int32_t* lengths, int B, int S, int rows, float* lse, float* w, float* loss_rows,
                                 hipStream_t stream);
+// The same merge on token-packed rows (row for row the same operations: a valid row's lse / w / loss are bit-equal to the
+// padded launch's): row row_start[b] + s, s < lengths[b], gets lse, w = 1 / (B * len_b) and its loss row; every other one of
+// the `rows` rows (the rest of a 128-row slot, the tail behind row_start[B]) gets lse = w = loss = 0.
+int plb_launch_token_ce_combine_packed(const float* pmax, const float* psum, int ntiles, const float* tlogit,
+                                       const int32_t* lengths, const int32_t* row_start, int B, int S, int rows, float* lse,
+                                       float* w, float* loss_rows, hipStream_t stream);
+// Token targets of a packed dual-head call: every one of the `rows` (a multiple of 128) entries of out (int64, 16-byte
+// aligned) is written exactly once — token_ids[b,s] on row row_start[b] + s for s < lengths[b], 0 on every other row.
+// token_ids ([B,S] int64) is not read at pad positions.
+int plb_launch_pack_token_targets(const int64_t* token_ids, const int32_t* lengths, const int32_t* row_start, int B, int S,
+                                  int rows, int64_t* out, hipStream_t stream);
 int plb_launch_add_scalar(float* out, const float* a, const float* b, hipStream_t stream);
 
 // Device-side word masking (mask.hip): labels [B,S] -> masked [B,S], counts [B], idx_padded [B,S],

@@ -874,7 +874,44 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* logits, int ldl, i
     *(uint2*)(dlogits + (size_t)r * ldd + c) = o;
   }
 }
-// Fused token-head CE, between its two GEMM passes: one wave per row merges the per-tile (max, sum) pairs.
+// Token targets of a packed dual-head call: ONE pass writes every one of the `rows` int64 targets exactly once —
+// token_ids[b, s] on row row_start[b] + s for s < lengths[b], 0 on every other row (the rest of a slot, the tail up to
+// `rows`) — so nothing has to clear the buffer first, and token_ids is never read at a pad position (it may hold anything
+// there). One lane per two rows (row_start and `rows` are multiples of 128: a pair never straddles two slots): two 8-byte
+// loads, one 16-byte store. The sample of a row is found by searching the plan, as the packed embedding kernel does.
+__global__ __launch_bounds__(256) void pack_token_targets_kernel(const int64_t* token_ids, const int32_t* lengths,
+                                                                 const int32_t* row_start, int B, int S, int pairs, int64_t* out) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < pairs; i += gridDim.x * 256) {
+    const int r = 2 * i;
+    int b, s;
+    longlong2 o = make_longlong2(0, 0);
+    if (packed_locate(row_start, lengths, B, S, r, &b, &s)) {
+      int len = lengths[b];
+      len = len < 1 ? 1 : (len > S ? S : len);
+      const int64_t* src = token_ids + (size_t)b * S + s;
+      o.x = src[0];
+      if (s + 1 < len) o.y = src[1];
+    }
+    *(longlong2*)(out + r) = o;
+  }
+}
+// Fused token-head CE, between its two GEMM passes: one wave per row merges the per-tile (max, sum) pairs. The merge of one
+// valid row (shared by the padded and the packed kernel: a row's lse / w / loss are the same bits in both layouts).
+__device__ __forceinline__ void token_ce_merge_row(const float* pmax, const float* psum, int ntiles, const float* tlogit, int t,
+                                                   int lane, int B, int len, float* lse, float* w, float* loss_rows) {
+  float m = -INFINITY, l = 0.f;
+  for (int i = lane; i < ntiles; i += 64) {
+    const float pm = pmax[(size_t)t * ntiles + i], ps = psum[(size_t)t * ntiles + i];
+    if (pm > m) { l *= __expf(m - pm); m = pm; }
+    l += ps * __expf(pm - m);
+  }
+  const float M = wave_max(m);
+  l = wave_sum(m == -INFINITY ? 0.f : l * __expf(m - M));
+  if (lane == 0) {
+    const float ls = M + __logf(l), wt = 1.0f / ((float)B * (float)len);
+    lse[t] = ls; w[t] = wt; loss_rows[t] = wt * (ls - tlogit[t]);
+  }
+}
 __global__ __launch_bounds__(256) void token_ce_combine_kernel(const float* pmax, const float* psum, int ntiles,
                                                                const float* tlogit, const int32_t* lengths, int B, int S,
                                                                int rows, float* lse, float* w, float* loss_rows) {
@@ -888,18 +925,25 @@ __global__ __launch_bounds__(256) void token_ce_combine_kernel(const float* pmax
     if (lane == 0) { lse[t] = 0.f; w[t] = 0.f; loss_rows[t] = 0.f; }
     return;
   }
-  float m = -INFINITY, l = 0.f;
-  for (int i = lane; i < ntiles; i += 64) {
-    const float pm = pmax[(size_t)t * ntiles + i], ps = psum[(size_t)t * ntiles + i];
-    if (pm > m) { l *= __expf(m - pm); m = pm; }
-    l += ps * __expf(pm - m);
+  token_ce_merge_row(pmax, psum, ntiles, tlogit, t, lane, B, len, lse, w, loss_rows);
+}
+// The same on token-packed rows: row t belongs to the sample the plan gives it (wave-uniform: one row per wave); the rest
+// of a slot and the tail up to `rows` get lse = w = loss = 0, which is what makes pass 2 write exact zeros there.
+__global__ __launch_bounds__(256) void token_ce_combine_packed_kernel(const float* pmax, const float* psum, int ntiles,
+                                                                      const float* tlogit, const int32_t* lengths,
+                                                                      const int32_t* row_start, int B, int S, int rows, float* lse,
+                                                                      float* w, float* loss_rows) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= rows) return;
+  int b, sp;
+  if (!packed_locate(row_start, lengths, B, S, t, &b, &sp)) {
+    if (lane == 0) { lse[t] = 0.f; w[t] = 0.f; loss_rows[t] = 0.f; }
+    return;
   }
-  const float M = wave_max(m);
-  l = wave_sum(m == -INFINITY ? 0.f : l * __expf(m - M));
-  if (lane == 0) {
-    const float ls = M + __logf(l), wt = 1.0f / ((float)B * (float)len);
-    lse[t] = ls; w[t] = wt; loss_rows[t] = wt * (ls - tlogit[t]);
-  }
+  int len = lengths[b];
+  len = len < 1 ? 1 : (len > S ? S : len);
+  token_ce_merge_row(pmax, psum, ntiles, tlogit, t, lane, B, len, lse, w, loss_rows);
 }
 __global__ void add_scalar_kernel(float* out, const float* a, const float* b) { out[0] = a[0] + b[0]; }
 __global__ __launch_bounds__(256) void sum_rows_kernel(const float* x, int n, float* out) {
@@ -1333,6 +1377,27 @@ extern "C" int plb_launch_token_ce_combine(const float* pmax, const float* psum,
   ProfScope ps(PLB_K_TOKEN_CE, stream, 0, (double)rows * ntiles * 8.0);
   hipLaunchKernelGGL(token_ce_combine_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, pmax, psum, ntiles, tlogit, lengths,
                      B, S, rows, lse, w, loss_rows);
+  return LAUNCH_OK();
+}
+extern "C" int plb_launch_token_ce_combine_packed(const float* pmax, const float* psum, int ntiles, const float* tlogit,
+                                                  const int32_t* lengths, const int32_t* row_start, int B, int S, int rows,
+                                                  float* lse, float* w, float* loss_rows, hipStream_t stream) {
+  if (!pmax || !psum || !tlogit || !lengths || !row_start || !lse || !w || !loss_rows) return 1;
+  if (ntiles < 1 || B < 1 || S < 1 || rows < 1) return 1;
+  ProfScope ps(PLB_K_TOKEN_CE, stream, 0, (double)rows * ntiles * 8.0);
+  hipLaunchKernelGGL(token_ce_combine_packed_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, pmax, psum, ntiles, tlogit,
+                     lengths, row_start, B, S, rows, lse, w, loss_rows);
+  return LAUNCH_OK();
+}
+extern "C" int plb_launch_pack_token_targets(const int64_t* token_ids, const int32_t* lengths, const int32_t* row_start, int B,
+                                             int S, int rows, int64_t* out, hipStream_t stream) {
+  if (!token_ids || !lengths || !row_start || !out || B < 1 || S < 1) return 1;
+  if (rows < 128 || rows % 128) return 1;   // (a plan's row count: pairs of rows never straddle two slots)
+  if (((uintptr_t)token_ids & 7) || ((uintptr_t)out & 15)) return 1;
+  const int pairs = rows / 2, blocks = (pairs + 255) / 256;
+  ProfScope ps(PLB_K_CAST, stream, 0, (double)rows * 16.0);
+  hipLaunchKernelGGL(pack_token_targets_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, stream, token_ids,
+                     lengths, row_start, B, S, pairs, out);
   return LAUNCH_OK();
 }
 extern "C" int plb_launch_add_scalar(float* out, const float* a, const float* b, hipStream_t stream) {

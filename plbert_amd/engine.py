@@ -8,6 +8,7 @@ hot path runs in libplbert_hip.so.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -76,10 +77,17 @@ def packing_plan(lengths, S):
     return PackingPlan(lengths, S)
 
 
+def packed_dual_default():
+    """PLBERT_PACKED_DUAL=1: dual-head loss calls follow a packing plan that packs (include/plbert.h: plb_set_packed_dual)
+    wherever the switch is left open. Anything else, or unset: off."""
+    return os.environ.get("PLBERT_PACKED_DUAL", "0").strip() == "1"
+
+
 class HipEngine:
     def __init__(self, cfg, num_phonemes, num_tokens=0, max_batch=32, max_seq=512, device=None, train=True):
         """``train=False``: inference / validation engine (README.md:91, train.py:288-304) — no gradient, moment or
-        per-layer activation buffers (forward and loss-only calls work, backward and AdamW raise)."""
+        per-layer activation buffers (forward and loss-only calls work, backward and AdamW raise).
+        PLBERT_PACKED_DUAL=1 in the environment turns ``set_packed_dual`` on at creation."""
         cfg.check_supported()
         if not torch.cuda.is_available():
             raise RuntimeError("HipEngine needs a ROCm GPU (torch.cuda.is_available() is False); "
@@ -128,6 +136,9 @@ class HipEngine:
         self._synced_version = -1
         self.comm_world = 1
         self._on_handoff_timeout = []   # callbacks(err): owners of an optimizer step count rewind it by err.skipped_updates
+        self.packed_dual = False
+        if packed_dual_default():
+            self.set_packed_dual(True)
 
     def _bind(self):
         if self._bound:
@@ -320,6 +331,12 @@ class HipEngine:
         _lib.check(self.L.plb_last_call_rows(self.handle, C.byref(r), C.byref(o)), "plb_last_call_rows")
         return int(r.value), int(o.value)
 
+    def set_packed_dual(self, on=True):
+        """Dual-head loss calls (``token_ids`` given) that are handed a PackingPlan that packs run token-packed, token head
+        included (plb_set_packed_dual). Off (the default): they run padded, plan or not. Host state only."""
+        _lib.check(self.L.plb_set_packed_dual(self.handle, int(bool(on))), "plb_set_packed_dual")
+        self.packed_dual = bool(on)
+
     def _packing(self, packing, B, S):
         if packing is None:
             return None
@@ -480,7 +497,8 @@ class HipEngine:
         loss = phoneme loss + token loss, ``self.loss_parts`` holds the two terms and the token head's
         gradients are produced too.
         ``packing`` (PackingPlan of these lengths, loss_fwd too): the call runs on the valid tokens only
-        (include/plbert.h: plb_loss_fwd_bwd_packed); dual-head and fp8 calls run padded all the same."""
+        (include/plbert.h: plb_loss_fwd_bwd_packed). fp8 calls run padded all the same, and so do dual-head calls unless
+        ``set_packed_dual`` is on (plb_loss_fwd_bwd_dual_packed)."""
         return self._loss_call(True, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids, packing)
 
     def _loss_call(self, backward, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids, packing=None):
@@ -511,7 +529,13 @@ class HipEngine:
                                                       self._loss.data_ptr(),
                                                       self._loss_parts.data_ptr() if tok is not None else None,
                                                       self._stream()), "plb_loss_fwd_packed")
-            elif pk is not None and tok is None:
+            elif pk is not None and tok is not None:
+                _lib.check(self.L.plb_loss_fwd_bwd_dual_packed(self.handle, masked_ids.data_ptr(), labels.data_ptr(),
+                                                               tok.data_ptr(), p(lens), offs.data_ptr(), flat_p, int(n_masked),
+                                                               B, S, C.byref(pk), self._loss.data_ptr(),
+                                                               self._loss_parts.data_ptr(), self._stream()),
+                           "plb_loss_fwd_bwd_dual_packed")
+            elif pk is not None:
                 _lib.check(self.L.plb_loss_fwd_bwd_packed(self.handle, masked_ids.data_ptr(), labels.data_ptr(), p(lens),
                                                           offs.data_ptr(), flat_p, int(n_masked), B, S, C.byref(pk),
                                                           self._loss.data_ptr(), self._stream()), "plb_loss_fwd_bwd_packed")

@@ -10,7 +10,13 @@ GPU.
 e.g. python tools/ragged_bench.py parent:PLBERT_HIP_LIB=plbert_amd/build/ab/lib_parent.so,PACKED=0 padded:PACKED=0 packed
 PACKED=0 in a variant's list: padded calls only (a library built before the packed entry points existed has no others);
 the default variant runs both legs, packed and padded.  Prints one JSON line per child and a summary with ms/step and
-VALID tokens/s (the batch's real tokens per second: the figure that packing can move)."""
+VALID tokens/s (the batch's real tokens per second: the figure that packing can move).
+--num-tokens N: the DUAL-HEAD step with a token head of N classes (the ragged fixture has no token ids: they are drawn
+from a fixed seed). The packed leg then runs with plb_set_packed_dual on, and a third leg, switch_off, hands the same plan
+to a trainer with the switch off (it must run padded: the control of the opt-in). A library that predates the switch takes
+PACKED=0 as before. One leg under a profiler:
+   rocprofv3 --kernel-trace --stats -d DIR -- python tools/ragged_bench.py --child --num-tokens 64000 --steps 20 --legs packed
+e.g. python tools/ragged_bench.py --num-tokens 64000 parent:PLBERT_HIP_LIB=plbert_amd/build/ab/lib_parent.so,PACKED=0 here"""
 import argparse
 import json
 import os
@@ -41,10 +47,20 @@ def child(a):
         labels, masked, lengths, idx = plbert_amd.synthetic_batch(B, S, seed=1234)
         lengths = [S] * B
     valid = int(np.sum(lengths))
-    for packed in ([False, True] if a.packed else [False]):
+    NT = a.num_tokens
+    tok = None
+    if NT:   # dual-head step: token targets from a fixed seed, the reference's initialisation with the second head
+        tok = np.random.RandomState(4321).randint(0, NT, size=(B, S)).astype(np.int64)
+        sd = plbert_amd.reference_init_state_dict(pcfg, int(g["num_phonemes"]), NT, seed=0)
+    names = ["padded"] + (["packed"] + (["switch_off"] if NT else []) if a.packed else [])
+    if a.legs:   # (one leg alone: a profiler run of a --child process)
+        names = [n for n in names if n in a.legs.split(",")]
+    for leg in names:
+        packed = leg != "padded"
         kw = {"packed": True} if packed else {}
-        tr = PLBertTrainer(pcfg, int(g["num_phonemes"]), max_batch=B, max_seq=S, lr=7e-5, device="cuda:0", state_dict=sd, **kw)
-        batch = tr.stage_batch(labels, masked, lengths, idx, **kw)
+        tkw = dict(kw, num_tokens=NT, **({"packed_dual": leg == "packed"} if packed else {})) if NT else kw
+        tr = PLBertTrainer(pcfg, int(g["num_phonemes"]), max_batch=B, max_seq=S, lr=7e-5, device="cuda:0", state_dict=sd, **tkw)
+        batch = tr.stage_batch(labels, masked, lengths, idx, token_ids=tok, **kw)
         for _ in range(a.warmup):
             tr.step(batch)
         torch.cuda.synchronize()
@@ -57,7 +73,7 @@ def child(a):
         ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(a.steps))
         med = ms[len(ms) // 2]
         rows = tr.engine.last_call_rows() if packed else (B * S, B * S)
-        legs["packed" if packed else "padded"] = {
+        legs[leg] = {
             "ms_per_step": round(med, 4), "ms_min": round(ms[0], 4), "ms_p90": round(ms[int(0.9 * (len(ms) - 1))], 4),
             "valid_tokens_per_s": round(valid / med * 1e3, 1), "rows": int(rows[0]), "of": int(rows[1]),
             "loss": float(loss.item()), "timeouts": tr.engine.status()["ln_exchange_timeouts"]}
@@ -74,6 +90,8 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--timeout", type=int, default=300, help="seconds, per child process")
+    ap.add_argument("--legs", default="", help="with --child: run these legs only (padded,packed,switch_off)")
+    ap.add_argument("--num-tokens", type=int, default=0, help="dual-head step with a token head of this many classes")
     ap.add_argument("variants", nargs="*", default=["here"])
     a = ap.parse_args()
     if a.child:
@@ -85,6 +103,7 @@ def main():
                 label, _, envs = v.partition(":")
                 env, packed = dict(os.environ), 1
                 env.pop("PLBERT_PACKED", None)
+                env.pop("PLBERT_PACKED_DUAL", None)
                 for kv in [e for e in envs.split(",") if e]:
                     k, _, val = kv.partition("=")
                     if k == "PACKED":
@@ -92,7 +111,7 @@ def main():
                     else:
                         env[k] = os.path.abspath(os.path.join(ROOT, val)) if k == "PLBERT_HIP_LIB" else val
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--batch", batch, "--packed", str(packed),
-                       "--steps", str(a.steps), "--warmup", str(a.warmup)]
+                       "--steps", str(a.steps), "--warmup", str(a.warmup), "--num-tokens", str(a.num_tokens)]
                 try:
                     out = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=a.timeout)
                 except subprocess.TimeoutExpired:
@@ -111,7 +130,7 @@ def main():
     for (batch, label, leg), rs in res.items():
         ms = [r["ms_per_step"] for r in rs]
         med[(batch, label, leg)] = statistics.median(ms)
-        print(f"{batch:7s} {label:10s} {leg:7s} {statistics.median(ms):8.3f} ({', '.join(f'{x:.3f}' for x in ms)}) | "
+        print(f"{batch:7s} {label:10s} {leg:10s} {statistics.median(ms):8.3f} ({', '.join(f'{x:.3f}' for x in ms)}) | "
               f"{statistics.median(r['valid_tokens_per_s'] for r in rs):10.0f} | {rs[0]['rows']} of {rs[0]['of']}")
     base = a.variants[0].partition(":")[0]
     for (batch, label, leg), m in med.items():
