@@ -228,8 +228,8 @@ int plb_status_import(PlbEngine* e, const float* summed, void* stream);
  * and then reads the masked ones (train.py:107-131: pred[b, :len_b][idx_b]), rows only meet inside attention, so the other
  * rows of that part reach neither the loss nor — their output gradient being exactly zero — any gradient. Same results,
  * ~5 % less arithmetic at 13 % masked positions. Reports what the last loss call did: rows = token rows that part ran on
- * (padded to 128), of = the call's padded token count (rows == of: every row — a dual-head call, an fp8 call, more than
- * half of the positions masked, or PLBERT_PRUNE_LAST=0). */
+ * (padded to 128), of = the call's padded token count (rows == of: every row — a dual-head call, more than half of the
+ * positions masked, or PLBERT_PRUNE_LAST=0; calls in fp8 mode prune like bf16 calls). */
 int plb_last_application_rows(const PlbEngine* e, int64_t* rows, int64_t* of);
 /* ---- token-packed execution of ragged batches (opt-in) ----
  * The reference collater zero-pads every sample to the batch maximum (dataloader.py:276-297) and the loss slices the pads
@@ -248,9 +248,10 @@ int plb_last_application_rows(const PlbEngine* e, int64_t* rows, int64_t* of);
  * plan it is graph-capturable like the padded call. Same results as the padded call up to bf16 summation order in the
  * weight gradients (each valid row's arithmetic is unchanged). A call runs PADDED, with the padded call's results bit for
  * bit, when the plan is the padded layout (S < 128 included: such a batch has no plan that packs), when lengths == NULL,
- * while fp8 mode is on, for plb_forward_packed with token_logits (a full [B,S,NT] fp32 output is a debugging output, not a
- * hot path) and for dual-head loss calls (token_ids given) unless plb_set_packed_dual is on. plb_forward_packed: hidden / phoneme_logits at pad positions (s >= lengths[b]) are ZEROS (the padded
- * path leaves values there that nothing reads). plb_pooler takes the [B,S,H] output as before.
+ * while fp8 mode is on unless plb_set_packed_fp8 is on, for plb_forward_packed with token_logits (a full [B,S,NT] fp32
+ * output is a debugging output, not a hot path) and for dual-head loss calls (token_ids given) unless plb_set_packed_dual
+ * is on. plb_forward_packed: hidden / phoneme_logits at pad positions (s >= lengths[b]) are ZEROS (the padded path leaves
+ * values there that nothing reads). plb_pooler takes the [B,S,H] output as before.
  * Rows of the packed axis that hold no token are given defined values in every call (zeros from the embeddings, computed
  * like padded rows inside a slot, a zeroed attention output and zero gradients in the tail), so a packed call does not
  * depend on what an earlier call left in the workspace.
@@ -279,15 +280,36 @@ int plb_last_call_rows(const PlbEngine* e, int64_t* rows, int64_t* of);
  * summation order: each valid row's forward arithmetic, token logit statistics and logit-gradient row are unchanged; the
  * token-loss sum and the weight / bias gradient sums run over another row set (rows that hold no token contribute exact
  * zeros in both layouts). plb_last_call_rows reports rows < of for such a call; plb_last_application_rows stays rows == of
- * (a dual-head call prunes nothing). Still padded with the switch on: fp8 mode (the delayed-scale maxima of the padded
- * call include rows a packed call does not run), S < 128 and plans that are the padded layout, lengths == NULL, and
- * plb_forward_packed with token_logits.
+ * (a dual-head call prunes nothing). Still padded with the switch on: fp8 mode unless plb_set_packed_fp8 is on as well,
+ * S < 128 and plans that are the padded layout, lengths == NULL, and plb_forward_packed with token_logits.
  * plb_loss_fwd_bwd_dual_packed: plb_loss_fwd_bwd_dual with a plan; packing == NULL, or the switch off: exactly
  * plb_loss_fwd_bwd_dual. */
 int plb_set_packed_dual(PlbEngine* e, int32_t on);
 int plb_loss_fwd_bwd_dual_packed(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int64_t* token_ids,
                                  const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n_masked,
                                  int32_t B, int32_t S, const PlbPacking* packing, float* loss, float* loss_parts, void* stream);
+/* Token-packed calls IN FP8 MODE (opt-in on top of the plan; off by default, engine state, no device state touched, a live
+ * plb_encode stash stays live). Off: every call made while fp8 mode is on runs padded, plan or not, as above. On: while
+ * fp8 mode is on, a call that is given a plan that packs and lengths runs on the plan's rows — plb_forward_packed without
+ * token_logits, plb_loss_fwd_bwd_packed, plb_loss_fwd_packed, and the dual-head forms (plb_loss_fwd_bwd_dual_packed,
+ * plb_loss_fwd_packed with token_ids) when plb_set_packed_dual is on too — the calibration call(s), which compute in bf16,
+ * and the fp8 calls alike. plb_last_call_rows reports rows < of, plb_last_application_rows what it reports for a bf16
+ * packed call. plb_encode keeps refusing fp8 mode.
+ * Site maxima: the per-site maxima a packed call in fp8 mode records are taken over the rows it executes — rows [0, used)
+ *   in a calibration call, every row an image-writing launch covers in an fp8 call (the tail [used, rows) included) — the
+ *   rest of a sample's slot included, just as pad rows count in a padded call: in fp8 mode those rows are embedded from
+ *   ids like pad positions (a bf16 packed call writes zero embeddings there), so a packed call whose slots all have one
+ *   size S' < S records the maxima, and gives the results, of the padded call on the batch trimmed to [B,S'] bit for bit.
+ *   Delayed scaling, the four-call history and plb_fp8_stats are otherwise unchanged; a run may mix padded and packed
+ *   calls, the history simply holds both.
+ * Tile forms: which fp8 forms a call gets follows the rows it executes (fp8 pipeline tiles: rows % 128; LayerNorm in the
+ *   GEMM epilogues: rows % 1024; gelu' stash; the fp8 weight-gradient GEMMs: layers x rows >= 8192). A packed call can
+ *   therefore take the weight gradients from the bf16 tensors where the padded call of the same batch took them from the
+ *   1-byte images.
+ * Rows that hold no token have zeros in every gradient image and finite values in every activation image that depend on
+ *   this call's inputs only, so a packed call in fp8 mode does not depend on what an earlier call left in the workspace.
+ * Not graph-captured by anything in this library; fp8 fine-tuning (plb_encode) stays out of scope. */
+int plb_set_packed_fp8(PlbEngine* e, int32_t on);
 /* ---- differentiable encoder: fine-tuning a checkpoint inside a downstream model ----
  * Stands in for the reference README's "Finetuning" use (README.md:36-119):
  *   bert_dur = model.bert(texts, attention_mask=(~text_mask).int()).last_hidden_state   -> plb_encode

@@ -56,6 +56,7 @@ PUBLIC_SYMBOLS = [
     "plb_set_fp8", "plb_fp8_state", "plb_fp8_stats", "plb_token_head_steps", "plb_set_token_head_steps", "plb_comm_unique_id", "plb_comm_init", "plb_comm_destroy",
     "plb_comm_info", "plb_comm_pieces", "plb_last_application_rows", "plb_last_call_rows",
     "plb_packing_plan", "plb_forward_packed", "plb_loss_fwd_bwd_packed", "plb_loss_fwd_packed", "plb_set_packed_dual",
+    "plb_set_packed_fp8",
     "plb_loss_fwd_bwd_dual_packed", "plb_encode", "plb_encode_bwd", "plb_status", "plb_status_ex", "plb_poll_status", "plb_status_export", "plb_status_import", "plb_broadcast_params", "plb_set_grad_overlap", "plb_allreduce_grads", "plb_apply_mask",
     "plb_mask_batch", "plb_profile_enable", "plb_profile_num_classes", "plb_profile_class_name", "plb_profile_read",
     # test / tuning hooks (documented as such at the end of the header)
@@ -120,7 +121,7 @@ class PlbEmbed(C.Structure):
         ("word", C.c_void_p), ("pos", C.c_void_p), ("type0", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
         ("eps", C.c_float), ("out", C.c_void_p), ("ldo", C.c_int), ("dout", C.c_void_p), ("lddo", C.c_int),
         ("dx", C.c_void_p), ("dword", C.c_void_p), ("dpos", C.c_void_p), ("partials", C.c_void_p), ("nblocks", C.c_int),
-        ("row_start", C.c_void_p), ("lengths", C.c_void_p), ("B", C.c_int),
+        ("row_start", C.c_void_p), ("lengths", C.c_void_p), ("B", C.c_int), ("fill_slots", C.c_int),
     ]
 
 
@@ -243,6 +244,9 @@ def lib():
         L.plb_launch_pack_token_targets.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
         L.plb_launch_token_ce_combine_packed.restype = C.c_int
         L.plb_launch_token_ce_combine_packed.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    if hasattr(L, "plb_set_packed_fp8"):   # (likewise: an A/B build may predate packed fp8 calls)
+        L.plb_set_packed_fp8.restype = C.c_int
+        L.plb_set_packed_fp8.argtypes = [vp, i32]
     L.plb_status_export.restype = C.c_int
     L.plb_status_export.argtypes = [vp, vp, vp]
     L.plb_status_import.restype = C.c_int

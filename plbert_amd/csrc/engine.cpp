@@ -391,6 +391,11 @@ extern "C" int plb_set_packed_dual(PlbEngine* e, int32_t on) {
   e->packed_dual = on != 0;
   return 0;
 }
+extern "C" int plb_set_packed_fp8(PlbEngine* e, int32_t on) {
+  if (!e) return fail("plb_set_packed_fp8: null engine");
+  e->packed_fp8 = on != 0;
+  return 0;
+}
 
 extern "C" int32_t plb_token_head_steps(const PlbEngine* e) { return e ? e->tok_steps : -1; }
 extern "C" int plb_set_token_head_steps(PlbEngine* e, int32_t steps) {

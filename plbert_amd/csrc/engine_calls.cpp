@@ -1,7 +1,7 @@
 // Call-level stages of the engine: row selection of a padded or token-packed call, the heads, the stages of a loss call and
 // the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd. Only
 // writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
-// last_exec_rows, tok_grads_live and head_grads_live. (packed_dual: plb_set_packed_dual, engine.cpp.)
+// last_exec_rows, tok_grads_live and head_grads_live. (packed_dual, packed_fp8: plb_set_packed_dual / _fp8, engine.cpp.)
 #include "engine_internal.h"
 
 // Every call that writes the workspace or moves the weights ends the life of a plb_encode stash.
@@ -18,8 +18,9 @@ static int check_shape(const PlbEngine* e, int B, int S, const char* who) {
 
 static Rows padded_rows(int B, int S) { return Rows{nullptr, B * S, rup(B * S, 128)}; }
 // Does this call run packed? It runs padded — same results as without a plan — when the plan saves nothing (every
-// sample full, or slots that add up to the padded rows), while fp8 mode is on, and when the caller says so (`padded`: a
-// forward call that returns token logits, a dual-head loss call while plb_set_packed_dual is off).
+// sample full, or slots that add up to the padded rows), while fp8 mode is on and plb_set_packed_fp8 is off, and when the
+// caller says so (`padded`: a forward call that returns token logits, a dual-head loss call while plb_set_packed_dual is
+// off, plb_encode_bwd never gets here in fp8 mode).
 static int pick_rows(PlbEngine* e, const PlbPacking* pk, const int32_t* lengths, bool padded, int B, int S, const char* who,
                      Rows* out) {
   *out = padded_rows(B, S);
@@ -28,7 +29,7 @@ static int pick_rows(PlbEngine* e, const PlbPacking* pk, const int32_t* lengths,
   if (pk->rows < 128 || pk->rows % 128 || pk->used < 1 || pk->used > pk->rows)
     return fail("%s: packing plan of %d rows (%d used) is not one plb_packing_plan made", who, pk->rows, pk->used);
   if (pk->rows > out->Tp) return fail("%s: packing plan of %d rows exceeds the call's %lld", who, pk->rows, (long long)out->Tp);
-  if (!lengths || padded || e->fp8_on || pk->rows == out->Tp) return 0;   // (rows == Tp: the plan is the padded layout)
+  if (!lengths || padded || (e->fp8_on && !e->packed_fp8) || pk->rows == out->Tp) return 0;   // (rows == Tp: the plan is the padded layout)
   if (pk->used % 128) return fail("%s: packing plan with %d used rows: slots are multiples of 128", who, pk->used);
   *out = Rows{pk->row_start, pk->used, pk->rows};
   e->last_exec_rows[0] = pk->rows;

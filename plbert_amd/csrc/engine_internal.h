@@ -97,6 +97,7 @@ struct PlbEngine {
   int f8n = 0;
   // ---- caller's switches: engine.cpp ----
   bool packed_dual = false;     // plb_set_packed_dual: dual-head loss calls follow a plan that packs (off: they run padded)
+  bool packed_fp8 = false;      // plb_set_packed_fp8: calls in fp8 mode follow a plan that packs (off: they run padded)
   // ---- workspace offsets (bytes): engine.cpp (plb_create) ----
   int64_t o_wbf, o_wqkvT, o_wdT, o_w1T, o_w2T, o_wpT, o_winT;
   int64_t o_e, o_x, o_qkv, o_ctx, o_pre1, o_a, o_u, o_g, o_pre2;

@@ -262,6 +262,11 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
   const int64_t Tp = rw.Tp;
   const bool f8 = f8_call(e, Tp, stash);
   const bool calib = e->fp8_on && !f8;
+  // Packed fp8 call: the launches that write a 1-byte image beside their rows cover the tail behind the last slot too (the
+  // layer-0 quantisation, the standalone LayerNorm forward; the GEMM epilogues store every row anyway), so every image row
+  // the next GEMM and the stacked weight-gradient GEMMs read holds a finite value that only this call's inputs decide. The
+  // tail rows are those of zero embeddings behind a zero attention output: the same in every call.
+  const int T8 = (f8 && rw.row_start) ? (int)Tp : T;
   if (e->fp8_on && e->fp8_wstale) TRY(fp8_quantize_weights(e, s));
   PlbEmbed em;
   memset(&em, 0, sizeof(em));
@@ -271,6 +276,9 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
   em.out = e->at<bf16_t>(e->o_e); em.ldo = E;
   if (rw.row_start) {   // packed: every row of the call gets a value (zeros where no token sits), the tail included
     em.row_start = rw.row_start; em.lengths = lengths; em.B = B; em.T = (int)Tp;
+    // fp8 mode (plb_set_packed_fp8): the rest of a slot is embedded like the pad positions of a padded call, so the sites'
+    // maxima — taken over every row of the slots — are those of the padded call on the batch trimmed to its slots
+    em.fill_slots = e->fp8_on;
   }
   TRY(plb_launch_embed_fwd(&em, s));
 
@@ -281,7 +289,7 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
   if (f8) {  // layer 0 reads the map-in output, which no LayerNorm produced: one quantisation pass
     // (image and the site's maximum in one pass: the rows are contiguous)
     const F8Site sX(e, F8_X, 0);
-    const void* src1[1] = {first.x}; const int bf1[1] = {1}; const size_t n1[1] = {(size_t)T * H};
+    const void* src1[1] = {first.x}; const int bf1[1] = {1}; const size_t n1[1] = {(size_t)T8 * H};
     const float* sc1[1] = {sX.scale}; uint8_t* dst1[1] = {first.x8}; float* am1[1] = {sX.amax};
     TRY(plb_launch_quantize_multi(1, src1, bf1, n1, sc1, dst1, am1, s));
   }
@@ -313,10 +321,20 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
     at.scale = 0.125f; at.ctx = ctx_att; at.ldctx = H; at.lse = sl.lse;
     // (pruned: nobody reads the context's image of all rows — the compact rows' image is made with the others, below)
     if (f8 && !pruned_layer) { at.ctx8 = sl.c8; at.ldctx8 = H; at.ctx_scale = sC.scale; at.ctx_amax = sC.amax; }
+    // packed fp8-mode call, S no multiple of 128: the slot of a full-length sample runs past position S, rows no attention
+    // workgroup stores. The calibration maxima and the images are taken over every row of the slots: zeros there, not what
+    // an earlier call left (bf16 calls leave them alone: finite is enough there)
+    if (rw.row_start && e->fp8_on && S % 128) {
+      HIPTRY(hipMemsetAsync(ctx_att, 0, (size_t)T * H * 2, s));
+      if (at.ctx8) HIPTRY(hipMemsetAsync(sl.c8, 0, (size_t)T * H, s));
+    }
     TRY(plb_launch_attn_fwd(&at, s));
     // packed: the tail behind the last slot (up to 1,023 rows) is written by no attention workgroup, and what sits there
     // goes through dense / LayerNorm / FFN into the stash the weight-gradient GEMMs read: zeros, not whatever was there
-    if (rw.row_start && Tp > T) HIPTRY(hipMemsetAsync(ctx_att + (int64_t)T * H, 0, (size_t)(Tp - T) * H * 2, s));
+    if (rw.row_start && Tp > T) {
+      HIPTRY(hipMemsetAsync(ctx_att + (int64_t)T * H, 0, (size_t)(Tp - T) * H * 2, s));
+      if (at.ctx8) HIPTRY(hipMemsetAsync(sl.c8 + (int64_t)T * H, 0, (size_t)(Tp - T) * H, s));   // (the image of those zeros)
+    }
     if (calib) TRY(plb_launch_amax(ctx_att, 1, (size_t)T, H, H, sC.amax, s));
     if (pruned_layer) {
       if (last_application_fwd_pruned(e, pr, stash, calib, tn8, sl, ctx_att, s)) return 1;
@@ -327,7 +345,7 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
     g = nt_desc(sl.ctx, e->wbf(PLB_DENSE_W), Tp, H, H);
     g.bias = e->par(PLB_DENSE_B); g.res = sl.x; g.ldr = H; g.C = sl.pre1; g.ldc = H;
     const F8Op od = f8_op(sl.c8, sC, F8Weight(e, F8W_D), 0);
-    if (gemm_ln_fwd(e, &g, f8 ? &od : nullptr, fuse_f, ln1_slot(e, sl), sl.a, T, f8 ? sl.a8 : nullptr, sA, s)) return 1;
+    if (gemm_ln_fwd(e, &g, f8 ? &od : nullptr, fuse_f, ln1_slot(e, sl), sl.a, T8, f8 ? sl.a8 : nullptr, sA, s)) return 1;
     if (calib) TRY(plb_launch_amax(sl.a, 1, (size_t)T, H, H, sA.amax, s));
     // FFN: u = a W1^T + b1, g = gelu_new(u); pre2 = g W2^T + b2 + a
     g = nt_desc(sl.a, e->wbf(PLB_FFN_W), Tp, I, H);
@@ -350,7 +368,7 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
     g.bias = e->par(PLB_FFNO_B); g.res = sl.a; g.ldr = H; g.C = sl.pre2; g.ldc = H;
     const F8Op o2 = f8_op(sl.g8, sG, F8Weight(e, F8W_2), 0);
     const bool next8 = f8 && l + 1 < L;
-    if (gemm_ln_fwd(e, &g, f8 ? &o2 : nullptr, fuse_f, ln2_slot(e, sl), sl.y, T, next8 ? sl.x8n : nullptr,
+    if (gemm_ln_fwd(e, &g, f8 ? &o2 : nullptr, fuse_f, ln2_slot(e, sl), sl.y, T8, next8 ? sl.x8n : nullptr,
                     next8 ? F8Site(e, F8_X, l + 1) : F8Site(), s))
       return 1;
     *xout = sl.y;
@@ -507,6 +525,8 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
   // full-length sample runs on to the next multiple of 128 — rows no launch of this call writes, which the weight-gradient
   // GEMMs read: zeros (their true value: no token sits there), not what an earlier call left
   if (c.row_start && c.S % 128 && at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv, 0, (size_t)T * 3 * H * 2, s));
+  // (their e5m2 image likewise: a stale byte there can be a NaN encoding, and 0 x NaN in the stacked weight-gradient GEMM is NaN)
+  if (c.row_start && c.S % 128 && at.dqkv8) HIPTRY(hipMemsetAsync(sl.dq8, 0, (size_t)T * 3 * H, s));
   TRY(plb_launch_attn_bwd(&at, s));
   if (c.Tp > T) {
     if (at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv + (int64_t)T * 3 * H, 0, (size_t)(c.Tp - T) * 3 * H * 2, s));

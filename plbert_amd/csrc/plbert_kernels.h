@@ -127,7 +127,11 @@ typedef struct {
   // rows and out / dout / dx are indexed by packed row: sample b's position s < lengths[b] is row row_start[b] + s, its
   // position embedding is pos[s]. Rows that belong to no sample (the rest of a sample's 128-aligned slot, the tail behind
   // row_start[B]) are written as zeros by the forward and the backward and add nothing to partials / dword / dpos.
-  const int32_t* row_start; const int32_t* lengths; int B;
+  // fill_slots (forward only): the rest of a sample's slot — positions lengths[b] <= s < min(S, ceil128(lengths[b])) — is
+  // embedded from ids like the pad positions of a padded call instead of written as zeros (a token-packed call in fp8 mode:
+  // the sites' maxima then see what the padded call on the batch trimmed to its slots sees). Positions at or past S and
+  // the tail stay zeros.
+  const int32_t* row_start; const int32_t* lengths; int B; int fill_slots;
 } PlbEmbed;
 int plb_launch_embed_fwd(const PlbEmbed* p, hipStream_t stream);
 int plb_launch_embed_bwd(const PlbEmbed* p, hipStream_t stream);  // grid = p->nblocks; writes dx + partials

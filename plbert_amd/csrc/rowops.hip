@@ -43,7 +43,9 @@ __global__ __launch_bounds__(256) void embed_kernel(PlbEmbed p) {
     int src = t, s = 0;
     if (p.row_start) {   // packed row t -> token (b, s) of the padded ids (wave-uniform: one row per wave)
       int b;
-      if (!packed_locate(p.row_start, p.lengths, p.B, p.S, t, &b, &s)) {
+      const bool owned = packed_locate(p.row_start, p.lengths, p.B, p.S, t, &b, &s);
+      // (fill_slots: a row behind the length but inside the sample's slot and the sequence is a pad position of the ids)
+      if (!owned && !(!BWD && p.fill_slots && s < p.S && t < p.row_start[b + 1])) {
         if (act) {
           if (!BWD) *(uint2*)(p.out + (size_t)t * p.ldo + c) = make_uint2(0u, 0u);
           else *(float4*)(p.dx + (size_t)t * E + c) = make_float4(0.f, 0.f, 0.f, 0.f);

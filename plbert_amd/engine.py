@@ -83,11 +83,18 @@ def packed_dual_default():
     return os.environ.get("PLBERT_PACKED_DUAL", "0").strip() == "1"
 
 
+def packed_fp8_default():
+    """PLBERT_PACKED_FP8=1: calls in fp8 mode follow a packing plan that packs (include/plbert.h: plb_set_packed_fp8)
+    wherever the switch is left open. Anything else, or unset: off."""
+    return os.environ.get("PLBERT_PACKED_FP8", "0").strip() == "1"
+
+
 class HipEngine:
     def __init__(self, cfg, num_phonemes, num_tokens=0, max_batch=32, max_seq=512, device=None, train=True):
         """``train=False``: inference / validation engine (README.md:91, train.py:288-304) — no gradient, moment or
         per-layer activation buffers (forward and loss-only calls work, backward and AdamW raise).
-        PLBERT_PACKED_DUAL=1 in the environment turns ``set_packed_dual`` on at creation."""
+        PLBERT_PACKED_DUAL=1 in the environment turns ``set_packed_dual`` on at creation, PLBERT_PACKED_FP8=1
+        ``set_packed_fp8``."""
         cfg.check_supported()
         if not torch.cuda.is_available():
             raise RuntimeError("HipEngine needs a ROCm GPU (torch.cuda.is_available() is False); "
@@ -139,6 +146,9 @@ class HipEngine:
         self.packed_dual = False
         if packed_dual_default():
             self.set_packed_dual(True)
+        self.packed_fp8 = False
+        if packed_fp8_default():
+            self.set_packed_fp8(True)
 
     def _bind(self):
         if self._bound:
@@ -337,6 +347,13 @@ class HipEngine:
         _lib.check(self.L.plb_set_packed_dual(self.handle, int(bool(on))), "plb_set_packed_dual")
         self.packed_dual = bool(on)
 
+    def set_packed_fp8(self, on=True):
+        """Calls in fp8 mode (``set_fp8``) that are handed a PackingPlan that packs run token-packed: the calibration
+        calls and the fp8 calls alike (plb_set_packed_fp8). Dual-head calls need ``set_packed_dual`` as well. Off (the
+        default): every call in fp8 mode runs padded, plan or not. Host state only."""
+        _lib.check(self.L.plb_set_packed_fp8(self.handle, int(bool(on))), "plb_set_packed_fp8")
+        self.packed_fp8 = bool(on)
+
     def _packing(self, packing, B, S):
         if packing is None:
             return None
@@ -497,8 +514,8 @@ class HipEngine:
         loss = phoneme loss + token loss, ``self.loss_parts`` holds the two terms and the token head's
         gradients are produced too.
         ``packing`` (PackingPlan of these lengths, loss_fwd too): the call runs on the valid tokens only
-        (include/plbert.h: plb_loss_fwd_bwd_packed). fp8 calls run padded all the same, and so do dual-head calls unless
-        ``set_packed_dual`` is on (plb_loss_fwd_bwd_dual_packed)."""
+        (include/plbert.h: plb_loss_fwd_bwd_packed). Calls in fp8 mode run padded all the same unless ``set_packed_fp8``
+        is on, and so do dual-head calls unless ``set_packed_dual`` is on (plb_loss_fwd_bwd_dual_packed)."""
         return self._loss_call(True, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids, packing)
 
     def _loss_call(self, backward, masked_ids, labels, lengths, idx_offsets, idx_flat, n_masked, token_ids, packing=None):

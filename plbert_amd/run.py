@@ -149,7 +149,8 @@ def initialize_model(config, log_dir, resuming, device=None, max_batch=None):
     per_rank = max(1, int(tp["batch_size"]) // world)           # split_batches=True: batch_size is global (train.py:220)
     trainer = PLBertTrainer(cfg, num_phonemes=len(symbols), max_batch=max_batch or per_rank,
                             max_seq=int(config["dataset_params"]["max_seq_length"]), lr=float(tp["learning_rate"]),
-                            device=device, packed_dual=tp.get("packed_dual"))   # (None: PLBERT_PACKED_DUAL)
+                            device=device, packed_dual=tp.get("packed_dual"),      # (None: PLBERT_PACKED_DUAL)
+                            packed_fp8=tp.get("packed_fp8"))                       # (None: PLBERT_PACKED_FP8)
     if config["model_params"].get("pretrained_model"):
         print(f"Loading pretrained model from: {config['model_params']['pretrained_model']}")
         load_checkpoint(trainer, config["model_params"]["pretrained_model"])

@@ -104,10 +104,11 @@ class PLBertTrainer:
 
     def __init__(self, cfg, num_phonemes, max_batch=32, max_seq=512, lr=7e-5, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.01, device=None, seed=0, state_dict=None, process_group=None, force_collectives=False,
-                 num_tokens=0, comm="auto", overlap=True, packed=None, packed_dual=None):
+                 num_tokens=0, comm="auto", overlap=True, packed=None, packed_dual=None, packed_fp8=None):
         """``packed``: ragged batches run on their valid tokens only (token-packed execution, include/plbert.h PlbPacking);
-        None = PLBERT_PACKED=1. fp8 steps run padded all the same, and so do dual-head steps unless ``packed_dual`` is on
-        (None = PLBERT_PACKED_DUAL=1; include/plbert.h plb_set_packed_dual): it only has an effect together with ``packed``.
+        None = PLBERT_PACKED=1. Steps in fp8 mode run padded all the same unless ``packed_fp8`` is on (None =
+        PLBERT_PACKED_FP8=1; include/plbert.h plb_set_packed_fp8), and so do dual-head steps unless ``packed_dual`` is on
+        (None = PLBERT_PACKED_DUAL=1; plb_set_packed_dual): both only have an effect together with ``packed``.
         ``comm``: how the gradient exchange of a data-parallel run travels.
         "rccl"  — the engine's own RCCL communicator behind the C ABI (plb_comm_init / plb_allreduce_grads): the
                   all-reduce is issued by plb_loss_fwd_bwd itself, piece by piece on the engine's communication
@@ -124,6 +125,9 @@ class PLBertTrainer:
         if packed_dual is not None:   # (None: the engine has read PLBERT_PACKED_DUAL itself)
             self.engine.set_packed_dual(packed_dual)
         self.packed_dual = self.engine.packed_dual
+        if packed_fp8 is not None:    # (None: the engine has read PLBERT_PACKED_FP8 itself)
+            self.engine.set_packed_fp8(packed_fp8)
+        self.packed_fp8 = self.engine.packed_fp8
         self.reducer = GradReducer(process_group, device=self.engine.device, force=force_collectives)
         self.world = self.reducer.world
         sd = state_dict if state_dict is not None else reference_init_state_dict(cfg, num_phonemes, num_tokens, seed=seed)

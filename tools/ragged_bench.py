@@ -16,7 +16,11 @@ from a fixed seed). The packed leg then runs with plb_set_packed_dual on, and a 
 to a trainer with the switch off (it must run padded: the control of the opt-in). A library that predates the switch takes
 PACKED=0 as before. One leg under a profiler:
    rocprofv3 --kernel-trace --stats -d DIR -- python tools/ragged_bench.py --child --num-tokens 64000 --steps 20 --legs packed
-e.g. python tools/ragged_bench.py --num-tokens 64000 parent:PLBERT_HIP_LIB=plbert_amd/build/ab/lib_parent.so,PACKED=0 here"""
+e.g. python tools/ragged_bench.py --num-tokens 64000 parent:PLBERT_HIP_LIB=plbert_amd/build/ab/lib_parent.so,PACKED=0 here
+--dtype fp8: every leg trains in fp8 mode (plb_set_fp8; the warm-up holds the calibration call). Three legs: padded (no
+plan), packed (plan + plb_set_packed_fp8 on) and switch_off (plan, switch off: it must run padded — the parent's code path
+with a plan in hand). --profile adds the per-class launch times of plb_profile_read (ms per step) of a few extra steps after
+the timed ones. The summary gives, per leg, the spread of its runs ((max - min) / median)."""
 import argparse
 import json
 import os
@@ -52,14 +56,19 @@ def child(a):
     if NT:   # dual-head step: token targets from a fixed seed, the reference's initialisation with the second head
         tok = np.random.RandomState(4321).randint(0, NT, size=(B, S)).astype(np.int64)
         sd = plbert_amd.reference_init_state_dict(pcfg, int(g["num_phonemes"]), NT, seed=0)
-    names = ["padded"] + (["packed"] + (["switch_off"] if NT else []) if a.packed else [])
+    f8 = a.dtype == "fp8"
+    names = ["padded"] + (["packed"] + (["switch_off"] if NT or f8 else []) if a.packed else [])
     if a.legs:   # (one leg alone: a profiler run of a --child process)
         names = [n for n in names if n in a.legs.split(",")]
     for leg in names:
         packed = leg != "padded"
         kw = {"packed": True} if packed else {}
-        tkw = dict(kw, num_tokens=NT, **({"packed_dual": leg == "packed"} if packed else {})) if NT else kw
+        tkw = dict(kw, num_tokens=NT, **({"packed_dual": leg == "packed"} if packed else {})) if NT else dict(kw)
+        if f8 and packed:   # (fp8 + dual head: the packed leg turns both switches on, switch_off neither)
+            tkw["packed_fp8"] = leg == "packed"
         tr = PLBertTrainer(pcfg, int(g["num_phonemes"]), max_batch=B, max_seq=S, lr=7e-5, device="cuda:0", state_dict=sd, **tkw)
+        if f8:
+            tr.engine.set_fp8(True)
         batch = tr.stage_batch(labels, masked, lengths, idx, token_ids=tok, **kw)
         for _ in range(a.warmup):
             tr.step(batch)
@@ -77,6 +86,18 @@ def child(a):
             "ms_per_step": round(med, 4), "ms_min": round(ms[0], 4), "ms_p90": round(ms[int(0.9 * (len(ms) - 1))], 4),
             "valid_tokens_per_s": round(valid / med * 1e3, 1), "rows": int(rows[0]), "of": int(rows[1]),
             "loss": float(loss.item()), "timeouts": tr.engine.status()["ln_exchange_timeouts"]}
+        if f8:
+            legs[leg]["fp8_calibrated"] = bool(tr.engine.fp8_state()[1])
+        if a.profile:   # per-class launch times, outside the timed steps (the profiler's events cost time of their own)
+            from plbert_amd import _lib
+            nprof = 5
+            _lib.profile_enable(True)
+            _lib.profile_read()
+            for _ in range(nprof):
+                tr.step(batch)
+            torch.cuda.synchronize()
+            legs[leg]["profile_ms_per_step"] = {k: round(v["ms"] / nprof, 4) for k, v in _lib.profile_read().items()}
+            _lib.profile_enable(False)
         del tr
     print(json.dumps({"batch": a.batch, "valid_tokens": valid, "legs": legs}), flush=True)
 
@@ -92,6 +113,8 @@ def main():
     ap.add_argument("--timeout", type=int, default=300, help="seconds, per child process")
     ap.add_argument("--legs", default="", help="with --child: run these legs only (padded,packed,switch_off)")
     ap.add_argument("--num-tokens", type=int, default=0, help="dual-head step with a token head of this many classes")
+    ap.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16", help="fp8: every leg in fp8 mode (plb_set_fp8)")
+    ap.add_argument("--profile", action="store_true", help="add plb_profile_read's per-class ms per step to every leg")
     ap.add_argument("variants", nargs="*", default=["here"])
     a = ap.parse_args()
     if a.child:
@@ -104,6 +127,7 @@ def main():
                 env, packed = dict(os.environ), 1
                 env.pop("PLBERT_PACKED", None)
                 env.pop("PLBERT_PACKED_DUAL", None)
+                env.pop("PLBERT_PACKED_FP8", None)
                 for kv in [e for e in envs.split(",") if e]:
                     k, _, val = kv.partition("=")
                     if k == "PACKED":
@@ -111,7 +135,7 @@ def main():
                     else:
                         env[k] = os.path.abspath(os.path.join(ROOT, val)) if k == "PLBERT_HIP_LIB" else val
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--batch", batch, "--packed", str(packed),
-                       "--steps", str(a.steps), "--warmup", str(a.warmup), "--num-tokens", str(a.num_tokens)]
+                       "--steps", str(a.steps), "--warmup", str(a.warmup), "--num-tokens", str(a.num_tokens), "--dtype", a.dtype] + (["--profile"] if a.profile else [])
                 try:
                     out = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=a.timeout)
                 except subprocess.TimeoutExpired:
@@ -125,13 +149,14 @@ def main():
                 print(json.dumps({"variant": label, "rep": rep, **d}), flush=True)
                 for leg, r in d["legs"].items():
                     res.setdefault((batch, label, leg), []).append(r)
-    print("--- median over the runs: ms/step (all runs) | valid tokens/s | rows executed")
+    print("--- median over the runs: ms/step (all runs) | valid tokens/s | rows executed | spread of the runs")
     med = {}
     for (batch, label, leg), rs in res.items():
         ms = [r["ms_per_step"] for r in rs]
         med[(batch, label, leg)] = statistics.median(ms)
         print(f"{batch:7s} {label:10s} {leg:10s} {statistics.median(ms):8.3f} ({', '.join(f'{x:.3f}' for x in ms)}) | "
-              f"{statistics.median(r['valid_tokens_per_s'] for r in rs):10.0f} | {rs[0]['rows']} of {rs[0]['of']}")
+              f"{statistics.median(r['valid_tokens_per_s'] for r in rs):10.0f} | {rs[0]['rows']} of {rs[0]['of']} | "
+              f"{100 * (max(ms) - min(ms)) / statistics.median(ms):.1f} %")
     base = a.variants[0].partition(":")[0]
     for (batch, label, leg), m in med.items():
         ref = med.get((batch, base, "padded"))
