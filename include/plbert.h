@@ -152,6 +152,64 @@ int plb_loss_fwd_bwd_dual(PlbEngine* e, const int64_t* masked_ids, const int64_t
 int plb_adamw_step(PlbEngine* e, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t step,
                    double grad_scale, void* stream);
 
+/* ---- gradient accumulation and global-norm clipping (opt-in: a step that calls none of these launches what it launched
+ * before) ----
+ * Stands in for what the reference's trio `optimizer.zero_grad(); accelerator.backward(loss); optimizer.step()`
+ * (train.py:355-357) gives a caller for free: .grad accumulates over several backward() calls until zero_grad, and
+ * torch.nn.utils.clip_grad_norm_ / accelerator.clip_grad_norm_ sits between backward and step. Every backward entry point
+ * here OVERWRITES the bound gradient buffer; these calls add the accumulation beside it, in a second flat buffer of the
+ * caller's, and a norm / clipping coefficient that never leaves the device. Plain vector loads and stores, no atomics on
+ * gradient data, fixed summation order: results are bitwise reproducible from run to run.
+ * plb_grad_accum_bind: accum = `total` floats laid out like grads (16-byte aligned, contents arbitrary); NULL unbinds.
+ *   Host state only. The workspace is not involved.
+ * plb_grad_accum_add: folds the gradients the LAST backward entry point (plb_loss_fwd_bwd*, plb_encode_bwd) left in the
+ *   gradient buffer into a WINDOW of micro-steps: phase 0 FIRST (accum = grads; opens the window), 1 ADD (accum += grads),
+ *   2 LAST (grads = accum + grads; closes the window: the gradient buffer then holds the sum of the window's micro-steps in
+ *   the order ((g1 + g2) + g3) + ..., fp32). A window of one micro-step needs no add at all.
+ *   Ranges: the ones plb_adamw_step steps — [0, trainable), or [0, offset of PLB_HEAD_W) after plb_encode_bwd, plus the
+ *   token head after a dual-head call. The engine keeps the UNION of what the window's micro-steps produced; a range in the
+ *   union that a micro-step did not produce contributes zeros (an ADD skips it; a LAST copies the accumulator out — that
+ *   part of the gradient buffer is never read, a phoneme-only call leaves the token range alone). After LAST the "has a
+ *   gradient" state of the phoneme head and the token head IS the union: plb_allreduce_grads, plb_grad_norm and either AdamW
+ *   entry cover exactly the accumulated ranges, and the token head's step count advances once per update.
+ *   norm_buf (LAST only; NULL: not wanted): every workgroup of the LAST pass also leaves the sum of squares of the values it
+ *   stored behind the four result floats of norm_buf, so that an accumulated and clipped step reads its gradients once
+ *   (plb_grad_norm with have_partials = 1).
+ *   Fails BEFORE anything is launched, with a text: no buffer bound; ADD or LAST without a FIRST; the same gradients added
+ *   twice (no backward entry point has run since the last add); micro-steps of one window on different parameters
+ *   (plb_adamw_step[_clipped], plb_sync_weights, plb_broadcast_params and plb_grad_accum_bind end a window); micro-steps of
+ *   which some were all-reduced and some not.
+ *   Ordering: like plb_adamw_step, an add first joins the all-reduce pieces its micro-step issued. No add drops a live
+ *   plb_encode stash.
+ * plb_grad_norm_floats: floats of norm_buf (16-byte aligned, ZERO-FILLED once by the caller): [0] total_norm, [1] coef,
+ *   [2] 1.0 when the norm was not finite else 0.0, [3] the number of updates plb_adamw_step_clipped left out for that reason
+ *   (it only ever grows; the caller may zero it), then the partial sums of every range.
+ * plb_grad_norm: total_norm = grad_scale * sqrt(sum of squares of the gradients plb_adamw_step is about to step), the sum
+ *   in fp32 per workgroup on a fixed grid and in double over the workgroups; coef = min(1, max_norm / (total_norm + 1e-6)),
+ *   the constants of torch.nn.utils.clip_grad_norm_; max_norm <= 0: no clipping, coef = 1. A norm that is not finite gives
+ *   [2] = 1 and coef = 0. have_partials = 1: use the partial sums the preceding plb_grad_accum_add(LAST, norm_buf) left
+ *   (fails if there are none in this buffer, or if the gradients were exchanged since); 0: one pass over the gradients.
+ *   Nothing is read back: the host may look at norm_buf whenever it reads the loss.
+ * plb_adamw_step_clipped: plb_adamw_step with the gradient (g * grad_scale) * coef, coef = norm_buf[1] loaded on the device
+ *   (the two products in that order: torch forms the mean gradient, then clips it). With coef == 1 every output is
+ *   bit-identical to plb_adamw_step's. norm_buf[2] != 0: parameters, moments and compute copies are left untouched — like
+ *   the hand-off skip, which is tested first and keeps its meaning — and norm_buf[3] grows by one (the launch writes that
+ *   one float although the argument is const). The host's step count, and plb_token_head_steps after a dual-head window,
+ *   have then advanced for an update that did not happen: a host that cares rewinds them when it sees [3] grow.
+ * HEALTH WORD (plb_status): unchanged. A micro-step whose hand-off timed out leaves the word set; either AdamW entry skips;
+ *   after plb_status has reported it the host starts the window again with FIRST.
+ * DATA-PARALLEL RUNS: with overlap off (plb_set_grad_overlap(e, 0)), or with a host-side exchange, the micro-steps do NOT
+ *   call plb_allreduce_grads and ONE exchange follows LAST (plb_allreduce_grads covers the accumulated ranges). With overlap
+ *   on every micro-step's pieces travel as usual and are joined by its add: the same sum, with k times the traffic.
+ *   grad_scale = 1 / (world * k) turns the sum over k micro-steps and `world` ranks into the mean. The norm is taken AFTER
+ *   the exchange (have_partials = 0 unless the window came in all-reduced), so every rank computes the same coef. */
+int64_t plb_grad_norm_floats(const PlbEngine* e);
+int plb_grad_accum_bind(PlbEngine* e, float* accum);
+int plb_grad_accum_add(PlbEngine* e, int32_t phase, float* norm_buf, void* stream);
+int plb_grad_norm(PlbEngine* e, double grad_scale, double max_norm, float* norm_buf, int32_t have_partials, void* stream);
+int plb_adamw_step_clipped(PlbEngine* e, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           int32_t step, double grad_scale, const float* norm_buf, void* stream);
+
 /* fp8 mode (BASELINE.json configs[4]): EVERY projection GEMM of the shared layer runs on OCP fp8 operands with fp32
  * accumulation through the block-scaled MFMA with unit block scales (twice the bf16 MFMA rate) — forward: QKV, dense
  * (+ LayerNorm 1), FFN up (+ gelu_new), FFN output (+ LayerNorm 2); backward: the four dX GEMMs (two of them carrying a

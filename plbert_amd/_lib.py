@@ -57,6 +57,7 @@ PUBLIC_SYMBOLS = [
     "plb_comm_info", "plb_comm_pieces", "plb_last_application_rows", "plb_last_call_rows",
     "plb_packing_plan", "plb_forward_packed", "plb_loss_fwd_bwd_packed", "plb_loss_fwd_packed", "plb_set_packed_dual",
     "plb_set_packed_fp8",
+    "plb_grad_norm_floats", "plb_grad_accum_bind", "plb_grad_accum_add", "plb_grad_norm", "plb_adamw_step_clipped",
     "plb_loss_fwd_bwd_dual_packed", "plb_encode", "plb_encode_bwd", "plb_status", "plb_status_ex", "plb_poll_status", "plb_status_export", "plb_status_import", "plb_broadcast_params", "plb_set_grad_overlap", "plb_allreduce_grads", "plb_apply_mask",
     "plb_mask_batch", "plb_profile_enable", "plb_profile_num_classes", "plb_profile_class_name", "plb_profile_read",
     # test / tuning hooks (documented as such at the end of the header)
@@ -139,6 +140,20 @@ class PlbLayerNorm(C.Structure):
         ("partials", C.c_void_p), ("nblocks", C.c_int), ("accumulate", C.c_int),
         ("out8", C.c_void_p), ("ld8", C.c_int), ("q_scale", C.c_void_p), ("q_amax", C.c_void_p),
     ]
+
+
+# csrc/plbert_kernels.h: the fixed grid of the partial-sum launches and the floats one of its workgroups owns
+PLB_NORM_PARTS = 1024
+
+
+def norm_chunk(n):
+    """plb_norm_chunk: floats per workgroup of a partial-sum launch over n floats (whole passes of 256 threads x float4)."""
+    return (n + PLB_NORM_PARTS * 1024 - 1) // (PLB_NORM_PARTS * 1024) * 1024
+
+
+def norm_chain(n):
+    """PLB_NORM_CHAIN: the longest chain of fp32 additions behind one partial sum of a launch over n floats."""
+    return 4 * (norm_chunk(n) // 1024) + 6 + 3
 
 
 _lib = None
@@ -247,6 +262,26 @@ def lib():
     if hasattr(L, "plb_set_packed_fp8"):   # (likewise: an A/B build may predate packed fp8 calls)
         L.plb_set_packed_fp8.restype = C.c_int
         L.plb_set_packed_fp8.argtypes = [vp, i32]
+    if hasattr(L, "plb_grad_accum_add"):   # (likewise: an A/B build may predate gradient accumulation and clipping)
+        L.plb_grad_norm_floats.restype = C.c_int64
+        L.plb_grad_norm_floats.argtypes = [vp]
+        L.plb_grad_accum_bind.restype = C.c_int
+        L.plb_grad_accum_bind.argtypes = [vp, vp]
+        L.plb_grad_accum_add.restype = C.c_int
+        L.plb_grad_accum_add.argtypes = [vp, i32, vp, vp]
+        L.plb_grad_norm.restype = C.c_int
+        L.plb_grad_norm.argtypes = [vp, f64, f64, vp, i32, vp]
+        L.plb_adamw_step_clipped.restype = C.c_int
+        L.plb_adamw_step_clipped.argtypes = [vp, f64, f64, f64, f64, f64, i32, f64, vp, vp]
+        L.plb_launch_grad_accum.restype = C.c_int
+        L.plb_launch_grad_accum.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp]
+        L.plb_launch_grad_sumsq.restype = C.c_int
+        L.plb_launch_grad_sumsq.argtypes = [vp, C.c_size_t, vp, vp]
+        L.plb_launch_grad_norm_finish.restype = C.c_int
+        L.plb_launch_grad_norm_finish.argtypes = [vp, C.c_int, f64, f64, vp, vp]
+        L.plb_launch_adamw_clipped.restype = C.c_int
+        L.plb_launch_adamw_clipped.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, f64, f64, f64, f64, f64, C.c_int, f64, vp, C.c_int,
+                                               vp, C.c_int, vp]
     L.plb_status_export.restype = C.c_int
     L.plb_status_export.argtypes = [vp, vp, vp]
     L.plb_status_import.restype = C.c_int

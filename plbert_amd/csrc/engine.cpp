@@ -12,7 +12,7 @@
 // This unit: the parameter layout, the workspace carve (plb_create / plb_bind), the weight copies (plb_sync_weights,
 // plb_adamw_step) and the entry points that are one launch. Only writer of PlbEngine's layout and capacity block, the
 // workspace offsets, the bound buffers, the side stream and its events, tok_pad_zeroed and (with plb_status) tok_steps.
-// The other units: engine_prof.cpp, engine_comm.cpp, engine_fp8.cpp, engine_layers.cpp, engine_calls.cpp.
+// The other units: engine_prof.cpp, engine_comm.cpp, engine_fp8.cpp, engine_layers.cpp, engine_calls.cpp, engine_optim.cpp.
 #include <stdarg.h>
 
 #include <new>
@@ -288,7 +288,7 @@ extern "C" int plb_bind(PlbEngine* e, float* params, float* grads, float* exp_av
   return 0;
 }
 
-static int sync_transposes(PlbEngine* e, hipStream_t s, bool exact_fp8 = true) {
+int sync_transposes(PlbEngine* e, hipStream_t s, bool exact_fp8) {
   const int H = e->H, I = e->I, E = e->E;
 
   if (e->NT) {  // bias of the token head padded to NTp columns (fused GEMM + CE passes)
@@ -322,6 +322,7 @@ static int sync_transposes(PlbEngine* e, hipStream_t s, bool exact_fp8 = true) {
 extern "C" int plb_sync_weights(PlbEngine* e, void* stream) {
   if (!e || !e->ws) return fail("plb_sync_weights: engine not bound");
   drop_stash(e, "plb_sync_weights refreshed the compute copies since");
+  end_accum_window(e, "plb_sync_weights refreshed the compute copies");
   hipStream_t s = (hipStream_t)stream;
   TRY(plb_launch_cast_bf16(e->params, e->at<bf16_t>(e->o_wbf), (size_t)e->ptotal, s));
   return sync_transposes(e, s);
@@ -447,6 +448,7 @@ extern "C" int plb_adamw_step(PlbEngine* e, double lr, double beta1, double beta
   if (e->infer) return fail("plb_adamw_step: inference-only engine");
   if (step < 1) return fail("plb_adamw_step: step counts from 1");
   drop_stash(e, "plb_adamw_step moved the weights since");
+  end_accum_window(e, "plb_adamw_step moved the weights");
   hipStream_t s = (hipStream_t)stream;
   if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
     HIPTRY(ev_wait(e, s, e->ev_comm_done));

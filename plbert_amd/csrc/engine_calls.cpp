@@ -1,7 +1,8 @@
 // Call-level stages of the engine: row selection of a padded or token-packed call, the heads, the stages of a loss call and
 // the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd. Only
 // writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
-// last_exec_rows, tok_grads_live and head_grads_live. (packed_dual, packed_fp8: plb_set_packed_dual / _fp8, engine.cpp.)
+// last_exec_rows, tok_grads_live and head_grads_live (which a LAST add of engine_optim.cpp replaces by its window's union).
+// (packed_dual, packed_fp8: plb_set_packed_dual / _fp8, engine.cpp.)
 #include "engine_internal.h"
 
 // Every call that writes the workspace or moves the weights ends the life of a plb_encode stash.
@@ -105,6 +106,8 @@ static int begin_training_call(PlbEngine* e, bool dual, hipStream_t s) {
   e->head_grads_live = true;
   e->comm_pending = false;
   e->grads_reduced = false;
+  e->grads_fresh = true;   // (plb_grad_accum_add: these gradients have not been added yet; partials of older ones are void)
+  e->norm_nparts = 0;
   e->piece_floats = 0;
   e->piece_count = 0;
   e->status_collectives = 0;

@@ -135,6 +135,17 @@ struct PlbEngine {
   bool head_grads_live = true;  // ... phoneme-head gradients (false after plb_encode_bwd: AdamW then stops at PLB_HEAD_W)
   bool tok_pad_zeroed = false;  // pad columns of the transposed copy are zeroed once
   int tok_steps = 0;            // AdamW steps the token head has taken (its own bias correction)
+  // ---- gradient accumulation window and norm partials: engine_optim.cpp (grads_fresh is set, and norm_nparts cleared, by
+  // begin_training_call in engine_calls.cpp; the calls that move the weights end a window through end_accum_window) ----
+  float* accum = nullptr;       // plb_grad_accum_bind: the caller's buffer, `total` floats like grads
+  bool grads_fresh = false;     // a backward entry point wrote the gradient buffer and no add has consumed it yet
+  bool win_open = false;        // between a FIRST add and its LAST
+  const char* win_closed_by = "no FIRST add has opened one";
+  bool win_head = false, win_tok = false;   // union of what the window's micro-steps produced (the encoder range always is)
+  bool win_reduced = false;     // the window's micro-steps came in all-reduced (overlap on) or not: they must agree
+  const float* norm_src = nullptr;   // the LAST add left norm_nparts partials behind the four result floats of this buffer
+  int norm_nparts = 0;
+  bool norm_reduced = false;    // ... taken from gradients in this exchange state
   // ---- encode stash: engine_calls.cpp (every unit ends its life through drop_stash) ----
   // plb_encode / plb_encode_bwd: the stash of a differentiable forward is live until a call writes the workspace or moves
   // the weights (stash_dead_by: which one — the text plb_encode_bwd fails with)
@@ -300,5 +311,9 @@ int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, in
                 int* du_rows, hipStream_t s);
 // engine_calls.cpp
 void drop_stash(PlbEngine* e, const char* by);
+// engine.cpp
+int sync_transposes(PlbEngine* e, hipStream_t s, bool exact_fp8 = true);
+// engine_optim.cpp
+void end_accum_window(PlbEngine* e, const char* by);
 
 #pragma GCC visibility pop

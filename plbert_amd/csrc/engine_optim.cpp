@@ -1,0 +1,170 @@
+// Gradient accumulation, the global gradient norm and the clipped AdamW update (include/plbert.h: plb_grad_accum_*,
+// plb_grad_norm, plb_adamw_step_clipped). Host bookkeeping of a window of micro-steps plus launches of rowops.hip; no
+// workspace of its own: the accumulator and the norm buffer are the caller's. Only writer of PlbEngine's accumulation
+// block (grads_fresh / norm_nparts are also reset by begin_training_call, engine_calls.cpp); after a LAST add it sets
+// head_grads_live, tok_grads_live and grads_reduced to what the window accumulated.
+#include "engine_internal.h"
+
+void end_accum_window(PlbEngine* e, const char* by) {
+  if (e && e->win_open) { e->win_open = false; e->win_closed_by = by; }
+}
+
+extern "C" int64_t plb_grad_norm_floats(const PlbEngine* e) {
+  // 4 result floats + one set of partials per range a launch can cover on its own: encoder, phoneme head, token head
+  return e ? 4 + 3 * (int64_t)PLB_NORM_PARTS : -1;
+}
+
+extern "C" int plb_grad_accum_bind(PlbEngine* e, float* accum) {
+  if (!e) return fail("plb_grad_accum_bind: null engine");
+  if ((uintptr_t)accum & 15) return fail("plb_grad_accum_bind: the buffer must be 16-byte aligned");
+  end_accum_window(e, "plb_grad_accum_bind changed the buffer");
+  e->accum = accum;
+  return 0;
+}
+
+namespace {
+struct Seg { int64_t a, b; int phase; };   // phase 4: sum of squares only
+}
+
+extern "C" int plb_grad_accum_add(PlbEngine* e, int32_t phase, float* norm_buf, void* stream) {
+  if (!e) return fail("plb_grad_accum_add: null engine");
+  if (e->infer) return fail("plb_grad_accum_add: inference-only engine");
+  if (!e->accum) return fail("plb_grad_accum_add: no accumulation buffer bound (plb_grad_accum_bind)");
+  if (phase < 0 || phase > 2) return fail("plb_grad_accum_add: phase %d is none of 0 (first), 1 (add), 2 (last)", phase);
+  if (norm_buf && phase != 2) return fail("plb_grad_accum_add: partial sums belong to the LAST add (phase 2)");
+  if ((uintptr_t)norm_buf & 15) return fail("plb_grad_accum_add: norm_buf must be 16-byte aligned");
+  if (phase != 0 && !e->win_open)
+    return fail("plb_grad_accum_add: phase %d without a FIRST add: no window is open (%s)", phase, e->win_closed_by);
+  if (!e->grads_fresh)
+    return fail("plb_grad_accum_add: the gradient buffer holds nothing new: no backward call has run since the last add "
+                "(the same gradients would be added twice)");
+  if (!e->ws || !e->grads) return fail("plb_grad_accum_add: gradient buffer not bound");
+  if (phase != 0 && e->grads_reduced != e->win_reduced)
+    return fail("plb_grad_accum_add: this micro-step's gradients are %s, the window's are %s", e->grads_reduced ? "all-reduced" : "local",
+                e->win_reduced ? "all-reduced" : "local");
+  hipStream_t s = (hipStream_t)stream;
+  if (e->comm_pending) {  // this micro-step's all-reduce pieces are still in flight on the communication stream
+    HIPTRY(ev_wait(e, s, e->ev_comm_done));
+    e->comm_pending = false;
+  }
+  // What this micro-step produced | what the window holds so far. The encoder range is always both.
+  const bool head = e->head_grads_live, tok = e->tok_grads_live && e->NT > 0;
+  const bool uhead = phase == 0 ? false : e->win_head, utok = phase == 0 ? false : e->win_tok;
+  const bool want_sq = norm_buf != nullptr;
+  auto pick = [&](bool produced, bool in_union) -> int {   // -1: nothing to launch
+    if (phase == 0) return produced ? 0 : -1;
+    if (phase == 1) return !produced ? -1 : in_union ? 1 : 0;   // a range that joins the window now starts from this copy
+    if (produced) return in_union ? 2 : want_sq ? 4 : -1;       // ... and at LAST it already is the sum
+    return in_union ? 3 : -1;                                   // zeros from this micro-step: its part of grads is not read
+  };
+  const int64_t hw = e->poff[PLB_HEAD_W], tw = e->poff[PLB_TOK_W];
+  Seg seg[3];
+  int nseg = 0;
+  seg[nseg++] = Seg{0, hw, pick(true, phase != 0)};
+  const int ph = pick(head, uhead);
+  if (ph >= 0) {
+    if (ph == seg[0].phase) seg[0].b = e->ptrain;   // adjacent and alike: one launch
+    else seg[nseg++] = Seg{hw, e->ptrain, ph};
+  }
+  const int pt = e->NT > 0 ? pick(tok, utok) : -1;
+  if (pt >= 0) seg[nseg++] = Seg{tw, e->ptotal, pt};
+  int nparts = 0;
+  for (int i = 0; i < nseg; ++i) {
+    const Seg& g = seg[i];
+    float* part = want_sq ? norm_buf + 4 + nparts : nullptr;
+    const size_t n = (size_t)(g.b - g.a);
+    if (g.phase != 3 && g.phase != 4) HB_R(s, e->grads + g.a, n * 4, "gradient accumulation (reads the gradient buffer)");
+    if (g.phase == 4) HB_R(s, e->grads + g.a, n * 4, "sum of squares (reads the gradient buffer)");
+    if (g.phase != 0 && g.phase != 4) HB_R(s, e->accum + g.a, n * 4, "gradient accumulation (reads the accumulator)");
+    if (g.phase < 2) HB_W(s, e->accum + g.a, n * 4, "gradient accumulation (writes the accumulator)");
+    if (g.phase == 2 || g.phase == 3) HB_W(s, e->grads + g.a, n * 4, "gradient accumulation (writes the gradient buffer)");
+    if (part) HB_W(s, part, PLB_NORM_PARTS * 4, "gradient accumulation (writes the partial sums)");
+    if (g.phase == 4) TRY(plb_launch_grad_sumsq(e->grads + g.a, n, part, s));
+    else TRY(plb_launch_grad_accum(e->accum + g.a, e->grads + g.a, n, g.phase, part, s));
+    if (part) nparts += PLB_NORM_PARTS;
+  }
+  e->grads_fresh = false;
+  e->win_head = uhead || head;
+  e->win_tok = utok || tok;
+  if (phase == 0) { e->win_open = true; e->win_reduced = e->grads_reduced; }
+  if (phase == 2) {
+    e->win_open = false;
+    e->win_closed_by = "the LAST add closed it";
+    // plb_allreduce_grads, plb_grad_norm and either AdamW entry now cover exactly what the window accumulated
+    e->head_grads_live = e->win_head;
+    e->tok_grads_live = e->win_tok;
+    e->grads_reduced = e->win_reduced;
+    e->norm_src = norm_buf; e->norm_nparts = nparts; e->norm_reduced = e->grads_reduced;
+  }
+  return 0;
+}
+
+extern "C" int plb_grad_norm(PlbEngine* e, double grad_scale, double max_norm, float* norm_buf, int32_t have_partials,
+                             void* stream) {
+  if (!e) return fail("plb_grad_norm: null engine");
+  if (e->infer) return fail("plb_grad_norm: inference-only engine");
+  if (!norm_buf || ((uintptr_t)norm_buf & 15)) return fail("plb_grad_norm: norm_buf must be a 16-byte aligned device buffer");
+  if (have_partials) {
+    if (e->norm_src != norm_buf || e->norm_nparts < 1)
+      return fail("plb_grad_norm: have_partials, but the last plb_grad_accum_add(LAST) left none in this buffer");
+    if (e->grads_reduced != e->norm_reduced)
+      return fail("plb_grad_norm: the partial sums were taken before the gradient exchange");
+  }
+  if (!e->ws || !e->grads) return fail("plb_grad_norm: gradient buffer not bound");
+  hipStream_t s = (hipStream_t)stream;
+  int nparts = e->norm_nparts;
+  if (!have_partials) {
+    if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
+      HIPTRY(ev_wait(e, s, e->ev_comm_done));
+      e->comm_pending = false;
+    }
+    // the ranges plb_adamw_step is about to step
+    const int64_t nstep = e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W];
+    HB_R(s, e->grads, nstep * 4, "gradient norm (reads the gradient buffer)");
+    HB_W(s, norm_buf + 4, PLB_NORM_PARTS * 4, "gradient norm (writes the partial sums)");
+    TRY(plb_launch_grad_sumsq(e->grads, (size_t)nstep, norm_buf + 4, s));
+    nparts = PLB_NORM_PARTS;
+    if (e->tok_grads_live && e->NT > 0) {
+      const int64_t o = e->poff[PLB_TOK_W];
+      HB_R(s, e->grads + o, (e->ptotal - o) * 4, "gradient norm (reads the token head's gradients)");
+      HB_W(s, norm_buf + 4 + nparts, PLB_NORM_PARTS * 4, "gradient norm (writes the partial sums)");
+      TRY(plb_launch_grad_sumsq(e->grads + o, (size_t)(e->ptotal - o), norm_buf + 4 + nparts, s));
+      nparts += PLB_NORM_PARTS;
+    }
+    e->norm_nparts = 0;   // (these partials are not a LAST add's: a later have_partials call must not take them for such)
+  }
+  HB_R(s, norm_buf + 4, (size_t)nparts * 4, "gradient norm (reads the partial sums)");
+  HB_W(s, norm_buf, 16, "gradient norm (writes norm, coefficient and flag)");
+  TRY(plb_launch_grad_norm_finish(norm_buf + 4, nparts, grad_scale, max_norm, norm_buf, s));
+  return 0;
+}
+
+extern "C" int plb_adamw_step_clipped(PlbEngine* e, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                      int32_t step, double grad_scale, const float* norm_buf, void* stream) {
+  if (!e || !e->ws || !e->grads || !e->m || !e->v) return fail("plb_adamw_step_clipped: optimizer buffers not bound");
+  if (e->infer) return fail("plb_adamw_step_clipped: inference-only engine");
+  if (step < 1) return fail("plb_adamw_step_clipped: step counts from 1");
+  if (!norm_buf) return fail("plb_adamw_step_clipped: norm_buf is null (plb_grad_norm writes it)");
+  drop_stash(e, "plb_adamw_step_clipped moved the weights since");
+  end_accum_window(e, "plb_adamw_step_clipped moved the weights");
+  hipStream_t s = (hipStream_t)stream;
+  if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
+    HIPTRY(ev_wait(e, s, e->ev_comm_done));
+    e->comm_pending = false;
+  }
+  float* norm = const_cast<float*>(norm_buf);   // (the launch counts the updates it leaves out in norm[3])
+  HB_R(s, e->grads, e->ptotal * 4, "clipped AdamW (reads the gradient buffer)");
+  HB_W(s, norm, 16, "clipped AdamW (reads the coefficient, counts a left-out update)");
+  // the ranges, the step counts and the skip word are plb_adamw_step's
+  const int64_t nstep = e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W];
+  TRY(plb_launch_adamw_clipped(e->params, e->grads, e->m, e->v, e->at<bf16_t>(e->o_wbf), (size_t)nstep, lr, beta1, beta2,
+                               eps, weight_decay, step, grad_scale, e->at<unsigned int>(e->o_lnerr), 1, norm, 1, s));
+  if (e->tok_grads_live) {
+    const int64_t o = e->poff[PLB_TOK_W];
+    e->tok_steps += 1;
+    TRY(plb_launch_adamw_clipped(e->params + o, e->grads + o, e->m + o, e->v + o, e->at<bf16_t>(e->o_wbf) + o,
+                                 (size_t)(e->ptotal - o), lr, beta1, beta2, eps, weight_decay, e->tok_steps, grad_scale,
+                                 e->at<unsigned int>(e->o_lnerr), 2, norm, 0, s));
+  }
+  return sync_transposes(e, s, false);
+}

@@ -311,6 +311,33 @@ int plb_launch_apply_mask(const PlbApplyMask* p, hipStream_t stream);
 int plb_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, size_t n, double lr, double beta1,
                      double beta2, double eps, double wd, int step, double grad_scale, unsigned int* skip_if_nonzero,
                      int count_skip, hipStream_t stream);
+// ---- gradient accumulation, global-norm clipping (rowops.hip; include/plbert.h plb_grad_accum_add / plb_grad_norm /
+// plb_adamw_step_clipped). Both partial-sum launches run on a FIXED grid of PLB_NORM_PARTS workgroups: workgroup b owns
+// floats [b * chunk, (b + 1) * chunk) of the range, chunk = plb_norm_chunk(n), and writes partials[b] (0 for an empty chunk).
+#define PLB_NORM_PARTS 1024
+// floats per workgroup: n / PLB_NORM_PARTS rounded up to whole passes of 256 threads x float4
+static inline size_t plb_norm_chunk(size_t n) {
+  return (n + (size_t)PLB_NORM_PARTS * 1024 - 1) / ((size_t)PLB_NORM_PARTS * 1024) * 1024;
+}
+// Longest chain of fp32 additions behind one partial: a thread adds 4 squares per pass (one fused multiply-add each),
+// then 6 steps of the wave reduction and 3 additions over the four waves.
+#define PLB_NORM_CHAIN(n) (4 * (plb_norm_chunk(n) / 1024) + 6 + 3)
+// phase 0: accum = grads | 1: accum += grads | 2: grads = accum + grads | 3: grads = accum. partials (phases 2 and 3 only,
+// or null): PLB_NORM_PARTS floats, the sums of squares of the values each workgroup stored. n % 4 == 0, 16-byte pointers.
+int plb_launch_grad_accum(float* accum, float* grads, size_t n, int phase, float* partials, hipStream_t stream);
+// partials[0 .. PLB_NORM_PARTS) = per-workgroup sums of squares of grads[0, n); nothing is written to grads
+int plb_launch_grad_sumsq(const float* grads, size_t n, float* partials, hipStream_t stream);
+// out[0] = total_norm = grad_scale * sqrt(sum of the nparts partials, in double, fixed order); out[1] = coef =
+// min(1, max_norm / (total_norm + 1e-6)), 1 when max_norm <= 0; total_norm not finite: out[2] = 1 and coef = 0, else
+// out[2] = 0. out[3] is left alone (plb_launch_adamw_clipped counts there).
+int plb_launch_grad_norm_finish(const float* partials, int nparts, double grad_scale, double max_norm, float* out,
+                                hipStream_t stream);
+// plb_launch_adamw with the gradient (g * grad_scale) * norm[1]; bit-identical to it when norm[1] == 1. norm[2] != 0: the
+// launch writes nothing (after the skip word, which is tested first) and, with count_nonfinite, adds 1 to norm[3].
+int plb_launch_adamw_clipped(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, size_t n, double lr, double beta1,
+                             double beta2, double eps, double wd, int step, double grad_scale,
+                             unsigned int* skip_if_nonzero, int count_skip, float* norm, int count_nonfinite,
+                             hipStream_t stream);
 // End of a loss call: mirror the hand-off error word into host-visible memory (host_mirror: device pointer of a pinned
 // host word) and, when it is non-zero, overwrite the loss with NaN — whoever reads the loss sees that the step is invalid
 int plb_launch_step_status(unsigned int* ln_err, float* loss, unsigned int* host_mirror, const float* summed, hipStream_t stream);

@@ -185,7 +185,8 @@ class HipEngine:
 
     def device_bytes(self):
         """Bytes of device memory this engine holds."""
-        ts = [self.params, self._grads, self._exp_avg, self._exp_avg_sq, self.workspace]
+        ts = [self.params, self._grads, self._exp_avg, self._exp_avg_sq, self.workspace,
+              getattr(self, "_accum", None), getattr(self, "_norm_buf", None)]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
     def __del__(self):
@@ -584,9 +585,54 @@ class HipEngine:
             return (self.total, self.total)
         return (self.layout["token_predictor.weight"][0], self.total)
 
-    def adamw_step(self, step, lr=7e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0):
+    def adamw_step(self, step, lr=7e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0, norm_buf=None):
+        """plb_adamw_step; with ``norm_buf`` (what ``grad_norm`` returned) plb_adamw_step_clipped: the gradient is
+        multiplied by the clipping coefficient the device holds there, and the update is left out when the norm was not
+        finite."""
         self._bind()
         with torch.cuda.device(self.device):
-            _lib.check(self.L.plb_adamw_step(self.handle, lr, betas[0], betas[1], eps, weight_decay, int(step),
-                                             grad_scale, self._stream()), "plb_adamw_step")
+            if norm_buf is None:
+                _lib.check(self.L.plb_adamw_step(self.handle, lr, betas[0], betas[1], eps, weight_decay, int(step),
+                                                 grad_scale, self._stream()), "plb_adamw_step")
+            else:
+                _lib.check(self.L.plb_adamw_step_clipped(self.handle, lr, betas[0], betas[1], eps, weight_decay, int(step),
+                                                         grad_scale, norm_buf.data_ptr(), self._stream()),
+                           "plb_adamw_step_clipped")
         self._synced_version = self.params._version
+
+    # ---- gradient accumulation and global-norm clipping (include/plbert.h: plb_grad_accum_add, plb_grad_norm) ----
+    GRAD_FIRST, GRAD_ADD, GRAD_LAST = 0, 1, 2
+
+    @property
+    def norm_buf(self):
+        """The engine's own norm buffer (plb_grad_norm_floats floats, zero-filled once): [0] total norm, [1] clipping
+        coefficient, [2] 1.0 when the norm was not finite, [3] updates left out for that reason; then the partial sums."""
+        if getattr(self, "_norm_buf", None) is None:
+            with torch.cuda.device(self.device):
+                self._norm_buf = torch.zeros(int(self.L.plb_grad_norm_floats(self.handle)), dtype=torch.float32,
+                                             device=self.device)
+        return self._norm_buf
+
+    def grad_accum_add(self, phase, want_partials=False):
+        """Fold the gradients of the last backward call into the accumulation window: ``phase`` GRAD_FIRST / GRAD_ADD /
+        GRAD_LAST (after LAST ``self.grads`` holds the window's sum). The accumulator (a second gradient-sized buffer) is
+        allocated and bound by the first call. ``want_partials`` (LAST only): the pass also leaves the partial sums of
+        squares in ``self.norm_buf`` for ``grad_norm(have_partials=True)``."""
+        self._bind()
+        with torch.cuda.device(self.device):
+            if getattr(self, "_accum", None) is None:
+                self._accum = torch.zeros(self.total, dtype=torch.float32, device=self.device)
+                _lib.check(self.L.plb_grad_accum_bind(self.handle, self._accum.data_ptr()), "plb_grad_accum_bind")
+            nb = self.norm_buf.data_ptr() if want_partials else None
+            _lib.check(self.L.plb_grad_accum_add(self.handle, int(phase), nb, self._stream()), "plb_grad_accum_add")
+
+    def grad_norm(self, grad_scale=1.0, max_norm=0.0, have_partials=False):
+        """Global norm of the gradients the next ``adamw_step`` covers, times ``grad_scale``, and the coefficient of
+        torch.nn.utils.clip_grad_norm_ for ``max_norm`` (<= 0: no clipping), on the device (plb_grad_norm). Returns
+        ``self.norm_buf``; its first four floats are the result. Nothing is read back."""
+        self._bind()
+        with torch.cuda.device(self.device):
+            nb = self.norm_buf
+            _lib.check(self.L.plb_grad_norm(self.handle, float(grad_scale), float(max_norm or 0.0), nb.data_ptr(),
+                                            int(bool(have_partials)), self._stream()), "plb_grad_norm")
+        return nb

@@ -150,7 +150,8 @@ def initialize_model(config, log_dir, resuming, device=None, max_batch=None):
     trainer = PLBertTrainer(cfg, num_phonemes=len(symbols), max_batch=max_batch or per_rank,
                             max_seq=int(config["dataset_params"]["max_seq_length"]), lr=float(tp["learning_rate"]),
                             device=device, packed_dual=tp.get("packed_dual"),      # (None: PLBERT_PACKED_DUAL)
-                            packed_fp8=tp.get("packed_fp8"))                       # (None: PLBERT_PACKED_FP8)
+                            packed_fp8=tp.get("packed_fp8"),                       # (None: PLBERT_PACKED_FP8)
+                            max_grad_norm=tp.get("max_grad_norm"))                 # (not in the reference's config.yml; absent: off)
     if config["model_params"].get("pretrained_model"):
         print(f"Loading pretrained model from: {config['model_params']['pretrained_model']}")
         load_checkpoint(trainer, config["model_params"]["pretrained_model"])
@@ -278,6 +279,33 @@ class _LossReader:
         return float(self.host[k][0])
 
 
+class _NormReader:
+    """The gradient norm of a clipped step (``trainer.last_grad_norm[0]``, overwritten by the next step), read back the way
+    ``_LossReader`` reads the loss: copied into one of two pinned host words on the step's stream, waited for by event."""
+
+    def __init__(self, trainer):
+        import torch
+        self.torch, self.trainer = torch, trainer
+        self.host = [torch.zeros(1).pin_memory() for _ in range(2)]
+        self.events = [torch.cuda.Event() for _ in range(2)]
+        self.n = 0
+
+    def post(self):
+        k = self.n & 1
+        self.n += 1
+        self.host[k].copy_(self.trainer.last_grad_norm[:1], non_blocking=True)
+        self.events[k].record(self.torch.cuda.current_stream(self.trainer.engine.device))
+        return k
+
+    def read(self, k):
+        self.events[k].synchronize()
+        return float(self.host[k][0])
+
+    def now(self):
+        """Behind a loss that has just been read back with ``.item()``: the stream is idle, the norm is this step's."""
+        return float(self.trainer.last_grad_norm[0])
+
+
 def train_loop(trainer, train_loader, val_loader, current_step, num_steps, save_interval, log_interval, log, log_dir,
                device_masking=False, word_separator=None, max_epochs=MAX_EPOCHS, deferred_readback=True, reader=None):
     """train.py:338-379: validation first, then epochs until ``num_steps``; checkpoint + validation every
@@ -307,12 +335,27 @@ def train_loop(trainer, train_loader, val_loader, current_step, num_steps, save_
     if reader is None:
         reader = _LossReader(trainer.engine.device)
     note = lambda **kw: log(step=current_step, epoch=epoch, **kw)
+    # training_params.max_grad_norm: the norm is logged wherever the loss is read back (a step that did not update, the
+    # zero-loss fallback, leaves no norm of its own: the record then carries the previous step's)
+    norms = _NormReader(trainer) if getattr(trainer, "max_grad_norm", None) is not None else None
 
-    def record(loss):
+    def enqueue(batch):
+        """One step and the posts of its read-backs: (loss handle, batch, norm handle)."""
+        loss = trainer.step(batch)
+        nk = norms.post() if norms is not None and trainer.last_grad_norm is not None else None
+        return (reader.post(loss), batch, nk)
+
+    def rerun(batch):
+        loss = _checked(trainer, lambda: trainer.step(batch), note)
+        return loss, (norms.now() if norms is not None and trainer.last_grad_norm is not None else None)
+
+    def record(loss, grad_norm=None):
         nonlocal current_step
         current_step += 1
         window.append(loss)
         rec = {"phoneme_loss": loss, "epoch": epoch, "step": current_step}
+        if grad_norm is not None:
+            rec["grad_norm"] = grad_norm
         if len(window) == log_interval:
             rec["phoneme_loss_avg"] = float(np.mean(window))
         log(**rec)
@@ -323,15 +366,16 @@ def train_loop(trainer, train_loader, val_loader, current_step, num_steps, save_
         loss is a number) — and whatever was enqueued behind this step was left out by the device: enqueue it again."""
         import math
         loss = reader.read(p[0])
+        grad_norm = norms.read(p[2]) if p[2] is not None else None
         redo = False
         try:
             trainer.engine.raise_if_failed()     # this step has completed: the word covers it (and may cover a later one)
         except HandoffTimeout as ex:
             note(handoff_timeout=str(ex), retry=1)
             if math.isnan(loss):
-                loss = _checked(trainer, lambda: trainer.step(p[1]), note)
+                loss, grad_norm = rerun(p[1])
             redo = True
-        record(loss)
+        record(loss, grad_norm)
         return redo
 
     pending = None                               # a step whose loss has not been read back yet
@@ -340,14 +384,14 @@ def train_loop(trainer, train_loader, val_loader, current_step, num_steps, save_
         for batch in _batches(train_loader, trainer, device_masking, word_separator, 0):
             ahead = current_step + (pending is not None)        # steps enqueued before this one
             try:
-                this = (reader.post(trainer.step(batch)), batch)
+                this = enqueue(batch)
             except HandoffTimeout as ex:         # the pending step completed, invalid, before this one was enqueued
                 note(handoff_timeout=str(ex), retry=1)
-                record(_checked(trainer, lambda: trainer.step(pending[1]), note))
+                record(*rerun(pending[1]))
                 pending = None
-                this = (reader.post(trainer.step(batch)), batch)
+                this = enqueue(batch)
             if pending is not None and finish(pending):
-                this = (reader.post(trainer.step(batch)), batch)
+                this = enqueue(batch)
             pending = this
             if not deferred_readback or (ahead + 1) % save_interval == 0 or ahead + 1 >= num_steps:
                 finish(pending)                  # (nothing is enqueued behind it: an invalid step is simply run again)

@@ -104,8 +104,12 @@ class PLBertTrainer:
 
     def __init__(self, cfg, num_phonemes, max_batch=32, max_seq=512, lr=7e-5, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.01, device=None, seed=0, state_dict=None, process_group=None, force_collectives=False,
-                 num_tokens=0, comm="auto", overlap=True, packed=None, packed_dual=None, packed_fp8=None):
-        """``packed``: ragged batches run on their valid tokens only (token-packed execution, include/plbert.h PlbPacking);
+                 num_tokens=0, comm="auto", overlap=True, packed=None, packed_dual=None, packed_fp8=None,
+                 max_grad_norm=None):
+        """``max_grad_norm`` (None or <= 0: off): every optimizer step clips the global norm of its mean gradient to this value
+        as torch.nn.utils.clip_grad_norm_ does, on the device (plb_grad_norm + plb_adamw_step_clipped); ``last_grad_norm``
+        then holds [norm, coefficient, not-finite flag, updates left out] as a device tensor. Nothing is read back.
+        ``packed``: ragged batches run on their valid tokens only (token-packed execution, include/plbert.h PlbPacking);
         None = PLBERT_PACKED=1. Steps in fp8 mode run padded all the same unless ``packed_fp8`` is on (None =
         PLBERT_PACKED_FP8=1; include/plbert.h plb_set_packed_fp8), and so do dual-head steps unless ``packed_dual`` is on
         (None = PLBERT_PACKED_DUAL=1; plb_set_packed_dual): both only have an effect together with ``packed``.
@@ -121,6 +125,8 @@ class PLBertTrainer:
         self.engine = HipEngine(cfg, num_phonemes, num_tokens, max_batch=max_batch, max_seq=max_seq, device=device)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.step_count = 0
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and float(max_grad_norm) > 0 else None
+        self.last_grad_norm = None   # the four result floats of the last clipped step (device)
         self.packed = packed_default() if packed is None else bool(packed)
         if packed_dual is not None:   # (None: the engine has read PLBERT_PACKED_DUAL itself)
             self.engine.set_packed_dual(packed_dual)
@@ -136,6 +142,7 @@ class PLBertTrainer:
         # raises HandoffTimeout from the next engine call: the bias-correction count goes back by the skipped updates
         self.engine._on_handoff_timeout.append(_rewind_steps(self))
         self.comm = "none"
+        self._overlap = False
         if self.reducer.active:
             if comm == "auto":   # PLBERT_COMM=rccl|torch overrides (tests: the engine's own exchange through a stand-in library)
                 comm = os.environ.get("PLBERT_COMM") or ("rccl" if own_gpu_per_rank() else "torch")
@@ -143,6 +150,7 @@ class PLBertTrainer:
                 uid = exchange_unique_id(HipEngine.comm_unique_id if self.reducer.rank == 0 else None, process_group)
                 self.engine.comm_init(uid, self.reducer.rank, self.world)
                 self.engine.set_grad_overlap(overlap)
+                self._overlap = bool(overlap)
                 self.engine.broadcast_params(0)  # DDP's start-up broadcast of rank 0's parameters
             elif comm == "torch":
                 self.reducer.broadcast_(self.engine.params)
@@ -210,10 +218,60 @@ class PLBertTrainer:
         if batch.n_masked == 0 and self.world == 1 and not dual:
             return loss  # reference: zero-loss fallback has no graph, the optimizer sees no gradients
         self.all_reduce_grads(dual)
-        self.step_count += 1
-        self.engine.adamw_step(self.step_count, self.lr, self.betas, self.eps, self.weight_decay,
-                               grad_scale=1.0 / self.world)
+        self._optimizer_step(1.0 / self.world)
         return loss
+
+    def _optimizer_step(self, grad_scale, have_partials=False):
+        """AdamW on what the gradient buffer holds; with ``max_grad_norm`` the norm (taken after the exchange, so every
+        rank computes the same coefficient) and the clipped update."""
+        self.step_count += 1
+        norm_buf = None
+        if self.max_grad_norm is not None:
+            norm_buf = self.engine.grad_norm(grad_scale, self.max_grad_norm, have_partials=have_partials)
+            self.last_grad_norm = norm_buf[:4]
+        if norm_buf is None:
+            self.engine.adamw_step(self.step_count, self.lr, self.betas, self.eps, self.weight_decay, grad_scale=grad_scale)
+        else:
+            self.engine.adamw_step(self.step_count, self.lr, self.betas, self.eps, self.weight_decay, grad_scale=grad_scale,
+                                   norm_buf=norm_buf)
+
+    def step_accumulated(self, batches):
+        """ONE optimizer step over a list of staged batches (gradient accumulation, include/plbert.h plb_grad_accum_add):
+        every batch is one loss + backward call, their gradients are summed on the device and the update uses their mean,
+        ``grad_scale = 1 / (world * len(batches))``. A data-parallel run exchanges ONCE, after the last micro-step (the
+        engine's own communicator runs with overlap off for the duration). Returns the mean of the micro-step losses as
+        a 1-element device tensor. A window in which no micro-step has a masked position (single rank, phoneme-only)
+        does not step, like ``step``."""
+        batches = list(batches)
+        if not batches:
+            raise ValueError("step_accumulated needs at least one batch")
+        if len(batches) == 1:
+            return self.step(batches[0])
+        eng = self.engine
+        k = len(batches)
+        rccl_overlap = self.comm == "rccl" and self._overlap
+        if rccl_overlap:
+            eng.set_grad_overlap(False)
+        try:
+            dual = False
+            loss_sum = None
+            clip_local = self.max_grad_norm is not None and not self.reducer.active
+            for i, b in enumerate(batches):
+                loss = self.loss_and_grads(b)
+                loss_sum = loss.clone() if loss_sum is None else loss_sum.add_(loss)
+                dual = dual or b.token_ids is not None
+                last = i == k - 1
+                eng.grad_accum_add(eng.GRAD_FIRST if i == 0 else eng.GRAD_LAST if last else eng.GRAD_ADD,
+                                   want_partials=last and clip_local)
+            loss_sum.mul_(1.0 / k)
+            if all(b.n_masked == 0 for b in batches) and self.world == 1 and not dual:
+                return loss_sum
+            self.all_reduce_grads(dual)
+            self._optimizer_step(1.0 / (self.world * k), have_partials=clip_local)
+        finally:
+            if rccl_overlap:
+                eng.set_grad_overlap(True)
+        return loss_sum
 
 
 def own_gpu_per_rank():
@@ -414,8 +472,13 @@ class AdamW:
     model's flat buffers. ``params`` must be the parameters of ONE plbert_amd model (it identifies the
     engine); state_dict()/load_state_dict() carry step + both moments (train.py:417-421 'optimizer')."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, model=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, model=None, max_grad_norm=None):
+        """``max_grad_norm`` (None or <= 0: off): ``step`` clips the global norm of the gradients it consumes (times
+        ``grad_scale``) as torch.nn.utils.clip_grad_norm_ does, on the device; ``last_grad_norm`` holds [norm, coefficient,
+        not-finite flag, updates left out] as a device tensor."""
         self.param_list = list(params)
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and float(max_grad_norm) > 0 else None
+        self.last_grad_norm = None
         if model is None:
             raise ValueError("pass model=<PhonemeOnlyModel|MultiTaskModel|AlbertModel(finetune=True)>: the fused optimizer updates the model's "
                              "flat parameter buffer")
@@ -453,7 +516,15 @@ class AdamW:
                 e.grads[off:off + size].view(shp).copy_(p.grad)
         self.step_count += 1
         d = self.defaults
-        self.engine.adamw_step(self.step_count, d["lr"], d["betas"], d["eps"], d["weight_decay"], self.grad_scale)
+        norm_buf = None
+        if self.max_grad_norm is not None:
+            norm_buf = e.grad_norm(self.grad_scale, self.max_grad_norm)
+            self.last_grad_norm = norm_buf[:4]
+        if norm_buf is None:
+            self.engine.adamw_step(self.step_count, d["lr"], d["betas"], d["eps"], d["weight_decay"], self.grad_scale)
+        else:
+            self.engine.adamw_step(self.step_count, d["lr"], d["betas"], d["eps"], d["weight_decay"], self.grad_scale,
+                                   norm_buf=norm_buf)
 
     def state_dict(self):
         """torch.optim.AdamW layout ({'state': {index: {step, exp_avg, exp_avg_sq}}, 'param_groups': [...]}) with
