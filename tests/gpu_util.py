@@ -21,25 +21,40 @@ def rel_l2(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
-def gemm_nt(A, B, N, bias=None, res=None, aux=None, act=0, out_f32=False, Mstore=None, ldout=None):
-    """A [M,K] bf16, B [>=ceil128(N),K] bf16 -> C (bf16 or fp32) [M, ldout]."""
+_byref = C.byref
+
+
+def _out(M, ld, dtype, dev, fill):
+    return torch.zeros((M, ld), dtype=dtype, device=dev) if fill is None else torch.full((M, ld), fill, dtype=dtype, device=dev)
+
+
+def gemm_nt(A, B, N, bias=None, res=None, aux=None, act=0, out_f32=False, Mstore=None, ldout=None, *, lda=None, ldb=None,
+            ldc=None, ldc2=None, ldcf=None, ldr=None, ldaux=None, C=None, colpart=None, fill=None):
+    """A [M,K] bf16, B [>=ceil128(N),K] bf16 -> C (bf16 or fp32) [M, ldout].
+    Leading dimensions: the inputs' default to their row strides (a column slice of a wider buffer is a strided operand),
+    the outputs' to ldout; each can be given per buffer. C: a caller-provided bf16 output [M, ldc] (the in-place case: the
+    buffer `res` is a view of); colpart: an fp32 buffer for the big-tile kernels' column-sum partials; fill: the value the
+    outputs this function allocates hold before the launch (default zeros). Returns the whole [M, ld] buffers."""
     L = _lib.lib()
     M, K = A.shape
     ldout = ldout or N
     dev = A.device
-    Cb = torch.zeros((M, ldout), dtype=torch.bfloat16, device=dev)
-    C2 = torch.zeros((M, ldout), dtype=torch.bfloat16, device=dev)
-    Cf = torch.zeros((M, ldout), dtype=torch.float32, device=dev)
+    ldc = ldc or (C.stride(0) if C is not None else ldout)
+    Cb = C if C is not None else _out(M, ldc, torch.bfloat16, dev, fill)
+    C2 = _out(M, ldc2 or ldout, torch.bfloat16, dev, fill)
+    Cf = _out(M, ldcf or ldout, torch.float32, dev, fill)
     p = _lib.PlbGemmNT()
-    p.A, p.lda, p.B, p.ldb = A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0)
+    p.A, p.lda, p.B, p.ldb = A.data_ptr(), lda or A.stride(0), B.data_ptr(), ldb or B.stride(0)
     p.M, p.N, p.K, p.Mstore = M, N, K, (M if Mstore is None else Mstore)
     p.bias = bias.data_ptr() if bias is not None else None
     if res is not None:
-        p.res, p.ldr = res.data_ptr(), res.stride(0)
+        p.res, p.ldr = res.data_ptr(), ldr or res.stride(0)
     if aux is not None:
-        p.aux, p.ldaux = aux.data_ptr(), aux.stride(0)
-    p.C, p.ldc, p.C2, p.ldc2, p.Cf, p.ldcf = Cb.data_ptr(), ldout, C2.data_ptr(), ldout, Cf.data_ptr(), ldout
-    rc = L.plb_launch_gemm_nt(C.byref(p), act, int(out_f32), stream())
+        p.aux, p.ldaux = aux.data_ptr(), ldaux or aux.stride(0)
+    p.C, p.ldc, p.C2, p.ldc2, p.Cf, p.ldcf = Cb.data_ptr(), ldc, C2.data_ptr(), C2.stride(0), Cf.data_ptr(), Cf.stride(0)
+    if colpart is not None:
+        p.colpart = colpart.data_ptr()
+    rc = L.plb_launch_gemm_nt(_byref(p), act, int(out_f32), stream())   # (the parameter C shadows ctypes here)
     assert rc == 0, rc
     torch.cuda.synchronize()
     return (Cf if out_f32 else Cb), C2
@@ -433,3 +448,304 @@ def assert_same_bits(engine_like, a, b, what):
     rec = first_difference(engine_like, a, b)
     if rec:
         raise AssertionError(f"{what}: {len(rec)} tensor{'s' * (len(rec) != 1)} differ — {format_difference(rec)}")
+
+
+# ---- exact arithmetic for the GEMM family (tests/test_gpu_gemm_exact.py, tests/test_gemm_exact_host.py) -------------------
+# With small-integer operands every product and every partial sum of a GEMM is an exact fp32 number as long as the sum of
+# the terms' magnitudes stays below 2^24 (times the power-of-two unit the operands are multiples of): the result no longer
+# depends on summation order, tile form, K-loop form or split count. fp32 outputs must then EQUAL the float64 reference
+# and bf16 outputs its round-to-nearest-even; a dropped, duplicated or misplaced contribution changes bits.
+EXACT_LIMIT = 2.0 ** 24
+SENTINEL = 0.33      # not a multiple of any unit used here, in bf16 (0.330078125) or fp32: no exact result can equal it
+_F8 = {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
+
+# The case tables. form -> (TM, TN, (M, N) with 9 workgroups in flight, K-tile counts of 64 elements)
+BIG_KTILES = (1, 2, 3, 4, 5, 6, 7, 10, 11, 13, 33)   # prologue, every drain length, the 10-slot ring's wraps (5 / 10) + 1, long
+NT_FORMS = {128: (128, 128, (384, 384), (1, 2, 3, 7)), 256: (256, 256, (768, 768), BIG_KTILES),
+            384: (128, 384, (384, 1152), BIG_KTILES), 1256: (128, 256, (384, 768), BIG_KTILES)}
+NT_FORM_PARAMS = [(128, -1), (256, 0), (256, 1), (384, 0), (384, 1), (1256, 0), (1256, 1)]   # (form, K-loop form)
+NT_TAILS = ((128, 4), (128, 124), (256, 188), (128, 260))        # the 128 kernel's column tails (M, N)
+NT_STRIDE_KTILES = 3
+FP8_NT_FORMS = {384: (128, 384, (384, 1152)), 1256: (128, 256, (1152, 256))}   # the tiles plb_launch_gemm_nt_fp8 picks
+FP8_KTILES = (1, 2, 3, 4, 5, 11)                                  # of 128 elements
+FP8_DEQ = (2.0 ** -3, 2.0 ** -2)
+LN_CASES = ((1024, 768, 64), (1024, 768, 192), (1024, 1024, 128))
+CE_SHAPE, CE_COLS, CE_TILES = (256, 512, 192), (200, 300, 512), (256, 1256)
+GELU_KTILES = 2      # K = 128: with B x 2^-4 the pre-activation has a standard deviation of about 4.7
+GELU_UNIT = 2.0 ** -4
+# (Mtot, Ncols, N, K, splits, rows_per_split, lda, ldb)
+TN_SMALL = ((64, 128, 128, 128, 1, 64, 128, 128), (192, 256, 188, 136, 1, 192, 264, 136),
+            (320, 128, 128, 64, 3, 128, 128, 64),      # the last split is short
+            (128, 256, 256, 256, 3, 64, 256, 256))     # the third split is empty
+# the big kernel: rows_per_split 64 x {1..5} with 2 splits over Ncols, K in {256, 512}; short and empty last split; N < Ncols;
+# splits == 1 is the direct form (the kernel writes the output itself)
+TN_BIG = tuple((mt, nc, n, k, sp, rps, nc + 8, k + 8) for mt, nc, n, k, sp, rps in (
+    (128, 256, 256, 256, 2, 64), (256, 512, 512, 256, 2, 128), (384, 256, 256, 512, 2, 192), (512, 512, 512, 512, 2, 256),
+    (640, 256, 256, 256, 2, 320), (320, 256, 256, 512, 2, 192), (128, 512, 512, 256, 2, 128), (256, 256, 188, 256, 2, 128),
+    (192, 256, 256, 256, 1, 192), (320, 512, 188, 512, 1, 320)))
+# the fp8 kernel: rows_per_split 128 x {1..5}; strides in bytes
+TN_FP8 = tuple((mt, nc, nc, k, sp, rps, nc + 16, k + 32) for mt, nc, k, sp, rps in (
+    (256, 256, 256, 2, 128), (512, 512, 256, 2, 256), (768, 256, 512, 2, 384), (1024, 512, 512, 2, 512),
+    (1280, 256, 256, 2, 640), (384, 256, 512, 2, 256), (256, 512, 256, 2, 256), (384, 256, 256, 1, 384)))
+
+
+def int_operands(shape, lo, hi, seed, kind="bf16", unit=1.0):
+    """Integers in [lo, hi] x unit (a power of two), generated on the CPU: kind "bf16" / "f32" -> a tensor of that type,
+    "e4m3" / "e5m2" -> the 1-byte image (uint8)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randint(lo, hi + 1, tuple(shape), generator=g).float() * unit
+    if kind == "f32":
+        return x
+    return x.to(torch.bfloat16) if kind == "bf16" else x.to(_F8[kind]).view(torch.uint8)
+
+
+def int_bias(n, seed, hi=64, unit=1.0):
+    return int_operands((n,), -hi, hi, seed, "f32", unit)
+
+
+def int_residual(M, N, seed, hi=128):
+    return int_operands((M, N), -hi, hi, seed, "bf16")
+
+
+def operand_values(x, kind="bf16"):
+    """The values an operand holds, as float64 (a 1-byte image decoded)."""
+    return x.view(_F8[kind]).float().double() if kind in _F8 else x.double()
+
+
+def exact_bound(A, B, bias=None, res=None, unit=1.0):
+    """max(|A|.|B|^T + |bias| + |res|) in float64, in units of `unit` (the power of two every term is a multiple of). Below
+    2^24 every partial sum, in any order, is an exact fp32 number. A condition, not a tolerance. A [M,K], B [N,K] values."""
+    s = A.double().abs() @ B.double().abs().T
+    if bias is not None:
+        s = s + bias.double().abs()
+    if res is not None:
+        s = s + res.double().abs()
+    return float(s.max()) / unit
+
+
+def exact_nt(A, B, bias=None, res=None, scale=1.0):
+    """(A.B^T) x scale + bias + res in float64: exact under exact_bound."""
+    s = (A.double() @ B.double().T) * scale
+    if bias is not None:
+        s = s + bias.double()
+    if res is not None:
+        s = s + res.double()
+    return s
+
+
+def rne_bf16(ref):
+    """The bf16 expectation of an exact float64 result: it fits fp32 exactly, torch's cast rounds to nearest even."""
+    return ref.float().to(torch.bfloat16)
+
+
+def first_mismatch(got, want, TM, TN):
+    """None when got == want element for element (value equality, as torch.equal: the sign of zero is not part of the
+    contract); else the report used as the assertion message: how many elements differ, the first (row, col), its row
+    tile, column tile and 64x32 wave patch inside the tile, and the two values there."""
+    g, w = got.double(), want.double()
+    assert g.shape == w.shape, (tuple(g.shape), tuple(w.shape))
+    bad = g != w
+    if not bool(bad.any()):
+        return None
+    r, c = (int(v) for v in bad.nonzero()[0])
+    return (f"{int(bad.sum())} of {bad.numel()} elements differ; first at ({r}, {c}) = row tile {r // TM}, column tile "
+            f"{c // TN}, wave patch ({r % TM // 64}, {c % TN // 32}): got {float(g[r, c])!r}, want {float(w[r, c])!r}")
+
+
+def mismatch_location(got, want, TM, TN):
+    """(count, row tile, column tile, (patch row, patch column)) of first_mismatch's report, or None."""
+    bad = got.double() != want.double()
+    if not bool(bad.any()):
+        return None
+    r, c = (int(v) for v in bad.nonzero()[0])
+    return int(bad.sum()), r // TM, c // TN, (r % TM // 64, c % TN // 32)
+
+
+def assert_exact(got, want, TM, TN, what):
+    msg = first_mismatch(got, want, TM, TN)
+    assert msg is None, f"{what}: {msg}"
+
+
+def assert_untouched(t, what):
+    """Every element still holds SENTINEL (as rounded to t's type)."""
+    s = torch.tensor(SENTINEL, dtype=t.dtype)
+    n = int((t != s.to(t.device)).sum())
+    assert n == 0, f"{what}: {n} elements that must not be written were"
+
+
+def spacing_bf16(x):
+    """The distance between neighbouring bf16 numbers at |x| (float64 in, float64 out; at 0: the smallest normal's)."""
+    a = x.double().abs().clamp_min(2.0 ** -126).contiguous()
+    return (a.view(torch.int64) & 0x7FF0000000000000).view(torch.float64) * 2.0 ** -7    # 2^floor(log2 |x|) x 2^-7, exactly
+
+
+_K0, _K1 = 0.7978845608028654, 0.044715
+
+
+def gelu64(x):
+    """gelu_new in float64 in the cancellation-free form x / (1 + exp(-2z)): 0.5 x (1 + tanh z) returns 0 below x = -7.2."""
+    x = x.double()
+    return x / (1.0 + torch.exp(-2.0 * _K0 * (x + _K1 * x ** 3)))
+
+
+def gelu_grad64(x):
+    x = x.double()
+    s = 1.0 / (1.0 + torch.exp(-2.0 * _K0 * (x + _K1 * x ** 3)))
+    return s + x * s * (1.0 - s) * 2.0 * _K0 * (1.0 + 3.0 * _K1 * x * x)
+
+
+def _fma32(a, b, c):
+    import numpy as np
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def gelu_f32_restatement(x):
+    """csrc/common.h gelu_new_f / gelu_new_grad_f restated in float32 numpy, same operation order and constants (exp2 and
+    the reciprocal by numpy instead of v_exp_f32 / v_rcp_f32). x: float32 array -> (gelu, gelu')."""
+    import numpy as np
+    f = np.float32
+    x = x.astype(f)
+    x2 = x * x
+    with np.errstate(over="ignore", under="ignore"):
+        e = np.exp2(x * _fma32(x2, np.full_like(x, f(-0.10294324)), np.full_like(x, f(-2.3022082)))).astype(f)
+        s = (f(1.0) / (f(1.0) + e)).astype(f)
+    w = x * _fma32(x2, np.full_like(x, f(0.21406444)), np.full_like(x, f(1.5957691)))
+    return x * s, _fma32(s, w * (f(1.0) - s), s)
+
+
+class Ln:
+    """Buffers of one fused GEMM + LayerNorm launch (tests/test_gpu_gemm_ln.py, tests/test_gpu_gemm_exact.py)."""
+
+    def __init__(self, M, N, K, seed=0, dev="cuda"):
+        def randbf(*shape, scale=1.0, seed=0):
+            g = torch.Generator(device="cpu").manual_seed(seed)
+            return (torch.randn(*shape, generator=g) * scale).to(torch.bfloat16).to(dev)
+
+        self.M, self.N, self.K = M, N, K
+        self.A, self.B = randbf(M, K, seed=seed + 1), randbf(N, K, scale=K ** -0.5, seed=seed + 2)
+        self.bias = torch.randn(N, generator=torch.Generator().manual_seed(seed + 3)).to(dev)
+        self.res = randbf(M, N, seed=seed + 4)
+        g = torch.Generator().manual_seed(seed + 5)
+        self.gamma = (1.0 + 0.3 * torch.randn(N, generator=g)).to(dev)
+        self.beta = (0.2 * torch.randn(N, generator=g)).to(dev)
+        nbn = N // (384 if N % 384 == 0 else 256)
+        self.nbn = nbn
+        self.xchg = torch.zeros(M // 128 * nbn * nbn * 128 * 2, dtype=torch.int64, device=dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.mean = torch.zeros(M, dtype=torch.float32, device=dev)
+        self.rstd = torch.zeros(M, dtype=torch.float32, device=dev)
+
+    def params(self):
+        p = _lib.PlbGemmNT()
+        p.A, p.lda, p.B, p.ldb = self.A.data_ptr(), self.K, self.B.data_ptr(), self.K
+        p.M, p.N, p.K, p.Mstore = self.M, self.N, self.K, self.M
+        p.ln_gamma, p.ln_beta, p.ln_mean, p.ln_rstd = self.gamma.data_ptr(), self.beta.data_ptr(), self.mean.data_ptr(), self.rstd.data_ptr()
+        p.ln_eps = 1e-12
+        p.ln_xchg, p.ln_err = self.xchg.data_ptr(), self.err.data_ptr()
+        return p
+
+
+def gemm_nt_fp8(A8, B8, N, deq, bias=None, res=None, a_bf8=0, C=None, fill=None):
+    """plb_launch_gemm_nt_fp8, act 0: A8 [M,K] / B8 [N,K] 1-byte images (uint8), deq = (1 / scale of A, of B) -> bf16
+    C [M,N] = (A.B^T) x deq_a x deq_b + bias + res. C: a caller-provided output (the in-place case)."""
+    L = _lib.lib()
+    M, K = A8.shape
+    d = torch.tensor(list(deq), dtype=torch.float32, device=A8.device)
+    Cb = C if C is not None else _out(M, N, torch.bfloat16, A8.device, fill)
+    p = _lib.PlbGemmNT()
+    p.A, p.lda, p.B, p.ldb = A8.data_ptr(), A8.stride(0), B8.data_ptr(), B8.stride(0)
+    p.M, p.N, p.K, p.Mstore = M, N, K, M
+    p.deq_a, p.deq_b = d.data_ptr(), d.data_ptr() + 4
+    p.bias = bias.data_ptr() if bias is not None else None
+    if res is not None:
+        p.res, p.ldr = res.data_ptr(), res.stride(0)
+    p.C, p.ldc = Cb.data_ptr(), Cb.stride(0)
+    rc = L.plb_launch_gemm_nt_fp8(_byref(p), 0, int(a_bf8), stream())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return Cb
+
+
+def gemm_tn_slabs(A, B, N, splits, rows_per_split, kind="small", deq=None, tail=0):
+    """The weight-gradient kernels without the reduction. A [Mtot, Ncols], B [Mtot, K]: bf16, or (kind "fp8") the e5m2 and
+    e4m3 images as uint8; row strides are the tensors' (bytes for the images). Returns the SENTINEL-filled flat fp32 buffer
+    the launch wrote its [splits][N][K] slabs into, with `tail` more floats behind them that must stay untouched."""
+    L = _lib.lib()
+    Mtot, Ncols = A.shape
+    K = B.shape[1]
+    buf = torch.full((splits * N * K + tail,), SENTINEL, dtype=torch.float32, device=A.device)
+    p = _lib.PlbGemmTN()
+    p.A, p.lda, p.Ncols, p.B, p.ldb = A.data_ptr(), A.stride(0), Ncols, B.data_ptr(), B.stride(0)
+    p.Mtot, p.N, p.K, p.rows_per_split, p.splits, p.slab = Mtot, N, K, rows_per_split, splits, buf.data_ptr()
+    if kind == "fp8":
+        d = torch.tensor(list(deq), dtype=torch.float32, device=A.device)
+        p.deq_a, p.deq_b = d.data_ptr(), d.data_ptr() + 4
+    fn = {"small": L.plb_launch_gemm_tn, "big": L.plb_launch_gemm_tn_big, "fp8": L.plb_launch_gemm_tn_fp8}[kind]
+    rc = fn(_byref(p), stream())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return buf
+
+
+def reduce_slabs(slab, splits, n, out, accumulate):
+    rc = _lib.lib().plb_launch_reduce_slabs(slab.data_ptr(), splits, n, out.data_ptr(), int(accumulate), stream())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return out
+
+
+def split_rows(Mtot, splits, rows_per_split):
+    """[(first row, end row)] of every split: the last may be short or empty."""
+    return [(min(s * rows_per_split, Mtot), min((s + 1) * rows_per_split, Mtot)) for s in range(splits)]
+
+
+def exact_tn(A, B, N, splits, rows_per_split, scale=1.0):
+    """float64 [splits][N][K]: slab s = A[rows of s, :N]^T . B[rows of s] x scale."""
+    A, B = A.double(), B.double()
+    return torch.stack([A[a:b, :N].T @ B[a:b] * scale for a, b in split_rows(A.shape[0], splits, rows_per_split)])
+
+
+def nt_operands(M, N, K, seed, kinds=("bf16", "bf16"), b_unit=1.0, brows=None, bias_hi=64):
+    """The operands of one exact NT case, on the CPU: A [M,K] and B [brows or N, K] in [-4, 4] (B x b_unit), integer bias
+    in [-bias_hi, bias_hi], integer bf16 residual in [-128, 128]."""
+    A = int_operands((M, K), -4, 4, seed, kinds[0])
+    B = int_operands((brows or N, K), -4, 4, seed + 1, kinds[1], b_unit)
+    return A, B, int_bias(N, seed + 2, bias_hi), int_residual(M, N, seed + 3)
+
+
+def tn_operands(Mtot, Ncols, K, seed, kinds=("bf16", "bf16")):
+    return int_operands((Mtot, Ncols), -4, 4, seed, kinds[0]), int_operands((Mtot, K), -4, 4, seed + 1, kinds[1])
+
+
+def exact_cases():
+    """Every (name, A values, B values, bias, res, unit) the GPU module launches, built as it builds them — for the premise
+    check of tests/test_gemm_exact_host.py. NT: A [M,K], B [N,K]; TN rows come transposed (A^T, B^T: the sum runs over rows)."""
+    for form, (TM, TN, (M, N), kts) in NT_FORMS.items():
+        for kt in kts:
+            A, B, bias, res = nt_operands(M, N, 64 * kt, 1000 * form + kt)
+            yield f"nt {form} kt {kt}", A, B, bias, res, 1.0
+        A, B, bias, res = nt_operands(M, N, 64 * GELU_KTILES, 7000 + form, b_unit=GELU_UNIT, bias_hi=2)
+        yield f"gelu {form}", A, B, bias, None, GELU_UNIT
+    for M, N in NT_TAILS:
+        for kt in NT_FORMS[128][3]:
+            A, B, bias, res = nt_operands(M, N, 64 * kt, 2000 + N + kt, brows=(N + 127) // 128 * 128)
+            yield f"tail {M}x{N} kt {kt}", A, B[:N], bias, res, 1.0
+    unit8 = FP8_DEQ[0] * FP8_DEQ[1]
+    for form, (TM, TN, (M, N)) in FP8_NT_FORMS.items():
+        for bf8 in (0, 1):
+            for kt in FP8_KTILES:
+                A, B, bias, res = nt_operands(M, N, 128 * kt, 3000 + form + 10 * kt + bf8, kinds=("e5m2" if bf8 else "e4m3", "e4m3"))
+                yield (f"fp8 nt {form} bf8 {bf8} kt {kt}", operand_values(A, "e5m2" if bf8 else "e4m3") * FP8_DEQ[0],
+                       operand_values(B, "e4m3") * FP8_DEQ[1], bias, res, unit8)
+    for M, N, K in LN_CASES:
+        A, B, bias, res = nt_operands(M, N, K, 4000 + N + K)
+        yield f"ln {M}x{N}x{K}", A, B, bias, res, 1.0
+    M, N, K = CE_SHAPE
+    A, B, bias, _ = nt_operands(M, N, K, 5000)
+    yield "ce", A, B, bias, None, 1.0
+    for i, (Mtot, Ncols, N, K, splits, rps, lda, ldb) in enumerate(TN_SMALL + TN_BIG):
+        A, B = tn_operands(Mtot, Ncols, K, 6000 + i)
+        yield f"tn {i}", A.T, B.T, None, None, 1.0
+    for i, (Mtot, Ncols, N, K, splits, rps, lda, ldb) in enumerate(TN_FP8):
+        A, B = tn_operands(Mtot, Ncols, K, 6500 + i, kinds=("e5m2", "e4m3"))
+        yield f"tn fp8 {i}", operand_values(A, "e5m2").T * FP8_DEQ[0], operand_values(B, "e4m3").T * FP8_DEQ[1], None, None, unit8

@@ -9,7 +9,7 @@ import ctypes as C
 import pytest
 import torch
 
-from gpu_util import gemm_nt, rel_l2, stream
+from gpu_util import Ln, gemm_nt, rel_l2, stream
 from plbert_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -19,34 +19,6 @@ DEV = "cuda"
 def randbf(*shape, scale=1.0, seed=0):
     g = torch.Generator(device="cpu").manual_seed(seed)
     return (torch.randn(*shape, generator=g) * scale).to(torch.bfloat16).to(DEV)
-
-
-class Ln:
-    """Buffers of one fused launch."""
-
-    def __init__(self, M, N, K, seed=0):
-        self.M, self.N, self.K = M, N, K
-        self.A, self.B = randbf(M, K, seed=seed + 1), randbf(N, K, scale=K ** -0.5, seed=seed + 2)
-        self.bias = torch.randn(N, generator=torch.Generator().manual_seed(seed + 3)).to(DEV)
-        self.res = randbf(M, N, seed=seed + 4)
-        g = torch.Generator().manual_seed(seed + 5)
-        self.gamma = (1.0 + 0.3 * torch.randn(N, generator=g)).to(DEV)
-        self.beta = (0.2 * torch.randn(N, generator=g)).to(DEV)
-        nbn = N // (384 if N % 384 == 0 else 256)
-        self.nbn = nbn
-        self.xchg = torch.zeros(M // 128 * nbn * nbn * 128 * 2, dtype=torch.int64, device=DEV)
-        self.err = torch.zeros(1, dtype=torch.int32, device=DEV)
-        self.mean = torch.zeros(M, dtype=torch.float32, device=DEV)
-        self.rstd = torch.zeros(M, dtype=torch.float32, device=DEV)
-
-    def params(self):
-        p = _lib.PlbGemmNT()
-        p.A, p.lda, p.B, p.ldb = self.A.data_ptr(), self.K, self.B.data_ptr(), self.K
-        p.M, p.N, p.K, p.Mstore = self.M, self.N, self.K, self.M
-        p.ln_gamma, p.ln_beta, p.ln_mean, p.ln_rstd = self.gamma.data_ptr(), self.beta.data_ptr(), self.mean.data_ptr(), self.rstd.data_ptr()
-        p.ln_eps = 1e-12
-        p.ln_xchg, p.ln_err = self.xchg.data_ptr(), self.err.data_ptr()
-        return p
 
 
 def _fwd(t, reps=1):

@@ -22,8 +22,9 @@ def randbf(*shape, scale=1.0, seed=0):
     return (torch.randn(*shape, generator=g) * scale).to(torch.bfloat16).to(DEV)
 
 
-# (the 128x128 kernel; grids of at most 256 workgroups with K >= 384 take its four-stage "deep" K loop: K-tile counts of 6, 7,
-#  12, 32 and 64 — every tail length of the counted waits)
+# (the 128x128 kernel: every shape here has M x N below 256 x 256 x 64, where the per-shape policy of gemm.hip keeps the
+#  small tile. Its K loop is two-stage — the next K-tile's DMA is issued, the current one is computed, one wait and one
+#  barrier per K-tile. K-tile counts here: 1, 2, 5, 6, 7, 12, 32 and 64; one column tail (N = 188); 1 to 96 workgroups)
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 384, 128), (384, 768, 2048), (128, 188, 768), (128, 128, 384),
                                    (256, 128, 448), (2048, 768, 2048), (1024, 1024, 4096), (128, 256, 320)])
 def test_gemm_nt_bias_residual(M, N, K):
