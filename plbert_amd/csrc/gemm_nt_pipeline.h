@@ -835,6 +835,9 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
         mean *= 1.0f / (float)nbn;
         float m2 = 0.f;
         for (int j = 0; j < nbn; ++j) m2 += qb[j] + (float)TN * (qa[j] - mean) * (qa[j] - mean);
+        // each tile's M2 comes from one pass (s2 - s1 * mean_tile): on a near-constant row it can round below zero, and
+        // m2 * invN + eps with it. Per row, threads tid < TM only; a row with m2 >= 0 keeps its bits
+        m2 = fmaxf(m2, 0.f);
         const float rstd = rsqrtf(m2 * invN + p.ln_eps);
         tab2[tid * 2] = mean; tab2[tid * 2 + 1] = rstd;
         const int m = bm * TM + tid;

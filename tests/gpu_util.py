@@ -749,3 +749,309 @@ def exact_cases():
     for i, (Mtot, Ncols, N, K, splits, rps, lda, ldb) in enumerate(TN_FP8):
         A, B = tn_operands(Mtot, Ncols, K, 6500 + i, kinds=("e5m2", "e4m3"))
         yield f"tn fp8 {i}", operand_values(A, "e5m2").T * FP8_DEQ[0], operand_values(B, "e4m3").T * FP8_DEQ[1], None, None, unit8
+
+
+# ---- the LayerNorm element contract (tests/test_gpu_layernorm_rows.py, tests/test_layernorm_rows_host.py) -----------------
+# Every element a LayerNorm kernel stores — the four standalone kernels of csrc/rowops.hip and forms 5 / 6 of the NT pipeline
+# GEMM, bf16 and fp8 — is held to the float64 evaluation of the same stored inputs:
+#     |got - ref| <= 0.5 x spacing_bf16(ref) + delta x cond
+# one round-to-nearest of the exact value plus the fp32 arithmetic behind it, weighted by the element's condition term.
+# Nothing below calls a kernel or reads a kernel's output to form a bound.
+LN_EPS = 1e-12
+DELTA0 = 2.0 ** -18        # <= 32 fp32 roundings stand behind any sum of these kernels (<= 24 sequential per lane, then the
+                           # trees): 32 x 2^-24 = 2^-19, and a factor 2
+LN_STAT_FLOOR = 2.0 ** -20  # 8 fp32 ulps: rsqrtf and the final multiply
+LN_CLASSES = ("plain", "off4", "off16", "small", "eps", "large", "spike", "zero", "nearconst")
+LN_BWD_CLASSES = ("plain", "off4", "off16", "small", "large", "spike")
+LN_NEARCONST_SEED = 0      # ln_rows(1024, 768, seed, ("nearconst",)) holds a row whose merged M2 is <= 0 in the tile
+                           # restatement (tests/test_layernorm_rows_host.py searches and pins it)
+
+
+def ln_rows(T, W, seed, classes=LN_CLASSES):
+    """bf16 rows [T, W] on the CPU, row r in class classes[r % len(classes)], and the class index per row. Classes: plain
+    N(0,1); off4 N(4,1); off16 N(16,1); small N(0,1) x 2^-12; eps N(0,1) x 2^-20 (variance ~ eps = 1e-12); large N(0,1) x
+    2^10; spike N(0,1) with one element 200 at column (r * 37) % W; zero; nearconst: a bf16 constant in [1, 60] that
+    varies with r, 1-3 elements one bf16 step up."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(T, W, generator=g)
+    u = torch.rand(T, 5, generator=g)
+    r = torch.arange(T)
+    cls = r % len(classes)
+    near = None
+    for k, name in enumerate(classes):
+        rows = (cls == k).nonzero().flatten()
+        if name == "plain":
+            pass
+        elif name in ("off4", "off16"):
+            x[rows] += float(name[3:])
+        elif name in ("small", "eps", "large"):
+            x[rows] *= {"small": 2.0 ** -12, "eps": 2.0 ** -20, "large": 2.0 ** 10}[name]
+        elif name == "spike":
+            x[rows, (rows * 37) % W] = 200.0
+        elif name == "zero":
+            x[rows] = 0.0
+        elif name == "nearconst":
+            near = rows
+        else:
+            raise ValueError(name)
+    xb = x.to(torch.bfloat16)
+    if near is not None and near.numel():
+        c = (1.0 + 59.0 * u[near, 0]).to(torch.bfloat16)
+        up = (c.view(torch.int16) + 1).view(torch.bfloat16)          # positive: the next bf16 up
+        xb[near] = c[:, None]
+        n = 1 + (u[near, 1] * 3).long().clamp(max=2)
+        cols = (u[near, 2:5] * W).long().clamp(max=W - 1)
+        for j in range(3):
+            sel = n > j
+            xb[near[sel], cols[sel, j]] = up[sel]
+    return xb, cls
+
+
+def layernorm_fp64(x, gamma, beta, eps=LN_EPS):
+    """(mean [T], rstd [T], xhat [T,H], y [T,H]) in float64 from the input as stored; biased variance, eps inside the root;
+    y is not rounded."""
+    x = x.double()
+    mean = x.mean(1)
+    d = x - mean[:, None]
+    rstd = ((d * d).mean(1) + eps) ** -0.5
+    xhat = d * rstd[:, None]
+    return mean, rstd, xhat, xhat * gamma.double() + beta.double()
+
+
+def ln_fwd_cond(xhat, gamma, beta, mean, rstd):
+    """|gamma_j| (1 + |xhat_ij| + |mu_i| rstd_i) + |beta_j|: what an fp32 rounding of the statistics or of the products moves
+    y by. The |mu| rstd term is the mean's own fp32 rounding (2^-24 |mu|, whatever the summation) seen through x - mean: it
+    is what conditions a near-constant row (sigma << |mu|), and on a centred row it adds nothing
+    (tests/test_layernorm_rows_host.py: without it honest fp32 arithmetic fails the nearconst class)."""
+    return gamma.double().abs() * (1.0 + xhat.abs() + (mean.abs() * rstd)[:, None]) + beta.double().abs()
+
+
+class LnBwd:
+    """layernorm_bwd_fp64's results: dx (unrounded), dgamma, dbeta, the magnitude sums per column and the condition term."""
+    __slots__ = ("dx", "dgamma", "dbeta", "mag_gamma", "mag_beta", "cond", "xhat")
+
+
+def layernorm_bwd_fp64(x, mean, rstd, gamma, dy):
+    """LayerNorm backward in float64 from x, dy as stored and the SUPPLIED fp32 mean / rstd (the backward kernels' contract:
+    they never recompute statistics). dx = rstd (g - mean_j g - xhat mean_j(g xhat)), g = dy gamma; dgamma = sum_i dy xhat,
+    dbeta = sum_i dy with sum |dy xhat|, sum |dy|; cond = rstd (|g| + mean_j |g| + |xhat| mean_j |g xhat|)."""
+    x, dy, rs = x.double(), dy.double(), rstd.double()[:, None]
+    xhat = (x - mean.double()[:, None]) * rs
+    g = dy * gamma.double()
+    o = LnBwd()
+    o.xhat = xhat
+    o.dx = rs * (g - g.mean(1, keepdim=True) - xhat * (g * xhat).mean(1, keepdim=True))
+    t = dy * xhat
+    o.dgamma, o.dbeta, o.mag_gamma, o.mag_beta = t.sum(0), dy.sum(0), t.abs().sum(0), dy.abs().sum(0)
+    o.cond = rs * (g.abs() + g.abs().mean(1, keepdim=True) + xhat.abs() * (g * xhat).abs().mean(1, keepdim=True))
+    return o
+
+
+def _np32(t):
+    return t.detach().cpu().float().numpy()
+
+
+def _tree(a):
+    """Pairwise fp32 sum over the last axis (a power of two): the butterfly of a wave reduction."""
+    while a.shape[-1] > 1:
+        h = a.shape[-1] // 2
+        a = a[..., :h] + a[..., h:]
+    return a[..., 0]
+
+
+def lane_tree_sum(v):
+    """fp32 sum over the last axis as the standalone kernels form it: 64 lanes each add their <= 16 values one after the
+    other, then a 6-level tree. v: float32 numpy [T, H], H <= 1024."""
+    import numpy as np
+    T, H = v.shape
+    L = -(-H // 64)
+    pad = np.zeros((T, L * 64), np.float32)
+    pad[:, :H] = v
+    pad = pad.reshape(T, L, 64)
+    s = np.zeros((T, 64), np.float32)
+    for i in range(L):
+        s = s + pad[:, i]
+    return _tree(s)
+
+
+def _two_pass(v, eps):
+    import numpy as np
+    f = np.float32
+    H = v.shape[1]
+    inv = f(1.0) / f(H)
+    mean = lane_tree_sum(v) * inv
+    d = v - mean[:, None]
+    var = lane_tree_sum(d * d) * inv
+    return mean, f(1.0) / np.sqrt(var + f(eps)), var * f(H)
+
+
+def _tile_stats(v, TN, eps, contract=True):
+    """Form 5 (csrc/gemm_nt_pipeline.h): per lane s1 / s2 over its 4-column groups in order, xor 16 / 32 across the four
+    lanes that share a row, the four wn partials, (mean, M2) of the tile in one pass, the merge across tiles. contract: the
+    tile's pb - pa * mt as one fused multiply-add (what the compiler is free to emit) or as two rounded operations."""
+    import numpy as np
+    f = np.float32
+    T, N = v.shape
+    nbn, nbh = N // TN, TN // 128
+    # column inside a tile = nh * 128 + wn * 32 + ni * 16 + fq * 4 + r  ->  [T, tile, wn, fq, (nh, ni), r]
+    t = v.reshape(T, nbn, nbh, 4, 2, 4, 4).transpose(0, 1, 3, 5, 2, 4, 6).reshape(T, nbn, 4, 4, nbh * 2, 4)
+    s1 = np.zeros((T, nbn, 4, 4), f)
+    s2 = np.zeros((T, nbn, 4, 4), f)
+    for gI in range(nbh * 2):
+        a, b, c, d = (t[..., gI, j] for j in range(4))
+        s1 = s1 + ((a + b) + (c + d))
+        s2 = s2 + ((a * a + b * b) + (c * c + d * d))
+    fold = lambda s: (s[..., 0] + s[..., 1]) + (s[..., 2] + s[..., 3])   # noqa: E731
+    pa, pb = fold(fold(s1)), fold(fold(s2))
+    mt = pa * (f(1.0) / f(TN))
+    pb = _fma32(-pa, mt, pb) if contract else pb - pa * mt
+    mean = np.zeros(T, f)
+    for j in range(nbn):
+        mean = mean + mt[:, j]
+    mean = mean * (f(1.0) / f(nbn))
+    m2 = np.zeros(T, f)
+    for j in range(nbn):
+        m2 = m2 + (pb[:, j] + f(TN) * (mt[:, j] - mean) * (mt[:, j] - mean))
+    rstd = f(1.0) / np.sqrt(np.maximum(m2, f(0.0)) * (f(1.0) / f(N)) + f(eps))
+    return mean, rstd, m2
+
+
+class LnStats:
+    """layernorm_stats_f32's results, per row: rstd_err, mean_err (worst over the orders), m2 (smallest over the orders: the
+    fp32 sum of squared deviations before the clamp), and mean / rstd of order 0 (the kernels' own column order)."""
+    __slots__ = ("rstd_err", "mean_err", "m2", "mean", "rstd")
+
+
+def layernorm_stats_f32(x, form, orders=8, eps=LN_EPS):
+    """A numpy float32 restatement of the statistics only. form "two_pass": the standalone kernels (lane_tree_sum, the mean
+    subtracted before squaring); form ("tile", TN): form 5 of the pipeline GEMM (_tile_stats). Evaluated over `orders`
+    summation orders (order 0: the columns as they are; the others: shuffled, inside a tile for the tile form; the tile form
+    each time with and without the contraction of pb - pa * mt) -> the worst
+    relative rstd error and the worst |mean - mu| / (|mu| + sigma) per row against float64. Reads no kernel output."""
+    import numpy as np
+    v = _np32(x)
+    T, H = v.shape
+    v64 = v.astype(np.float64)
+    mu = v64.mean(1)
+    var = ((v64 - mu[:, None]) ** 2).mean(1)
+    rs = (var + eps) ** -0.5
+    o = LnStats()
+    o.rstd_err, o.mean_err, o.m2 = np.zeros(T), np.zeros(T), np.full(T, np.inf)
+    rng = np.random.default_rng(H)
+    for k in range(orders):
+        w = v
+        if k:
+            if form == "two_pass":
+                w = v[:, rng.permutation(H)]
+            else:
+                TN = form[1]
+                w = v.reshape(T, H // TN, TN)[:, :, rng.permutation(TN)].reshape(T, H)
+        w = np.ascontiguousarray(w)
+        evals = [_two_pass(w, eps)] if form == "two_pass" else [_tile_stats(w, form[1], eps, c) for c in (True, False)]
+        if k == 0:
+            o.mean, o.rstd = evals[0][0], evals[0][1]
+        for mean, rstd, m2 in evals:
+            o.rstd_err = np.maximum(o.rstd_err, np.abs(rstd.astype(np.float64) / rs - 1.0))
+            o.mean_err = np.maximum(o.mean_err, np.abs(mean.astype(np.float64) - mu) / (np.abs(mu) + np.sqrt(var) + 1e-300))
+            o.m2 = np.minimum(o.m2, m2.astype(np.float64))
+    return o
+
+
+def ln_class_worst(per_row, cls, classes):
+    """{class: the worst of a per-row figure over the rows of the class}."""
+    import numpy as np
+    c = cls.cpu().numpy()
+    a = np.asarray(per_row, dtype=np.float64)
+    return {name: float(a[c == k].max()) for k, name in enumerate(classes) if bool((c == k).any())}
+
+
+def ln_row_bound(worst, cls, classes, floor, dev="cpu"):
+    """Per row: max(floor, ROW_FACTOR x its class's worst restated figure) — the statistics' bound (floor LN_STAT_FLOOR) and
+    the delta of the fused forward forms (floor DELTA0)."""
+    per = torch.tensor([max(floor, ROW_FACTOR * worst.get(name, 0.0)) for name in classes], dtype=torch.float64)
+    return per[cls.cpu()].to(dev)
+
+
+def check_ln_elements(name, got, ref, cond, delta, cls=None, classes=LN_CLASSES):
+    """Every element: |got - ref| <= 0.5 x spacing_bf16(ref) + delta_row x cond. got [T,H] as stored, ref / cond float64,
+    delta a number or a float64 tensor [T]; cls [T]: the class index per row (for the report). Raises naming row, column,
+    class, got, want and the count of elements over. Returns {class: the worst share of the fp32 allowance in use,
+    max(0, err - 0.5 spacing) / (delta x cond)}: err / bound itself sits next to 1 on every element that falls near a
+    rounding tie, whatever the arithmetic, so the share of the arithmetic term is what tells a tight kernel from a loose
+    one. 0 where the element is within its rounding term (also where cond = 0: an exact zero)."""
+    g = got.double()
+    assert g.shape == ref.shape == cond.shape, (tuple(g.shape), tuple(ref.shape), tuple(cond.shape))
+    T = g.shape[0]
+    d = delta.to(ref.device).double()[:, None] if torch.is_tensor(delta) else float(delta)
+    half = 0.5 * spacing_bf16(ref)
+    arith = d * cond
+    err = (g - ref).abs()
+    err = torch.where(torch.isfinite(g), err, torch.full_like(err, float("inf")))
+    cl = (torch.zeros(T, dtype=torch.long) if cls is None else cls).to(ref.device)
+    bad = err > half + arith
+    if bool(bad.any()):
+        r, c = (int(v) for v in bad.nonzero()[0])
+        cname = classes[int(cl[r])] if cls is not None else "-"
+        raise AssertionError(f"{name}: element ({r}, {c}) of class {cname}: got {float(g[r, c])!r}, want {float(ref[r, c])!r}: "
+                             f"off by {float(err[r, c]):.3e} > 0.5 x {float(2 * half[r, c]):.3e} + {float(arith[r, c]):.3e}; "
+                             f"{int(bad.sum())} of {bad.numel()} elements over")
+    over = (err - half).clamp_min(0.0)
+    share = torch.where(over > 0, over / arith.clamp_min(1e-300), torch.zeros_like(over)).amax(1) if g.shape[1] else over.sum(1)
+    return {classes[k] if cls is not None else "-": float(share[cl == k].max()) for k in cl.unique().tolist()}
+
+
+def check_ln_stats(name, mean, rstd, x, bound_mean, bound_rstd, cls=None, classes=LN_CLASSES, eps=LN_EPS):
+    """Per row: |rstd / rstd_ref - 1| <= bound_rstd and |mean - mu| / (|mu| + sigma) <= bound_mean (numbers or [T] tensors)
+    against float64 statistics of x as stored. An all-zero row: mean == 0 exactly. Returns the (mean, rstd) figures per row."""
+    x = x.double()
+    mu = x.mean(1)
+    var = ((x - mu[:, None]) ** 2).mean(1)
+    rs = (var + eps) ** -0.5
+    m, s = mean.double().to(x.device), rstd.double().to(x.device)
+    em = (m - mu).abs() / (mu.abs() + var.sqrt()).clamp_min(1e-300)
+    em = torch.where(m == mu, torch.zeros_like(em), em)          # an exact mean (a zero row: 0 / 0)
+    es = (s / rs - 1.0).abs()
+    as_rows = lambda b: b.to(x.device).double() if torch.is_tensor(b) else torch.full_like(em, float(b))   # noqa: E731
+    for what, e, b, gv, rv in (("mean", em, as_rows(bound_mean), m, mu), ("rstd", es, as_rows(bound_rstd), s, rs)):
+        bad = ~(torch.isfinite(gv) & (e <= b))
+        if bool(bad.any()):
+            r = int(bad.nonzero()[0])
+            cname = classes[int(cls[r])] if cls is not None else "-"
+            raise AssertionError(f"{name}: {what} of row {r} (class {cname}): got {float(gv[r])!r}, want {float(rv[r])!r}: off by "
+                                 f"{float(e[r]):.3e} > {float(b[r]):.3e}; {int(bad.sum())} rows over")
+    zero = (x == 0).all(1)
+    if bool(zero.any()):
+        assert bool((m[zero] == 0).all()), f"{name}: the mean of an all-zero row is not exactly 0"
+    return em, es
+
+
+def check_ln_partials(name, got, ref, mag, rows_per_lane):
+    """A column sum accumulated in fp32, its partial rows summed in float64 by the caller: per column
+    |got - ref| <= (rows_per_lane + 8) x 2^-24 x sum_rows |term| (the lane's chain, then the folds across lanes / waves and
+    the roundings inside a term). Returns the worst err / bound."""
+    err = (got.double() - ref.double()).abs()
+    bound = (rows_per_lane + 8) * 2.0 ** -24 * mag.double()
+    bad = ~(torch.isfinite(got.double()) & (err <= bound))
+    if bool(bad.any()):
+        c = int(bad.nonzero()[0])
+        raise AssertionError(f"{name}: column {c}: got {float(got[c])!r}, want {float(ref[c])!r}: off by {float(err[c]):.3e} > "
+                             f"{rows_per_lane + 8} x 2^-24 x {float(mag[c]):.3e}; {int(bad.sum())} columns over")
+    return float((err / bound.clamp_min(1e-300)).max())
+
+
+LN_DY_KINDS = ("plain", "tiny", "spike", "zero")
+
+
+def ln_dy(T, W, seed):
+    """bf16 output gradients [T, W] on the CPU and the kind index per row: N(0,1); N(0,1) x 2^-14; N(0,1) with one element
+    x 50 at column (r * 53) % W; an all-zero row (its dx row must be exactly zero). Kind (r + r // 6) % 4: every kind
+    meets every one of the six backward input classes within 24 rows."""
+    g = torch.Generator().manual_seed(seed)
+    dy = torch.randn(T, W, generator=g)
+    r = torch.arange(T)
+    kind = (r + r // 6) % 4
+    dy[kind == 1] *= 2.0 ** -14
+    sp = (kind == 2).nonzero().flatten()
+    dy[sp, (sp * 53) % W] *= 50.0
+    dy[kind == 3] = 0.0
+    return dy.to(torch.bfloat16), kind
