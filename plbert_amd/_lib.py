@@ -49,22 +49,6 @@ PLB_PARAM_NAMES = [
 ]
 PLB_NPARAM = len(PLB_PARAM_NAMES)
 
-# every symbol include/plbert.h declares (tests check the library exports all of them)
-PUBLIC_SYMBOLS = [
-    "plb_last_error", "plb_create", "plb_destroy", "plb_param_layout", "plb_workspace_bytes", "plb_bind",
-    "plb_sync_weights", "plb_forward", "plb_pooler", "plb_loss_fwd_bwd", "plb_loss_fwd", "plb_loss_fwd_bwd_dual", "plb_adamw_step",
-    "plb_set_fp8", "plb_fp8_state", "plb_fp8_stats", "plb_token_head_steps", "plb_set_token_head_steps", "plb_comm_unique_id", "plb_comm_init", "plb_comm_destroy",
-    "plb_comm_info", "plb_comm_pieces", "plb_last_application_rows", "plb_last_call_rows",
-    "plb_packing_plan", "plb_forward_packed", "plb_loss_fwd_bwd_packed", "plb_loss_fwd_packed", "plb_set_packed_dual",
-    "plb_set_packed_fp8",
-    "plb_grad_norm_floats", "plb_grad_accum_bind", "plb_grad_accum_add", "plb_grad_norm", "plb_adamw_step_clipped",
-    "plb_loss_fwd_bwd_dual_packed", "plb_encode", "plb_encode_bwd", "plb_status", "plb_status_ex", "plb_poll_status", "plb_status_export", "plb_status_import", "plb_broadcast_params", "plb_set_grad_overlap", "plb_allreduce_grads", "plb_apply_mask",
-    "plb_mask_batch", "plb_profile_enable", "plb_profile_num_classes", "plb_profile_class_name", "plb_profile_read",
-    # test / tuning hooks (documented as such at the end of the header)
-    "plb_debug_skip_piece", "plb_debug_ln_fault", "plb_debug_hb_audit", "plb_debug_hb_report", "plb_comm_trace", "plb_comm_trace_read",
-    "plb_set_gemm_nt_tile", "plb_set_gemm_nt_prefetch", "plb_set_attn_bwd_fused", "plb_set_prune_last",
-]
-
 
 class PlbConfig(C.Structure):
     _fields_ = [
@@ -156,6 +140,153 @@ def norm_chain(n):
     return 4 * (norm_chunk(n) // 1024) + 6 + 3
 
 
+# ---- the signature tables: name -> (restype, [argtypes]), one entry per prototype of the two headers ----------------------
+# int / int32_t -> i32, uint32_t -> u32, int64_t -> i64, uint64_t -> u64, size_t -> sz, float -> f32, double -> f64; a
+# pointer to a struct mirrored above -> P(that struct); any other pointer and a stream -> vp, or P(scalar) where the callers
+# pass byref / a ctypes array. tests/test_binding_host.py holds both tables and the struct mirrors to the headers.
+vp, i32, u32, i64, u64, sz, f32, f64, P = (C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_size_t, C.c_float,
+                                           C.c_double, C.POINTER)
+# include/plbert.h (the last ten are the test / tuning hooks documented as such at the end of the header)
+PUBLIC = {
+    "plb_last_error": (C.c_char_p, []),
+    "plb_create": (i32, [P(PlbConfig), P(vp)]),
+    "plb_destroy": (None, [vp]),
+    "plb_param_layout": (i32, [vp, P(i64), P(i64), P(i64), P(i64)]),
+    "plb_workspace_bytes": (i64, [vp]),
+    "plb_bind": (i32, [vp, vp, vp, vp, vp, vp, i64]),
+    "plb_sync_weights": (i32, [vp, vp]),
+    "plb_forward": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "plb_pooler": (i32, [vp, vp, i32, i32, vp, vp]),
+    "plb_loss_fwd_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "plb_loss_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "plb_loss_fwd_bwd_dual": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "plb_adamw_step": (i32, [vp, f64, f64, f64, f64, f64, i32, f64, vp]),
+    "plb_grad_norm_floats": (i64, [vp]),
+    "plb_grad_accum_bind": (i32, [vp, vp]),
+    "plb_grad_accum_add": (i32, [vp, i32, vp, vp]),
+    "plb_grad_norm": (i32, [vp, f64, f64, vp, i32, vp]),
+    "plb_adamw_step_clipped": (i32, [vp, f64, f64, f64, f64, f64, i32, f64, vp, vp]),
+    "plb_set_fp8": (i32, [vp, i32, vp]),
+    "plb_fp8_state": (i32, [vp, P(i32), P(i32)]),
+    "plb_fp8_stats": (i32, [vp, P(f32), P(f32), vp]),
+    "plb_token_head_steps": (i32, [vp]),
+    "plb_set_token_head_steps": (i32, [vp, i32]),
+    "plb_comm_unique_id": (i32, [vp]),
+    "plb_comm_init": (i32, [vp, vp, i32, i32]),
+    "plb_comm_destroy": (i32, [vp]),
+    "plb_comm_info": (i32, [vp, P(i32), P(i32), P(i32)]),
+    "plb_status": (i32, [vp, P(i32)]),
+    "plb_status_ex": (i32, [vp, P(i32), P(i32)]),
+    "plb_poll_status": (i32, [vp, P(i32)]),
+    "plb_status_export": (i32, [vp, vp, vp]),
+    "plb_status_import": (i32, [vp, vp, vp]),
+    "plb_last_application_rows": (i32, [vp, P(i64), P(i64)]),
+    "plb_packing_plan": (i32, [vp, i32, i32, vp, P(i32), P(i32)]),
+    "plb_forward_packed": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp, vp, vp]),
+    "plb_loss_fwd_bwd_packed": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, P(PlbPacking), vp, vp]),
+    "plb_loss_fwd_packed": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, P(PlbPacking), vp, vp, vp]),
+    "plb_last_call_rows": (i32, [vp, P(i64), P(i64)]),
+    "plb_set_packed_dual": (i32, [vp, i32]),
+    "plb_loss_fwd_bwd_dual_packed": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, P(PlbPacking), vp, vp, vp]),
+    "plb_set_packed_fp8": (i32, [vp, i32]),
+    "plb_encode": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp]),
+    "plb_encode_bwd": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp]),
+    "plb_comm_pieces": (i32, [vp, P(i32), P(i64)]),
+    "plb_broadcast_params": (i32, [vp, i32, vp]),
+    "plb_set_grad_overlap": (i32, [vp, i32]),
+    "plb_allreduce_grads": (i32, [vp, vp]),
+    "plb_apply_mask": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "plb_mask_batch": (i32, [vp, vp, i32, i32, u64, u32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp]),
+    "plb_profile_enable": (None, [i32]),
+    "plb_profile_num_classes": (i32, []),
+    "plb_profile_class_name": (C.c_char_p, [i32]),
+    "plb_profile_read": (i32, [P(f64), P(i64), P(f64), P(f64)]),
+    "plb_debug_skip_piece": (None, [i32]),
+    "plb_debug_ln_fault": (None, [i32, i32]),
+    "plb_debug_hb_audit": (i32, [vp, i32, i32]),
+    "plb_debug_hb_report": (i32, [vp, P(i64), P(i32), vp, i32]),
+    "plb_comm_trace": (i32, [vp, i32]),
+    "plb_comm_trace_read": (i32, [vp, i32, P(i32), P(i64), P(i64), P(f32), P(f32), P(f32)]),
+    "plb_set_gemm_nt_tile": (None, [i32]),
+    "plb_set_gemm_nt_prefetch": (None, [i32]),
+    "plb_set_attn_bwd_fused": (None, [i32]),
+    "plb_set_prune_last": (None, [i32]),
+}
+PUBLIC_SYMBOLS = list(PUBLIC)
+# csrc/plbert_kernels.h: the launchers the kernel-level tests and tools call; it declares five of the public hooks again
+INTERNAL = {
+    **{name: PUBLIC[name] for name in ("plb_set_gemm_nt_tile", "plb_set_gemm_nt_prefetch", "plb_debug_skip_piece",
+                                       "plb_debug_ln_fault", "plb_set_attn_bwd_fused")},
+    "plb_prof_begin": (i32, [i32, vp, f64, f64]),
+    "plb_prof_end": (None, [i32, vp]),
+    "plb_launch_gemm_nt_ln": (i32, [P(PlbGemmNT), i32, vp]),
+    "plb_launch_gemm_nt_gelud": (i32, [P(PlbGemmNT), i32, vp]),
+    "plb_launch_gemm_nt_fp8": (i32, [P(PlbGemmNT), i32, i32, vp]),
+    "plb_launch_gemm_nt_fp8_ln": (i32, [P(PlbGemmNT), i32, i32, vp]),
+    "plb_launch_gemm_nt_fp8_gelud": (i32, [P(PlbGemmNT), i32, i32, vp]),
+    "plb_gemm_nt_fp8_gelud_tile_rows": (i32, [i32]),
+    "plb_ln_fault_take": (i32, []),
+    "plb_launch_gemm_nt": (i32, [P(PlbGemmNT), i32, i32, vp]),
+    "plb_launch_gemm_nt_big": (i32, [P(PlbGemmNT), i32, i32, i32, vp]),
+    "plb_gemm_nt_colpart_rows": (i32, [i32, i32, i32]),
+    "plb_launch_gemm_tn": (i32, [P(PlbGemmTN), vp]),
+    "plb_launch_gemm_tn_fp8": (i32, [P(PlbGemmTN), vp]),
+    "plb_launch_gemm_tn_big": (i32, [P(PlbGemmTN), vp]),
+    "plb_launch_reduce_slabs": (i32, [vp, i32, sz, vp, i32, vp]),
+    "plb_launch_embed_fwd": (i32, [P(PlbEmbed), vp]),
+    "plb_launch_embed_bwd": (i32, [P(PlbEmbed), vp]),
+    "plb_launch_embed_scatter": (i32, [P(PlbEmbed), i32, vp]),
+    "plb_launch_amax": (i32, [vp, i32, sz, i32, i32, vp, vp]),
+    "plb_launch_fp8_scales": (i32, [vp, vp, vp, i32, f32, i32, vp]),
+    "plb_launch_fp8_scales2": (i32, [vp, vp, vp, i32, f32, i32, i32, f32, vp, i32, vp]),
+    "plb_launch_quantize": (i32, [vp, i32, sz, i32, i32, vp, vp, i32, i32, vp]),
+    "plb_launch_quantize_multi": (i32, [i32, vp, vp, vp, vp, vp, vp, vp]),
+    "plb_launch_ln_fwd": (i32, [P(PlbLayerNorm), vp]),
+    "plb_launch_ln_bwd": (i32, [P(PlbLayerNorm), vp]),
+    "plb_launch_colsum": (i32, [vp, i32, sz, i32, i32, vp, i32, i32, vp, i32, vp]),
+    "plb_launch_copy_cols": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "plb_launch_pooler": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    "plb_launch_attn_fwd": (i32, [P(PlbAttn), vp]),
+    "plb_launch_attn_bwd": (i32, [P(PlbAttn), vp]),
+    "plb_launch_attn_bwd_fused": (i32, [P(PlbAttn), vp]),
+    "plb_launch_gather_rows": (i32, [vp, i32, vp, i32, i32, i32, vp, i32, vp]),
+    "plb_launch_scatter_rows": (i32, [vp, i32, vp, i32, i32, vp, i32, vp]),
+    "plb_launch_ce_prepare": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "plb_launch_ce_prepare_packed": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "plb_launch_unpack_rows": (i32, [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
+    "plb_launch_seed_dy": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "plb_launch_ce_fwd_bwd": (i32, [vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, vp]),
+    "plb_launch_sum_rows": (i32, [vp, i32, vp, vp]),
+    "plb_launch_token_ce_combine": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "plb_launch_token_ce_combine_packed": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "plb_launch_pack_token_targets": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+    "plb_launch_add_scalar": (i32, [vp, vp, vp, vp]),
+    "plb_launch_mask": (i32, [vp, vp]),
+    "plb_launch_apply_mask": (i32, [vp, vp]),
+    "plb_launch_adamw": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i32, f64, vp, i32, vp]),
+    "plb_launch_grad_accum": (i32, [vp, vp, sz, i32, vp, vp]),
+    "plb_launch_grad_sumsq": (i32, [vp, sz, vp, vp]),
+    "plb_launch_grad_norm_finish": (i32, [vp, i32, f64, f64, vp, vp]),
+    "plb_launch_adamw_clipped": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i32, f64, vp, i32, vp, i32, vp]),
+    "plb_launch_step_status": (i32, [vp, vp, vp, vp, vp]),
+    "plb_launch_status_export": (i32, [vp, vp, vp]),
+    "plb_launch_cast_bf16": (i32, [vp, vp, sz, vp]),
+    "plb_launch_transpose_cast": (i32, [vp, i32, i32, vp, i32, vp]),
+    "plb_launch_transpose_cast_multi": (i32, [i32, vp, vp, vp, vp, vp, vp]),
+    "plb_launch_bf16_to_f32": (i32, [vp, i32, vp, i32, i32, i32, vp]),
+}
+
+
+def declare(L):
+    """Set restype / argtypes of every table entry that L exports and return L. A symbol L lacks is skipped on its own: a
+    build named by PLBERT_HIP_LIB that predates a feature still loads, with everything it does have fully declared."""
+    for name, (restype, argtypes) in {**PUBLIC, **INTERNAL}.items():
+        fn = getattr(L, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, list(argtypes)
+    return L
+
+
 _lib = None
 
 
@@ -173,200 +304,10 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m plbert_amd.build` (needs hipcc, gfx950). "
             "There is no CPU fallback for the PL-BERT hot path.")
     try:
-        L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
+        _lib = declare(C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL))
     except OSError as ex:
         raise HipLibraryMissing(f"cannot load {LIB_PATH}: {ex}") from ex
-    vp, i32, i64p, f32, f64 = C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_float, C.c_double
-    L.plb_last_error.restype = C.c_char_p
-    L.plb_last_error.argtypes = []
-    L.plb_create.restype = C.c_int
-    L.plb_create.argtypes = [C.POINTER(PlbConfig), C.POINTER(vp)]
-    L.plb_destroy.restype = None
-    L.plb_destroy.argtypes = [vp]
-    L.plb_param_layout.restype = C.c_int
-    L.plb_param_layout.argtypes = [vp, i64p, i64p, i64p, i64p]
-    L.plb_workspace_bytes.restype = C.c_int64
-    L.plb_workspace_bytes.argtypes = [vp]
-    L.plb_bind.restype = C.c_int
-    L.plb_bind.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64]
-    L.plb_sync_weights.restype = C.c_int
-    L.plb_sync_weights.argtypes = [vp, vp]
-    L.plb_forward.restype = C.c_int
-    L.plb_forward.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    L.plb_loss_fwd_bwd.restype = C.c_int
-    L.plb_loss_fwd_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-    L.plb_loss_fwd_bwd_dual.restype = C.c_int
-    L.plb_loss_fwd_bwd_dual.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    L.plb_pooler.restype = C.c_int
-    L.plb_pooler.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.plb_loss_fwd.restype = C.c_int
-    L.plb_loss_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    L.plb_set_fp8.restype = C.c_int
-    L.plb_set_fp8.argtypes = [vp, i32, vp]
-    L.plb_fp8_state.restype = C.c_int
-    L.plb_fp8_state.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    L.plb_token_head_steps.restype = i32
-    L.plb_token_head_steps.argtypes = [vp]
-    L.plb_set_token_head_steps.restype = C.c_int
-    L.plb_set_token_head_steps.argtypes = [vp, i32]
-    L.plb_comm_unique_id.restype = C.c_int
-    L.plb_comm_unique_id.argtypes = [vp]
-    L.plb_comm_init.restype = C.c_int
-    L.plb_comm_init.argtypes = [vp, vp, i32, i32]
-    L.plb_comm_destroy.restype = C.c_int
-    L.plb_comm_destroy.argtypes = [vp]
-    L.plb_comm_info.restype = C.c_int
-    L.plb_comm_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    L.plb_status.restype = C.c_int
-    L.plb_status.argtypes = [vp, C.POINTER(i32)]
-    L.plb_status_ex.restype = C.c_int
-    L.plb_status_ex.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    L.plb_poll_status.restype = C.c_int
-    L.plb_poll_status.argtypes = [vp, C.POINTER(i32)]
-    L.plb_fp8_stats.restype = C.c_int
-    L.plb_fp8_stats.argtypes = [vp, C.POINTER(f32), C.POINTER(f32), vp]
-    L.plb_last_application_rows.restype = C.c_int
-    L.plb_last_application_rows.argtypes = [vp, i64p, i64p]
-    if hasattr(L, "plb_packing_plan"):   # (PLBERT_HIP_LIB may name an A/B build that predates token-packed execution)
-        pk = C.POINTER(PlbPacking)
-        L.plb_last_call_rows.restype = C.c_int
-        L.plb_last_call_rows.argtypes = [vp, i64p, i64p]
-        L.plb_packing_plan.restype = C.c_int
-        L.plb_packing_plan.argtypes = [vp, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
-        L.plb_forward_packed.restype = C.c_int
-        L.plb_forward_packed.argtypes = [vp, vp, vp, i32, i32, pk, vp, vp, vp, vp]
-        L.plb_loss_fwd_bwd_packed.restype = C.c_int
-        L.plb_loss_fwd_bwd_packed.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, pk, vp, vp]
-        L.plb_loss_fwd_packed.restype = C.c_int
-        L.plb_loss_fwd_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, pk, vp, vp, vp]
-        L.plb_launch_ce_prepare_packed.restype = C.c_int
-        L.plb_launch_ce_prepare_packed.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-        L.plb_launch_unpack_rows.restype = C.c_int
-        L.plb_launch_unpack_rows.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
-    if hasattr(L, "plb_encode"):   # (an A/B build named by PLBERT_HIP_LIB may predate the differentiable encoder)
-        L.plb_encode.restype = C.c_int
-        L.plb_encode.argtypes = [vp, vp, vp, i32, i32, C.POINTER(PlbPacking), vp, vp]
-        L.plb_encode_bwd.restype = C.c_int
-        L.plb_encode_bwd.argtypes = [vp, vp, vp, i32, i32, C.POINTER(PlbPacking), vp, vp]
-        L.plb_launch_seed_dy.restype = C.c_int
-        L.plb_launch_seed_dy.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-    if hasattr(L, "plb_set_packed_dual"):   # (an A/B build named by PLBERT_HIP_LIB may predate packed dual-head calls)
-        L.plb_set_packed_dual.restype = C.c_int
-        L.plb_set_packed_dual.argtypes = [vp, i32]
-        L.plb_loss_fwd_bwd_dual_packed.restype = C.c_int
-        L.plb_loss_fwd_bwd_dual_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(PlbPacking), vp, vp, vp]
-        L.plb_launch_pack_token_targets.restype = C.c_int
-        L.plb_launch_pack_token_targets.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
-        L.plb_launch_token_ce_combine_packed.restype = C.c_int
-        L.plb_launch_token_ce_combine_packed.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
-    if hasattr(L, "plb_set_packed_fp8"):   # (likewise: an A/B build may predate packed fp8 calls)
-        L.plb_set_packed_fp8.restype = C.c_int
-        L.plb_set_packed_fp8.argtypes = [vp, i32]
-    if hasattr(L, "plb_grad_accum_add"):   # (likewise: an A/B build may predate gradient accumulation and clipping)
-        L.plb_grad_norm_floats.restype = C.c_int64
-        L.plb_grad_norm_floats.argtypes = [vp]
-        L.plb_grad_accum_bind.restype = C.c_int
-        L.plb_grad_accum_bind.argtypes = [vp, vp]
-        L.plb_grad_accum_add.restype = C.c_int
-        L.plb_grad_accum_add.argtypes = [vp, i32, vp, vp]
-        L.plb_grad_norm.restype = C.c_int
-        L.plb_grad_norm.argtypes = [vp, f64, f64, vp, i32, vp]
-        L.plb_adamw_step_clipped.restype = C.c_int
-        L.plb_adamw_step_clipped.argtypes = [vp, f64, f64, f64, f64, f64, i32, f64, vp, vp]
-        L.plb_launch_grad_accum.restype = C.c_int
-        L.plb_launch_grad_accum.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp]
-        L.plb_launch_grad_sumsq.restype = C.c_int
-        L.plb_launch_grad_sumsq.argtypes = [vp, C.c_size_t, vp, vp]
-        L.plb_launch_grad_norm_finish.restype = C.c_int
-        L.plb_launch_grad_norm_finish.argtypes = [vp, C.c_int, f64, f64, vp, vp]
-        L.plb_launch_adamw_clipped.restype = C.c_int
-        L.plb_launch_adamw_clipped.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, f64, f64, f64, f64, f64, C.c_int, f64, vp, C.c_int,
-                                               vp, C.c_int, vp]
-    L.plb_status_export.restype = C.c_int
-    L.plb_status_export.argtypes = [vp, vp, vp]
-    L.plb_status_import.restype = C.c_int
-    L.plb_status_import.argtypes = [vp, vp, vp]
-    L.plb_debug_hb_audit.restype = C.c_int
-    L.plb_debug_hb_audit.argtypes = [vp, i32, i32]
-    L.plb_debug_hb_report.restype = C.c_int
-    L.plb_debug_hb_report.argtypes = [vp, i64p, C.POINTER(i32), C.c_char_p, i32]
-    L.plb_comm_trace.restype = C.c_int
-    L.plb_comm_trace.argtypes = [vp, i32]
-    L.plb_comm_trace_read.restype = C.c_int
-    L.plb_comm_trace_read.argtypes = [vp, i32, C.POINTER(i32), i64p, i64p, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]
-    L.plb_debug_ln_fault.restype = None
-    L.plb_debug_ln_fault.argtypes = [C.c_int, C.c_int]
-    L.plb_debug_skip_piece.restype = None
-    L.plb_debug_skip_piece.argtypes = [C.c_int]
-    L.plb_comm_pieces.restype = C.c_int
-    L.plb_comm_pieces.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_int64)]
-    L.plb_broadcast_params.restype = C.c_int
-    L.plb_broadcast_params.argtypes = [vp, i32, vp]
-    L.plb_set_grad_overlap.restype = C.c_int
-    L.plb_set_grad_overlap.argtypes = [vp, i32]
-    L.plb_allreduce_grads.restype = C.c_int
-    L.plb_allreduce_grads.argtypes = [vp, vp]
-    L.plb_apply_mask.restype = C.c_int
-    L.plb_apply_mask.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.plb_adamw_step.restype = C.c_int
-    L.plb_adamw_step.argtypes = [vp, f64, f64, f64, f64, f64, i32, f64, vp]
-    L.plb_mask_batch.restype = C.c_int
-    L.plb_mask_batch.argtypes = [vp, vp, i32, i32, C.c_uint64, C.c_uint32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp]
-    L.plb_profile_enable.restype = None
-    L.plb_profile_enable.argtypes = [C.c_int]
-    L.plb_profile_num_classes.restype = C.c_int
-    L.plb_profile_num_classes.argtypes = []
-    L.plb_profile_class_name.restype = C.c_char_p
-    L.plb_profile_class_name.argtypes = [C.c_int]
-    L.plb_profile_read.restype = C.c_int
-    L.plb_profile_read.argtypes = [C.POINTER(C.c_double), i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    # internal launchers (kernel-level tests)
-    L.plb_launch_gemm_nt.restype = C.c_int
-    L.plb_launch_gemm_nt.argtypes = [C.POINTER(PlbGemmNT), C.c_int, C.c_int, vp]
-    L.plb_set_gemm_nt_tile.restype = None
-    L.plb_set_gemm_nt_tile.argtypes = [C.c_int]
-    L.plb_set_gemm_nt_prefetch.restype = None
-    L.plb_set_gemm_nt_prefetch.argtypes = [C.c_int]
-    L.plb_launch_gemm_nt_fp8.restype = C.c_int
-    L.plb_launch_gemm_nt_fp8.argtypes = [C.POINTER(PlbGemmNT), C.c_int, C.c_int, vp]
-    L.plb_launch_gemm_nt_fp8_ln.restype = C.c_int
-    L.plb_launch_gemm_nt_fp8_ln.argtypes = [C.POINTER(PlbGemmNT), C.c_int, C.c_int, vp]
-    L.plb_launch_gemm_nt_fp8_gelud.restype = C.c_int
-    L.plb_launch_gemm_nt_fp8_gelud.argtypes = [C.POINTER(PlbGemmNT), C.c_int, C.c_int, vp]
-    L.plb_launch_gemm_tn.restype = C.c_int
-    L.plb_launch_gemm_tn.argtypes = [C.POINTER(PlbGemmTN), vp]
-    L.plb_launch_gemm_tn_big.restype = C.c_int
-    L.plb_launch_gemm_tn_big.argtypes = [C.POINTER(PlbGemmTN), vp]
-    L.plb_launch_gemm_tn_fp8.restype = C.c_int
-    L.plb_launch_gemm_tn_fp8.argtypes = [C.POINTER(PlbGemmTN), vp]
-    L.plb_launch_reduce_slabs.restype = C.c_int
-    L.plb_launch_reduce_slabs.argtypes = [vp, C.c_int, C.c_size_t, vp, C.c_int, vp]
-    L.plb_launch_attn_fwd.restype = C.c_int
-    L.plb_launch_attn_fwd.argtypes = [C.POINTER(PlbAttn), vp]
-    L.plb_launch_gemm_nt_ln.restype = C.c_int
-    L.plb_launch_gemm_nt_ln.argtypes = [C.POINTER(PlbGemmNT), C.c_int, vp]
-    L.plb_launch_gemm_nt_gelud.restype = C.c_int
-    L.plb_launch_gemm_nt_gelud.argtypes = [C.POINTER(PlbGemmNT), C.c_int, vp]
-    L.plb_launch_attn_bwd.restype = C.c_int
-    L.plb_launch_attn_bwd.argtypes = [C.POINTER(PlbAttn), vp]
-    L.plb_launch_attn_bwd_fused.restype = C.c_int
-    L.plb_launch_attn_bwd_fused.argtypes = [C.POINTER(PlbAttn), vp]
-    L.plb_set_prune_last.restype = None
-    L.plb_set_prune_last.argtypes = [C.c_int]
-    L.plb_set_attn_bwd_fused.restype = None
-    L.plb_set_attn_bwd_fused.argtypes = [C.c_int]
-    L.plb_launch_ln_fwd.restype = C.c_int
-    L.plb_launch_ln_fwd.argtypes = [C.POINTER(PlbLayerNorm), vp]
-    L.plb_launch_ln_bwd.restype = C.c_int
-    L.plb_launch_ln_bwd.argtypes = [C.POINTER(PlbLayerNorm), vp]
-    L.plb_launch_embed_scatter.restype = C.c_int
-    L.plb_launch_embed_scatter.argtypes = [C.POINTER(PlbEmbed), C.c_int, vp]
-    L.plb_launch_ce_prepare.restype = C.c_int
-    L.plb_launch_ce_prepare.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.plb_launch_colsum.restype = C.c_int
-    L.plb_launch_colsum.argtypes = [vp, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]
-    _lib = L
-    return L
+    return _lib
 
 
 def profile_enable(on):

@@ -115,41 +115,6 @@ def torch_attention(qkv, lengths, B, S, NH):
     return ctx.detach(), lse.detach(), grad
 
 
-# ---- raw launchers of the row and fp8 kernels (csrc/plbert_kernels.h) --------------------------------------------------
-# ctypes passes a Python int as a C int unless told otherwise: a size_t or float parameter would then receive garbage in
-# its upper bits / the bit pattern of an int. bind() declares the launchers the kernel-level tests call with scalar
-# arguments that plbert_amd/_lib.py leaves undeclared; struct-taking launchers are called with C.byref(struct).
-_vp, _i, _sz, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
-_SIGNATURES = {
-    "plb_launch_amax": [_vp, _i, _sz, _i, _i, _vp, _vp],
-    "plb_launch_fp8_scales": [_vp, _vp, _vp, _i, _f, _i, _vp],
-    "plb_launch_fp8_scales2": [_vp, _vp, _vp, _i, _f, _i, _i, _f, _vp, _i, _vp],
-    "plb_launch_quantize": [_vp, _i, _sz, _i, _i, _vp, _vp, _i, _i, _vp],
-    "plb_launch_quantize_multi": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "plb_launch_copy_cols": [_vp, _i, _i, _i, _i, _vp, _vp],
-    "plb_launch_pooler": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "plb_launch_gather_rows": [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp],
-    "plb_launch_scatter_rows": [_vp, _i, _vp, _i, _i, _vp, _i, _vp],
-    "plb_launch_ce_prepare": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
-    "plb_launch_ce_fwd_bwd": [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp],
-    "plb_launch_sum_rows": [_vp, _i, _vp, _vp],
-    "plb_launch_cast_bf16": [_vp, _vp, _sz, _vp],
-    "plb_launch_transpose_cast": [_vp, _i, _i, _vp, _i, _vp],
-    "plb_launch_transpose_cast_multi": [_i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "plb_launch_bf16_to_f32": [_vp, _i, _vp, _i, _i, _i, _vp],
-}
-
-
-def bind(L=None):
-    """Declare restype / argtypes of the scalar-argument launchers; returns the library."""
-    L = L or _lib.lib()
-    for name, args in _SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = C.c_int
-        fn.argtypes = args
-    return L
-
-
 def ptr_array(tensors, ctype=C.c_void_p):
     """A C array of device pointers (None stays NULL)."""
     return (ctype * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])

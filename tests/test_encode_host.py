@@ -2,12 +2,10 @@
 library built for gfx950 exports the entry points and the new launcher, header and ctypes binding agree on their
 signatures, and plbert_amd.train.AdamW exposes torch's ``param_groups`` over its live hyper-parameters."""
 import ctypes as C
-import os
-import re
 
+import c_header
 from plbert_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("plb_encode", "plb_encode_bwd")
 
 
@@ -19,46 +17,21 @@ def test_library_exports_the_encode_entry_points():
         assert hasattr(L, s), s
 
 
-def _c_params(text, name):
-    m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, text, re.S)
-    assert m, name
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
-def _ctype_of(decl):
-    if "*" in decl:
-        return "ptr"
-    if decl.startswith("int32_t") or decl.startswith("int "):
-        return "i32"
-    if decl.startswith("hipStream_t"):
-        return "ptr"
-    raise AssertionError(decl)
-
-
-def _kind(t):
-    if t is C.c_void_p or (isinstance(t, type) and issubclass(t, C._Pointer)):
-        return "ptr"
-    assert t in (C.c_int32, C.c_int), t
-    return "i32"
-
-
 def test_header_and_binding_agree_on_the_signatures():
     L = _lib.lib()
-    hdr = open(os.path.join(ROOT, "include", "plbert.h")).read()
+    hdr, khdr = c_header.public(), c_header.kernels()
     for name in ENTRY_POINTS:
-        params = _c_params(hdr, name)
         fn = getattr(L, name)
         assert fn.restype is C.c_int
-        assert [_ctype_of(p) for p in params] == [_kind(t) for t in fn.argtypes], (name, params)
+        assert c_header.bound_mismatch(hdr, fn, _lib) is None
     # both take (engine, ids, lengths, B, S, packing, buffer, stream); the plan is a PlbPacking pointer
     for name, buf in (("plb_encode", "float* hidden"), ("plb_encode_bwd", "const float* d_hidden")):
-        params = _c_params(hdr, name)
+        params = c_header.c_params(hdr, name)
         assert params[0] == "PlbEngine* e" and params[5] == "const PlbPacking* packing" and params[6] == buf, params
         assert params[-1] == "void* stream" and len(params) == 8
         assert getattr(L, name).argtypes[5] is C.POINTER(_lib.PlbPacking)
-    khdr = open(os.path.join(ROOT, "plbert_amd", "csrc", "plbert_kernels.h")).read()
-    params = _c_params(khdr, "plb_launch_seed_dy")
-    assert [_ctype_of(p) for p in params] == [_kind(t) for t in L.plb_launch_seed_dy.argtypes], params
+    params = c_header.c_params(khdr, "plb_launch_seed_dy")
+    assert c_header.bound_mismatch(khdr, L.plb_launch_seed_dy, _lib) is None
     assert len(params) == 9 and params[0] == "const float* d_hidden" and params[7] == "bf16_t* dy"
 
 

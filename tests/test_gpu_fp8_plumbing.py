@@ -16,7 +16,8 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_util import F8_SLOTS, F8_STRIDE, assert_fp8_image, bind, fp8_fmax, ptr_array, site_max, stream
+from gpu_util import F8_SLOTS, F8_STRIDE, assert_fp8_image, fp8_fmax, ptr_array, site_max, stream
+from plbert_amd import _lib
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -78,7 +79,7 @@ SCALES = [1.0, float(np.float32(448.0 / 3.7)), 2.0 ** -7, 2.0 ** 9]
 @pytest.mark.parametrize("bf8", [0, 1])
 @pytest.mark.parametrize("scale", SCALES)
 def test_quantize_every_bf16_value(bf8, scale):
-    L = bind()
+    L = _lib.lib()
     x = _all_bf16()
     out, s = _quantize(L, x, scale, bf8)
     assert_fp8_image(out, x, s, bf8, slice(None))
@@ -89,7 +90,7 @@ def test_quantize_every_bf16_value(bf8, scale):
 def test_quantize_fp32_midpoints_saturation_and_subnormals(bf8, scale):
     """At a power-of-two scale the product is exact and the midpoints stay midpoints (the ties of round-to-nearest-even);
     448 / 3.7 moves them off the grid (the product's own rounding then decides)."""
-    L = bind()
+    L = _lib.lib()
     x = _fp32_edges(bf8)
     x = (x / scale if scale != float(np.float32(448.0 / 3.7)) else x).float().reshape(-1, 8)
     out, s = _quantize(L, x, scale, bf8)
@@ -98,7 +99,7 @@ def test_quantize_fp32_midpoints_saturation_and_subnormals(bf8, scale):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_quantize_strided_with_sentinel_gaps(dtype):
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(3)
     rows, cols, ld, ldo = 37, 40, 56, 48
     x = (torch.randn(rows, cols, generator=g) * 3).to(dtype)
@@ -109,7 +110,7 @@ def test_quantize_strided_with_sentinel_gaps(dtype):
 
 def test_quantize_grid_stride_loop():
     """More than 2048 blocks x 256 threads x 8 elements: every thread runs the loop more than once."""
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(4)
     rows, cols = 4100, 1032
     assert rows * cols > 2048 * 256 * 8
@@ -126,7 +127,7 @@ def test_quantize_grid_stride_loop():
 @pytest.mark.parametrize("where", ["first", "last", "negative"])
 @pytest.mark.parametrize("prior", [0.0, 0.5, 1e9])
 def test_amax_site(dtype, where, prior):
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(5)
     rows, cols, ld = 301, 48, 64
     x = torch.rand(rows, ld, generator=g) * 2 - 1
@@ -155,7 +156,7 @@ def test_amax_site(dtype, where, prior):
 
 
 def test_amax_refuses_unaligned_columns():
-    L = bind()
+    L = _lib.lib()
     site = torch.zeros(SITE, device=DEV)
     x = torch.zeros(4, 16, device=DEV)
     assert L.plb_launch_amax(x.data_ptr(), 0, 4, 12, 16, site.data_ptr(), stream()) != 0
@@ -165,7 +166,7 @@ def test_amax_refuses_unaligned_columns():
 # ---------------------------------------------------------------------------------------------------- quantize_multi
 @pytest.mark.parametrize("case", ["one", "eight"])
 def test_quantize_multi(case):
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(6)
     if case == "one":
         specs = [(1 << 21) + 8 * 7, 0]                       # (elements, flags): one matrix, the 1024-block grid
@@ -201,7 +202,7 @@ def test_quantize_multi(case):
 
 
 def test_quantize_multi_refuses():
-    L = bind()
+    L = _lib.lib()
     x = torch.zeros(16, device=DEV)
     d = torch.zeros(16, dtype=torch.uint8, device=DEV)
     s = torch.ones(1, device=DEV)
@@ -340,7 +341,7 @@ def _same_bits(a, b):
 
 @pytest.mark.parametrize("L,hist_from", [(4, 0), (12, 0), (12, 5)])
 def test_fp8_scales2_state_machine_in_the_engine_layout(L, hist_from):
-    Lb = bind()
+    Lb = _lib.lib()
     g = np.random.default_rng(L * 10 + hist_from)
     n, ncalls = 8 * L, 12
     model = ScalesModel(n, 448.0, L, 4 * L, 28672.0, stats=True, hist_from=hist_from)
@@ -365,7 +366,7 @@ def test_fp8_scales2_state_machine_in_the_engine_layout(L, hist_from):
 
 def test_fp8_scales2_cases_one_by_one():
     """The individual rules, each visible in a short sequence at L = 4 (n = 32, group 4, n2 = 16, 448 / 28672)."""
-    Lb = bind()
+    Lb = _lib.lib()
     L, n = 4, 32
     scale = torch.zeros(n, device=DEV)
     deq = torch.zeros(n, device=DEV)
@@ -397,7 +398,7 @@ def test_fp8_scales2_cases_one_by_one():
 
 def test_fp8_scales_weight_update_group_one():
     """The weight images' update (csrc/engine_fp8.cpp: fp8_quantize_weights): group 1, no stats, target 448."""
-    Lb = bind()
+    Lb = _lib.lib()
     n = 8
     g = np.random.default_rng(2)
     model = ScalesModel(n, 448.0, 1)
@@ -428,8 +429,7 @@ SENT = 0x6D
 @pytest.mark.parametrize("H", [768, 1024])
 @pytest.mark.parametrize("T", [1, 333, 4097])
 def test_layernorm_forward_writes_the_fp8_image(H, T):
-    from plbert_amd import _lib
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(H + T)
     x = (torch.randn(T, H, generator=g) * 2 + 0.5).to(torch.bfloat16).to(DEV)
     gam = (1 + 0.3 * torch.randn(H, generator=g)).to(DEV)
@@ -454,8 +454,7 @@ def test_layernorm_forward_writes_the_fp8_image(H, T):
 @pytest.mark.parametrize("T,Tzero", [(333, 340), (4096, 4096 + 128), (5, 5)])
 def test_layernorm_backward_writes_the_fp8_image(H, T, Tzero):
     """e5m2 image of dx; rows T..Tzero of the image are zero BYTES (the fp8 weight-gradient GEMMs sum over them)."""
-    from plbert_amd import _lib
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(H + T + 1)
     x = (torch.randn(T, H, generator=g) * 2).to(torch.bfloat16)
     xf = x.float()
@@ -494,7 +493,7 @@ def test_attention_forward_writes_the_fp8_image(B, S, NH, lens):
     """ctx8 = e4m3 image of the context rows (csrc/attn_common.h). The forward stores a context row for EVERY query row
     (lengths mask keys only): rows [0, B*S) are stored, the rows past them and the columns past H of the image stay."""
     from gpu_util import attn_args
-    L = bind()
+    L = _lib.lib()
     H = NH * 64
     qkv = _qkv(B, S, NH, S + NH)
     lengths = torch.tensor(lens, dtype=torch.int32, device=DEV)
@@ -520,7 +519,7 @@ def test_attention_backward_compact_queries_writes_the_fp8_images(B, S, NH, lens
     rows, dqkv8's K / V blocks the image of dqkv's K / V rows (padded keys: zero bytes); dqkv8's Q block is not written.
     Both images report into the one dqkv site: its maximum is the maximum over everything stored."""
     from gpu_util import attn_args
-    L = bind()
+    L = _lib.lib()
     H = NH * 64
     qkv = _qkv(B, S, NH, 81 + S)
     lengths = torch.tensor(lens, dtype=torch.int32, device=DEV)
@@ -570,7 +569,7 @@ def test_attention_backward_single_kernel_writes_the_fp8_image(B, S, NH, lens):
     image must be ocp_bytes of the first run's rows (the kernel is deterministic: test_attention_race_screen), padded rows
     zero bytes, rows past B*S untouched, and the site's maximum the maximum of those rows."""
     from gpu_util import attn_args
-    L = bind()
+    L = _lib.lib()
     H = NH * 64
     qkv = _qkv(B, S, NH, 91 + S)
     lengths = torch.tensor(lens, dtype=torch.int32, device=DEV)

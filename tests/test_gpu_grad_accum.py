@@ -10,8 +10,6 @@ _lib.norm_chain(n) = 4 * chunk(n) / 1024 + 6 + 3 fp32 additions at the most lie 
 PLB_NORM_CHAIN). All terms are non-negative, so each rounding is at most 2^-24 of the final partial: the sum of squares is
 within (chain + 2) * 2^-24 relative of the float64 sum (the 2: the double sum over the partials and the result's rounding
 to fp32), the norm within half of that."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -214,13 +212,8 @@ def test_a_non_finite_norm_leaves_the_update_out_and_counts_it():
 
 
 # ---- 3. the clipped AdamW -----------------------------------------------------------------------------------------------
-_ADAMW_ARGS = [C.c_void_p] * 5 + [C.c_size_t] + [C.c_double] * 5 + [C.c_int, C.c_double, C.c_void_p, C.c_int]
-
-
 def test_clipped_launcher_equals_the_plain_one_at_coef_one_and_skips_on_the_flag():
     L = _lib.lib()
-    L.plb_launch_adamw.restype = C.c_int
-    L.plb_launch_adamw.argtypes = _ADAMW_ARGS + [C.c_void_p]
     n = 1024 * 3 + 4
     gen = torch.Generator(device="cuda").manual_seed(11)
     g = _wide(n, gen)

@@ -522,11 +522,6 @@ def test_fused_gemm_cross_entropy_passes(NT, B, S, lens, tile):
     1 / (B * len), gradient (softmax - onehot) * w in bf16, zeros on padded positions, on rows >= B*S and on columns
     >= NT, and the column-sum partials (bias gradient) of the gradient as stored."""
     L = _lib.lib()
-    L.plb_launch_gemm_nt_big.restype = C.c_int
-    L.plb_launch_gemm_nt_big.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.plb_launch_token_ce_combine.restype = C.c_int
-    L.plb_launch_token_ce_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     T, H = B * S, 128
     Tp = (T + 255) // 256 * 256 if tile == 256 else (T + 127) // 128 * 128
     NTp = (NT + 255) // 256 * 256

@@ -39,7 +39,7 @@ import pytest
 import torch
 
 from gpu_util import (DELTA0, F8_SLOTS, F8_STRIDE, LN_BWD_CLASSES, LN_CLASSES, LN_EPS, LN_NEARCONST_SEED, LN_STAT_FLOOR, SENTINEL,
-                      EXACT_LIMIT, Ln, assert_fp8_image, bind, check_ln_elements, check_ln_partials, check_ln_stats, exact_bound,
+                      EXACT_LIMIT, Ln, assert_fp8_image, check_ln_elements, check_ln_partials, check_ln_stats, exact_bound,
                       exact_nt, int_operands, layernorm_bwd_fp64, layernorm_fp64, layernorm_stats_f32, ln_class_worst, ln_dy,
                       ln_fwd_cond, ln_row_bound, ln_rows, operand_values, stream)
 from plbert_amd import _lib
@@ -88,7 +88,7 @@ def _fwd_kernel_name(H, ldx, ldy):
 
 
 def _forward(T, H, ldx=None, ldy=None, out8=False, seed=0):
-    L = bind()
+    L = _lib.lib()
     ldx, ldy = ldx or H, ldy or H
     case = f"fwd {_fwd_kernel_name(H, ldx, ldy)} H {H} T {T} ld {ldx}/{ldy} out8 {int(out8)}"
     x, cls = ln_rows(T, H, 100 + seed + H + T)
@@ -160,7 +160,7 @@ def test_forward_odd_stride_falls_to_the_8_byte_kernels(H):
     for T in (3, 37):
         _forward(T, H, H + 4, H)
         _forward(T, H, H + 4, H + 4)
-    L = bind()
+    L = _lib.lib()
     p = _lib.PlbLayerNorm()
     buf = torch.zeros(8 * (H + 16), device=DEV)
     p.x, p.ldx, p.gamma, p.beta, p.eps = buf.data_ptr(), H + 4, buf.data_ptr(), buf.data_ptr(), LN_EPS
@@ -184,7 +184,7 @@ def _bwd_kernel_name(H, ldx, lddy, lddx, out8):
 
 
 def _backward(T, H, nblocks, ldx=None, lddy=None, lddx=None, out8=False, accumulate=False):
-    L = bind()
+    L = _lib.lib()
     ldx, lddy, lddx = ldx or H, lddy or H, lddx or H
     kname = _bwd_kernel_name(H, ldx, lddy, lddx, out8)
     case = f"bwd {kname} H {H} T {T} nblocks {nblocks} ld {ldx}/{lddy}/{lddx} out8 {int(out8)}"

@@ -8,7 +8,6 @@ Shapes (plans from plb_packing_plan; between them every branch of the token head
   (6, 200, [200,127,64,13,1,1])   896 used / 1024 rows of 1280: 256-row tiles, a 128-row tail that no sample owns
   (2, 512, [512,300]) (fixture)   896 used /  896 rows of 1024: Tp % 256 != 0, the 128 x 256 tile form
 Vocabularies: 1000 token classes (padded to 1024 columns) and 300 with the fixture's batch."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -100,9 +99,6 @@ def test_token_ce_combine_packed_kernel_is_bit_equal_to_the_padded_launch(name, 
     loss row of every valid token are the same bits, every slot-pad and tail row is exactly 0.0 (outputs prefilled with
     NaN). 4 tiles: lanes without a tile; 250: lanes with three and four."""
     L = _lib.lib()
-    L.plb_launch_token_ce_combine.restype = C.c_int
-    L.plb_launch_token_ce_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     B, S, lengths, NT, used, rows, padded = SHAPES[name]
     plan = _shape_plan(name)
     pr, dr, hole = _row_index(plan)

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_util import bind, ptr_array, stream
+from gpu_util import ptr_array, stream
 import plbert_amd
 from plbert_amd import _lib
 
@@ -47,7 +47,7 @@ def _ce_case(B, S, V, counts, seed):
 
 
 def _run_ce(off, flat, labels, B, S, V, logits_rows, npad, ldd=256):
-    L = bind()
+    L = _lib.lib()
     n = int(off[-1])
     d_off = torch.from_numpy(off).to(DEV)
     d_flat = torch.from_numpy(flat if len(flat) else np.zeros(1, np.int32)).to(DEV)
@@ -116,7 +116,7 @@ def test_masked_cross_entropy(B, S, V, counts):
 
 @pytest.mark.parametrize("n", [0, 1, 257, 5000])
 def test_sum_rows(n):
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(n)
     x = (torch.rand(max(n, 1), generator=g) - 0.3) * 10
     xd = x.to(DEV)
@@ -135,7 +135,7 @@ def test_sum_rows(n):
 
 
 def test_ce_refuses_beyond_its_width():
-    L = bind()
+    L = _lib.lib()
     buf = torch.zeros(1024, device=DEV)
     assert L.plb_launch_ce_fwd_bwd(buf.data_ptr(), 300, 257, buf.data_ptr(), buf.data_ptr(), 1, 1, buf.data_ptr(),
                                    buf.data_ptr(), 256, stream()) != 0
@@ -147,7 +147,7 @@ def test_ce_refuses_beyond_its_width():
 @pytest.mark.parametrize("E", [64, 128, 256])
 @pytest.mark.parametrize("nblocks", [1, 64])
 def test_embeddings_forward_backward_scatter(E, nblocks):
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(E + nblocks)
     V, S, P, T = 188, 512, 520, 9003                  # T > 2048 blocks x 4 waves, not a multiple of 4; P > S
     word = torch.randn(V, E, generator=g)
@@ -210,7 +210,7 @@ def test_embeddings_forward_backward_scatter(E, nblocks):
 @pytest.mark.parametrize("H", [128, 768, 1024])
 @pytest.mark.parametrize("B,S", [(1, 1), (3, 512)])
 def test_pooler_launch(H, B, S):
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(H + B + S)
     hidden = torch.randn(B, S, H, generator=g)
     W = torch.randn(H, H, generator=g) * H ** -0.5
@@ -244,7 +244,7 @@ def test_pooler_through_an_engine(H, NH):
 
 # ----------------------------------------------------------------------------------------------- copies and casts
 def test_gather_and_scatter_rows():
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(11)
     T, H, lds, ldd, n, npad = 300, 768, 776, 784, 57, 64
     src = torch.randn(T, lds, generator=g).to(torch.bfloat16)
@@ -269,7 +269,7 @@ def test_gather_and_scatter_rows():
 
 
 def test_transpose_cast_single_and_multi():
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(12)
     shapes = [(33, 1, 33), (1, 1, 8), (768, 2304, 768), (45, 70, 64), (32, 32, 40), (100, 3, 100), (7, 129, 7), (64, 33, 72)]
     srcs = [torch.randn(R, Cc, generator=g) * 3 for R, Cc, _ in shapes]
@@ -297,7 +297,7 @@ def test_transpose_cast_single_and_multi():
 
 
 def test_cast_bf16_rounding():
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(13)
     b = (torch.randn(4000, generator=g) * 10.0 ** torch.randint(-30, 30, (4000,), generator=g)).to(torch.bfloat16)
     bits = b.view(torch.int16).int()
@@ -321,7 +321,7 @@ def test_cast_bf16_rounding():
 
 
 def test_bf16_to_f32_strided():
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(14)
     R, Cc, lds, ldd = 130, 77, 96, 80
     src = torch.randn(R, lds, generator=g).to(torch.bfloat16)
@@ -335,7 +335,7 @@ def test_bf16_to_f32_strided():
 
 @pytest.mark.parametrize("is_bf16", [1, 0])
 def test_colsum_then_copy_cols(is_bf16):
-    L = bind()
+    L = _lib.lib()
     g = torch.Generator().manual_seed(15 + is_bf16)
     R, N, ld, Nout, nsplit, col0, Nout2 = 1001, 264, 272, 200, 7, 200, 64
     X = 0.5 + torch.randn(R, ld, generator=g)

@@ -3,14 +3,12 @@ and the two launchers of the packed token head; header and ctypes binding agree 
 read the way the other environment switches are; the trainer and the engine carry the switch."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import pytest
 
+import c_header
 from plbert_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("plb_set_packed_dual", "plb_loss_fwd_bwd_dual_packed")
 LAUNCHERS = ("plb_launch_pack_token_targets", "plb_launch_token_ce_combine_packed")
 
@@ -23,36 +21,15 @@ def test_library_exports_the_packed_dual_entry_points():
         assert hasattr(L, s), s
 
 
-def _c_params(text, name):
-    m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, text, re.S)
-    assert m, name
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
-def _ctype_of(decl):
-    if "*" in decl or decl.startswith("hipStream_t"):
-        return "ptr"
-    assert decl.startswith("int32_t ") or decl.startswith("int "), decl
-    return "i32"
-
-
-def _kind(t):
-    if t is C.c_void_p or (isinstance(t, type) and issubclass(t, C._Pointer)):
-        return "ptr"
-    assert t in (C.c_int32, C.c_int), t
-    return "i32"
-
-
 def test_header_and_binding_agree_on_the_signatures():
     L = _lib.lib()
-    hdr = open(os.path.join(ROOT, "include", "plbert.h")).read()
-    khdr = open(os.path.join(ROOT, "plbert_amd", "csrc", "plbert_kernels.h")).read()
-    for text, names in ((hdr, ENTRY_POINTS), (khdr, LAUNCHERS)):
+    hdr, khdr = c_header.public(), c_header.kernels()
+    _c_params = c_header.c_params
+    for header, names in ((hdr, ENTRY_POINTS), (khdr, LAUNCHERS)):
         for name in names:
-            params = _c_params(text, name)
             fn = getattr(L, name)
             assert fn.restype is C.c_int
-            assert [_ctype_of(p) for p in params] == [_kind(t) for t in fn.argtypes], (name, params)
+            assert c_header.bound_mismatch(header, fn, _lib) is None
     assert _c_params(hdr, "plb_set_packed_dual") == ["PlbEngine* e", "int32_t on"]
     # plb_loss_fwd_bwd_dual with a plan in front of the outputs
     dual, packed = _c_params(hdr, "plb_loss_fwd_bwd_dual"), _c_params(hdr, "plb_loss_fwd_bwd_dual_packed")

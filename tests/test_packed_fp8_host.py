@@ -92,24 +92,6 @@ def test_run_hands_training_params_packed_fp8_to_the_trainer(monkeypatch, tmp_pa
     assert got["packed_fp8"] is setting and got["packed_dual"] is True
 
 
-def test_binding_guards_keep_the_packed_dual_entry_points_under_their_own_symbol():
-    """A library named by PLBERT_HIP_LIB may have packed dual-head calls and predate this switch: the guard of the new
-    symbol binds the new symbol only, and plb_loss_fwd_bwd_dual_packed stays under the guard of plb_set_packed_dual (an
-    entry point without argtypes gets its device pointers marshalled as 32-bit ints)."""
-    import ast
-    tree = ast.parse(inspect.getsource(_lib))
-    guards = {}
-    for node in ast.walk(tree):
-        if (isinstance(node, ast.If) and isinstance(node.test, ast.Call) and getattr(node.test.func, "id", "") == "hasattr"
-                and isinstance(node.test.args[1], ast.Constant)):
-            bound = {t.value.attr for st in node.body if isinstance(st, ast.Assign) for t in st.targets
-                     if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Attribute)}
-            guards[node.test.args[1].value] = bound
-    assert guards["plb_set_packed_fp8"] == {"plb_set_packed_fp8"}
-    assert {"plb_set_packed_dual", "plb_loss_fwd_bwd_dual_packed", "plb_launch_pack_token_targets",
-            "plb_launch_token_ce_combine_packed"} <= guards["plb_set_packed_dual"]
-
-
 def test_trainer_passes_the_setting_to_its_engine(monkeypatch):
     """PLBertTrainer without a GPU: a stand-in engine records what the constructor hands on (None: the engine's own
     reading of PLBERT_PACKED_FP8 stands)."""

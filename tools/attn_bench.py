@@ -28,8 +28,6 @@ def bench(L, B, S, NH, iters=30):
     p.dctx, p.lddctx, p.delta, p.dqkv, p.lddqkv = dctx.data_ptr(), H, delta.data_ptr(), dqkv.data_ptr(), 3 * H
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     out = []
-    L.plb_profile_enable.argtypes = [C.c_int]
-    L.plb_profile_read.argtypes = [C.c_void_p] * 4
     for fn in (L.plb_launch_attn_fwd, L.plb_launch_attn_bwd):
         for _ in range(3):
             assert fn(C.byref(p), s) == 0
@@ -50,7 +48,6 @@ def bench(L, B, S, NH, iters=30):
     torch.cuda.synchronize()
     L.plb_profile_read(ms, cnt, fl, by)
     L.plb_profile_enable(0)
-    L.plb_profile_class_name.restype = C.c_char_p
     names = [L.plb_profile_class_name(i).decode() for i in range(n)]
     split = {names[i]: ms[i] / cnt[i] * 1e3 for i in range(n) if cnt[i]}
     out.append(split.get("attn_bwd_dq", 0.0))
@@ -68,7 +65,7 @@ def main():
     libs = [("main", _lib.lib())]
     _lib.lib().plb_set_attn_bwd_fused(1 if args.fused else 0)
     for path in [q for q in args.libs.split(",") if q]:
-        libs.append((os.path.basename(path), C.CDLL(os.path.abspath(path), mode=C.RTLD_LOCAL)))
+        libs.append((os.path.basename(path), _lib.declare(C.CDLL(os.path.abspath(path), mode=C.RTLD_LOCAL))))
         libs[-1][1].plb_set_attn_bwd_fused(1 if args.fused else 0)
     res = {}
     for rep in range(args.reps):

@@ -98,7 +98,7 @@ def main():
     WITH_RES = args.res
     L = _lib.lib()
     if args.tn:
-        libs = [("main", L)] + [(os.path.basename(q), C.CDLL(os.path.abspath(q), mode=C.RTLD_LOCAL))
+        libs = [("main", L)] + [(os.path.basename(q), _lib.declare(C.CDLL(os.path.abspath(q), mode=C.RTLD_LOCAL)))
                                 for q in args.libs.split(",") if q]
         res = {}
         shapes_tn = TN_SHAPES[:2] if args.quick else TN_SHAPES[4:] if args.small else TN_SHAPES
@@ -119,10 +119,7 @@ def main():
     # rounds is reported per variant.
     libs = [("main", L)]
     for path in [q for q in args.libs.split(",") if q]:
-        X = C.CDLL(os.path.abspath(path), mode=C.RTLD_LOCAL)
-        X.plb_set_gemm_nt_tile.argtypes = [C.c_int]
-        X.plb_set_gemm_nt_prefetch.argtypes = [C.c_int]
-        libs.append((os.path.basename(path), X))
+        libs.append((os.path.basename(path), _lib.declare(C.CDLL(os.path.abspath(path), mode=C.RTLD_LOCAL))))
     variants = [(ln, lib, pf, tile) for (ln, lib) in libs for pf in [int(t) for t in args.prefetch.split(",")]
                 for tile in [int(t) for t in args.tiles.split(",")]]
     time_nt(L, *SHAPES[0], args.act)  # warm the clocks
