@@ -74,7 +74,7 @@ def round_bf16(x):
 
 def fake_quant(x, amax, fmt, target=None):
     """dequantise(quantise(x)): x -> round(x * s) / s with s = target / amax; the scale and the scaled value in fp32 as
-    on the device (rowops.hip fp8_scales_kernel: scale = fmax / amax, deq = amax / fmax)."""
+    on the device (operand_images.hip fp8_scales_kernel: scale = fmax / amax, deq = amax / fmax)."""
     if not (amax > 0 and np.isfinite(amax)):
         return x
     t = np.float32(fmt["fmax"] if target is None else target)

@@ -222,7 +222,7 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
   }
   e->f8n = 8 * (int)L + 8;
   e->o_f8amax = cv.take((int64_t)e->f8n * 64 * 16 * 4); e->o_f8scale = cv.take(e->f8n * 4); e->o_f8deq = cv.take(e->f8n * 4);
-  e->o_f8stats = cv.take(8 * 8 * 4);   // per operand site: maxima history, clamped-call count, worst overshoot (rowops.hip: fp8_scales_kernel)
+  e->o_f8stats = cv.take(8 * 8 * 4);   // per operand site: maxima history, clamped-call count, worst overshoot (operand_images.hip: fp8_scales_kernel)
   e->ws_bytes = cv.off;
   *out = e;
   return 0;

@@ -1,5 +1,5 @@
 // Gradient accumulation, the global gradient norm and the clipped AdamW update (include/plbert.h: plb_grad_accum_*,
-// plb_grad_norm, plb_adamw_step_clipped). Host bookkeeping of a window of micro-steps plus launches of rowops.hip; no
+// plb_grad_norm, plb_adamw_step_clipped). Host bookkeeping of a window of micro-steps plus launches of optim.hip; no
 // workspace of its own: the accumulator and the norm buffer are the caller's. Only writer of PlbEngine's accumulation
 // block (grads_fresh / norm_nparts are also reset by begin_training_call, engine_calls.cpp); after a LAST add it sets
 // head_grads_live, tok_grads_live and grads_reduced to what the window accumulated.

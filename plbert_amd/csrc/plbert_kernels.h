@@ -155,7 +155,7 @@ typedef struct {
   // backward dx8 = e5m2(dx * s); q_amax collects max |value| (the next step's scale); all NULL = off
   uint8_t* out8; int ld8; const float* q_scale; float* q_amax;
 } PlbLayerNorm;
-// fp8 plumbing (rowops.hip). An "amax" argument anywhere in this file is one SITE: 64 words on 64-byte lines (common.h:
+// fp8 plumbing (operand_images.hip). An "amax" argument anywhere in this file is one SITE: 64 words on 64-byte lines (common.h:
 // F8_SLOTS x F8_STRIDE floats) that the waves of a launch spread their atomic maxima over; plb_launch_fp8_scales reduces
 // n consecutive sites. |x| maximum of a bf16 / fp32 buffer into a site (atomic max; zero it first),
 // scale update (delayed scaling: scale = fmax / amax, deq = 1 / scale, amax reset), quantisation of a bf16 / fp32 matrix
@@ -311,7 +311,7 @@ int plb_launch_apply_mask(const PlbApplyMask* p, hipStream_t stream);
 int plb_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, size_t n, double lr, double beta1,
                      double beta2, double eps, double wd, int step, double grad_scale, unsigned int* skip_if_nonzero,
                      int count_skip, hipStream_t stream);
-// ---- gradient accumulation, global-norm clipping (rowops.hip; include/plbert.h plb_grad_accum_add / plb_grad_norm /
+// ---- gradient accumulation, global-norm clipping (optim.hip; include/plbert.h plb_grad_accum_add / plb_grad_norm /
 // plb_adamw_step_clipped). Both partial-sum launches run on a FIXED grid of PLB_NORM_PARTS workgroups: workgroup b owns
 // floats [b * chunk, (b + 1) * chunk) of the range, chunk = plb_norm_chunk(n), and writes partials[b] (0 for an empty chunk).
 #define PLB_NORM_PARTS 1024

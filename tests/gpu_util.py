@@ -717,7 +717,7 @@ def exact_cases():
 
 
 # ---- the LayerNorm element contract (tests/test_gpu_layernorm_rows.py, tests/test_layernorm_rows_host.py) -----------------
-# Every element a LayerNorm kernel stores — the four standalone kernels of csrc/rowops.hip and forms 5 / 6 of the NT pipeline
+# Every element a LayerNorm kernel stores — the four standalone kernels of csrc/layernorm.hip and forms 5 / 6 of the NT pipeline
 # GEMM, bf16 and fp8 — is held to the float64 evaluation of the same stored inputs:
 #     |got - ref| <= 0.5 x spacing_bf16(ref) + delta x cond
 # one round-to-nearest of the exact value plus the fp32 arithmetic behind it, weighted by the element's condition term.

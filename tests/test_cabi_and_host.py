@@ -416,6 +416,21 @@ def test_library_compiles_without_warnings(tmp_path):
         assert "warning" not in out, f"{src}:\n{out[:3000]}"
 
 
+def test_build_lists_name_every_file_of_csrc():
+    """Every *.hip / *.cpp of csrc/ is in build.SOURCES, every *.h and exports.map in build.HEADERS, and neither list names
+    a file that is missing: a forgotten unit would only show as a link error on another machine, a forgotten header as a
+    needs_build() that misses an edit."""
+    from plbert_amd import build as B
+
+    files = sorted(os.listdir(B.CSRC))
+    assert sorted(B.SOURCES) == [f for f in files if f.endswith((".hip", ".cpp"))]
+    assert len(set(B.SOURCES)) == len(B.SOURCES) and len(set(B.HEADERS)) == len(B.HEADERS)
+    in_csrc = sorted(h for h in B.HEADERS if os.path.dirname(h) == "")
+    assert in_csrc == [f for f in files if f.endswith(".h") or f == "exports.map"]
+    missing = [f for f in B.SOURCES + B.HEADERS if not os.path.isfile(os.path.join(B.CSRC, f))]
+    assert not missing, missing
+
+
 def test_fp8_mfmas_stay_in_their_hand_placed_slots(tmp_path):
     """The interleaved K loops place ONE MFMA per slot and deal LDS reads / DMA issues into its shadow; sched_barrier pins
     that order for the machine scheduler, but LLVM's MachineSink pass runs later and — in the fp8 builds only (8-register

@@ -1,5 +1,5 @@
 """fp8 plumbing at kernel level (-m gpu): the conversion every 1-byte image goes through, the amax sites, the weight-image
-launch and the delayed-scaling state machine (csrc/rowops.hip), each against a plain CPU restatement, bit for bit.
+launch and the delayed-scaling state machine (csrc/operand_images.hip), each against a plain CPU restatement, bit for bit.
 
  * plb_launch_quantize over every finite bf16 bit pattern and +-inf, the fp32 midpoints between neighbouring fp8 values
    and their neighbours, the saturation edge and subnormals, in both formats: the device's clamp + v_cvt_pk_{fp8,bf8}_f32

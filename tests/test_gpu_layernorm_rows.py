@@ -8,7 +8,7 @@ max(DELTA0, 4 x the class's worst rstd error in the float32 restatement of form 
 max(2^-20, 4 x restated). Column sums (dgamma, dbeta, column sums of dx as stored): partial rows summed in float64, per
 column within (rows_per_lane + 8) x 2^-24 x sum |term|. No bound is taken from a kernel's output.
 
-Which instantiation a case runs follows from the launchers' conditions (csrc/rowops.hip plb_launch_ln_fwd / _bwd; the
+Which instantiation a case runs follows from the launchers' conditions (csrc/layernorm.hip plb_launch_ln_fwd / _bwd; the
 launch profile has one class per launcher, not per instantiation), and the case ids name it:
   forward   H = 768 / 1024 with ldx % 8 == 0 and ldy % 8 == 0 -> ln_fwd_wide_kernel<96 | 128>; else ln_fwd_kernel<ceil(H / 256)>
   backward  H = 1024 with every ld % 8 == 0, or out8 at 768 / 1024 -> ln_bwd_wide_kernel<128 | 96>; else ln_bwd_kernel<ceil(H / 256)>

@@ -1,5 +1,5 @@
-"""Row kernels of the step at kernel level (-m gpu; csrc/rowops.hip), each launched through the C ABI and compared with a
-float64 restatement of the operation (or bit for bit, where the kernel only moves or rounds values):
+"""Row kernels of the step at kernel level (-m gpu; csrc/embed.hip, reduce.hip, loss_rows.hip, operand_images.hip), each
+launched through the C ABI and compared with a float64 restatement of the operation (or bit for bit, where the kernel only moves or rounds values):
  * the masked-phoneme cross-entropy (ce_prepare -> ce_fwd_bwd -> sum_rows), the loss bench.py times;
  * LayerNorm_E of the embedding sum, forward and backward, the dgamma / dbeta partials and the scatter into the tables;
  * the pooler, as a launch and through an engine;

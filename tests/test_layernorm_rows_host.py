@@ -39,7 +39,7 @@ def forward_f32(x, gamma, beta):
 
 
 def backward_f32(x, mean, rstd, gamma, dy):
-    """The standalone backward in float32 numpy (csrc/rowops.hip ln_bwd_kernel): one lane set walks every row, so each
+    """The standalone backward in float32 numpy (csrc/layernorm.hip ln_bwd_kernel): one lane set walks every row, so each
     column sum is a chain of T additions."""
     v, d, g = x.float().numpy(), dy.float().numpy(), gamma.numpy()
     H = v.shape[1]
