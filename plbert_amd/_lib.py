@@ -126,6 +126,27 @@ class PlbLayerNorm(C.Structure):
     ]
 
 
+class PlbMask(C.Structure):
+    _fields_ = [
+        ("labels", C.c_void_p), ("lengths", C.c_void_p), ("B", C.c_int), ("S", C.c_int),
+        ("seed", C.c_uint64), ("step", C.c_uint32),
+        ("word_pred_prob", C.c_float), ("mask_prob", C.c_float), ("replace_prob", C.c_float),
+        ("mask_id", C.c_int), ("sep_id", C.c_int),
+        ("masked", C.c_void_p), ("counts", C.c_void_p), ("idx_padded", C.c_void_p), ("offsets", C.c_void_p),
+        ("flat", C.c_void_p),
+    ]
+
+
+class PlbApplyMask(C.Structure):
+    _fields_ = [
+        ("ids", C.c_void_p), ("sample_off", C.c_void_p), ("word_off", C.c_void_p), ("word_begin", C.c_void_p),
+        ("word_len", C.c_void_p), ("action", C.c_void_p), ("repl", C.c_void_p), ("word_token", C.c_void_p),
+        ("sep_token", C.c_int64), ("crop_start", C.c_void_p), ("B", C.c_int), ("S", C.c_int), ("mask_id", C.c_int),
+        ("labels", C.c_void_p), ("masked", C.c_void_p), ("tokens", C.c_void_p), ("lengths_out", C.c_void_p),
+        ("counts", C.c_void_p), ("idx_padded", C.c_void_p), ("offsets", C.c_void_p), ("flat", C.c_void_p),
+    ]
+
+
 # csrc/plbert_kernels.h: the fixed grid of the partial-sum launches and the floats one of its workgroups owns
 PLB_NORM_PARTS = 1024
 
@@ -261,8 +282,8 @@ INTERNAL = {
     "plb_launch_token_ce_combine_packed": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "plb_launch_pack_token_targets": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
     "plb_launch_add_scalar": (i32, [vp, vp, vp, vp]),
-    "plb_launch_mask": (i32, [vp, vp]),
-    "plb_launch_apply_mask": (i32, [vp, vp]),
+    "plb_launch_mask": (i32, [P(PlbMask), vp]),
+    "plb_launch_apply_mask": (i32, [P(PlbApplyMask), vp]),
     "plb_launch_adamw": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i32, f64, vp, i32, vp]),
     "plb_launch_grad_accum": (i32, [vp, vp, sz, i32, vp, vp]),
     "plb_launch_grad_sumsq": (i32, [vp, sz, vp, vp]),

@@ -1020,3 +1020,184 @@ def ln_dy(T, W, seed):
     dy[sp, (sp * 53) % W] *= 50.0
     dy[kind == 3] = 0.0
     return dy.to(torch.bfloat16), kind
+
+
+# ---- the AdamW element contract (tests/test_gpu_adamw_elements.py, tests/test_adamw_elements_host.py) ----------------------
+# Every element of p, m and v that plb_launch_adamw / plb_launch_adamw_clipped store is held to one step in float64 from the
+# same fp32 inputs, all scalars in double, within an allowance that counts the roundings of the kernel's operation list
+# (csrc/optim.hip) and the one rounding of each host scalar, u = 2^-24:
+#     tol_m = 4u (|m| + |gj|)      tol_v = 8u v'  (v' = 0: exactly 0)      tol_p = 4u |p| + 20u |upd| + (lr / bc1) / den x tol_m
+# Nothing below calls a kernel or reads a kernel's output to form a bound; everything is numpy on the CPU.
+ADAMW_U = 2.0 ** -24
+ADAMW_B1, ADAMW_B2, ADAMW_EPS = 0.9, 0.999, 1e-8
+ADAMW_TRIPLES = ((7e-5, 0.01, 1.0), (1e-3, 0.01, 0.125), (1e-3, 0.0, 1.0))     # (lr, wd, grad_scale)
+ADAMW_DECAY_TRIPLE = (1e-2, 0.1, 1.0)    # decay before / after the update differ by lr x wd = 1e-3 of the update
+ADAMW_STEPS = (1, 2, 10, 1000, 100000)
+ADAMW_FLOOR = 1e-30                      # no non-zero intermediate of the reference is below it: subnormals are not the subject
+ADAMW_BIG = 2e4                          # the sparse set of large parameters (what a norm over the range is made of)
+
+
+def adamw_state(n, seed=2024, shared_exponent=True):
+    """(p, g, m, v) float32 numpy [n]. p N(0, 0.05), every 53rd exactly 0, every 257th x 2e4; g N(0,1) exp(N(-6,4)), every
+    97th 0; m N(0,1) exp(N(-7,3)), every 31st 0; v exp(N(-14,7)), every 41st 0, every 89th (+5) 1e-30 where g != 0 (sqrt(v)
+    far below eps); every 211th (+7) element has g = m = v = 0: its update is exactly 0.
+    m and v share the draw of their exponent (m = N(0,1) exp(3z - 7), v = exp(7z - 14)): the marginals are the ones above
+    and |m| / sqrt(v) stays within a few tens, as in any state AdamW itself produced; where v is 0 or 1e-30, m is N(0,1) x
+    1e-8, on the scale of eps. Drawn independently (shared_exponent=False), m / sqrt(v) reaches 10^7, the parameter range
+    is made of updates, and a whole-range norm then does see a wrong decay (tests/test_adamw_elements_host.py)."""
+    import numpy as np
+    r = np.random.RandomState(seed)
+    i = np.arange(n)
+    p = r.standard_normal(n) * 0.05
+    g = r.standard_normal(n) * np.exp(r.standard_normal(n) * 4.0 - 6.0)
+    z = r.standard_normal(n)
+    m = r.standard_normal(n) * np.exp(z * 3.0 - 7.0)
+    v = np.exp((z if shared_exponent else r.standard_normal(n)) * 7.0 - 14.0)
+    p[i % 257 == 3] *= ADAMW_BIG
+    p[i % 53 == 0] = 0.0
+    g[i % 97 == 0] = 0.0
+    v[i % 41 == 0] = 0.0
+    p, g, m, v = (a.astype(np.float32) for a in (p, g, m, v))
+    v[(i % 89 == 5) & (g != 0) & (v != 0)] = np.float32(1e-30)
+    edge = v <= np.float32(1e-30)
+    m[edge] = (r.standard_normal(n) * 1e-8).astype(np.float32)[edge]
+    m[i % 31 == 0] = 0.0
+    still = i % 211 == 7
+    g[still], m[still], v[still] = 0.0, 0.0, 0.0
+    return p, g, m, v
+
+
+def bf16_rne_bits(x):
+    """The bf16 bit patterns (uint16) of float32 numpy values rounded to nearest, ties to even (finite values)."""
+    import numpy as np
+    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return ((b + np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+
+
+class AdamwRef:
+    """adamw_fp64's results: the new p, m, v, the intermediates and the three allowances, float64 [n]."""
+    __slots__ = ("p", "m", "v", "gj", "upd", "den", "decay", "tol_p", "tol_m", "tol_v", "p_in")
+
+
+def adamw_fp64(p, g, m, v, lr, wd, gs, step, coef=None, b1=ADAMW_B1, b2=ADAMW_B2, eps=ADAMW_EPS):
+    """One AdamW step in float64 from the fp32 inputs, every scalar in double; coef: the clipped form's (g gs) coef. Asserts
+    that no non-zero intermediate is below ADAMW_FLOOR."""
+    import numpy as np
+    p, g, m, v = (np.asarray(a, dtype=np.float64) for a in (p, g, m, v))
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    o = AdamwRef()
+    o.p_in = p
+    o.gj = g * gs if coef is None else (g * gs) * float(coef)
+    o.m = m + (1.0 - b1) * (o.gj - m)
+    o.v = b2 * v + (1.0 - b2) * o.gj * o.gj
+    o.den = np.sqrt(o.v) / np.sqrt(bc2) + eps
+    o.upd = (lr / bc1) * o.m / o.den
+    o.decay = 1.0 - lr * wd
+    o.p = p * o.decay - o.upd
+    for name, a in (("gj", o.gj), ("gj - m", o.gj - m), ("m'", o.m), ("gj^2", o.gj * o.gj), ("v'", o.v), ("upd", o.upd),
+                    ("p decay", p * o.decay)):
+        nz = np.abs(a[a != 0])
+        assert nz.size == 0 or float(nz.min()) >= ADAMW_FLOOR, f"{name}: a non-zero intermediate of {float(nz.min()):.3e}"
+    u = ADAMW_U
+    o.tol_m = 4 * u * (np.abs(m) + np.abs(o.gj))
+    o.tol_v = 8 * u * o.v
+    o.tol_p = 4 * u * np.abs(p) + 20 * u * np.abs(o.upd) + (lr / bc1) / o.den * o.tol_m
+    return o
+
+
+def adamw_f32_restatement(p, g, m, v, lr, wd, gs, step, coef=None, fused=False, defect=None, b1=ADAMW_B1, b2=ADAMW_B2,
+                          eps=ADAMW_EPS):
+    """adamw_kernel's operation list (csrc/optim.hip) in numpy float32, the scalars formed in double and rounded once as the
+    launcher forms them. fused: g gs - m as ONE operation (the contraction hipcc makes in adamw_kernel). defect: one of the
+    planted faults of tests/test_adamw_elements_host.py ("omb2", "step+1", "no_sqrt_bc2", "eps_inside", "decay_after").
+    Returns (p', m', v') float32."""
+    import numpy as np
+    f = np.float32
+    p, g, m, v = (np.asarray(a, dtype=f) for a in (p, g, m, v))
+    st = step + 1 if defect == "step+1" else step
+    bc1, bc2 = 1.0 - b1 ** st, 1.0 - b2 ** st
+    decay, omb1, b2f, epsf = f(1.0 - lr * wd), f(1.0 - b1), f(b2), f(eps)
+    omb2 = f(1.0) - f(b2) if defect == "omb2" else f(1.0 - b2)
+    stepf, bc2s, gsf = f(lr / bc1), f(np.sqrt(bc2)), f(gs)
+    gj = g * gsf
+    if coef is not None:
+        gj = gj * f(coef)
+    if fused and coef is None:
+        d = (g.astype(np.float64) * np.float64(gsf) - m.astype(np.float64)).astype(f)
+    else:
+        d = gj - m
+    m1 = m + omb1 * d
+    v1 = b2f * v + omb2 * (gj * gj)
+    if defect == "no_sqrt_bc2":
+        den = np.sqrt(v1) + epsf
+    elif defect == "eps_inside":
+        den = (np.sqrt(v1) + epsf) / bc2s
+    else:
+        den = np.sqrt(v1) / bc2s + epsf
+    if defect == "decay_after":
+        p1 = (p - stepf * (m1 / den)) * decay
+    else:
+        p1 = p * decay - stepf * (m1 / den)
+    return p1.astype(f), m1.astype(f), v1.astype(f)
+
+
+def adamw_offender(got_p, got_m, got_v, ref, limit=1.0):
+    """(ratios, offender): ratios = {"p", "m", "v": the worst |got - ref| / allowance}; offender = None, or (array name,
+    index, got, want, allowance) of the FIRST element — m, then v, then p, lowest index — that is not finite, is over
+    limit x its allowance, or is not exactly 0 where v' = 0."""
+    import numpy as np
+    ratios, offender = {}, None
+    for name, got, want, tol in (("m", got_m, ref.m, ref.tol_m), ("v", got_v, ref.v, ref.tol_v), ("p", got_p, ref.p, ref.tol_p)):
+        got = np.asarray(got, dtype=np.float64)
+        assert got.shape == want.shape, (name, got.shape, want.shape)
+        err = np.abs(got - want)
+        exact = tol == 0
+        bad = ~np.isfinite(got) | np.where(exact, err != 0, err > limit * tol)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where(exact, 0.0, err / np.where(exact, 1.0, tol))
+        ratios[name] = float(r.max()) if r.size else 0.0
+        if offender is None and bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            offender = (name, i, float(got[i]), float(want[i]), float(tol[i]))
+    return ratios, offender
+
+
+def check_adamw(what, got_p, got_m, got_v, ref, limit=1.0):
+    """Raises AssertionError naming the first offending element; returns the worst share of each allowance in use. Where
+    g = m = v = 0 the update is exactly 0: m' = v' = 0 and p' = fl(p x fl(decay)), whichever contraction the compiler made."""
+    import numpy as np
+    ratios, off = adamw_offender(got_p, got_m, got_v, ref, limit)
+    if off is not None:
+        name, i, got, want, tol = off
+        raise AssertionError(f"{what}: {name}[{i}] (float4 {i // 4} component {i % 4}, workgroup {i // 1024}): got {got!r}, "
+                             f"want {want!r}: off by {abs(got - want):.3e} > {limit:g} x {tol:.3e}")
+    still = (ref.gj == 0) & (ref.m == 0) & (ref.v == 0)
+    want = (ref.p_in.astype(np.float32) * np.float32(ref.decay)).astype(np.float32)
+    bad = still & (np.asarray(got_p, dtype=np.float32) != want)
+    assert not bad.any(), f"{what}: p[{int(np.flatnonzero(bad)[0])}] has a zero update and is not p x decay"
+    return ratios
+
+
+def check_bf16_copy(what, pb_bits, p_out):
+    """The bf16 copy (uint16 bit patterns) must be the round-to-nearest-even of the fp32 p the SAME launch stored, at every
+    element, bit for bit."""
+    import numpy as np
+    want = bf16_rne_bits(p_out)
+    got = np.asarray(pb_bits).view(np.uint16) if np.asarray(pb_bits).dtype != np.uint16 else np.asarray(pb_bits)
+    bad = got != want
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise AssertionError(f"{what}: bf16 copy [{i}]: got 0x{int(got[i]):04x}, want 0x{int(want[i]):04x} for p = "
+                             f"{float(np.asarray(p_out)[i])!r}; {int(bad.sum())} elements differ")
+
+
+def bf16_tie_values():
+    """float32 values exactly half way between two bf16 numbers, both signs: the even neighbour below (round down), the even
+    neighbour above (round up), at several exponents; and the values one fp32 step either side of each tie."""
+    import numpy as np
+    out = []
+    for hi in (0x3F80, 0x3F81, 0x4000, 0x4049, 0x3DCC, 0x3DCD, 0x2000, 0x7F00, 0x3FFF):
+        for sign in (0, 0x8000):
+            for low in (0x8000, 0x7FFF, 0x8001):
+                out.append(((hi | sign) << 16) | low)
+    return np.array(out, dtype=np.uint32).view(np.float32)

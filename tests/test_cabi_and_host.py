@@ -465,20 +465,7 @@ def test_fp8_mfmas_stay_in_their_hand_placed_slots(tmp_path):
 
 # Launchers of csrc/plbert_kernels.h that no test calls by name, each with the test that reaches it through a public entry
 # point: (test module, a name that module must contain, why the launcher is not called directly).
-LAUNCHERS_REACHED_THROUGH_ENTRY_POINTS = {
-    "plb_launch_adamw": ("test_gpu_adamw_kernel.py", "adamw_step",
-                         "plb_adamw_step is a thin wrapper; pinned there against torch.optim.AdamW"),
-    "plb_launch_mask": ("test_gpu_device_mask.py", "device_mask_batch",
-                        "plb_mask_batch launches it alone; its statistics and CSR output are tested there"),
-    "plb_launch_apply_mask": ("test_gpu_apply_mask.py", "apply_mask",
-                              "plb_apply_mask launches it alone; compared bit for bit with the host masking there"),
-    "plb_launch_step_status": ("test_gpu_handoff_fault.py", "poll_status",
-                               "the end-of-call status word; its effect (NaN loss, skipped update) is what those tests assert"),
-    "plb_launch_status_export": ("test_gpu_comm_fake_rccl.py", "plb_debug_ln_fault",
-                                 "the word the ranks all-reduce: a fault on rank 1 only must stop the update on both ranks"),
-    "plb_launch_add_scalar": ("test_gpu_dual_head.py", "loss_fwd_bwd_dual",
-                              "the dual-head loss is phoneme + token loss; tested as that sum"),
-}
+LAUNCHERS_REACHED_THROUGH_ENTRY_POINTS = {}   # empty: every launcher is called by name in a kernel-level test
 
 
 def test_every_kernel_launcher_is_named_by_a_test():
