@@ -13,7 +13,7 @@ import os
 import torch  # noqa: F401  (must precede the CDLL: see module docstring)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# PLBERT_HIP_LIB: load another build of the same C ABI (kernel timing experiments, tools/build_dbg.sh)
+# PLBERT_HIP_LIB: load another build of the same C ABI (kernel timing experiments, tools/build_variant.py)
 LIB_PATH = os.environ.get("PLBERT_HIP_LIB") or os.path.join(HERE, "libplbert_hip.so")
 
 PLB_PARAM_NAMES = [

@@ -22,9 +22,9 @@
 // two waves of a SIMD half a phase apart) — see the comments at the loops.
 #include "gemm_nt_pipeline.h"
 
-// Timing experiments only (tools/build_dbg.sh): -DNT_DBG=<bit mask> 1 no MFMA, 2 no fragment reads, 4 no DMA
-// after the prologue, 8 no barriers in the K loop (results are garbage with any of those), 16 print the shader
-// clock over the K loop (results stay valid). The shipped library has 0.
+// Timing builds (tools/build_variant.py <name> --only <the pipeline units> -DNT_DBG=<bit mask>): 16 prints the shader
+// clock over the K loop, 32 the phase stamps of one workgroup (tools/nt_stamps.py, tools/nt_stamps_fp8.py). Results stay
+// valid. The shipped library has 0.
 namespace {
 
 template <int V, bool PF>
@@ -42,14 +42,18 @@ int launch_big(const PlbGemmNT* p, int act, int out_f32, hipStream_t stream) {
     hipLaunchKernelGGL((gemm_nt_big_kernel<V, 1, false, PF>), grid, block, 0, stream, *p);
   } else if (act == 2) {
     hipLaunchKernelGGL((gemm_nt_big_kernel<V, 2, false, PF>), grid, block, 0, stream, *p);
-  } else if ((act == 3 || act == 4) && TN == 256) {  // fused GEMM + cross-entropy passes: 256-column tiles only
-    if (!p->ce_tgt || p->ce_cols < 1 || p->ce_cols > p->N) return 1;
-    if (act == 3) {
-      if (!p->ce_pmax || !p->ce_psum || !p->ce_tlogit) return 1;
-      hipLaunchKernelGGL((gemm_nt_big_kernel<V, 3, false, PF>), grid, block, 0, stream, *p);
+  } else if (act == 3 || act == 4) {  // fused GEMM + cross-entropy passes: 256-column tiles only
+    if constexpr (TN == 256) {
+      if (!p->ce_tgt || p->ce_cols < 1 || p->ce_cols > p->N) return 1;
+      if (act == 3) {
+        if (!p->ce_pmax || !p->ce_psum || !p->ce_tlogit) return 1;
+        hipLaunchKernelGGL((gemm_nt_big_kernel<V, 3, false, PF>), grid, block, 0, stream, *p);
+      } else {
+        if (!p->ce_lse || !p->ce_w || !p->C) return 1;
+        hipLaunchKernelGGL((gemm_nt_big_kernel<V, 4, false, PF>), grid, block, 0, stream, *p);
+      }
     } else {
-      if (!p->ce_lse || !p->ce_w || !p->C) return 1;
-      hipLaunchKernelGGL((gemm_nt_big_kernel<V, 4, false, PF>), grid, block, 0, stream, *p);
+      return 1;
     }
   } else {
     return 1;

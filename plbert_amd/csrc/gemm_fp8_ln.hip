@@ -19,16 +19,10 @@ extern "C" int plb_launch_gemm_nt_fp8_ln(const PlbGemmNT* p_in, int mode, int a_
   PlbGemmNT q_ = *p_in;
   q_.ln_fault = plb_ln_fault_take();
   const PlbGemmNT* p = &q_;
-  if (mode != 5 && mode != 6) return 1;
-  if (p->M % 1024 || p->K % 128 || p->M <= 0 || p->N <= 0 || p->K <= 0) return 3;
-  const int tile = p->N % 384 == 0 ? 384 : p->N % 256 == 0 ? 256 : 0;
-  if (!tile || p->N / tile > 4) return 3;
+  if (const int rc = ln_launch_check(p, mode, 128)) return rc;
+  const int tile = p->N % 384 == 0 ? 384 : 256;
+  // fp8 only (every check behind the shape checks returns 1, so their order among themselves does not show)
   if (!p->deq_a || !p->deq_b) return 1;
-  if (!p->ln_gamma || !p->ln_mean || !p->ln_rstd || !p->ln_xchg || !p->ln_err || !p->C) return 1;
-  if (mode == 5 && (!p->ln_beta || !p->C2)) return 1;
-  if (mode == 6 && (!p->aux || !p->colpart)) return 1;
-  if (p->res && (((uintptr_t)p->res & 15) || p->ldr % 8)) return 1;
-  if (mode == 6 && (((uintptr_t)p->aux & 15) || p->ldaux % 8)) return 1;
   if (p->C8 && (!p->q_scale || p->ldc8 % 16 || ((uintptr_t)p->C8 & 15))) return 1;
   dim3 grid((p->M / 128) * (p->N / tile));
   const double mnk = (double)p->M * p->N * p->K;

@@ -1,4 +1,5 @@
-// LayerNorm fused into the epilogue of the GEMM that produces its input (gemm_nt_pipeline.h, ACT 5 / 6): the dense and
+// LayerNorm fused into the epilogue of the GEMM that produces its input (gemm_nt_pipeline.h, ACT 5 / 6; the argument checks
+// its launchers share are ln_launch_check there): the dense and
 // FFN-output projections of the shared layer (forward: AlbertAttention.LayerNorm / full_layer_layer_norm,
 // modeling_albert.py:196-200, 225-238) and the two dX GEMMs whose output is the gradient of a LayerNorm's output
 // (backward). A translation unit of its own so that the plain instantiations keep their register allocation.
@@ -16,16 +17,8 @@ extern "C" int plb_launch_gemm_nt_ln(const PlbGemmNT* p_in, int mode, hipStream_
   PlbGemmNT q_ = *p_in;
   q_.ln_fault = plb_ln_fault_take();
   const PlbGemmNT* p = &q_;
-  if (mode != 5 && mode != 6) return 1;
-  if (p->M % 1024 || p->K % 64 || p->M <= 0 || p->N <= 0 || p->K <= 0) return 3;   // 8 XCDs x whole row blocks
-  const int tile = p->N % 384 == 0 ? 384 : p->N % 256 == 0 ? 256 : 0;
-  if (!tile || p->N / tile > 4) return 3;
-  if (!p->ln_gamma || !p->ln_mean || !p->ln_rstd || !p->ln_xchg || !p->ln_err || !p->C) return 1;
-  if (mode == 5 && (!p->ln_beta || !p->C2)) return 1;
-  if (mode == 6 && (!p->aux || !p->colpart)) return 1;
-  // the epilogue's operand tiles arrive by LDS-DMA, 16 bytes per lane: rows must start on 16-byte boundaries
-  if (p->res && (((uintptr_t)p->res & 15) || p->ldr % 8)) return 1;
-  if (mode == 6 && (((uintptr_t)p->aux & 15) || p->ldaux % 8)) return 1;
+  if (const int rc = ln_launch_check(p, mode, 64)) return rc;
+  const int tile = p->N % 384 == 0 ? 384 : 256;
   dim3 grid((p->M / 128) * (p->N / tile)), block(512);
   const double mnk = (double)p->M * p->N * p->K;
   const double bytes = 2.0 * ((double)p->M * p->K + (double)p->N * p->K) + (double)p->M * p->N * (mode == 5 ? 4 : 4) +

@@ -1,6 +1,8 @@
-// The multi-phase, counted-vmcnt LDS-DMA pipeline kernel of the large NT GEMMs (gfx950), shared by the bf16 build
-// (gemm_big.hip) and the fp8 build (gemm_fp8.hip). See gemm_big.hip for the description of the pipeline.
+// The multi-phase, counted-vmcnt LDS-DMA pipeline kernel of the large NT GEMMs (gfx950), shared by the bf16 builds
+// (gemm_big.hip, gemm_ln.hip) and the fp8 builds (gemm_fp8.hip, gemm_fp8_ln.hip). See gemm_big.hip for the description of
+// the pipeline.
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "plbert_kernels.h"
 #include "gemm_epilogue.h"
@@ -12,26 +14,16 @@
 // output per launch otherwise sweep the weights and the activation panels out of the XCD's 4 MB L2 (PMC: the 2-round gelu
 // launches fetched their weights once per round). Measured per form on one box (profiles/r03_nt_store_ab.txt): gelu forms
 // -0.15 ms/step, gelu + LayerNorm forms -0.29 ms/step; on the plain launches the hint is neutral (the QKV output is what
-// the attention kernel reads next: it lost what the GEMM won). NT_OUT_NT (bit mask, A/B builds): 1 plain launches (act 0),
-// 2 gelu forms (1, 2, 7, 8), 4 LayerNorm forms (5, 6), 8 only the pre-LayerNorm image of form 5.
-#ifndef NT_OUT_NT
-#define NT_OUT_NT 6
-#endif
-// NT_LN_STAGE (A/B builds; default on): the LayerNorm forms bring their epilogue operand tiles (residual; form 6 also the
-// pre-LayerNorm sums) into LDS by LDS-DMA as FULL lines, in the output image's layout, instead of loading them in MFMA
-// layout (where one load instruction is 16 partial lines: 48 such loads cost the texture addresser ~6 us per operand).
-#ifndef NT_LN_STAGE
-#define NT_LN_STAGE 1
-#endif
+// the attention kernel reads next: it lost what the GEMM won). So OUT_NT (in the kernel) is true for the gelu forms
+// (1, 2, 7, 8) and the LayerNorm forms (5, 6); the LayerNorm epilogue, which has no other form, calls the builtin itself.
+// (The chunk travels by value into the builtin and by reference into the plain copy: the other way round hipcc
+// re-associates the image addresses of the loops that call this, +1 to +7 instructions per kernel.)
 typedef unsigned int u32x4nt __attribute__((ext_vector_type(4)));
-#define OUT_STORE(ptr, v)                                                                               \
-  do {                                                                                                  \
-    if constexpr (((NT_OUT_NT & 1) && ACT == 0) || ((NT_OUT_NT & 2) && (ACT == 1 || ACT == 2 || ACT == 7 || ACT == 8)) || \
-                  ((NT_OUT_NT & 4) && (ACT == 5 || ACT == 6)))                                          \
-      __builtin_nontemporal_store(u32x4nt{(v).x, (v).y, (v).z, (v).w}, (u32x4nt*)(ptr));                \
-    else                                                                                                \
-      *(uint4*)(ptr) = (v);                                                                             \
-  } while (0)
+template <bool NT>
+DEVI void out_store(bf16_t* ptr, std::conditional_t<NT, const uint4, const uint4&> v) {
+  if constexpr (NT) __builtin_nontemporal_store(u32x4nt{v.x, v.y, v.z, v.w}, (u32x4nt*)ptr);
+  else *(uint4*)ptr = v;
+}
 
 typedef int i32x4v __attribute__((ext_vector_type(4)));
 typedef int i32x8v __attribute__((ext_vector_type(8)));
@@ -66,7 +58,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 #define BARRIER()                                        \
   do {                                                   \
     __builtin_amdgcn_s_waitcnt(0xC07F);                  \
-    if (!(NT_DBG & 8)) asm volatile("s_barrier" ::: "memory"); \
+    asm volatile("s_barrier" ::: "memory");              \
   } while (0)
 #define PIN() __builtin_amdgcn_sched_barrier(0)
 
@@ -156,7 +148,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
 // issue half-tile number NH*t + c of the stream (c is a literal), if it exists
 #define ISSUE(c)                                                          \
   do {                                                                    \
-    if ((!(NT_DBG & 4) || PRO) && NH * t + (c) < htot) STAGE_I((c) % NH, ring_slot(rb + (c)), t + (c) / NH); \
+    if (NH * t + (c) < htot) STAGE_I((c) % NH, ring_slot(rb + (c)), t + (c) / NH); \
   } while (0)
 
   // ---- fragment reads: row-in-half = wm*64 + mi*16 + frow (A) / wn*32 + ni*16 + frow (B);
@@ -169,17 +161,13 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
   // loop ping-pongs them; the staggered loop uses afr[0] and both B buffers.
   bf16x8 afr[2][4][2], bfr[2][2][2];
   i32x8v afr8[2][4], bfr8[2][2];  // FP8 mode: the same fragments as 8-register tuples (afr / bfr are then unused)
-  if (NT_DBG & 2) {
-    __builtin_memset(afr, 0, sizeof(afr));
-    __builtin_memset(bfr, 0, sizeof(bfr));
-  }
 #define READ_A(ab, slot)                                                             \
   do {                                                                               \
     const bf16_t* s_ = &smem[(slot) * HT + offA];                                    \
     if constexpr (FP8) _Pragma("unroll") for (int mi = 0; mi < 4; ++mi) {            \
       set_half<0>(afr8[ab][mi], *(const i32x4v*)&s_[mi * 16 * 64 + c0]);             \
       set_half<1>(afr8[ab][mi], *(const i32x4v*)&s_[mi * 16 * 64 + c1]);             \
-    } else if (!(NT_DBG & 2)) _Pragma("unroll") for (int mi = 0; mi < 4; ++mi) {     \
+    } else _Pragma("unroll") for (int mi = 0; mi < 4; ++mi) {                        \
       afr[ab][mi][0] = *(const bf16x8*)&s_[mi * 16 * 64 + c0];                       \
       afr[ab][mi][1] = *(const bf16x8*)&s_[mi * 16 * 64 + c1];                       \
     }                                                                                \
@@ -190,7 +178,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     if constexpr (FP8) _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) {            \
       set_half<0>(bfr8[bb][ni], *(const i32x4v*)&s_[ni * 16 * 64 + c0]);             \
       set_half<1>(bfr8[bb][ni], *(const i32x4v*)&s_[ni * 16 * 64 + c1]);             \
-    } else if (!(NT_DBG & 2)) _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) {     \
+    } else _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) {                        \
       bfr[bb][ni][0] = *(const bf16x8*)&s_[ni * 16 * 64 + c0];                       \
       bfr[bb][ni][1] = *(const bf16x8*)&s_[ni * 16 * 64 + c1];                       \
     }                                                                                \
@@ -205,22 +193,6 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
       for (int c = 0; c < NBH; ++c)
 #pragma unroll
         for (int d = 0; d < 2; ++d) acc[a][b][c][d] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (ACT == 6 && !NT_LN_STAGE) {
-    // LayerNorm-backward form WITHOUT operand staging (A/B builds): the residual is the accumulators' START value (its segments arrive under the prologue's
-    // DMA), not an epilogue operand — beside the kept pre segments it would not fit the epilogue's registers
-    if (p.res) {
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int nh = 0; nh < NBH; ++nh)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni) {
-            const uint2 r = *(const uint2*)(p.res + (size_t)(bm * TM + wm * 64 + mi * 16 + frow) * p.ldr + bn * TN + wn * 32 +
-                                            fq * 4 + nh * 128 + ni * 16);
-            acc[0][mi][nh][ni] = f32x4{bf_lo(r.x), bf_hi(r.x), bf_lo(r.y), bf_hi(r.y)};
-          }
-    }
-  }
   // swapped MFMA operands: D[row = n][col = m] -> each lane owns 4 consecutive n of one row m
 #define MFMA_Q(mh, nh, ab, bb)                                                                                 \
   do {                                                                                                         \
@@ -228,7 +200,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
       _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                                         \
         _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                       \
           acc[mh][mi][nh][ni] = mfma_fp8<ABF8>(bfr8[bb][ni], afr8[ab][mi], acc[mh][mi][nh][ni]);               \
-    } else if (!(NT_DBG & 1)) _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                 \
+    } else _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                    \
       _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                                         \
         _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                       \
           acc[mh][mi][nh][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[bb][ni][kk], afr[ab][mi][kk],     \
@@ -241,17 +213,6 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     MFMA_Q(mh, nh, 0, bb);               \
     __builtin_amdgcn_s_setprio(0);       \
     PIN(); BARRIER(); PIN();             \
-  } while (0)
-// prefetching form of a phase: one barrier, then the fragment reads of the NEXT phase are issued ahead
-// of this phase's 16 MFMAs and complete underneath them (retired by the next BARRIER's lgkmcnt(0))
-#define PHASE(reads, mh, nh, ab, bb)     \
-  do {                                   \
-    BARRIER(); PIN();                    \
-    reads;                               \
-    __builtin_amdgcn_s_setprio(1);       \
-    MFMA_Q(mh, nh, ab, bb);              \
-    __builtin_amdgcn_s_setprio(0);       \
-    PIN();                               \
   } while (0)
 // Wait until everything but the newest N DMA instructions has landed (N = 2 x half-tiles allowed in
 // flight); once the stream has run out (an expected issue was skipped) drain completely.
@@ -268,7 +229,6 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
   // the wait that precedes a K-tile, against 3 with a double-buffered 128 KiB layout.
   const int htot = NH * nk;
   int rb = 0;  // (NH * t) % RING
-  bool PRO = true;  // NT_DBG only
   {
     const int t = 0;
     ISSUE(0); ISSUE(1); ISSUE(2); ISSUE(3); ISSUE(4); ISSUE(5); ISSUE(6); ISSUE(7); ISSUE(8);
@@ -282,12 +242,11 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     }
   }
   BARRIER();
-  PRO = false;
 #if NT_DBG & 32
   st_[1] = __builtin_amdgcn_s_memrealtime();
 #endif
   if constexpr (PF) {
-    // ---- interleaved loop (default). Measured on the staggered loop (tools/build_dbg.sh): MFMA, fragment
+    // ---- interleaved loop (default). Measured on the staggered loop: MFMA, fragment
     // reads and DMA cost 0.64 + 0.41 + 0.29 us per K-tile and the K-tile takes their SUM — a wave issues in
     // order, so a burst of 4-12 ds_read_b128 ahead of its MFMAs holds them back until the LDS has
     // accepted every wave's burst. Here a phase is {BARRIER, 16 MFMAs}, and the fragment reads for the
@@ -311,7 +270,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
       if (((j) & 1) == 0)                                                                              \
         acc[mh][((j) >> 2) & 3][nh][((j) >> 1) & 1] = mfma_fp8<ABF8>(                                  \
             bfr8[bb][((j) >> 1) & 1], afr8[ab][((j) >> 2) & 3], acc[mh][((j) >> 2) & 3][nh][((j) >> 1) & 1]); \
-    } else if (!(NT_DBG & 1))                                                                          \
+    } else                                                                                             \
       acc[mh][((j) >> 1) & 3][nh][(j) & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                  \
           bfr[bb][(j) & 1][(j) >> 3], afr[ab][((j) >> 1) & 3][(j) >> 3], acc[mh][((j) >> 1) & 3][nh][(j) & 1], 0, 0, 0); \
     PIN();                                                                                             \
@@ -321,7 +280,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
   do {                                                                                                 \
     if constexpr (FP8)                                                                                 \
       set_half<(i) & 1>(afr8[ab][(i) >> 1], *(const i32x4v*)&smem[(slot) * HT + offA + ((i) >> 1) * 16 * 64 + (((i) & 1) ? c1 : c0)]); \
-    else if (!(NT_DBG & 2))                                                                            \
+    else                                                                                               \
       afr[ab][(i) >> 1][(i) & 1] = *(const bf16x8*)&smem[(slot) * HT + offA + ((i) >> 1) * 16 * 64 + (((i) & 1) ? c1 : c0)]; \
     PIN();                                                                                             \
   } while (0)
@@ -329,7 +288,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
   do {                                                                                                 \
     if constexpr (FP8)                                                                                 \
       set_half<(i) & 1>(bfr8[bb][(i) >> 1], *(const i32x4v*)&smem[(slot) * HT + offB + ((i) >> 1) * 16 * 64 + (((i) & 1) ? c1 : c0)]); \
-    else if (!(NT_DBG & 2))                                                                            \
+    else                                                                                               \
       bfr[bb][(i) >> 1][(i) & 1] = *(const bf16x8*)&smem[(slot) * HT + offB + ((i) >> 1) * 16 * 64 + (((i) & 1) ? c1 : c0)]; \
     PIN();                                                                                             \
   } while (0)
@@ -462,7 +421,6 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
 #undef READ_B
 #undef MFMA_Q
 #undef MFMA_PART
-#undef PHASE
 #undef LANDED
 
 #if NT_DBG & 16
@@ -494,10 +452,9 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
   // half-wave's 8-byte accesses in MFMA layout (ds_write_b64 / ds_read_b64: rows frow, 2 dwords per lane) then cover
   // the 64 banks exactly once. With TN + 16 (8 dwords modulo 64) rows r and r + 8 met in the same banks: SQ_LDS_BANK_CONFLICT
   // 1.6e8 cycles per step over the NT kernels, none in the token-major kernel that has no such image (profiles/r03_sq_counters.csv).
-#ifndef NT_OROW_PAD
-#define NT_OROW_PAD 8
-#endif
-  constexpr int OROW = TN + NT_OROW_PAD;
+  constexpr int OROW_PAD = 8;
+  constexpr int OROW = TN + OROW_PAD;
+  constexpr bool OUT_NT = ACT == 1 || ACT == 2 || ACT == 5 || ACT == 6 || ACT == 7 || ACT == 8;   // see out_store
   static_assert(TM * OROW <= RING * HT, "output image must fit the ring");
   f32x4 csum[NBH][2];  // column sums of this wave's rows (only when p.colpart is set)
   float4 bz[NBH][2];
@@ -582,7 +539,6 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     // per-launch memset, no epoch argument: the launch can be captured in a graph). The wait is bounded: a time-out
     // raises *ln_err instead of hanging the device.
     static_assert(NAH == 1, "LayerNorm epilogues: 128-row tiles");
-    static_assert(!FP8 || NT_LN_STAGE, "the fp8 LayerNorm forms exist in the staged form only");
     if constexpr (FP8) {   // fp8 operands: the per-tensor dequantisation first, everything below is the bf16 form's arithmetic
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi)
@@ -622,7 +578,10 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     // (Also measured, not kept: touching the backward form's pre-LayerNorm tile from inside the K loop — one 4-byte load
     // per 128-byte line, 4 or 8 K-tiles before the end — so that this DMA would find it in L2: the class got slower,
     // 1.583 -> 1.605 / 1.65 ms per step; loads return in order, so the touches sit in front of the K loop's counted waits.)
-    // ---- staged operands (NT_LN_STAGE): one DMA instruction per tile row (TN / 8 active lanes x 16 B = the row's TN
+    // ---- staged operands: the epilogue operand tiles (residual; form 6 also the pre-LayerNorm sums) come into LDS by
+    // LDS-DMA as FULL lines, in the output image's layout, instead of being loaded in MFMA layout (where one load
+    // instruction is 16 partial lines: 48 such loads cost the texture addresser ~6 us per operand).
+    // One DMA instruction per tile row (TN / 8 active lanes x 16 B = the row's TN
     // bf16), wave w taking rows w, w + 8, ...; destination = the row's place in the output image (row stride OROW), so
     // every lane later finds its 8-byte segments where it will write its results: both passes work IN PLACE.
     // R2 (behind the tables): 64 rows, for the residual of form 6 in two halves — rows of mi 0,1 then rows of mi 2,3 —
@@ -639,7 +598,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     // from global memory every group waited out an L2 round trip; the tile's gamma row is fetched once, here, beside the
     // operand tiles' DMA
     float* const gam_lds = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + GAMOFF);
-    if constexpr (ACT == 6 && NT_LN_STAGE) {
+    if constexpr (ACT == 6) {
       if (tid < TN / 4) reinterpret_cast<float4*>(gam_lds)[tid] = *(const float4*)(p.ln_gamma + bn * TN + tid * 4);
     }
     bf16_t* const r2 = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(smem) + R2OFF);
@@ -654,29 +613,18 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
       }
     };
     const uint32_t img_lds = LDS_ADDR(&smem[0]), r2_lds = img_lds + R2OFF;
-    if constexpr (NT_LN_STAGE) {
-      if constexpr (ACT == 5) {
-        if (p.res) { stage_rows(p.res, p.ldr, TM, img_lds, -1); DMA_WAIT(); }
-        __syncthreads();
-      } else {
-        stage_rows(p.aux, p.ldaux, TM, img_lds, -1);
-        if (p.res) stage_rows(p.res, p.ldr, 64, r2_lds, 0);
-        DMA_WAIT();
-        __syncthreads();
-      }
+    if constexpr (ACT == 5) {
+      if (p.res) { stage_rows(p.res, p.ldr, TM, img_lds, -1); DMA_WAIT(); }
+      __syncthreads();
+    } else {
+      stage_rows(p.aux, p.ldaux, TM, img_lds, -1);
+      if (p.res) stage_rows(p.res, p.ldr, 64, r2_lds, 0);
+      DMA_WAIT();
+      __syncthreads();
     }
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
       const int m = bm * TM + wm * 64 + mi * 16 + frow;
-      if constexpr (!NT_LN_STAGE) {
-#pragma unroll
-        for (int nh = 0; nh < NBH; ++nh)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni) {
-            if constexpr (ACT == 5) { if (p.res) rr[mi][nh][ni] = *(const uint2*)(p.res + (size_t)m * p.ldr + ncol0 + nh * 128 + ni * 16); }
-            if constexpr (ACT == 6) ux[mi][nh][ni] = *(const uint2*)(p.aux + (size_t)m * p.ldaux + ncol0 + nh * 128 + ni * 16);
-          }
-      }
       if constexpr (ACT == 6 && !LEAN) { rmean[mi] = p.ln_mean[m]; rrstd[mi] = p.ln_rstd[m]; }
       if constexpr (LEAN) {   // (behind the staging barrier above: tab3 is complete)
         const float2 ms = *(const float2*)&tab3[(wm * 64 + mi * 16 + frow) * 2];
@@ -686,8 +634,8 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
     // form 6, staged: the first pass runs per half of the rows (mi 0,1 | mi 2,3) around the residual's two halves
 #pragma unroll
-    for (int hf = 0; hf < ((ACT == 6 && NT_LN_STAGE) ? 2 : 1); ++hf) {
-    if constexpr (ACT == 6 && NT_LN_STAGE) {
+    for (int hf = 0; hf < (ACT == 6 ? 2 : 1); ++hf) {
+    if constexpr (ACT == 6) {
       if (p.res) {
         if (hf == 1) { DMA_WAIT(); __syncthreads(); }   // second half has landed (issued below, under the first half's sums)
 #pragma unroll
@@ -707,17 +655,15 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     for (int nh = 0; nh < NBH; ++nh)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        if constexpr (ACT == 6 && NT_LN_STAGE) PIN();   // one column group at a time: hoisting every group's LDS reads to the top spilled
-        const float4 gz = (ACT == 6 && NT_LN_STAGE) ? *(const float4*)(gam_lds + (ncol0 - bn * TN) + nh * 128 + ni * 16)
-                                                    : *(const float4*)(p.ln_gamma + ncol0 + nh * 128 + ni * 16);
+        if constexpr (ACT == 6) PIN();   // one column group at a time: hoisting every group's LDS reads to the top spilled
+        const float4 gz = ACT == 6 ? *(const float4*)(gam_lds + (ncol0 - bn * TN) + nh * 128 + ni * 16)
+                                   : *(const float4*)(p.ln_gamma + ncol0 + nh * 128 + ni * 16);
 #pragma unroll
-        for (int mi = ((ACT == 6 && NT_LN_STAGE) ? hf * 2 : 0); mi < ((ACT == 6 && NT_LN_STAGE) ? hf * 2 + 2 : 4); ++mi) {
+        for (int mi = (ACT == 6 ? hf * 2 : 0); mi < (ACT == 6 ? hf * 2 + 2 : 4); ++mi) {
           const int lrow = wm * 64 + mi * 16 + frow;
-          if constexpr (NT_LN_STAGE) {
-            if constexpr (ACT == 6) PIN();
-            const uint2 t = *(const uint2*)&smem[lrow * OROW + nh * 128 + wn * 32 + ni * 16 + fq * 4];
-            if constexpr (ACT == 5) rr[mi][nh][ni] = t; else ux[mi][nh][ni] = t;
-          }
+          if constexpr (ACT == 6) PIN();
+          const uint2 t = *(const uint2*)&smem[lrow * OROW + nh * 128 + wn * 32 + ni * 16 + fq * 4];
+          if constexpr (ACT == 5) rr[mi][nh][ni] = t; else ux[mi][nh][ni] = t;
           f32x4 v = acc[0][mi][nh][ni];
           if constexpr (ACT == 5) { v[0] += bz[nh][ni].x; v[1] += bz[nh][ni].y; v[2] += bz[nh][ni].z; v[3] += bz[nh][ni].w; }
           if constexpr (ACT == 5) {
@@ -786,10 +732,8 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
       for (int c = tid; c < TM * CPR; c += 512) {
         const int r = c / CPR, cc = c - r * CPR;
         const uint4 v = *(const uint4*)&smem[r * OROW + cc * 8];
-        if (r < rows_ok) {
-          if constexpr (NT_OUT_NT & 8) __builtin_nontemporal_store(u32x4nt{v.x, v.y, v.z, v.w}, (u32x4nt*)(cbase + (size_t)r * p.ldc + cc * 8));
-          else OUT_STORE((cbase + (size_t)r * p.ldc + cc * 8), v);
-        }
+        if (r < rows_ok)   // non-temporal like every output of the LayerNorm forms: see out_store
+          __builtin_nontemporal_store(u32x4nt{v.x, v.y, v.z, v.w}, (u32x4nt*)(cbase + (size_t)r * p.ldc + cc * 8));
       }
     }
 #if NT_DBG & 32
@@ -868,10 +812,10 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     for (int nh = 0; nh < NBH; ++nh)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        if constexpr (ACT == 6 && NT_LN_STAGE) PIN();
+        if constexpr (ACT == 6) PIN();
         float4 bt = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 gz = (ACT == 6 && NT_LN_STAGE) ? *(const float4*)(gam_lds + (ncol2 - bn * TN) + nh * 128 + ni * 16)
-                                                    : *(const float4*)(p.ln_gamma + ncol2 + nh * 128 + ni * 16);
+        const float4 gz = ACT == 6 ? *(const float4*)(gam_lds + (ncol2 - bn * TN) + nh * 128 + ni * 16)
+                                   : *(const float4*)(p.ln_gamma + ncol2 + nh * 128 + ni * 16);
         if constexpr (ACT == 5) bt = *(const float4*)(p.ln_beta + ncol2 + nh * 128 + ni * 16);
         f32x4 cs = {0.f, 0.f, 0.f, 0.f}, dg = {0.f, 0.f, 0.f, 0.f}, db = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -889,9 +833,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
                       (x[2] - t0[mi]) * t1[mi] * gz.z + bt.z, (x[3] - t0[mi]) * t1[mi] * gz.w + bt.w};
           } else {
             const float mu = rmean[mi], rs = rrstd[mi];
-            uint2 u;
-            if constexpr (NT_LN_STAGE) u = *(const uint2*)&smem[lrow * OROW + nh * 128 + wn * 32 + ni * 16 + fq * 4];   // still there: dx replaces it below
-            else u = ux[mi][nh][ni];
+            uint2 u = *(const uint2*)&smem[lrow * OROW + nh * 128 + wn * 32 + ni * 16 + fq * 4];   // still there: dx replaces it below
             // opaque copy: otherwise hipcc keeps the first pass's 96 unpacked xhat values alive across the hand-off
             // (common sub-expressions of the two passes) instead of the 48 packed registers, and spills
             asm volatile("" : "+v"(u.x), "+v"(u.y));
@@ -905,7 +847,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
           if (ACT == 6 && bm * TM + lrow < p.Mstore) cs += f32x4{bf_lo(o.x), bf_hi(o.x), bf_lo(o.y), bf_hi(o.y)};
 
         }
-        if constexpr (ACT == 6 && !(NT_DBG & 64)) {   // (NT_DBG 64: timing build without these outputs)
+        if constexpr (ACT == 6) {
           // dgamma | dbeta | column sums of dx over this wave's 64 rows: one partial row per (row tile, wm)
 #pragma unroll
           for (int q3 = 0; q3 < 3; ++q3) {
@@ -938,7 +880,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
         const int r = c / CPR, cc = c - r * CPR;
         const uint4 v = *(const uint4*)&smem[r * OROW + cc * 8];
         if (r < rows_ok) {
-          OUT_STORE((obase + (size_t)r * ldo + cc * 8), v);
+          __builtin_nontemporal_store(u32x4nt{v.x, v.y, v.z, v.w}, (u32x4nt*)(obase + (size_t)r * ldo + cc * 8));
           if constexpr (FP8) {
             if (img8) {
               const float f0 = bf_lo(v.x), f1 = bf_hi(v.x), f2 = bf_lo(v.y), f3 = bf_hi(v.y);
@@ -1128,7 +1070,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
       for (int c = tid; c < TM * CPR; c += 512) {
         const int r = c / CPR, cc = c - r * CPR;
         const uint4 v = *(const uint4*)&smem[r * OROW + cc * 8];
-        if (r < rows_ok) OUT_STORE((cbase + (size_t)r * ldimg + cc * 8), v);
+        if (r < rows_ok) out_store<OUT_NT>(cbase + (size_t)r * ldimg + cc * 8, v);
       }
     }
     if (ACT == 1) {  // gelu forward: C keeps the bf16 pre-activation u, C2 = gelu_new(u)
@@ -1161,7 +1103,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
       for (int c = tid; c < TM * CPR; c += 512) {
         const int r = c / CPR, cc = c - r * CPR;
         const uint4 v = *(const uint4*)&smem[r * OROW + cc * 8];
-        if (r < rows_ok) OUT_STORE((gbase + (size_t)r * p.ldc2 + cc * 8), v);
+        if (r < rows_ok) out_store<OUT_NT>(gbase + (size_t)r * p.ldc2 + cc * 8, v);
       }
     }
     if constexpr (FP8) {
@@ -1217,6 +1159,23 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
     printf("blk %d: start %llu | fill %llu | kloop %llu | image %llu | stores issued %llu | drained %llu (x10 ns)\n", (int)blockIdx.x,
            st_[0] % 1000000ull, st_[1] - st_[0], st_[2] - st_[1], st_[3] - st_[2], st_[4] - st_[3], st_[5] - st_[4]);
 #endif
+}
+
+// Argument checks shared by the launchers of the LayerNorm forms (gemm_ln.hip, gemm_fp8_ln.hip). kmult: the K-tile depth in
+// elements (64 bf16, 128 fp8). 0: launchable; 3: a shape these forms do not take (the caller runs the unfused path);
+// 1: a bad argument.
+inline int ln_launch_check(const PlbGemmNT* p, int mode, int kmult) {
+  if (mode != 5 && mode != 6) return 1;
+  if (p->M % 1024 || p->K % kmult || p->M <= 0 || p->N <= 0 || p->K <= 0) return 3;   // 8 XCDs x whole row blocks
+  const int tile = p->N % 384 == 0 ? 384 : p->N % 256 == 0 ? 256 : 0;
+  if (!tile || p->N / tile > 4) return 3;
+  if (!p->ln_gamma || !p->ln_mean || !p->ln_rstd || !p->ln_xchg || !p->ln_err || !p->C) return 1;
+  if (mode == 5 && (!p->ln_beta || !p->C2)) return 1;
+  if (mode == 6 && (!p->aux || !p->colpart)) return 1;
+  // the epilogue's operand tiles arrive by LDS-DMA, 16 bytes per lane: rows must start on 16-byte boundaries
+  if (p->res && (((uintptr_t)p->res & 15) || p->ldr % 8)) return 1;
+  if (mode == 6 && (((uintptr_t)p->aux & 15) || p->ldaux % 8)) return 1;
+  return 0;
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
-"""Phase stamps of the NT pipeline kernel (build: tools/build_dbg.sh 32; run on the GPU box):
-   PLBERT_HIP_LIB=plbert_amd/build/dbg/libplbert_dbg32.so python tools/nt_stamps.py M,N,K [act]"""
+"""Phase stamps of the NT pipeline kernel (build: python tools/build_variant.py dbg32
+--only gemm_big.hip,gemm_ln.hip,gemm_fp8.hip,gemm_fp8_ln.hip -DNT_DBG=32; run on the GPU box):
+   PLBERT_HIP_LIB=plbert_amd/build/ab/lib_dbg32.so python tools/nt_stamps.py M,N,K [act]"""
 import ctypes as C
 import os
 import sys
