@@ -402,6 +402,51 @@ int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t
                float* hidden, void* stream);
 int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing,
                    const float* d_hidden, void* stream);
+/* ---- masked-phoneme evaluation: accuracy, top-k and fill-mask from a loss call (opt-in: a step that does not ask launches
+ * what it launched before) ----
+ * The reference reports the scalar loss only (train.py:288-336, 395-410). A masked LM's users also expect the accuracy at the
+ * masked positions, the per-sample losses behind the scalar and the model's predictions at chosen positions ("fill-mask").
+ * Every loss call leaves the fp32 logits of exactly its masked rows on the device; plb_masked_report reads them there.
+ * plb_masked_report reports on the LAST plb_loss_* call of this engine — plb_loss_fwd_bwd, plb_loss_fwd_bwd_packed,
+ *   plb_loss_fwd_bwd_dual, plb_loss_fwd_bwd_dual_packed, plb_loss_fwd, plb_loss_fwd_packed: training or loss-only, padded or
+ *   packed, pruned or not, bf16 or fp8, phoneme-only or dual-head, on a training or an inference-only engine. The report is
+ *   available from that call's return until the next plb_loss_* call replaces it (one that fails after its first launch
+ *   leaves none) or plb_bind rebinds the buffers. Every other entry point leaves it available and unchanged — plb_adamw_step[_clipped],
+ *   plb_grad_accum_add, plb_grad_norm, plb_allreduce_grads, plb_status*, plb_sync_weights, plb_set_fp8, plb_forward*,
+ *   plb_encode, plb_encode_bwd — so a training loop may ask after its optimizer step.
+ *   idx_offsets (device, int32 [B+1]) and B as given to that loss call; rows are in the CSR order of its index lists.
+ *   Every pointer of PlbMaskedReport is optional (NULL = not wanted) and names DEVICE memory of the caller:
+ *     with the classes of a row ordered by (logit descending, class index ascending — among equal logits the LOWEST index
+ *     wins): pred = the first class; rank = the 0-based position of the label in that order (pred == label iff rank == 0, the
+ *     label is in the top-k list iff rank < topk); topk_ids / topk_logprob = the first topk classes and their log-softmax
+ *     (fp32), 0 <= topk <= 8, entries past num_phonemes: id -1, -inf; nll = -log_softmax at the label, the very value the
+ *     loss call summed; logits = the rows' logits [n_masked][num_phonemes]. A row with a NaN logit: pred -1, rank
+ *     num_phonemes, nll NaN, ids -1, logprobs NaN — never counted correct.
+ *     sample_loss [B] = mean nll of the sample's rows (0 without rows): the mean of these over the samples that have rows IS
+ *     the phoneme loss the call returned, up to fp32 summation order. sample_top1 / sample_topk [B] = the sample's rows with
+ *     rank == 0 / rank < topk. totals [4] = {rows, top-1 correct, top-k correct, samples that have rows}.
+ *     token_totals [2] (after a dual-head call only) = {valid positions, positions whose target logit EQUALS the row maximum
+ *     of the token head}: top-1 only, and TIE-INCLUSIVE (a target that ties for the maximum counts), because the fused token
+ *     head keeps per-tile maxima but no arg-max index. Predicted token ids are not available.
+ *   Fails before anything is launched, with a text: no loss call has run; B differs from that call's; token_totals after a
+ *   phoneme-only call; topk outside [0, 8]; a sample output or totals wanted with idx_offsets == NULL.
+ *   A call with n_masked == 0 reports zeros (sample outputs, totals) and writes no row output.
+ *   The call writes the caller's buffers and scratch regions of its own inside the workspace that no other entry point
+ *   touches: it changes no engine state, does not drop a live plb_encode stash, leaves the health word alone, and the next
+ *   call computes what it would have computed without it. Nothing is read back; bitwise reproducible (no atomics).
+ *   HEALTH WORD: after a hand-off time-out (plb_status) the logits are whatever the poisoned call left; the report does not
+ *   look at the word, which stays the authority — read the report wherever the loss is read, behind the same check.
+ *   DATA-PARALLEL RUNS: counts are per rank; a host that wants global accuracy sums totals over the ranks itself. */
+typedef struct {
+  int32_t* pred; int32_t* rank; float* nll;                         /* [n_masked], CSR order of the call's index lists */
+  int32_t* topk_ids; float* topk_logprob;                           /* [n_masked][topk] */
+  float* logits;                                                    /* [n_masked][num_phonemes] */
+  float* sample_loss; int32_t* sample_top1; int32_t* sample_topk;   /* [B] */
+  int32_t* totals;                                                  /* [4] */
+  int32_t* token_totals;                                            /* [2]; dual-head calls only */
+} PlbMaskedReport;
+int plb_masked_report(PlbEngine* e, const int32_t* idx_offsets, int32_t B, int32_t topk, const PlbMaskedReport* out,
+                      void* stream);
 /* What the last training step exchanged: the number of collectives it issued (10 pieces for the reference's phoneme-only
  * step with overlap on, 1 with overlap off; one more after a dual-head step) and the floats they covered. The reference
  * has no counterpart (DDP's bucket count is internal to torch, train.py:218-221); a caller logs it to see which form of

@@ -115,6 +115,15 @@ class PlbPacking(C.Structure):
     _fields_ = [("row_start", C.c_void_p), ("rows", C.c_int32), ("used", C.c_int32)]
 
 
+class PlbMaskedReport(C.Structure):
+    """include/plbert.h: what plb_masked_report writes (every pointer optional, device memory of the caller)."""
+    _fields_ = [
+        ("pred", C.c_void_p), ("rank", C.c_void_p), ("nll", C.c_void_p), ("topk_ids", C.c_void_p), ("topk_logprob", C.c_void_p),
+        ("logits", C.c_void_p), ("sample_loss", C.c_void_p), ("sample_top1", C.c_void_p), ("sample_topk", C.c_void_p),
+        ("totals", C.c_void_p), ("token_totals", C.c_void_p),
+    ]
+
+
 class PlbLayerNorm(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("ldx", C.c_int), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float),
@@ -212,6 +221,7 @@ PUBLIC = {
     "plb_set_packed_fp8": (i32, [vp, i32]),
     "plb_encode": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp]),
     "plb_encode_bwd": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp]),
+    "plb_masked_report": (i32, [vp, vp, i32, i32, P(PlbMaskedReport), vp]),
     "plb_comm_pieces": (i32, [vp, P(i32), P(i64)]),
     "plb_broadcast_params": (i32, [vp, i32, vp]),
     "plb_set_grad_overlap": (i32, [vp, i32]),
@@ -282,6 +292,9 @@ INTERNAL = {
     "plb_launch_token_ce_combine_packed": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "plb_launch_pack_token_targets": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
     "plb_launch_add_scalar": (i32, [vp, vp, vp, vp]),
+    "plb_launch_masked_report_rows": (i32, [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "plb_launch_masked_report_samples": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "plb_launch_token_top1": (i32, [vp, i32, vp, vp, i32, vp, vp, vp]),
     "plb_launch_mask": (i32, [P(PlbMask), vp]),
     "plb_launch_apply_mask": (i32, [P(PlbApplyMask), vp]),
     "plb_launch_adamw": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i32, f64, vp, i32, vp]),

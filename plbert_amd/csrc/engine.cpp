@@ -12,7 +12,8 @@
 // This unit: the parameter layout, the workspace carve (plb_create / plb_bind), the weight copies (plb_sync_weights,
 // plb_adamw_step) and the entry points that are one launch. Only writer of PlbEngine's layout and capacity block, the
 // workspace offsets, the bound buffers, the side stream and its events, tok_pad_zeroed and (with plb_status) tok_steps.
-// The other units: engine_prof.cpp, engine_comm.cpp, engine_fp8.cpp, engine_layers.cpp, engine_calls.cpp, engine_optim.cpp.
+// The other units: engine_prof.cpp, engine_comm.cpp, engine_fp8.cpp, engine_layers.cpp, engine_calls.cpp, engine_eval.cpp,
+// engine_optim.cpp.
 #include <stdarg.h>
 
 #include <new>
@@ -151,6 +152,9 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
   e->o_logm = cv.take(NM * 256 * 4);
   e->o_dlog = cv.take(NM * 256 * 2);
   e->o_rows = cv.take(NM * 4); e->o_tgt = cv.take(NM * 4); e->o_w = cv.take(NM * 4); e->o_lrows = cv.take(NM * 4);
+  // (plb_masked_report reads o_logm and o_tgt — and o_tpmax, o_ttl, o_tw below — as the last loss call left them: nothing but
+  // the heads of a loss call writes those regions: phoneme_head, token_head and the ce_prepare launch of loss_impl in
+  // engine_calls.cpp.)
   if (tr) {
     e->o_dhm = cv.take(NM * H * 2);
     // reductions
@@ -223,6 +227,10 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
   e->f8n = 8 * (int)L + 8;
   e->o_f8amax = cv.take((int64_t)e->f8n * 64 * 16 * 4); e->o_f8scale = cv.take(e->f8n * 4); e->o_f8deq = cv.take(e->f8n * 4);
   e->o_f8stats = cv.take(8 * 8 * 4);   // per operand site: maxima history, clamped-call count, worst overshoot (operand_images.hip: fp8_scales_kernel)
+  // What plb_masked_report itself writes: regions of its own, carved last (every other region keeps its offset) — the ranks
+  // and row losses of a report whose caller takes none, plb_launch_token_top1's per-block counts.
+  e->o_rep_rank = cv.take(NM * 4); e->o_rep_nll = cv.take(NM * 4);
+  if (e->NT) e->o_rep_tok = cv.take((Tp / 4) * 2 * 4);
   e->ws_bytes = cv.off;
   *out = e;
   return 0;
@@ -262,6 +270,7 @@ extern "C" int plb_bind(PlbEngine* e, float* params, float* grads, float* exp_av
   if ((uintptr_t)workspace & 255) return fail("plb_bind: workspace must be 256-byte aligned");
   e->params = params; e->grads = grads; e->m = exp_avg; e->v = exp_avg_sq;
   e->ws = (char*)workspace;
+  e->rep_valid = false;   // (plb_masked_report: what a loss call left lies in the workspace bound before)
   if (!e->host_err) {  // once, outside any launch sequence
     void* h = nullptr;
     if (hipHostMalloc(&h, 64, hipHostMallocMapped) == hipSuccess && h) {

@@ -1,7 +1,8 @@
 // Call-level stages of the engine: row selection of a padded or token-packed call, the heads, the stages of a loss call and
 // the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd. Only
 // writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
-// last_exec_rows, tok_grads_live and head_grads_live (which a LAST add of engine_optim.cpp replaces by its window's union).
+// last_exec_rows, tok_grads_live and head_grads_live (which a LAST add of engine_optim.cpp replaces by its window's union),
+// and of what plb_masked_report reads (rep_*: engine_eval.cpp; plb_bind clears rep_valid).
 // (packed_dual, packed_fp8: plb_set_packed_dual / _fp8, engine.cpp.)
 #include "engine_internal.h"
 
@@ -419,8 +420,15 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   Rows rw;
   if (pick_rows(e, pk, lengths, token_targets != nullptr && !e->packed_dual, B, S, who, &rw)) return 1;
   const int64_t Tp = rw.Tp;
+  // from here on the call launches: what plb_masked_report reads is this call's, once it has gone through
+  e->rep_valid = false;
+  e->rep_n = n_masked; e->rep_B = B; e->rep_dual = token_targets != nullptr; e->rep_tok_rows = token_targets ? Tp : 0;
   if (backward && begin_training_call(e, token_targets != nullptr, s)) return 1;
-  if (n_masked == 0 && !token_targets) return zero_loss_call(e, backward, loss, s);
+  if (n_masked == 0 && !token_targets) {
+    if (zero_loss_call(e, backward, loss, s)) return 1;
+    e->rep_valid = true;
+    return 0;
+  }
 
   // the row list first: a phoneme-only call runs the post-attention part of its LAST application on these rows alone
   // (last_application_fwd_pruned) when that is less than half of the batch; dual-head calls run every row
@@ -452,6 +460,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
     // and travels with the next training call's exchange.)
     e->last_loss = loss;
     TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), loss, e->host_err_dev, nullptr, s));
+    e->rep_valid = true;
     return 0;
   }
 
@@ -470,7 +479,9 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   }
   // Last launch of the step: a hand-off of the fused LayerNorm launches that timed out — on ANY rank — turns the loss into
   // NaN and shows in plb_poll_status; plb_adamw_step skips on the same word. No host round trip anywhere.
-  return status_finish(e, loss, s);
+  if (status_finish(e, loss, s)) return 1;
+  e->rep_valid = true;
+  return 0;
 }
 
 extern "C" int plb_loss_fwd_bwd(PlbEngine* e, const int64_t* masked_ids, const int64_t* labels, const int32_t* lengths,

@@ -107,6 +107,9 @@ struct PlbEngine {
   int64_t o_hm, o_logm, o_dlog, o_dhm, o_rows, o_tgt, o_w, o_lrows;
   int64_t o_slab, o_part1, o_part2, o_parte, o_scratch, o_dxe, o_ducol, o_slab2, o_scratch2, o_qkvcol = 0;
   int64_t o_lnx = 0, o_lnerr = 0;
+  // plb_masked_report's own regions (engine_eval.cpp): ranks and row losses when the caller takes none, the token head's
+  // per-block counts. No other entry point reads or writes them.
+  int64_t o_rep_rank = 0, o_rep_nll = 0, o_rep_tok = 0;
   // token (grapheme) head training: padded copies and the [Tp][NTp] logit / gradient images (NT > 0 only)
   int64_t o_bt = 0, o_wtT = 0, o_tdl = 0, o_tlrows = 0, o_tscr = 0, o_tgrad = 0, o_tloss = 0;
   int64_t o_tpmax = 0, o_tpsum = 0, o_ttl = 0, o_tlse = 0, o_tw = 0, o_ttgt = 0, o_tcolp = 0;
@@ -135,6 +138,12 @@ struct PlbEngine {
   bool head_grads_live = true;  // ... phoneme-head gradients (false after plb_encode_bwd: AdamW then stops at PLB_HEAD_W)
   bool tok_pad_zeroed = false;  // pad columns of the transposed copy are zeroed once
   int tok_steps = 0;            // AdamW steps the token head has taken (its own bias correction)
+  // ---- what the last loss call left for plb_masked_report (engine_eval.cpp): set by loss_impl in engine_calls.cpp, cleared by
+  // plb_bind. o_logm / o_tgt hold the rep_n masked rows' logits and labels; after a dual-head call o_tpmax / o_ttl / o_tw hold
+  // the token head's statistics of rep_tok_rows rows.
+  bool rep_valid = false, rep_dual = false;
+  int rep_n = 0, rep_B = 0;
+  int64_t rep_tok_rows = 0;
   // ---- gradient accumulation window and norm partials: engine_optim.cpp (grads_fresh is set, and norm_nparts cleared, by
   // begin_training_call in engine_calls.cpp; the calls that move the weights end a window through end_accum_window) ----
   float* accum = nullptr;       // plb_grad_accum_bind: the caller's buffer, `total` floats like grads

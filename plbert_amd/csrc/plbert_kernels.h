@@ -283,6 +283,35 @@ int plb_launch_pack_token_targets(const int64_t* token_ids, const int32_t* lengt
                                   int rows, int64_t* out, hipStream_t stream);
 int plb_launch_add_scalar(float* out, const float* a, const float* b, hipStream_t stream);
 
+// ---- evaluation rows (eval_rows.hip): what a report on a loss call's masked rows is made of. No atomics, fixed-order sums.
+// Per row j < n of logits [n][ldl] (fp32; one wave per row, V <= 256, V % 4 == 0 — ce_kernel's layout; columns >= V are never
+// read), with the classes ordered by (logit descending, class index ascending — among equal logits the lowest index wins):
+//   pred[j] = the first class; rank[j] = the 0-based position of tgt[j] = #{c : z_c > z_t} + #{c < t : z_c == z_t}, so
+//   pred == tgt iff rank == 0 and tgt is in the top-k list iff rank < topk; topk_ids[j][0..topk) = the first topk classes and
+//   topk_logprob = z - lse (fp32), entries past V (topk > V): id -1, logprob -inf; nll[j] = lse - z_t by ce_kernel's own
+//   expression (w[j] * nll[j] is plb_launch_ce_fwd_bwd's loss_rows[j] bit for bit); logits_out[j][0..V) = a copy of the row
+//   ([n][V], dense). A row with a NaN logit: pred -1, rank V, nll NaN, ids -1, logprobs NaN. Every output pointer may be
+//   NULL. topk in [0, 8]. Returns 1, launching nothing, for any other V or topk.
+int plb_launch_masked_report_rows(const float* logits, int ldl, int V, const int32_t* tgt, int n, int topk, int32_t* pred,
+                                  int32_t* rank, float* nll, int32_t* topk_ids, float* topk_logprob, float* logits_out,
+                                  hipStream_t stream);
+// Per sample b < B (<= 1024) of the CSR offsets [B+1]: sample_loss[b] = mean of nll over its rows (per-thread chains 256 rows
+// apart, wave butterfly, the four waves in order; 0 for a sample without rows), sample_top1 / sample_topk [b] = its rows with
+// rank == 0 / rank < topk; totals int32 [4] = {rows, rows with rank == 0, rows with rank < topk, samples that have rows}.
+// topk here is only the counting threshold: a caller hands over min(topk, V), so that the rank V of a NaN row never counts.
+// Outputs may be NULL; at most two launches (one when only the totals, or only sample outputs, are wanted).
+int plb_launch_masked_report_samples(const int32_t* offsets, int B, const int32_t* rank, const float* nll, int topk,
+                                     float* sample_loss, int32_t* sample_top1, int32_t* sample_topk, int32_t* totals,
+                                     hipStream_t stream);
+// Top-1 count of the fused token head from what its first GEMM pass keeps (PlbGemmNT.ce_pmax [rows][ntiles], ce_tlogit
+// [rows]) and the row weights of plb_launch_token_ce_combine: totals2[0] = rows with w != 0 (the valid positions),
+// totals2[1] = those whose target logit EQUALS the maximum of the row's ntiles per-tile maxima. The rule is TIE-INCLUSIVE —
+// a target that ties for the maximum counts — unlike the phoneme rule above (lowest index wins): the fused head keeps no
+// arg-max index, only values, and the equality is exact because ce_tlogit is stored from the very fp32 value that enters
+// the tile maximum. scratch: int32 [2 * ceil(rows / 4)]. Two launches.
+int plb_launch_token_top1(const float* pmax, int ntiles, const float* tlogit, const float* w, int rows, int32_t* scratch,
+                          int32_t* totals2, hipStream_t stream);
+
 // Device-side word masking (mask.hip): labels [B,S] -> masked [B,S], counts [B], idx_padded [B,S],
 // then offsets [B+1] and flat (CSR of the modified positions).
 typedef struct {

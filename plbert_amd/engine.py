@@ -571,7 +571,52 @@ class HipEngine:
                 _lib.check(self.L.plb_loss_fwd_bwd(self.handle, masked_ids.data_ptr(), labels.data_ptr(), p(lens),
                                                    offs.data_ptr(), flat_p, int(n_masked), B, S, self._loss.data_ptr(),
                                                    self._stream()), "plb_loss_fwd_bwd")
+        self._last_loss_call = (int(B), int(n_masked), tok is not None)
         return self._loss
+
+    # ---- masked-phoneme evaluation (include/plbert.h: plb_masked_report) ---------------------------------
+    # output name -> (dtype, shape as a function of (n_masked, B, topk, num_phonemes))
+    REPORT_OUTPUTS = {
+        "pred": (torch.int32, lambda n, B, k, V: (n,)), "rank": (torch.int32, lambda n, B, k, V: (n,)),
+        "nll": (torch.float32, lambda n, B, k, V: (n,)),
+        "topk_ids": (torch.int32, lambda n, B, k, V: (n, k)), "topk_logprob": (torch.float32, lambda n, B, k, V: (n, k)),
+        "logits": (torch.float32, lambda n, B, k, V: (n, V)),
+        "sample_loss": (torch.float32, lambda n, B, k, V: (B,)), "sample_top1": (torch.int32, lambda n, B, k, V: (B,)),
+        "sample_topk": (torch.int32, lambda n, B, k, V: (B,)),
+        "totals": (torch.int32, lambda n, B, k, V: (4,)), "token_totals": (torch.int32, lambda n, B, k, V: (2,)),
+    }
+
+    def masked_report(self, offsets, topk=5, want=("totals",), out=None):
+        """Accuracy, top-k and losses of the LAST ``loss_fwd`` / ``loss_fwd_bwd`` call of this engine, from the logits that
+        call left on the device (plb_masked_report). ``offsets``: the call's CSR offsets; ``want``: names of
+        ``REPORT_OUTPUTS`` — per masked row (CSR order) pred / rank / nll / topk_ids / topk_logprob / logits, per sample
+        sample_loss / sample_top1 / sample_topk, totals = [rows, top-1 correct, top-k correct, samples with rows] and, after a
+        dual-head call, token_totals = [valid positions, positions whose target ties the token head's maximum]. Returns
+        {name: device tensor}; only what is asked for is allocated (``out``: {name: tensor} to write into instead), nothing
+        is read back. Available until the next loss call, an optimizer step in between included."""
+        last = getattr(self, "_last_loss_call", None)
+        if last is None:
+            raise RuntimeError("masked_report: no loss call has run on this engine")
+        B, n, _ = last
+        unknown = [w for w in want if w not in self.REPORT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"masked_report: unknown output(s) {unknown}; the outputs are {sorted(self.REPORT_OUTPUTS)}")
+        offs = self._dev_i32(offsets)
+        res, rep = {}, _lib.PlbMaskedReport()
+        with torch.cuda.device(self.device):
+            for name in want:
+                dtype, shape = self.REPORT_OUTPUTS[name]
+                shp = shape(n, B, int(topk), self.num_phonemes)
+                t = out.get(name) if out else None
+                if t is None:
+                    t = torch.empty(shp, dtype=dtype, device=self.device)
+                elif t.dtype != dtype or tuple(t.shape) != shp or t.device != self.device or not t.is_contiguous():
+                    raise ValueError(f"masked_report: out[{name!r}] must be a contiguous {dtype} tensor of shape {shp} on {self.device}")
+                res[name] = t
+                setattr(rep, name, t.data_ptr() if t.numel() else None)
+            _lib.check(self.L.plb_masked_report(self.handle, None if offs is None else offs.data_ptr(), B, int(topk),
+                                                C.byref(rep), self._stream()), "plb_masked_report")
+        return res
 
     @property
     def loss_parts(self):

@@ -233,6 +233,38 @@ class _HeadModel(nn.Module):
     def engine(self):
         return self._engine
 
+    def fill_mask(self, phonemes, positions, attention_mask=None, topk=5):
+        """The model's predictions at chosen positions: ``phonemes`` int64 [B,S] (the input as the model is to see it,
+        mask tokens included), ``positions`` one list of positions per sample (inside the sample's valid length, no
+        position twice). Returns ``(ids int64 [n, topk], probs fp32 [n, topk])`` on the device, n = all listed positions in
+        the order given, classes by descending probability (among equal logits the lowest id first). One loss-only call
+        whose labels are the ids themselves (plb_loss_fwd: works in eval mode and on an inference-only engine) followed by
+        the report on the rows it left (plb_masked_report); no [B,S,num_phonemes] logits are materialised."""
+        import numpy as np
+        from .data import masked_indices_to_csr
+        eng = self._engine
+        ids = eng._dev_i64(phonemes)
+        B, S = ids.shape
+        if len(positions) != B:
+            raise ValueError(f"fill_mask: {len(positions)} position lists for {B} samples")
+        lengths = _lengths_from_mask(attention_mask)
+        lens = [S] * B if lengths is None else lengths.cpu().tolist()
+        for b, (idx, ln) in enumerate(zip(positions, lens)):
+            a = np.asarray(idx, dtype=np.int64).reshape(-1)
+            if a.size and (a.min() < 0 or a.max() >= ln):
+                raise ValueError(f"fill_mask: sample {b}: position outside [0, {ln})")
+            if len(np.unique(a)) != a.size:
+                raise ValueError(f"fill_mask: sample {b}: duplicate position")
+        off, flat = masked_indices_to_csr([np.asarray(idx, dtype=np.int64).reshape(-1) for idx in positions])
+        n = int(off[-1])
+        if n == 0:
+            return (torch.empty((0, topk), dtype=torch.int64, device=eng.device),
+                    torch.empty((0, topk), dtype=torch.float32, device=eng.device))
+        offs = torch.from_numpy(off).to(eng.device)
+        eng.loss_fwd(ids, ids, lengths, offs, torch.from_numpy(flat).to(eng.device), n)
+        rep = eng.masked_report(offs, topk=topk, want=("topk_ids", "topk_logprob"))
+        return rep["topk_ids"].to(torch.int64), rep["topk_logprob"].exp()
+
 
 class PhonemeOnlyModel(_HeadModel):
     """model.py:19-30 — ``forward(phonemes, attention_mask=None) -> phoneme_pred`` (fp32 [B,S,num_phonemes])."""

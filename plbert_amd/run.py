@@ -151,7 +151,8 @@ def initialize_model(config, log_dir, resuming, device=None, max_batch=None):
                             max_seq=int(config["dataset_params"]["max_seq_length"]), lr=float(tp["learning_rate"]),
                             device=device, packed_dual=tp.get("packed_dual"),      # (None: PLBERT_PACKED_DUAL)
                             packed_fp8=tp.get("packed_fp8"),                       # (None: PLBERT_PACKED_FP8)
-                            max_grad_norm=tp.get("max_grad_norm"))                 # (not in the reference's config.yml; absent: off)
+                            max_grad_norm=tp.get("max_grad_norm"),                 # (not in the reference's config.yml; absent: off)
+                            track_accuracy=bool(tp.get("eval_accuracy", False)))   # (likewise)
     if config["model_params"].get("pretrained_model"):
         print(f"Loading pretrained model from: {config['model_params']['pretrained_model']}")
         load_checkpoint(trainer, config["model_params"]["pretrained_model"])
@@ -253,6 +254,54 @@ def validate(trainer, val_loader, device_masking=False, word_separator=None):
     return total / max(n, 1)
 
 
+def validate_metrics(trainer, val_loader, device_masking=False, word_separator=None, topk=5):
+    """``validate`` plus the accuracy at the masked positions: {'val_phoneme_loss': the mean of the per-batch losses, exactly
+    what ``validate`` returns, 'val_phoneme_acc', 'val_phoneme_top<topk>': MICRO-averages over the pass — correct rows
+    summed over the batches, over masked rows summed over the batches (0.0 for a pass without masked rows)}. The counts of
+    every batch (plb_masked_report, totals only) are added up on the device and read back once, behind the last batch."""
+    total, n, counts = 0.0, 0, None
+    for b in _batches(val_loader, trainer, device_masking, word_separator):
+        total += _checked(trainer, lambda: trainer.loss_only(b))
+        t = trainer.engine.masked_report(b.offsets, topk=topk, want=("totals",))["totals"]
+        counts = t.to(torch.int64) if counts is None else counts.add_(t)
+        n += 1
+    rows, top1, topk_n = (int(v) for v in counts[:3].tolist()) if counts is not None else (0, 0, 0)
+    return {"val_phoneme_loss": total / max(n, 1), "val_phoneme_acc": top1 / rows if rows else 0.0,
+            f"val_phoneme_top{topk}": topk_n / rows if rows else 0.0}
+
+
+class _AccReader:
+    """The masked-row counts of a step (``trainer.last_accuracy``, overwritten by the next step), read back the way
+    ``_LossReader`` reads the loss: copied into one of two pinned host buffers on the step's stream, waited for by event."""
+
+    def __init__(self, trainer):
+        import torch
+        self.torch, self.trainer = torch, trainer
+        self.host = [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(2)]
+        self.events = [torch.cuda.Event() for _ in range(2)]
+        self.n = 0
+
+    @staticmethod
+    def ratio(counts):
+        rows, top1 = int(counts[0]), int(counts[1])
+        return top1 / rows if rows else 0.0
+
+    def post(self):
+        k = self.n & 1
+        self.n += 1
+        self.host[k].copy_(self.trainer.last_accuracy, non_blocking=True)
+        self.events[k].record(self.torch.cuda.current_stream(self.trainer.engine.device))
+        return k
+
+    def read(self, k):
+        self.events[k].synchronize()
+        return self.ratio(self.host[k])
+
+    def now(self):
+        """Behind a loss that has just been read back with ``.item()``: the stream is idle, the counts are this step's."""
+        return self.ratio(self.trainer.last_accuracy.tolist())
+
+
 class _LossReader:
     """Read a step's loss back WITHOUT stalling the step behind it: ``post`` copies the engine's one-element loss buffer
     (overwritten by the next step) into one of two pinned host words on the step's stream and records an event;
@@ -307,7 +356,8 @@ class _NormReader:
 
 
 def train_loop(trainer, train_loader, val_loader, current_step, num_steps, save_interval, log_interval, log, log_dir,
-               device_masking=False, word_separator=None, max_epochs=MAX_EPOCHS, deferred_readback=True, reader=None):
+               device_masking=False, word_separator=None, max_epochs=MAX_EPOCHS, deferred_readback=True, reader=None,
+               eval_accuracy=False, acc_reader=None):
     """train.py:338-379: validation first, then epochs until ``num_steps``; checkpoint + validation every
     ``save_interval`` steps; every rank logs its LOCAL loss (the reference's rank 0 does).
 
@@ -316,12 +366,26 @@ def train_loop(trainer, train_loader, val_loader, current_step, num_steps, save_
     that end an interval (checkpoint + validation next) or the run are read back at once, so those happen on exactly the
     weights the reference has there. A step the engine declared invalid (HandoffTimeout; never observed) is found when its
     loss is read — exactly, and at the same step on every rank — and it and the step enqueued behind it (which the device
-    left out too: the word is sticky) are run again in order."""
+    left out too: the word is sticky) are run again in order.
+
+    ``eval_accuracy`` (training_params.eval_accuracy; needs a trainer with ``track_accuracy``): every validation record also
+    carries val_phoneme_acc / val_phoneme_top5 (``validate_metrics``) and every training record phoneme_acc, the step's top-1
+    accuracy at its masked positions, read back beside the loss (``_AccReader``: no new stall). Off: every record is what it
+    was."""
     from .engine import HandoffTimeout
     main = world_info()[0] == 0
     window = deque(maxlen=log_interval)
     epoch = 0
-    log(val_phoneme_loss=validate(trainer, val_loader, device_masking, word_separator), step=current_step, epoch=epoch)
+    if eval_accuracy and not getattr(trainer, "track_accuracy", False):
+        raise ValueError("eval_accuracy needs a trainer built with track_accuracy=True")
+
+    def log_validation():
+        if eval_accuracy:
+            log(**validate_metrics(trainer, val_loader, device_masking, word_separator), step=current_step, epoch=epoch)
+        else:
+            log(val_phoneme_loss=validate(trainer, val_loader, device_masking, word_separator), step=current_step, epoch=epoch)
+
+    log_validation()
     train_feeder = _feeder(_source(train_loader, trainer), trainer, word_separator, 0)
 
     def grant():
@@ -338,24 +402,29 @@ def train_loop(trainer, train_loader, val_loader, current_step, num_steps, save_
     # training_params.max_grad_norm: the norm is logged wherever the loss is read back (a step that did not update, the
     # zero-loss fallback, leaves no norm of its own: the record then carries the previous step's)
     norms = _NormReader(trainer) if getattr(trainer, "max_grad_norm", None) is not None else None
+    accs = (acc_reader if acc_reader is not None else _AccReader(trainer)) if eval_accuracy else None
 
     def enqueue(batch):
-        """One step and the posts of its read-backs: (loss handle, batch, norm handle)."""
+        """One step and the posts of its read-backs: (loss handle, batch, norm handle, accuracy handle)."""
         loss = trainer.step(batch)
         nk = norms.post() if norms is not None and trainer.last_grad_norm is not None else None
-        return (reader.post(loss), batch, nk)
+        ak = accs.post() if accs is not None else None
+        return (reader.post(loss), batch, nk, ak)
 
     def rerun(batch):
         loss = _checked(trainer, lambda: trainer.step(batch), note)
-        return loss, (norms.now() if norms is not None and trainer.last_grad_norm is not None else None)
+        return (loss, (norms.now() if norms is not None and trainer.last_grad_norm is not None else None),
+                accs.now() if accs is not None else None)
 
-    def record(loss, grad_norm=None):
+    def record(loss, grad_norm=None, acc=None):
         nonlocal current_step
         current_step += 1
         window.append(loss)
         rec = {"phoneme_loss": loss, "epoch": epoch, "step": current_step}
         if grad_norm is not None:
             rec["grad_norm"] = grad_norm
+        if acc is not None:
+            rec["phoneme_acc"] = acc
         if len(window) == log_interval:
             rec["phoneme_loss_avg"] = float(np.mean(window))
         log(**rec)
@@ -367,15 +436,16 @@ def train_loop(trainer, train_loader, val_loader, current_step, num_steps, save_
         import math
         loss = reader.read(p[0])
         grad_norm = norms.read(p[2]) if p[2] is not None else None
+        acc = accs.read(p[3]) if p[3] is not None else None
         redo = False
         try:
             trainer.engine.raise_if_failed()     # this step has completed: the word covers it (and may cover a later one)
         except HandoffTimeout as ex:
             note(handoff_timeout=str(ex), retry=1)
             if math.isnan(loss):
-                loss, grad_norm = rerun(p[1])
+                loss, grad_norm, acc = rerun(p[1])
             redo = True
-        record(loss, grad_norm)
+        record(loss, grad_norm, acc)
         return redo
 
     pending = None                               # a step whose loss has not been read back yet
@@ -398,8 +468,7 @@ def train_loop(trainer, train_loader, val_loader, current_step, num_steps, save_
                 pending = None
                 if current_step % save_interval == 0:
                     save_checkpoint(trainer, current_step, log_dir, epoch, main)
-                    log(val_phoneme_loss=validate(trainer, val_loader, device_masking, word_separator), step=current_step,
-                        epoch=epoch)
+                    log_validation()
                     grant()
                 if current_step >= num_steps:
                     return current_step, epoch
@@ -438,7 +507,8 @@ def train(args=None, dataset=None, device=None):
     print("Start training...")
     current_step, epoch = train_loop(trainer, train_loader, val_loader, current_step, int(tp["num_steps"]),
                                      int(tp["save_interval"]), int(tp["log_interval"]), log, log_dir,
-                                     decisions, dp.get("word_separator"))
+                                     decisions, dp.get("word_separator"),
+                                     eval_accuracy=bool(tp.get("eval_accuracy", False)))
     print(f"Training completed at step {current_step}, epoch {epoch}")
     if dist.is_available() and dist.is_initialized():
         dist.barrier()

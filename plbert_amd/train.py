@@ -105,8 +105,12 @@ class PLBertTrainer:
     def __init__(self, cfg, num_phonemes, max_batch=32, max_seq=512, lr=7e-5, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.01, device=None, seed=0, state_dict=None, process_group=None, force_collectives=False,
                  num_tokens=0, comm="auto", overlap=True, packed=None, packed_dual=None, packed_fp8=None,
-                 max_grad_norm=None):
-        """``max_grad_norm`` (None or <= 0: off): every optimizer step clips the global norm of its mean gradient to this value
+                 max_grad_norm=None, track_accuracy=False):
+        """``track_accuracy`` (default off: a step then launches what it launched before): every ``step`` also launches the
+        totals-only report on its loss call's masked rows (plb_masked_report) and keeps ``last_accuracy`` — a device int32 [4]:
+        masked rows, top-1 correct, top-5 correct, samples that have rows; ``step_accumulated``: summed over its micro-steps —
+        the way ``last_grad_norm`` is kept: nothing is read back.
+        ``max_grad_norm`` (None or <= 0: off): every optimizer step clips the global norm of its mean gradient to this value
         as torch.nn.utils.clip_grad_norm_ does, on the device (plb_grad_norm + plb_adamw_step_clipped); ``last_grad_norm``
         then holds [norm, coefficient, not-finite flag, updates left out] as a device tensor. Nothing is read back.
         ``packed``: ragged batches run on their valid tokens only (token-packed execution, include/plbert.h PlbPacking);
@@ -127,6 +131,8 @@ class PLBertTrainer:
         self.step_count = 0
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and float(max_grad_norm) > 0 else None
         self.last_grad_norm = None   # the four result floats of the last clipped step (device)
+        self.track_accuracy = bool(track_accuracy)
+        self.last_accuracy = None    # int32 [4] of the last step's masked rows (device; track_accuracy)
         self.packed = packed_default() if packed is None else bool(packed)
         if packed_dual is not None:   # (None: the engine has read PLBERT_PACKED_DUAL itself)
             self.engine.set_packed_dual(packed_dual)
@@ -191,6 +197,26 @@ class PLBertTrainer:
         return self.engine.loss_fwd(batch.masked, batch.labels, batch.lengths, batch.offsets, batch.flat, batch.n_masked,
                                     token_ids=batch.token_ids, packing=self.packing_of(batch))
 
+    ACCURACY_TOPK = 5
+
+    def evaluate(self, batch: StagedBatch, topk=5):
+        """``loss_only`` plus the report on its masked rows (plb_masked_report): {'loss': the batch's loss (1 element),
+        'totals': int32 [4] = masked rows, top-1 correct, top-``topk`` correct, samples that have rows, 'sample_loss' /
+        'sample_top1' / 'sample_topk': [B], and after a dual-head batch 'token_totals': int32 [2] = valid positions, positions
+        whose target ties the token head's maximum}, all on the device."""
+        loss = self.loss_only(batch).clone()
+        want = ("totals", "sample_loss", "sample_top1", "sample_topk") + (("token_totals",) if batch.token_ids is not None else ())
+        return {"loss": loss, **self.engine.masked_report(batch.offsets, topk=topk, want=want)}
+
+    def _track(self, batch, first=True):
+        """The totals of the loss call that has just run, into ``last_accuracy`` (``first``) or added to it."""
+        if self.last_accuracy is None:
+            self.last_accuracy = torch.zeros(4, dtype=torch.int32, device=self.engine.device)
+        if first:
+            self.engine.masked_report(batch.offsets, topk=self.ACCURACY_TOPK, out={"totals": self.last_accuracy})
+        else:
+            self.last_accuracy.add_(self.engine.masked_report(batch.offsets, topk=self.ACCURACY_TOPK)["totals"])
+
     def all_reduce_grads(self, dual=False):
         """Sum the trainable gradient range over ranks (RCCL over xGMI, one collective in the step's stream:
         see dist.GradReducer); the AdamW kernel applies the 1/world factor. A dual-head step also carries
@@ -214,6 +240,8 @@ class PLBertTrainer:
         loop that does not may see it one step late and — in a data-parallel run — at different steps on different
         ranks: such a caller must treat it as the end of the run (resume from the replicas, which are consistent)."""
         loss = self.loss_and_grads(batch)
+        if self.track_accuracy:
+            self._track(batch)
         dual = batch.token_ids is not None
         if batch.n_masked == 0 and self.world == 1 and not dual:
             return loss  # reference: zero-loss fallback has no graph, the optimizer sees no gradients
@@ -258,6 +286,8 @@ class PLBertTrainer:
             clip_local = self.max_grad_norm is not None and not self.reducer.active
             for i, b in enumerate(batches):
                 loss = self.loss_and_grads(b)
+                if self.track_accuracy:
+                    self._track(b, first=i == 0)
                 loss_sum = loss.clone() if loss_sum is None else loss_sum.add_(loss)
                 dual = dual or b.token_ids is not None
                 last = i == k - 1
