@@ -427,7 +427,8 @@ int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int
  *     rank == 0 / rank < topk. totals [4] = {rows, top-1 correct, top-k correct, samples that have rows}.
  *     token_totals [2] (after a dual-head call only) = {valid positions, positions whose target logit EQUALS the row maximum
  *     of the token head}: top-1 only, and TIE-INCLUSIVE (a target that ties for the maximum counts), because the fused token
- *     head keeps per-tile maxima but no arg-max index. Predicted token ids are not available.
+ *     head keeps per-tile maxima but no arg-max index. Predicted token ids, exact (lowest-index) accuracy and top-k of the
+ *     token head: plb_token_report below.
  *   Fails before anything is launched, with a text: no loss call has run; B differs from that call's; token_totals after a
  *   phoneme-only call; topk outside [0, 8]; a sample output or totals wanted with idx_offsets == NULL.
  *   A call with n_masked == 0 reports zeros (sample outputs, totals) and writes no row output.
@@ -447,6 +448,52 @@ typedef struct {
 } PlbMaskedReport;
 int plb_masked_report(PlbEngine* e, const int32_t* idx_offsets, int32_t B, int32_t topk, const PlbMaskedReport* out,
                       void* stream);
+/* ---- token-head predictions without logits (the reference has no counterpart: its loop reports the scalar loss only) ------
+ * What the token (grapheme) head predicts at chosen positions: the best topk classes with their log-probabilities, the
+ * log-sum-exp, the target's log-probability and its position in the list, exact counts — from one fused GEMM + top-k pass
+ * over the vocabulary that never stores a logit (plb_forward's token_logits is a full fp32 [B,S,num_tokens] array: 4.2 GB at
+ * 32 x 512 x 64000).
+ * WHAT IT REPORTS ON: the final hidden state of the LAST call of this engine that ran the encoder on every row and left it
+ *   in the workspace — plb_forward / plb_forward_packed, plb_encode, and plb_loss_fwd* / plb_loss_fwd_bwd* unless the call
+ *   pruned its last application (a phoneme-only loss call whose masked rows are less than half of the batch; a dual-head
+ *   call never prunes) — padded or packed, bf16 or fp8, training or inference-only engine; multiplied by the bf16 compute
+ *   copy of token_predictor.weight as that call saw it, plus the fp32 bias.
+ * UNTIL WHEN: the next call that runs the encoder replaces the state. A call that moves the weights ends it —
+ *   plb_adamw_step[_clipped], plb_sync_weights, plb_broadcast_params: a report behind the update would multiply old hidden
+ *   rows by new weights, so a training loop asks BETWEEN the loss call and the optimizer step — and so does plb_bind.
+ *   plb_encode_bwd, plb_masked_report, plb_grad_*, plb_allreduce_grads, plb_status*, plb_set_fp8 leave it alone.
+ * ROWS: the CSR position lists of the loss calls — idx_offsets (device, int32 [B+1]) and idx_flat (int32 [n], positions
+ *   < lengths[b]) — or idx_offsets == NULL: every position in [B,S] order, n == B*S; a position s >= lengths[b] then has NO
+ *   ROW (ids -1, log-probs -inf, lse / target_logprob NaN, target_pos -1, logits 0; never counted). lengths (NULL: no
+ *   padding), B, S and packing as given to the call reported on, as plb_encode_bwd asks for them.
+ * OUTPUTS: every pointer of PlbTokenReport is optional and names DEVICE memory of the caller. Classes are ordered by (logit
+ *   descending, class index ascending): topk_ids / topk_logprob = the first topk classes and their log-softmax (fp32),
+ *   0 <= topk <= 8, entries past num_tokens: id -1, -inf; lse = the row's log-sum-exp; with token_ids (device, int64 [B,S],
+ *   read at the reported positions only): target_logprob = log-softmax at the target (minus the mean over samples of the mean
+ *   over valid positions of it IS the token loss of a dual-head call, up to fp32 summation order), target_pos = the 0-based
+ *   position of the target in the list, -1 when it is not among the first topk; totals [3] = {rows counted, rows with
+ *   target_pos == 0 (exact top-1: the lowest index wins a tie, unlike token_totals), rows with target_pos >= 0 (top-k)};
+ *   logits [n][num_tokens] = the kernel's own fp32 values, for small n and debugging. A row with a NaN (or +inf) logit: ids
+ *   -1, log-probs, lse and target_logprob NaN, target_pos -1; counted as a row, never as a hit.
+ * REFUSALS, each before anything is launched, with a text: engine not bound; num_tokens == 0; no qualifying call since
+ *   plb_bind (or the last one failed, or had nothing to run); the call pruned; the weights moved since; another B / S / plan;
+ *   topk outside [0, 8]; target_logprob, target_pos or totals wanted without token_ids; n < 0, n larger than B*S, or
+ *   idx_offsets == NULL with n != B*S. n == 0 is no refusal: totals are zeros and no row output is written.
+ * SIDE EFFECTS: none. The call writes the caller's buffers and scratch regions of its own inside the workspace (at most
+ *   2 KiB per row of the engine's capacity, independent of num_tokens; none when num_tokens == 0): it changes no engine
+ *   state, keeps a live plb_encode stash live, leaves the health word and plb_masked_report's regions alone, runs on the
+ *   caller's stream only and reads nothing back. No atomics: bitwise reproducible.
+ * HEALTH WORD and DATA-PARALLEL RUNS: as for plb_masked_report. */
+typedef struct {
+  int32_t* topk_ids; float* topk_logprob;        /* [n][topk] */
+  float* lse;                                    /* [n] */
+  float* target_logprob; int32_t* target_pos;    /* [n]; need token_ids */
+  float* logits;                                 /* [n][num_tokens]; small n / debugging */
+  int32_t* totals;                               /* [3] = {rows counted, target_pos == 0, target_pos >= 0}; need token_ids */
+} PlbTokenReport;
+int plb_token_report(PlbEngine* e, const int32_t* lengths, const int32_t* idx_offsets, const int32_t* idx_flat, int32_t n,
+                     int32_t B, int32_t S, const PlbPacking* packing, const int64_t* token_ids, int32_t topk,
+                     const PlbTokenReport* out, void* stream);
 /* What the last training step exchanged: the number of collectives it issued (10 pieces for the reference's phoneme-only
  * step with overlap on, 1 with overlap off; one more after a dual-head step) and the floats they covered. The reference
  * has no counterpart (DDP's bucket count is internal to torch, train.py:218-221); a caller logs it to see which form of

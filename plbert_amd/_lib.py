@@ -124,6 +124,14 @@ class PlbMaskedReport(C.Structure):
     ]
 
 
+class PlbTokenReport(C.Structure):
+    """include/plbert.h: what plb_token_report writes (every pointer optional, device memory of the caller)."""
+    _fields_ = [
+        ("topk_ids", C.c_void_p), ("topk_logprob", C.c_void_p), ("lse", C.c_void_p), ("target_logprob", C.c_void_p),
+        ("target_pos", C.c_void_p), ("logits", C.c_void_p), ("totals", C.c_void_p),
+    ]
+
+
 class PlbLayerNorm(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("ldx", C.c_int), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float),
@@ -222,6 +230,7 @@ PUBLIC = {
     "plb_encode": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp]),
     "plb_encode_bwd": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp]),
     "plb_masked_report": (i32, [vp, vp, i32, i32, P(PlbMaskedReport), vp]),
+    "plb_token_report": (i32, [vp, vp, vp, vp, i32, i32, i32, P(PlbPacking), vp, i32, P(PlbTokenReport), vp]),
     "plb_comm_pieces": (i32, [vp, P(i32), P(i64)]),
     "plb_broadcast_params": (i32, [vp, i32, vp]),
     "plb_set_grad_overlap": (i32, [vp, i32]),
@@ -295,6 +304,10 @@ INTERNAL = {
     "plb_launch_masked_report_rows": (i32, [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "plb_launch_masked_report_samples": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "plb_launch_token_top1": (i32, [vp, i32, vp, vp, i32, vp, vp, vp]),
+    "plb_launch_token_topk": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "plb_token_topk_strips": (i32, [i32, i32, i32]),
+    "plb_token_topk_scratch_bytes": (sz, [i32]),
+    "plb_launch_token_topk_prepare": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "plb_launch_mask": (i32, [P(PlbMask), vp]),
     "plb_launch_apply_mask": (i32, [P(PlbApplyMask), vp]),
     "plb_launch_adamw": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i32, f64, vp, i32, vp]),

@@ -231,6 +231,13 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
   // and row losses of a report whose caller takes none, plb_launch_token_top1's per-block counts.
   e->o_rep_rank = cv.take(NM * 4); e->o_rep_nll = cv.take(NM * 4);
   if (e->NT) e->o_rep_tok = cv.take((Tp / 4) * 2 * 4);
+  // What plb_token_report itself writes, carved behind everything else for the same reason. Proportional to the row
+  // capacity, not to the vocabulary: 4 + 4 B of row list and target and plb_token_topk_scratch_bytes (16 strips x (8
+  // candidates x 8 B + 16 B of statistics) + 3 counts per 4 rows) = 1291 B per row of Tcap.
+  if (e->NT) {
+    e->o_tr_rows = cv.take(Tp * 4); e->o_tr_tgt = cv.take(Tp * 4);
+    e->o_tr_scratch = cv.take((int64_t)plb_token_topk_scratch_bytes((int)Tp));
+  }
   e->ws_bytes = cv.off;
   *out = e;
   return 0;
@@ -271,6 +278,7 @@ extern "C" int plb_bind(PlbEngine* e, float* params, float* grads, float* exp_av
   e->params = params; e->grads = grads; e->m = exp_avg; e->v = exp_avg_sq;
   e->ws = (char*)workspace;
   e->rep_valid = false;   // (plb_masked_report: what a loss call left lies in the workspace bound before)
+  drop_final(e, "plb_bind bound a workspace since");
   if (!e->host_err) {  // once, outside any launch sequence
     void* h = nullptr;
     if (hipHostMalloc(&h, 64, hipHostMallocMapped) == hipSuccess && h) {
@@ -331,6 +339,7 @@ int sync_transposes(PlbEngine* e, hipStream_t s, bool exact_fp8) {
 extern "C" int plb_sync_weights(PlbEngine* e, void* stream) {
   if (!e || !e->ws) return fail("plb_sync_weights: engine not bound");
   drop_stash(e, "plb_sync_weights refreshed the compute copies since");
+  drop_final(e, "plb_sync_weights refreshed the compute copies since: the hidden state is that of the weights before");
   end_accum_window(e, "plb_sync_weights refreshed the compute copies");
   hipStream_t s = (hipStream_t)stream;
   TRY(plb_launch_cast_bf16(e->params, e->at<bf16_t>(e->o_wbf), (size_t)e->ptotal, s));
@@ -457,6 +466,7 @@ extern "C" int plb_adamw_step(PlbEngine* e, double lr, double beta1, double beta
   if (e->infer) return fail("plb_adamw_step: inference-only engine");
   if (step < 1) return fail("plb_adamw_step: step counts from 1");
   drop_stash(e, "plb_adamw_step moved the weights since");
+  drop_final(e, "plb_adamw_step moved the weights since: ask between the loss call and the optimizer step");
   end_accum_window(e, "plb_adamw_step moved the weights");
   hipStream_t s = (hipStream_t)stream;
   if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream

@@ -2,13 +2,23 @@
 // the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd. Only
 // writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
 // last_exec_rows, tok_grads_live and head_grads_live (which a LAST add of engine_optim.cpp replaces by its window's union),
-// and of what plb_masked_report reads (rep_*: engine_eval.cpp; plb_bind clears rep_valid).
+// and of what plb_masked_report reads (rep_*: engine_eval.cpp; plb_bind clears rep_valid) and of the record of the final
+// hidden state plb_token_report reads (fin_*: note_final here; ended through drop_final by the calls that move the weights).
 // (packed_dual, packed_fp8: plb_set_packed_dual / _fp8, engine.cpp.)
 #include "engine_internal.h"
 
 // Every call that writes the workspace or moves the weights ends the life of a plb_encode stash.
 void drop_stash(PlbEngine* e, const char* by) {
   if (e && e->stash_live) { e->stash_live = false; e->stash_dead_by = by; }
+}
+
+// plb_token_report (engine_eval.cpp) reads the final hidden state of the last call that ran the encoder on every row.
+void drop_final(PlbEngine* e, const char* by) {
+  if (e) { e->fin_live = false; e->fin_dead_by = by; }
+}
+static void note_final(PlbEngine* e, const bf16_t* x, int B, int S, const Rows& rw) {
+  e->fin_live = true; e->fin_x = x; e->fin_B = B; e->fin_S = S;
+  e->fin_rows = rw.Tp; e->fin_used = rw.T; e->fin_row_start = rw.row_start;
 }
 
 static int check_shape(const PlbEngine* e, int B, int S, const char* who) {
@@ -42,6 +52,7 @@ static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths
                         const PlbPacking* pk, float* hidden, float* phoneme_logits, float* token_logits, void* stream) {
   if (check_shape(e, B, S, "plb_forward")) return 1;
   drop_stash(e, "plb_forward rewrote the workspace since");
+  drop_final(e, "the last call that ran the encoder (plb_forward) failed");
   if (!ids) return fail("plb_forward: ids is null");
   if (token_logits && !e->NT) return fail("plb_forward: token_logits requested but num_tokens = 0");
   hipStream_t s = (hipStream_t)stream;
@@ -84,6 +95,7 @@ static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths
     e->fp8_ready = true;
   }
   TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), nullptr, e->host_err_dev, nullptr, s));
+  note_final(e, x, B, S, rw);
   return 0;
 }
 extern "C" int plb_forward(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, float* hidden,
@@ -402,6 +414,10 @@ static int backward_tail(PlbEngine* e, const int64_t* masked_ids, const int32_t*
   return pieces_done(e);
 }
 
+static const char* const kPrunedText =
+    "the last loss call was phoneme-only and pruned its last application to the masked rows: it left no final hidden state "
+    "of every row (a dual-head call, a forward or plb_set_prune_last(0) leaves one)";
+
 // token_targets == NULL: the reference's phoneme-only step. Otherwise dual-head: loss = phoneme loss + token loss.
 // backward == false: validate() — forward and loss only, one layer of activations, the gradient buffer untouched.
 static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, const int64_t* labels,
@@ -411,6 +427,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   const char* who = backward ? "plb_loss_fwd_bwd" : "plb_loss_fwd";
   if (check_shape(e, B, S, who)) return 1;
   drop_stash(e, "a plb_loss_* call rewrote the workspace since");
+  drop_final(e, "the last call that ran the encoder (a plb_loss_* call) failed");
   if (backward && e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1)", who);
   if (backward && !e->grads) return fail("%s: no gradient buffer bound", who);
   if (!masked_ids || !labels || !idx_offsets || !loss) return fail("%s: null argument", who);
@@ -425,6 +442,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   e->rep_n = n_masked; e->rep_B = B; e->rep_dual = token_targets != nullptr; e->rep_tok_rows = token_targets ? Tp : 0;
   if (backward && begin_training_call(e, token_targets != nullptr, s)) return 1;
   if (n_masked == 0 && !token_targets) {
+    drop_final(e, "the last loss call had no masked position and no token targets: it did not run the encoder");
     if (zero_loss_call(e, backward, loss, s)) return 1;
     e->rep_valid = true;
     return 0;
@@ -461,6 +479,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
     e->last_loss = loss;
     TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), loss, e->host_err_dev, nullptr, s));
     e->rep_valid = true;
+    if (prune) drop_final(e, kPrunedText); else note_final(e, xL, B, S, rw);
     return 0;
   }
 
@@ -481,6 +500,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   // NaN and shows in plb_poll_status; plb_adamw_step skips on the same word. No host round trip anywhere.
   if (status_finish(e, loss, s)) return 1;
   e->rep_valid = true;
+  if (prune) drop_final(e, kPrunedText); else note_final(e, xL, B, S, rw);
   return 0;
 }
 
@@ -546,6 +566,7 @@ extern "C" int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengt
   Rows rw;
   if (pick_rows(e, pk, lengths, false, B, S, "plb_encode", &rw)) return 1;
   drop_stash(e, "a plb_encode call that failed rewrote the workspace since");
+  drop_final(e, "the last call that ran the encoder (plb_encode) failed");
   // (whatever an earlier call left on the side / communication stream was joined by that call's tail; audit on: checked)
   HB_W(s, e->ws, e->ws_bytes, "plb_encode (whole workspace)");
   e->last_app_rows[0] = e->last_app_rows[1] = rw.Tp;
@@ -558,6 +579,7 @@ extern "C" int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengt
   TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), nullptr, e->host_err_dev, nullptr, s));
   e->stash_live = true;
   e->stash_B = B; e->stash_S = S; e->stash_rows = rw.Tp; e->stash_used = rw.T; e->stash_row_start = rw.row_start;
+  note_final(e, x, B, S, rw);
   return 0;
 }
 

@@ -375,6 +375,7 @@ extern "C" int plb_set_grad_overlap(PlbEngine* e, int32_t overlap) {
 extern "C" int plb_broadcast_params(PlbEngine* e, int32_t root, void* stream) {
   if (!e || !e->ws) return fail("plb_broadcast_params: engine not bound");
   drop_stash(e, "plb_broadcast_params moved the weights since");
+  drop_final(e, "plb_broadcast_params moved the weights since");
   end_accum_window(e, "plb_broadcast_params moved the weights");
   if (!e->comm) return 0;
   hipStream_t s = (hipStream_t)stream;

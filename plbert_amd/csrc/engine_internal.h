@@ -110,6 +110,9 @@ struct PlbEngine {
   // plb_masked_report's own regions (engine_eval.cpp): ranks and row losses when the caller takes none, the token head's
   // per-block counts. No other entry point reads or writes them.
   int64_t o_rep_rank = 0, o_rep_nll = 0, o_rep_tok = 0;
+  // plb_token_report's own regions (engine_eval.cpp; NT > 0 only): the row list and gathered targets its prepare launch
+  // writes, the scratch of plb_launch_token_topk. No other entry point reads or writes them.
+  int64_t o_tr_rows = 0, o_tr_tgt = 0, o_tr_scratch = 0;
   // token (grapheme) head training: padded copies and the [Tp][NTp] logit / gradient images (NT > 0 only)
   int64_t o_bt = 0, o_wtT = 0, o_tdl = 0, o_tlrows = 0, o_tscr = 0, o_tgrad = 0, o_tloss = 0;
   int64_t o_tpmax = 0, o_tpsum = 0, o_ttl = 0, o_tlse = 0, o_tw = 0, o_ttgt = 0, o_tcolp = 0;
@@ -144,6 +147,18 @@ struct PlbEngine {
   bool rep_valid = false, rep_dual = false;
   int rep_n = 0, rep_B = 0;
   int64_t rep_tok_rows = 0;
+  // ---- the final hidden state of the last call that ran the encoder on every row, for plb_token_report (engine_eval.cpp):
+  // recorded by the entry points of engine_calls.cpp through note_final, ended through drop_final by every call that runs
+  // the encoder again, moves the weights (plb_adamw_step[_clipped], plb_sync_weights, plb_broadcast_params) or binds
+  // (fin_dead_by: which one — the text plb_token_report fails with). fin_x is the last slot of o_x, which nothing but
+  // run_encoder writes (engine_layers.cpp: the map-in GEMM writes slot 0, LayerNorm 2 of application l slot l + 1; the
+  // backward only reads the slots), so the state is intact until the next encoder run.
+  bool fin_live = false;
+  const char* fin_dead_by = "no call has run the encoder on this engine since plb_bind";
+  const bf16_t* fin_x = nullptr;
+  int fin_B = 0, fin_S = 0;
+  int64_t fin_rows = 0, fin_used = 0;           // Tp and T of that call
+  const int32_t* fin_row_start = nullptr;       // its plan's table (null: it ran padded)
   // ---- gradient accumulation window and norm partials: engine_optim.cpp (grads_fresh is set, and norm_nparts cleared, by
   // begin_training_call in engine_calls.cpp; the calls that move the weights end a window through end_accum_window) ----
   float* accum = nullptr;       // plb_grad_accum_bind: the caller's buffer, `total` floats like grads
@@ -320,6 +335,7 @@ int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, in
                 int* du_rows, hipStream_t s);
 // engine_calls.cpp
 void drop_stash(PlbEngine* e, const char* by);
+void drop_final(PlbEngine* e, const char* by);
 // engine.cpp
 int sync_transposes(PlbEngine* e, hipStream_t s, bool exact_fp8 = true);
 // engine_optim.cpp

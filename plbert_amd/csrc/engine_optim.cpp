@@ -146,6 +146,7 @@ extern "C" int plb_adamw_step_clipped(PlbEngine* e, double lr, double beta1, dou
   if (step < 1) return fail("plb_adamw_step_clipped: step counts from 1");
   if (!norm_buf) return fail("plb_adamw_step_clipped: norm_buf is null (plb_grad_norm writes it)");
   drop_stash(e, "plb_adamw_step_clipped moved the weights since");
+  drop_final(e, "plb_adamw_step_clipped moved the weights since: ask between the loss call and the optimizer step");
   end_accum_window(e, "plb_adamw_step_clipped moved the weights");
   hipStream_t s = (hipStream_t)stream;
   if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream

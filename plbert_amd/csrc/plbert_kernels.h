@@ -312,6 +312,43 @@ int plb_launch_masked_report_samples(const int32_t* offsets, int B, const int32_
 int plb_launch_token_top1(const float* pmax, int ntiles, const float* tlogit, const float* w, int rows, int32_t* scratch,
                           int32_t* totals2, hipStream_t stream);
 
+// ---- token-head predictions without logits (token_topk.hip): a fused GEMM + top-k + log-sum-exp over the vocabulary.
+// For j < n: z[c] = X[rows[j]] · W[c] + bias[c], c < NT (X [.][ldx], W [.][ldw] bf16 with K % 64 == 0 elements used per row,
+// ldx / ldw multiples of 8, 4-byte aligned; bias fp32 [NT]; fp32 accumulation). rows == NULL: the identity; rows[j] == -1:
+// position j has NO ROW. W is read in whole 128-row tiles, i.e. up to row rup(NT, 128): those rows must be readable, their
+// values never count (columns >= NT are excluded by index). Row 0 of X is read on behalf of positions without a row.
+// Outputs (device, each may be NULL), classes ordered by (logit descending, class index ascending):
+//   topk_ids int32 / topk_logprob fp32 [n][topk], 0 <= topk <= PLB_TOPK_MAX: the first topk classes and z - lse; entries past
+//   NT: id -1, -inf. lse fp32 [n]. With tgt (int32 [n]): target_logprob [n] = z[tgt] - lse (NaN for a target outside [0, NT))
+//   and target_pos [n] = the 0-based position of tgt in the list, -1 when it is not in it (always -1 with topk == 0).
+//   logits fp32 [n][NT]: the kernel's own values. totals int32 [3] = {positions that have a row, those with target_pos == 0,
+//   those with target_pos >= 0}.
+//   A row with a NaN logit (or +inf, whose softmax is NaN): ids -1, log-probs NaN, lse and target_logprob NaN, target_pos -1
+//   (it counts in totals[0] only).
+//   A position without a row: ids -1, log-probs -inf, lse and target_logprob NaN, target_pos -1, logits 0; never counted.
+// strips: 0 = the policy (plb_token_topk_strips), 1 .. PLB_TOPK_MAX_STRIPS forces the count (ids and target_pos do not depend
+// on it; lse and the log-probabilities differ by rounding). scratch: plb_token_topk_scratch_bytes(n) bytes, 16-byte aligned.
+// n == 0: totals = zeros, nothing else is written. Three launches (two without totals); no atomics, bitwise reproducible.
+// Returns 1, launching nothing, on any argument it cannot run.
+#define PLB_TOPK_MAX 8
+#define PLB_TOPK_MAX_STRIPS 16
+int plb_launch_token_topk(const bf16_t* X, int ldx, const int32_t* rows, int n, const bf16_t* W, int ldw, const float* bias,
+                          int NT, int K, int topk, int strips, void* scratch, const int32_t* tgt, int32_t* topk_ids,
+                          float* topk_logprob, float* lse, float* target_logprob, int32_t* target_pos, float* logits,
+                          int32_t* totals, hipStream_t stream);
+// strips the launch above runs for (n, NT, strips): with row_tiles = ceil(n / 128), the policy takes ceil(512 / row_tiles)
+// (256 CUs about twice); at most PLB_TOPK_MAX_STRIPS and the number of 128-column tiles; then the fewest strips of that
+// tile count per strip (no strip is empty). 0 for n < 1 or NT < 1.
+int plb_token_topk_strips(int n, int NT, int strips);
+// bytes of scratch for n rows: per row PLB_TOPK_MAX_STRIPS x (8 candidates x 8 B + 16 B of statistics), 3 counts per 4 rows
+size_t plb_token_topk_scratch_bytes(int n);
+// Row list and targets of a report from the position lists of a call: CSR (offsets int32 [B+1], flat [n]) or, offsets ==
+// NULL, every position of [B,S] in order (n == B*S). rows[j] = row_start[b] + s (row_start == NULL: b*S + s) for a position
+// s < lengths[b] (lengths == NULL: S), else -1; tgt[j] = token_ids[b,s] (NULL, or no row: -1).
+int plb_launch_token_topk_prepare(const int32_t* offsets, const int32_t* flat, const int32_t* lengths, const int32_t* row_start,
+                                  const int64_t* token_ids, int n, int B, int S, int32_t* rows, int32_t* tgt,
+                                  hipStream_t stream);
+
 // Device-side word masking (mask.hip): labels [B,S] -> masked [B,S], counts [B], idx_padded [B,S],
 // then offsets [B+1] and flat (CSR of the modified positions).
 typedef struct {

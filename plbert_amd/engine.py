@@ -432,7 +432,9 @@ class HipEngine:
     def forward(self, ids, lengths=None, want_hidden=False, want_phoneme=True, want_token=False, packing=None):
         """ids int64 [B,S]; lengths per-sample valid-token counts (None = no padding).
         Returns (hidden | None, phoneme_logits | None, token_logits | None), fp32 on the device.
-        ``packing`` (PackingPlan of these lengths): token-packed execution; pad positions of the outputs are zeros."""
+        ``packing`` (PackingPlan of these lengths): token-packed execution; pad positions of the outputs are zeros.
+        With all three ``want_*`` False the call outputs nothing: it runs the encoder and leaves the final hidden state
+        on the device for ``token_report``."""
         self._ensure_synced()
         ids = self._dev_i64(ids)
         B, S = ids.shape
@@ -449,6 +451,7 @@ class HipEngine:
             else:
                 _lib.check(self.L.plb_forward_packed(self.handle, ids.data_ptr(), p(lens), B, S, C.byref(pk), p(hid), p(ph),
                                                      p(tk), self._stream()), "plb_forward_packed")
+        self._last_encoder_call = (int(B), int(S), lens, packing)
         return hid, ph, tk
 
     def encode(self, ids, lengths=None, packing=None):
@@ -472,6 +475,7 @@ class HipEngine:
                                          None if pk is None else C.byref(pk), hid.data_ptr(), self._stream()), "plb_encode")
         self._encode_serial = getattr(self, "_encode_serial", 0) + 1
         self._live_encode = (ids, lens, packing, B, S)   # (holds the tensors the backward reads again)
+        self._last_encoder_call = (int(B), int(S), lens, packing)
         return hid
 
     def encode_bwd(self, d_hidden):
@@ -572,6 +576,7 @@ class HipEngine:
                                                    offs.data_ptr(), flat_p, int(n_masked), B, S, self._loss.data_ptr(),
                                                    self._stream()), "plb_loss_fwd_bwd")
         self._last_loss_call = (int(B), int(n_masked), tok is not None)
+        self._last_encoder_call = (int(B), int(S), lens, packing)   # (token_report: the tensors that call was given)
         return self._loss
 
     # ---- masked-phoneme evaluation (include/plbert.h: plb_masked_report) ---------------------------------
@@ -616,6 +621,61 @@ class HipEngine:
                 setattr(rep, name, t.data_ptr() if t.numel() else None)
             _lib.check(self.L.plb_masked_report(self.handle, None if offs is None else offs.data_ptr(), B, int(topk),
                                                 C.byref(rep), self._stream()), "plb_masked_report")
+        return res
+
+    # ---- token-head predictions without logits (include/plbert.h: plb_token_report) ----------------------------
+    # output name -> (dtype, shape as a function of (n, topk, num_tokens))
+    TOKEN_REPORT_OUTPUTS = {
+        "topk_ids": (torch.int32, lambda n, k, V: (n, k)), "topk_logprob": (torch.float32, lambda n, k, V: (n, k)),
+        "lse": (torch.float32, lambda n, k, V: (n,)), "target_logprob": (torch.float32, lambda n, k, V: (n,)),
+        "target_pos": (torch.int32, lambda n, k, V: (n,)), "logits": (torch.float32, lambda n, k, V: (n, V)),
+        "totals": (torch.int32, lambda n, k, V: (3,)),
+    }
+
+    def token_report(self, positions=None, token_ids=None, topk=5, want=("topk_ids", "topk_logprob"), out=None):
+        """What the token head predicts on the final hidden state of the LAST call of this engine that ran the encoder —
+        ``forward`` (``want_*`` all False outputs nothing else), ``encode``, ``loss_fwd`` / ``loss_fwd_bwd`` (a dual-head call,
+        or a phoneme-only one that did not prune) — from one fused GEMM + top-k pass that stores no logits
+        (plb_token_report). ``positions``: None = every position of [B,S] in order (a pad position has no row: ids -1,
+        log-probabilities -inf, never counted), or ``(offsets, flat)``, the CSR position lists of the loss calls.
+        ``token_ids`` (int64 [B,S]): the targets, needed for target_logprob / target_pos / totals. ``want``: names of
+        ``TOKEN_REPORT_OUTPUTS`` — per position topk_ids / topk_logprob [n, topk], lse, target_logprob, target_pos [n],
+        logits [n, num_tokens] (small n), and totals = [positions counted, target first (exact top-1), target in the top-k].
+        Returns {name: device tensor}; only what is asked for is allocated (``out``: {name: tensor} to write into), nothing
+        is read back. Available until the next call that runs the encoder or moves the weights (``adamw_step``,
+        ``sync_weights``, ``broadcast_params``): a training loop asks between the loss call and the optimizer step."""
+        last = getattr(self, "_last_encoder_call", None)
+        if last is None:
+            raise RuntimeError("token_report: no call has run the encoder on this engine")
+        B, S, lens, packing = last
+        unknown = [w for w in want if w not in self.TOKEN_REPORT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"token_report: unknown output(s) {unknown}; the outputs are {sorted(self.TOKEN_REPORT_OUTPUTS)}")
+        offs = flat = None
+        n = B * S
+        if positions is not None:
+            offs, flat = self._dev_i32(positions[0]), self._dev_i32(positions[1])
+            n = int(flat.numel())
+        tok = None if token_ids is None else self._dev_i64(token_ids)
+        if tok is not None and tuple(tok.shape) != (B, S):
+            raise ValueError(f"token_report: token_ids must be [{B}, {S}], got {tuple(tok.shape)}")
+        res, rep = {}, _lib.PlbTokenReport()
+        p = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(self.device):
+            for name in want:
+                dtype, shape = self.TOKEN_REPORT_OUTPUTS[name]
+                shp = shape(n, int(topk), self.num_tokens)
+                t = out.get(name) if out else None
+                if t is None:
+                    t = torch.empty(shp, dtype=dtype, device=self.device)
+                elif t.dtype != dtype or tuple(t.shape) != shp or t.device != self.device or not t.is_contiguous():
+                    raise ValueError(f"token_report: out[{name!r}] must be a contiguous {dtype} tensor of shape {shp} on {self.device}")
+                res[name] = t
+                setattr(rep, name, t.data_ptr() if t.numel() else None)
+            pk = self._packing(packing, B, S)
+            _lib.check(self.L.plb_token_report(self.handle, p(lens), p(offs), p(flat) if n else None, n, B, S,
+                                               None if pk is None else C.byref(pk), p(tok), int(topk), C.byref(rep),
+                                               self._stream()), "plb_token_report")
         return res
 
     @property

@@ -287,3 +287,34 @@ class MultiTaskModel(_HeadModel):
     def forward(self, phonemes, attention_mask=None):
         _, ph, tk = self._engine.forward(phonemes, _lengths_from_mask(attention_mask), want_token=True)
         return ph, tk
+
+    def predict_tokens(self, phonemes, attention_mask=None, positions=None, topk=5):
+        """The token (grapheme) head's predictions: ``phonemes`` int64 [B,S], ``positions`` one list of positions per sample
+        (inside the sample's valid length) or None = every valid position. Returns ``(ids int64 [n, topk], probs fp32
+        [n, topk])`` on the device, n = the positions in (sample, position) order, classes by descending probability (among
+        equal logits the lowest id first; -1 / 0 behind num_tokens). One forward that outputs nothing (it honours ``packed``
+        like ``PhonemeOnlyModel.forward``; works in eval mode and on an inference-only engine) followed by the fused
+        top-k over the vocabulary (plb_token_report): no [B,S,num_tokens] logits are materialised, unlike ``forward``."""
+        import numpy as np
+        from .data import masked_indices_to_csr
+        eng = self._engine
+        ids = eng._dev_i64(phonemes)
+        B, S = ids.shape
+        lengths = _lengths_from_mask(attention_mask)
+        lens = [S] * B if lengths is None else [min(max(int(v), 1), S) for v in lengths.cpu().tolist()]
+        if positions is None:
+            positions = [np.arange(ln, dtype=np.int64) for ln in lens]
+        if len(positions) != B:
+            raise ValueError(f"predict_tokens: {len(positions)} position lists for {B} samples")
+        lists = [np.asarray(idx, dtype=np.int64).reshape(-1) for idx in positions]
+        for b, (a, ln) in enumerate(zip(lists, lens)):
+            if a.size and (a.min() < 0 or a.max() >= ln):
+                raise ValueError(f"predict_tokens: sample {b}: position outside [0, {ln})")
+        off, flat = masked_indices_to_csr(lists)
+        if int(off[-1]) == 0:
+            return (torch.empty((0, topk), dtype=torch.int64, device=eng.device),
+                    torch.empty((0, topk), dtype=torch.float32, device=eng.device))
+        eng.forward(ids, lengths, want_hidden=False, want_phoneme=False, want_token=False,
+                    packing=_packing_from_lengths(self, lengths, ids))
+        rep = eng.token_report((torch.from_numpy(off), torch.from_numpy(flat)), topk=topk, want=("topk_ids", "topk_logprob"))
+        return rep["topk_ids"].to(torch.int64), rep["topk_logprob"].exp()

@@ -258,16 +258,31 @@ def validate_metrics(trainer, val_loader, device_masking=False, word_separator=N
     """``validate`` plus the accuracy at the masked positions: {'val_phoneme_loss': the mean of the per-batch losses, exactly
     what ``validate`` returns, 'val_phoneme_acc', 'val_phoneme_top<topk>': MICRO-averages over the pass — correct rows
     summed over the batches, over masked rows summed over the batches (0.0 for a pass without masked rows)}. The counts of
-    every batch (plb_masked_report, totals only) are added up on the device and read back once, behind the last batch."""
-    total, n, counts = 0.0, 0, None
+    every batch (plb_masked_report, totals only) are added up on the device and read back once, behind the last batch.
+    When the batches carry token ids (dual-head) the token head is counted too, over every valid position
+    (plb_token_report, totals only, summed and read back with the others): 'val_token_acc' (the target is the head's first
+    class) and 'val_token_top<topk>'. A phoneme-only pass returns the three phoneme keys alone."""
+    total, n, counts, tcounts = 0.0, 0, None, None
     for b in _batches(val_loader, trainer, device_masking, word_separator):
         total += _checked(trainer, lambda: trainer.loss_only(b))
         t = trainer.engine.masked_report(b.offsets, topk=topk, want=("totals",))["totals"]
         counts = t.to(torch.int64) if counts is None else counts.add_(t)
+        tok = getattr(b, "token_ids", None)
+        if tok is not None:
+            t = trainer.engine.token_report(None, tok, topk=topk, want=("totals",))["totals"]
+            tcounts = t.to(torch.int64) if tcounts is None else tcounts.add_(t)
         n += 1
-    rows, top1, topk_n = (int(v) for v in counts[:3].tolist()) if counts is not None else (0, 0, 0)
-    return {"val_phoneme_loss": total / max(n, 1), "val_phoneme_acc": top1 / rows if rows else 0.0,
-            f"val_phoneme_top{topk}": topk_n / rows if rows else 0.0}
+    if tcounts is not None:   # one read-back for both heads
+        both = torch.cat([counts[:3], tcounts]).tolist()
+        (rows, top1, topk_n), (trows, ttop1, ttopk) = (int(v) for v in both[:3]), (int(v) for v in both[3:])
+    else:
+        rows, top1, topk_n = (int(v) for v in counts[:3].tolist()) if counts is not None else (0, 0, 0)
+    res = {"val_phoneme_loss": total / max(n, 1), "val_phoneme_acc": top1 / rows if rows else 0.0,
+           f"val_phoneme_top{topk}": topk_n / rows if rows else 0.0}
+    if tcounts is not None:
+        res["val_token_acc"] = ttop1 / trows if trows else 0.0
+        res[f"val_token_top{topk}"] = ttopk / trows if trows else 0.0
+    return res
 
 
 class _AccReader:

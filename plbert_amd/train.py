@@ -203,10 +203,15 @@ class PLBertTrainer:
         """``loss_only`` plus the report on its masked rows (plb_masked_report): {'loss': the batch's loss (1 element),
         'totals': int32 [4] = masked rows, top-1 correct, top-``topk`` correct, samples that have rows, 'sample_loss' /
         'sample_top1' / 'sample_topk': [B], and after a dual-head batch 'token_totals': int32 [2] = valid positions, positions
-        whose target ties the token head's maximum}, all on the device."""
+        whose target ties the token head's maximum, and 'token_exact': int32 [3] = valid positions, positions whose target is
+        the token head's first class (the lowest index wins a tie), positions whose target is among its first ``topk``
+        (plb_token_report)}, all on the device."""
         loss = self.loss_only(batch).clone()
         want = ("totals", "sample_loss", "sample_top1", "sample_topk") + (("token_totals",) if batch.token_ids is not None else ())
-        return {"loss": loss, **self.engine.masked_report(batch.offsets, topk=topk, want=want)}
+        res = {"loss": loss, **self.engine.masked_report(batch.offsets, topk=topk, want=want)}
+        if batch.token_ids is not None:
+            res["token_exact"] = self.engine.token_report(None, batch.token_ids, topk=topk, want=("totals",))["totals"]
+        return res
 
     def _track(self, batch, first=True):
         """The totals of the loss call that has just run, into ``last_accuracy`` (``first``) or added to it."""
