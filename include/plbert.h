@@ -402,6 +402,50 @@ int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t
                float* hidden, void* stream);
 int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing,
                    const float* d_hidden, void* stream);
+/* ---- per-application outputs: output_hidden_states / output_attentions, with gradients (opt-in: a call that asks for
+ * nothing launches what it launched before) ----
+ * The shared layer is applied num_hidden_layers (L) times, so hidden_states[l] is the model after l applications: what depth
+ * probing, weighted sums over depths and early exit read. Semantics follow HuggingFace modeling_albert.py with the deviations
+ * this library already makes for plb_encode.
+ * PlbLayerOutputs: two HOST arrays of DEVICE pointers, read on the host during the call (they need not outlive it).
+ *   hidden_states: L + 1 entries, each NULL (not wanted) or fp32 [B,S,H]. hidden_states[0] is the output of
+ *     embedding_hidden_mapping_in (H wide, not the embedding), hidden_states[l] the output of application l, hidden_states[L]
+ *     is last_hidden_state. Values are the fp32 image of the bf16 rows the call itself computed: nothing is recomputed. At
+ *     valid positions every slot is bit-equal between the padded and the packed layout, between plb_forward_layers and
+ *     plb_encode_layers, and slot L to the `hidden` of the same call.
+ *   attentions: L entries, each NULL or fp32 [B,NH,S,S]. attentions[l][b,h,i,j] = softmax over the keys j < lengths[b] of
+ *     scale * q_i·k_j of application l, from the bf16 qkv that application wrote and the log-sum-exp its attention kernel
+ *     stored: the probabilities the call's attention used, up to fp32 rounding. Key columns j >= lengths[b] are exactly 0.
+ *   Pad positions (s >= lengths[b]): every hidden-state slot is ZERO there and every attention QUERY row i >= lengths[b] is
+ *     ZERO, in both layouts. This deviates from HuggingFace, which leaves values in pad query rows: the same deviation, for
+ *     the same reason, as plb_encode. lengths == NULL: no padding. Every element of every requested output is written
+ *     exactly once by the call: the caller need not zero anything. Either array may be NULL (none of that kind).
+ * plb_forward_layers: plb_forward_packed(hidden, no logits) plus the outputs; hidden may be NULL. Training and inference-only
+ *   engines, padded or packed, bf16 or fp8 mode (the outputs are those of the arithmetic that call ran). Engine state
+ *   afterwards is exactly that of the plb_forward_packed call: the final hidden state for plb_token_report,
+ *   plb_last_call_rows, the fp8 scale update, the dropped plb_encode stash.
+ * plb_encode_layers: plb_encode plus the outputs; with layers == NULL it is exactly plb_encode. Same refusals, same live
+ *   stash, hidden required.
+ * plb_encode_bwd_layers: plb_encode_bwd with gradients entering at the application boundaries too. d_below: HOST array of L
+ *   DEVICE pointers; d_below[l] (l in [0, L)) is NULL (no gradient there) or fp32 [B,S,H] = d(loss)/d(hidden_states[l]); slot
+ *   L's gradient is d_hidden, and a NULL d_hidden means a zero output gradient of the last application. Values at pad
+ *   positions are never read. With d_below == NULL or all-NULL and d_hidden given it is exactly plb_encode_bwd: the same
+ *   launches, the gradient buffer bit for bit. All of plb_encode_bwd's bookkeeping is unchanged (the stash is consumed, the
+ *   head range is zeroed and marked without gradient, the exchange's pieces and the status exchange keep their order).
+ *   Attentions are outputs only: no gradient enters through them.
+ * Refusals, each before anything is launched and with a text: a NULL engine or one that is not bound, every refusal of the
+ *   namesake call, and for plb_encode_bwd_layers nothing to differentiate (d_hidden == NULL and no entry of d_below). A
+ *   `layers` whose arrays are both NULL, or hold NULL entries only, is no refusal: it is the namesake call. */
+typedef struct {
+  float* const* hidden_states;  /* HOST array of num_hidden_layers + 1 DEVICE pointers (each NULL = not wanted, else fp32 [B,S,H]); NULL = none */
+  float* const* attentions;     /* HOST array of num_hidden_layers DEVICE pointers (each NULL = not wanted, else fp32 [B,NH,S,S]); NULL = none */
+} PlbLayerOutputs;
+int plb_forward_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing,
+                       float* hidden, const PlbLayerOutputs* layers, void* stream);
+int plb_encode_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing,
+                      float* hidden, const PlbLayerOutputs* layers, void* stream);
+int plb_encode_bwd_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                          const PlbPacking* packing, const float* d_hidden, const float* const* d_below, void* stream);
 /* ---- masked-phoneme evaluation: accuracy, top-k and fill-mask from a loss call (opt-in: a step that does not ask launches
  * what it launched before) ----
  * The reference reports the scalar loss only (train.py:288-336, 395-410). A masked LM's users also expect the accuracy at the

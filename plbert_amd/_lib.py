@@ -115,6 +115,12 @@ class PlbPacking(C.Structure):
     _fields_ = [("row_start", C.c_void_p), ("rows", C.c_int32), ("used", C.c_int32)]
 
 
+class PlbLayerOutputs(C.Structure):
+    """include/plbert.h: per-application outputs of plb_forward_layers / plb_encode_layers — two HOST arrays of device
+    pointers (L + 1 hidden-state slots, L attention maps; an entry or a whole array may be NULL)."""
+    _fields_ = [("hidden_states", C.c_void_p), ("attentions", C.c_void_p)]
+
+
 class PlbMaskedReport(C.Structure):
     """include/plbert.h: what plb_masked_report writes (every pointer optional, device memory of the caller)."""
     _fields_ = [
@@ -229,6 +235,9 @@ PUBLIC = {
     "plb_set_packed_fp8": (i32, [vp, i32]),
     "plb_encode": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp]),
     "plb_encode_bwd": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp]),
+    "plb_forward_layers": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
+    "plb_encode_layers": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
+    "plb_encode_bwd_layers": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp, vp]),
     "plb_masked_report": (i32, [vp, vp, i32, i32, P(PlbMaskedReport), vp]),
     "plb_token_report": (i32, [vp, vp, vp, vp, i32, i32, i32, P(PlbPacking), vp, i32, P(PlbTokenReport), vp]),
     "plb_comm_pieces": (i32, [vp, P(i32), P(i64)]),
@@ -295,6 +304,8 @@ INTERNAL = {
     "plb_launch_ce_prepare_packed": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "plb_launch_unpack_rows": (i32, [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
     "plb_launch_seed_dy": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "plb_launch_attn_probs": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, f32, vp, vp]),
+    "plb_launch_add_row_grad": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "plb_launch_ce_fwd_bwd": (i32, [vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, vp]),
     "plb_launch_sum_rows": (i32, [vp, i32, vp, vp]),
     "plb_launch_token_ce_combine": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),

@@ -1,5 +1,6 @@
 // Call-level stages of the engine: row selection of a padded or token-packed call, the heads, the stages of a loss call and
-// the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd. Only
+// the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd and their
+// *_layers forms (per-application outputs; a gradient at every application boundary). Only
 // writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
 // last_exec_rows, tok_grads_live and head_grads_live (which a LAST add of engine_optim.cpp replaces by its window's union),
 // and of what plb_masked_report reads (rep_*: engine_eval.cpp; plb_bind clears rep_valid) and of the record of the final
@@ -48,13 +49,15 @@ static int pick_rows(PlbEngine* e, const PlbPacking* pk, const int32_t* lengths,
   return 0;
 }
 
+// layers (or null): the per-application outputs of plb_forward_layers, written by run_encoder as the call goes
 static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
-                        const PlbPacking* pk, float* hidden, float* phoneme_logits, float* token_logits, void* stream) {
-  if (check_shape(e, B, S, "plb_forward")) return 1;
+                        const PlbPacking* pk, float* hidden, float* phoneme_logits, float* token_logits,
+                        const PlbLayerOutputs* layers, const char* who, void* stream) {
+  if (check_shape(e, B, S, who)) return 1;
   drop_stash(e, "plb_forward rewrote the workspace since");
   drop_final(e, "the last call that ran the encoder (plb_forward) failed");
-  if (!ids) return fail("plb_forward: ids is null");
-  if (token_logits && !e->NT) return fail("plb_forward: token_logits requested but num_tokens = 0");
+  if (!ids) return fail("%s: ids is null", who);
+  if (token_logits && !e->NT) return fail("%s: token_logits requested but num_tokens = 0", who);
   hipStream_t s = (hipStream_t)stream;
   const int H = e->H;
   Rows rw;
@@ -62,11 +65,11 @@ static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths
   // Phoneme logits of a packed call pass, as [Tp][NP] fp32, through a slot
   // of the forward-only call that is free once the encoder is done: QKV (6H bytes per row) or the FFN's u (2I))
   const int64_t lg_off = 4 * e->NP <= 6 * H ? e->o_qkv : 4 * e->NP <= 2 * e->I ? e->o_u : -1;
-  if (pick_rows(e, pk, lengths, token_logits != nullptr || lg_off < 0, B, S, "plb_forward", &rw)) return 1;
+  if (pick_rows(e, pk, lengths, token_logits != nullptr || lg_off < 0, B, S, who, &rw)) return 1;
   const int T = rw.T;
   const int64_t Tp = rw.Tp;
   bf16_t* x = nullptr;
-  if (run_encoder(e, ids, lengths, B, S, rw, false, &x, s)) return 1;
+  if (run_encoder(e, ids, lengths, B, S, rw, false, &x, s, nullptr, layers)) return 1;
   if (rw.row_start) {
     // back to the caller's [B,S,*] layout, zeros at the pad positions
     if (hidden) TRY(plb_launch_unpack_rows(x, 1, H, rw.row_start, lengths, B, S, H, hidden, s));
@@ -100,12 +103,17 @@ static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths
 }
 extern "C" int plb_forward(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, float* hidden,
                            float* phoneme_logits, float* token_logits, void* stream) {
-  return forward_impl(e, ids, lengths, B, S, nullptr, hidden, phoneme_logits, token_logits, stream);
+  return forward_impl(e, ids, lengths, B, S, nullptr, hidden, phoneme_logits, token_logits, nullptr, "plb_forward", stream);
 }
 extern "C" int plb_forward_packed(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                                   const PlbPacking* packing, float* hidden, float* phoneme_logits, float* token_logits,
                                   void* stream) {
-  return forward_impl(e, ids, lengths, B, S, packing, hidden, phoneme_logits, token_logits, stream);
+  return forward_impl(e, ids, lengths, B, S, packing, hidden, phoneme_logits, token_logits, nullptr, "plb_forward", stream);
+}
+// plb_forward_packed(hidden, no logits) plus the per-application outputs (include/plbert.h: PlbLayerOutputs)
+extern "C" int plb_forward_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                                  const PlbPacking* packing, float* hidden, const PlbLayerOutputs* layers, void* stream) {
+  return forward_impl(e, ids, lengths, B, S, packing, hidden, nullptr, nullptr, layers, "plb_forward_layers", stream);
 }
 
 // ---- stages of a loss call ----------------------------------------------------------------------------------------------
@@ -550,28 +558,29 @@ extern "C" int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, cons
 }
 
 // ---- differentiable encoder: forward now, backward from a caller's gradient later (include/plbert.h) --------------------
-// plb_encode is run_encoder with the stash on and nothing pruned; the stash then waits, marked live, while the caller's
+// plb_encode[_layers] is run_encoder with the stash on and nothing pruned; the stash then waits, marked live, while the caller's
 // downstream model runs. plb_encode_bwd turns the caller's d(last_hidden_state) into the output gradient of the last
 // application (plb_launch_seed_dy) and runs the stages of a loss call's backward behind it. The phoneme head takes no
 // part: its gradient range is written as zeros (and still travels as the first piece of the exchange, as in
 // zero_loss_call: the collective sequence of a step is the same whatever the step computes).
-extern "C" int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
-                          const PlbPacking* pk, float* hidden, void* stream) {
-  if (check_shape(e, B, S, "plb_encode")) return 1;
-  if (e->infer) return fail("plb_encode: inference-only engine (PlbConfig.inference_only = 1): a differentiable forward keeps every application's activations");
-  if (!e->grads) return fail("plb_encode: no gradient buffer bound");
-  if (e->fp8_on) return fail("plb_encode: fp8 mode is on (the gradient sites' delayed scales belong to the pre-training loss); call plb_set_fp8(e, 0, stream) first");
-  if (!ids || !hidden) return fail("plb_encode: %s is null", !ids ? "ids" : "hidden");
+// layers (or null): the per-application outputs of plb_encode_layers, written by run_encoder as the call goes.
+static int encode_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* pk,
+                       float* hidden, const PlbLayerOutputs* layers, const char* who, void* stream) {
+  if (check_shape(e, B, S, who)) return 1;
+  if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1): a differentiable forward keeps every application's activations", who);
+  if (!e->grads) return fail("%s: no gradient buffer bound", who);
+  if (e->fp8_on) return fail("%s: fp8 mode is on (the gradient sites' delayed scales belong to the pre-training loss); call plb_set_fp8(e, 0, stream) first", who);
+  if (!ids || !hidden) return fail("%s: %s is null", who, !ids ? "ids" : "hidden");
   hipStream_t s = (hipStream_t)stream;
   Rows rw;
-  if (pick_rows(e, pk, lengths, false, B, S, "plb_encode", &rw)) return 1;
+  if (pick_rows(e, pk, lengths, false, B, S, who, &rw)) return 1;
   drop_stash(e, "a plb_encode call that failed rewrote the workspace since");
   drop_final(e, "the last call that ran the encoder (plb_encode) failed");
   // (whatever an earlier call left on the side / communication stream was joined by that call's tail; audit on: checked)
   HB_W(s, e->ws, e->ws_bytes, "plb_encode (whole workspace)");
   e->last_app_rows[0] = e->last_app_rows[1] = rw.Tp;
   bf16_t* x = nullptr;
-  if (run_encoder(e, ids, lengths, B, S, rw, true, &x, s)) return 1;
+  if (run_encoder(e, ids, lengths, B, S, rw, true, &x, s, nullptr, layers)) return 1;
   // .last_hidden_state in the caller's [B,S,H] layout, ZEROS at the pad positions in both layouts: a downstream model must
   // not be handed numbers that carry no gradient
   if (lengths) TRY(plb_launch_unpack_rows(x, 1, e->H, rw.row_start, lengths, B, S, e->H, hidden, s));
@@ -582,27 +591,52 @@ extern "C" int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengt
   note_final(e, x, B, S, rw);
   return 0;
 }
+extern "C" int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                          const PlbPacking* pk, float* hidden, void* stream) {
+  return encode_impl(e, ids, lengths, B, S, pk, hidden, nullptr, "plb_encode", stream);
+}
+extern "C" int plb_encode_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                                 const PlbPacking* pk, float* hidden, const PlbLayerOutputs* layers, void* stream) {
+  return encode_impl(e, ids, lengths, B, S, pk, hidden, layers, "plb_encode_layers", stream);
+}
 
-extern "C" int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
-                              const PlbPacking* pk, const float* d_hidden, void* stream) {
-  if (check_shape(e, B, S, "plb_encode_bwd")) return 1;
-  if (e->infer) return fail("plb_encode_bwd: inference-only engine (PlbConfig.inference_only = 1)");
-  if (!e->grads) return fail("plb_encode_bwd: no gradient buffer bound");
-  if (!ids || !d_hidden) return fail("plb_encode_bwd: %s is null", !ids ? "ids" : "d_hidden");
-  if (!e->stash_live) return fail("plb_encode_bwd: no live plb_encode stash: %s", e->stash_dead_by);
+// plb_encode_bwd_layers, and plb_encode_bwd as a call of it (layers_call false: its own name in the texts, d_hidden required).
+// d_below[l] (host array of L device pointers, or null): the caller's gradient of hidden_states[l], the input of application
+// l; it joins the residual operand of the dX GEMM that produces that state's gradient (attention_bwd_dx). d_hidden == NULL:
+// the output gradient of the last application is zero.
+static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                           const PlbPacking* pk, const float* d_hidden, const float* const* d_below, bool layers_call,
+                           void* stream) {
+  const char* who = layers_call ? "plb_encode_bwd_layers" : "plb_encode_bwd";
+  if (check_shape(e, B, S, who)) return 1;
+  if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1)", who);
+  if (!e->grads) return fail("%s: no gradient buffer bound", who);
+  // the pointer array is read here, on the host: a copy without its NULL-only form
+  std::vector<const float*> below;
+  if (d_below) {
+    below.assign(d_below, d_below + e->L);
+    bool any = false;
+    for (const float* p : below) any = any || p != nullptr;
+    if (!any) below.clear();
+  }
+  if (!ids) return fail("%s: ids is null", who);
+  if (!d_hidden && below.empty())
+    return layers_call ? fail("%s: nothing to differentiate (d_hidden is null and d_below has no entry)", who)
+                       : fail("%s: d_hidden is null", who);
+  if (!e->stash_live) return fail("%s: no live plb_encode stash: %s", who, e->stash_dead_by);
   if (B != e->stash_B || S != e->stash_S)
-    return fail("plb_encode_bwd: batch %d x seq %d differs from the plb_encode call's %d x %d", B, S, e->stash_B, e->stash_S);
+    return fail("%s: batch %d x seq %d differs from the plb_encode call's %d x %d", who, B, S, e->stash_B, e->stash_S);
   hipStream_t s = (hipStream_t)stream;
   Rows rw;
   // (a call that fails launches nothing and leaves what plb_last_call_rows reports alone)
   const int64_t exec_rows[2] = {e->last_exec_rows[0], e->last_exec_rows[1]};
-  const bool plan_ok = pick_rows(e, pk, lengths, false, B, S, "plb_encode_bwd", &rw) == 0;   // (its own text names the plan)
+  const bool plan_ok = pick_rows(e, pk, lengths, false, B, S, who, &rw) == 0;   // (its own text names the plan)
   const bool same = plan_ok && rw.Tp == e->stash_rows && rw.T == e->stash_used && rw.row_start == e->stash_row_start;
   if (!same) {
     e->last_exec_rows[0] = exec_rows[0]; e->last_exec_rows[1] = exec_rows[1];
     if (!plan_ok) return 1;
-    return fail("plb_encode_bwd: packing plan differs from the plb_encode call's (%lld rows, %lld used, %s; that call: %lld rows, %lld used, %s)",
-                (long long)rw.Tp, (long long)rw.T, rw.row_start ? "packed" : "padded", (long long)e->stash_rows,
+    return fail("%s: packing plan differs from the plb_encode call's (%lld rows, %lld used, %s; that call: %lld rows, %lld used, %s)",
+                who, (long long)rw.Tp, (long long)rw.T, rw.row_start ? "packed" : "padded", (long long)e->stash_rows,
                 (long long)e->stash_used, e->stash_row_start ? "packed" : "padded");
   }
   if (begin_training_call(e, false, s)) return 1;
@@ -613,14 +647,23 @@ extern "C" int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* l
   const int64_t Tp = rw.Tp;
   bf16_t* dy = e->at<bf16_t>(e->o_dy0);
   HB_W(s, dy, Tp * e->H * 2, "output gradient of the last application, seeded from d_hidden");
-  TRY(plb_launch_seed_dy(d_hidden, lengths, rw.row_start, B, S, e->H, (int)Tp, dy, s));
+  if (d_hidden) TRY(plb_launch_seed_dy(d_hidden, lengths, rw.row_start, B, S, e->H, (int)Tp, dy, s));
+  else HIPTRY(hipMemsetAsync(dy, 0, (size_t)Tp * e->H * 2, s));   // (no gradient at the last slot: every row zero)
   // the phoneme head took no part: zeros, final before the layer loop — its piece travels where a regular step's does
   HB_W(s, e->grd(PLB_HEAD_W), (e->ptrain - e->poff[PLB_HEAD_W]) * 4, "phoneme head gradients (zeros: plb_encode_bwd)");
   HIPTRY(hipMemsetAsync(e->grd(PLB_HEAD_W), 0, (size_t)(e->ptrain - e->poff[PLB_HEAD_W]) * 4, s));
   if (overlapping(e) && reduce_pieces(e, kPieceHead, kPieceHead + 1, s)) return 1;
   int du_rows = 0;
-  if (encoder_bwd(e, nullptr, lengths, B, S, rw, &dy, &du_rows, s)) return 1;
+  if (encoder_bwd(e, nullptr, lengths, B, S, rw, &dy, &du_rows, s, below.empty() ? nullptr : below.data())) return 1;
   if (status_exchange(e, s)) return 1;
   if (backward_tail(e, ids, lengths, dy, B, S, rw, du_rows, s)) return 1;
   return status_finish(e, nullptr, s);
+}
+extern "C" int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                              const PlbPacking* pk, const float* d_hidden, void* stream) {
+  return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, nullptr, false, stream);
+}
+extern "C" int plb_encode_bwd_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
+                                     const PlbPacking* pk, const float* d_hidden, const float* const* d_below, void* stream) {
+  return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, d_below, true, stream);
 }

@@ -325,14 +325,14 @@ int qkvcol_rows(int B, int S);
 Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int prows = 0, int du_rows = 0);
 bool prune_enabled();
 int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B, int S, const Rows& rw, bool stash,
-                bf16_t** xout, hipStream_t s, const Prune* pr = nullptr);
+                bf16_t** xout, hipStream_t s, const Prune* pr = nullptr, const PlbLayerOutputs* taps = nullptr);
 int tn_splits(int64_t Mtot, int N, int K, int* rows_per_split);
 int weight_grad(PlbEngine* e, const bf16_t* A, int lda, int Ncols, const bf16_t* Bm, int ldb, int64_t Mtot, int N,
                 int K, float* out, hipStream_t s, bool side_slab = false);
 int weight_grad8(PlbEngine* e, const uint8_t* A8, const uint8_t* B8, int64_t Mtot, int N, int K, int site_a, int site_b,
                  float* out, hipStream_t s);
 int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, int S, const Rows& rw, bf16_t** dy,
-                int* du_rows, hipStream_t s);
+                int* du_rows, hipStream_t s, const float* const* d_below = nullptr);
 // engine_calls.cpp
 void drop_stash(PlbEngine* e, const char* by);
 void drop_final(PlbEngine* e, const char* by);

@@ -247,8 +247,23 @@ static int last_application_fwd_pruned(PlbEngine* e, const Prune* pr, bool stash
   return 0;
 }
 
+// Hidden-state slot `slot` of a call's taps (include/plbert.h: PlbLayerOutputs), when wanted: the fp32 image of the bf16 rows
+// x in the caller's [B,S,H] layout, zeros at the pad positions in both layouts (plb_encode's conversion pass).
+static int tap_hidden(PlbEngine* e, const PlbLayerOutputs* taps, int slot, const bf16_t* x, const int32_t* lengths, int B, int S,
+                      const Rows& rw, hipStream_t s) {
+  float* const out = (taps && taps->hidden_states) ? taps->hidden_states[slot] : nullptr;
+  if (!out) return 0;
+  if (lengths) TRY(plb_launch_unpack_rows(x, 1, e->H, rw.row_start, lengths, B, S, e->H, out, s));
+  else TRY(plb_launch_bf16_to_f32(x, e->H, out, e->H, rw.T, e->H, s));
+  return 0;
+}
+
 // Embeddings + L applications of the shared layer. stash: keep every layer's activations (training)
 // or reuse the layer-0 slots (inference). Returns the final hidden buffer in *xout.
+// taps (or null; never with a pruned last application): the per-application outputs the caller asked for — the map-in
+// output and every application's output as they are written, the attention probabilities from the qkv rows and the
+// log-sum-exp of the attention forward that has just run (without a stash the next application reuses that slot: stream
+// order protects it).
 // fp8 mode: EVERY large GEMM of the layer runs on 1-byte images — QKV, dense (+ LayerNorm 1), FFN up (+ gelu), FFN output
 // (+ LayerNorm 2) on e4m3 images of x, the attention context, a and gelu(u). Each image is written, with the scale its
 // site learnt in the previous call, by the launch that produces the tensor (the fused LayerNorm / gelu epilogues, the
@@ -256,7 +271,7 @@ static int last_application_fwd_pruned(PlbEngine* e, const Prune* pr, bool stash
 // call: the weight-gradient GEMMs read them all at the end of the backward. A calibration call (the first after
 // plb_set_fp8, and a training call whose gradient sites have not been seen yet) runs in bf16 and only records the maxima.
 int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B, int S, const Rows& rw, bool stash,
-                       bf16_t** xout, hipStream_t s, const Prune* pr) {
+                       bf16_t** xout, hipStream_t s, const Prune* pr, const PlbLayerOutputs* taps) {
   const int E = e->E, H = e->H, I = e->I, L = e->L;
   const int T = rw.T;
   const int64_t Tp = rw.Tp;
@@ -286,6 +301,7 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
   PlbGemmNT g = nt_desc(em.out, e->wbf(PLB_MAP_W), Tp, H, E);
   g.bias = e->par(PLB_MAP_B); g.C = first.x; g.ldc = H;
   TRY(plb_launch_gemm_nt(&g, 0, 0, s));
+  if (tap_hidden(e, taps, 0, first.x, lengths, B, S, rw, s)) return 1;
   if (f8) {  // layer 0 reads the map-in output, which no LayerNorm produced: one quantisation pass
     // (image and the site's maximum in one pass: the rows are contiguous)
     const F8Site sX(e, F8_X, 0);
@@ -329,6 +345,8 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
       if (at.ctx8) HIPTRY(hipMemsetAsync(sl.c8, 0, (size_t)T * H, s));
     }
     TRY(plb_launch_attn_fwd(&at, s));
+    if (float* const probs = (taps && taps->attentions) ? taps->attentions[l] : nullptr)
+      TRY(plb_launch_attn_probs(sl.qkv, 3 * H, sl.lse, lengths, rw.row_start, B, S, e->NH, at.scale, probs, s));
     // packed: the tail behind the last slot (up to 1,023 rows) is written by no attention workgroup, and what sits there
     // goes through dense / LayerNorm / FFN into the stash the weight-gradient GEMMs read: zeros, not whatever was there
     if (rw.row_start && Tp > T) {
@@ -371,6 +389,7 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
     if (gemm_ln_fwd(e, &g, f8 ? &o2 : nullptr, fuse_f, ln2_slot(e, sl), sl.y, T8, next8 ? sl.x8n : nullptr,
                     next8 ? F8Site(e, F8_X, l + 1) : F8Site(), s))
       return 1;
+    if (tap_hidden(e, taps, l + 1, sl.y, lengths, B, S, rw, s)) return 1;
     *xout = sl.y;
   }
   return 0;
@@ -505,10 +524,21 @@ static int last_application_bwd_pruned(PlbEngine* e, const Bwd& c, const Slots& 
 // End of application l's backward, on all rows: the attention backward of dCtx (o_dctx; ctx = the forward's attention
 // output), then dX = dQKV · Wqkv + res into dx — the gradient of LayerNorm 2's output of application l-1, whose backward
 // follows (in the GEMM's epilogue where fused) and writes dpre2 of application l-1.
+// d_in (or null): the caller's fp32 [B,S,H] gradient of hidden_states[l], the INPUT of application l (plb_encode_bwd_layers).
+// It must enter before the fused LayerNorm backward of application l-1 runs in the GEMM's epilogue, i.e. through res:
+// res' = res + d_in goes to o_da, which is dead here (dA of this application was consumed by its LayerNorm-1 backward; the
+// pruned path uses the buffer the same way); res itself (dpre1: the weight-gradient GEMMs read it) is left alone.
 static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, bf16_t* ctx, const bf16_t* res,
-                            bf16_t* dx) {
+                            bf16_t* dx, const float* d_in = nullptr) {
   const int H = e->H, T = c.T;
   hipStream_t s = c.s;
+  if (d_in) {
+    bf16_t* const res_in = e->at<bf16_t>(e->o_da);
+    HB_R(s, res, c.Tp * H * 2, "residual operand of the dX GEMM");
+    HB_W(s, res_in, c.Tp * H * 2, "residual operand + the caller's gradient of this application's input");
+    TRY(plb_launch_add_row_grad(res, d_in, c.lengths, c.row_start, c.B, c.S, H, (int)c.Tp, res_in, s));
+    res = res_in;
+  }
   const F8Site sDQ(e, F8_DQ, l);
   PlbAttn at;
   memset(&at, 0, sizeof(at));
@@ -552,7 +582,7 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
 // produces the gradient (fused LayerNorm-backward / gelu-backward epilogues, the attention-backward kernels, the
 // standalone LayerNorm backward), one image per layer for the weight-gradient GEMMs at the end.
 int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, int S, const Rows& rw, bf16_t** dy,
-                       int* du_rows, hipStream_t s) {
+                       int* du_rows, hipStream_t s, const float* const* d_below) {
   const int I = e->I, L = e->L;
   Bwd c;
   c.lengths = lengths; c.row_start = rw.row_start; c.B = B; c.S = S; c.T = rw.T; c.Tp = rw.Tp; c.s = s;
@@ -577,7 +607,7 @@ int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, in
       if (attention_bwd_dx(e, c, l, sl, e->at<bf16_t>(e->o_dy1), e->at<bf16_t>(e->o_da), dx)) return 1;
     } else {
       if (post_attention_bwd(e, c, l, sl, *dy)) return 1;
-      if (attention_bwd_dx(e, c, l, sl, sl.ctx, sl.dpre1, dx)) return 1;
+      if (attention_bwd_dx(e, c, l, sl, sl.ctx, sl.dpre1, dx, d_below ? d_below[l] : nullptr)) return 1;
     }
     bf16_t* tmp = *dy; *dy = dx; dx = tmp;
   }

@@ -260,6 +260,23 @@ int plb_launch_unpack_rows(const void* src, int src_is_bf16, int lds_, const int
 // positions. H a multiple of 4.
 int plb_launch_seed_dy(const float* d_hidden, const int32_t* lengths, const int32_t* row_start, int B, int S, int H, int Tp,
                        bf16_t* dy, hipStream_t stream);
+// ---- per-application outputs (layer_outputs.hip; include/plbert.h PlbLayerOutputs, plb_encode_bwd_layers)
+// The attention probabilities of one application from what it left behind: out fp32 [B,NH,S,S], out[b,h,i,j] =
+// exp(scale * q_i·k_j - LSE_i) for i, j < lengths[b] — qkv as PlbAttn.qkv (bf16 [T,ldqkv], Q | K | V, head h at columns
+// h*64.., 16-byte aligned, ldqkv % 8 == 0), lse as PlbAttn.lse ([B,NH,S], MINUS the log-sum-exp in raw-score units, as
+// plb_launch_attn_fwd stored it for the same qkv): one pass, no second normalisation. Key columns j >= lengths[b] and query
+// rows i >= lengths[b] are exact zeros; every element of out is written exactly once (no memset, no atomics). row_start
+// (or NULL; needs lengths): token-packed rows, sample b's position i is row row_start[b] + i; lse and out keep their (b, S)
+// indexing. lengths == NULL: S. Any S >= 1; 16-byte stores when S % 4 == 0 and out is 16-byte aligned.
+int plb_launch_attn_probs(const bf16_t* qkv, int ldqkv, const float* lse, const int32_t* lengths, const int32_t* row_start,
+                          int B, int S, int NH, float scale, float* out, hipStream_t stream);
+// A caller's fp32 gradient joins a bf16 residual operand: every one of the Tp rows of out [Tp,H] is written exactly once —
+// bf16(float(res[r,:]) + g[b,s,:]), rounded to nearest even, on row r = row_start[b] + s (row_start == NULL: b*S + s) for
+// s < lengths[b] (lengths == NULL, padded only: every position), res[r,:] unchanged on every other row: pad positions, the
+// rest of a 128-row slot, the tail up to Tp. res, out bf16 [Tp,H] (8-byte aligned, distinct or the same buffer); g fp32
+// [B,S,H] (16-byte aligned) is not read at pad positions. H a multiple of 4. Shape and argument rules of plb_launch_seed_dy.
+int plb_launch_add_row_grad(const bf16_t* res, const float* g, const int32_t* lengths, const int32_t* row_start, int B, int S,
+                            int H, int Tp, bf16_t* out, hipStream_t stream);
 // per row: loss_rows[j] = w*(lse - z[tgt]); dlogits[j,:] = w*(softmax - onehot) (bf16, zero padded to ldd cols)
 int plb_launch_ce_fwd_bwd(const float* logits, int ldl, int V, const int32_t* tgt, const float* w, int n, int npad,
                           float* loss_rows, bf16_t* dlogits, int ldd, hipStream_t stream);

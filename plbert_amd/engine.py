@@ -454,11 +454,88 @@ class HipEngine:
         self._last_encoder_call = (int(B), int(S), lens, packing)
         return hid, ph, tk
 
-    def encode(self, ids, lengths=None, packing=None):
+    # ---- per-application outputs (include/plbert.h: PlbLayerOutputs) ----
+    @staticmethod
+    def _slot_choice(want, n, what):
+        """True -> every slot, False / None -> none, a list -> those slots (negative indices count from the end)."""
+        if want is True:
+            return list(range(n))
+        if not want:
+            return []
+        idx = sorted({int(i) + n if int(i) < 0 else int(i) for i in want})
+        if idx and not (0 <= idx[0] and idx[-1] < n):
+            raise ValueError(f"{what}: slot outside [0, {n})")
+        return idx
+
+    def _alloc_layer_outputs(self, B, S, hidden_states, attentions):
+        """(hidden-state tensors [L+1], attention tensors [L]) with None in the slots not asked for; nothing is zeroed:
+        the call writes every element of what it is handed."""
+        nl, H, NH = self.cfg.num_hidden_layers, self.cfg.hidden_size, self.cfg.num_attention_heads
+        hs, at = [None] * (nl + 1), [None] * nl
+        for i in self._slot_choice(hidden_states, nl + 1, "hidden_states"):
+            hs[i] = torch.empty((B, S, H), dtype=torch.float32, device=self.device)
+        for i in self._slot_choice(attentions, nl, "attentions"):
+            at[i] = torch.empty((B, NH, S, S), dtype=torch.float32, device=self.device)
+        return hs, at
+
+    def _ptr_array(self, tensors, n, what, shape=None):
+        """Host array of n device pointers (None -> NULL) over ``tensors``, or None when there is nothing in it."""
+        if tensors is None:
+            return None
+        tensors = list(tensors)
+        if len(tensors) != n:
+            raise ValueError(f"{what}: {len(tensors)} entries, the model has {n} slots")
+        for t in tensors:
+            if t is not None and (t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()
+                                  or (shape is not None and tuple(t.shape) != tuple(shape))):
+                raise ValueError(f"{what}: every entry must be a contiguous fp32 tensor{'' if shape is None else ' ' + str(list(shape))} "
+                                 f"on {self.device}")
+        if all(t is None for t in tensors):
+            return None
+        return (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in tensors])
+
+    def _layer_outputs(self, hs, at, B, S):
+        """(PlbLayerOutputs or None, what must stay alive across the call)"""
+        nl, H, NH = self.cfg.num_hidden_layers, self.cfg.hidden_size, self.cfg.num_attention_heads
+        ha = self._ptr_array(hs, nl + 1, "hidden_states", (B, S, H))
+        aa = self._ptr_array(at, nl, "attentions", (B, NH, S, S))
+        if ha is None and aa is None:
+            return None, None
+        lo = _lib.PlbLayerOutputs(None if ha is None else C.addressof(ha), None if aa is None else C.addressof(aa))
+        return lo, (ha, aa)
+
+    def forward_layers(self, ids, lengths=None, packing=None, hidden_states=True, attentions=False, want_hidden=False,
+                       out=None):
+        """The encoder's per-application outputs (plb_forward_layers): ``hidden_states`` / ``attentions`` = True (every
+        slot), False, or a list of slots. Returns ``(hidden_states, attentions)``: lists of L + 1 fp32 [B,S,H] and of L
+        fp32 [B,NH,S,S] tensors with None in the slots not asked for; ``hidden_states[0]`` is the output of
+        embedding_hidden_mapping_in, ``hidden_states[l]`` the output of application l. Pad positions of every hidden
+        state and pad query rows / key columns of every attention map are zeros. ``want_hidden``: a third element, the
+        ``hidden`` of ``forward`` itself. ``out`` = (hidden-state list, attention list): the caller's tensors (None = slot
+        not wanted) instead of new ones. Works on inference-only engines, with a plan, and in fp8 mode."""
+        self._ensure_synced()
+        ids = self._dev_i64(ids)
+        B, S = ids.shape
+        lens = self._dev_i32(lengths)
+        with torch.cuda.device(self.device):
+            hs, at = self._alloc_layer_outputs(B, S, hidden_states, attentions) if out is None else (list(out[0]), list(out[1]))
+            hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device) if want_hidden else None
+            lo, keep = self._layer_outputs(hs, at, B, S)
+            pk = self._packing(packing, B, S)
+            _lib.check(self.L.plb_forward_layers(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
+                                                 None if pk is None else C.byref(pk), None if hid is None else hid.data_ptr(),
+                                                 None if lo is None else C.byref(lo), self._stream()), "plb_forward_layers")
+            del keep
+        self._last_encoder_call = (int(B), int(S), lens, packing)
+        return (hs, at, hid) if want_hidden else (hs, at)
+
+    def encode(self, ids, lengths=None, packing=None, layers=None):
         """Differentiable forward (include/plbert.h: plb_encode): ``.last_hidden_state`` fp32 [B,S,H] with every
         application's activations kept for ``encode_bwd``; ZEROS at pad positions. Training engines only, not in fp8
         mode. The ids, lengths and plan are remembered for the backward; any other computing call on this engine in
-        between (forward, a loss call, another encode, an optimizer step) ends the life of the kept activations."""
+        between (forward, a loss call, another encode, an optimizer step) ends the life of the kept activations.
+        ``layers`` = dict(hidden_states=True | False | slots, attentions=...) (plb_encode_layers): returns
+        ``(hidden, hidden_states, attentions)`` as ``forward_layers`` does."""
         if not self.train_mode:
             raise RuntimeError("this HipEngine was built with train=False (inference / validation only): encode() keeps "
                                "the activations of every layer for a backward")
@@ -471,32 +548,58 @@ class HipEngine:
         with torch.cuda.device(self.device):
             hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device)
             pk = self._packing(packing, B, S)
-            _lib.check(self.L.plb_encode(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
-                                         None if pk is None else C.byref(pk), hid.data_ptr(), self._stream()), "plb_encode")
+            if layers is None:
+                _lib.check(self.L.plb_encode(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
+                                             None if pk is None else C.byref(pk), hid.data_ptr(), self._stream()), "plb_encode")
+            else:
+                hs, at = self._alloc_layer_outputs(B, S, layers.get("hidden_states", False), layers.get("attentions", False))
+                lo, keep = self._layer_outputs(hs, at, B, S)
+                _lib.check(self.L.plb_encode_layers(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
+                                                    None if pk is None else C.byref(pk), hid.data_ptr(),
+                                                    None if lo is None else C.byref(lo), self._stream()), "plb_encode_layers")
+                del keep
         self._encode_serial = getattr(self, "_encode_serial", 0) + 1
         self._live_encode = (ids, lens, packing, B, S)   # (holds the tensors the backward reads again)
         self._last_encoder_call = (int(B), int(S), lens, packing)
-        return hid
+        return hid if layers is None else (hid, hs, at)
 
-    def encode_bwd(self, d_hidden):
+    def encode_bwd(self, d_hidden, d_below=None):
         """Backward of the live ``encode`` from ``d_hidden`` = d(loss)/d(hidden), fp32 [B,S,H] (values at pad positions
         are ignored): the encoder range of ``self.grads`` is overwritten, the phoneme head's is zeroed and the next
-        ``adamw_step`` leaves the head alone (plb_encode_bwd)."""
+        ``adamw_step`` leaves the head alone (plb_encode_bwd). ``d_below`` (plb_encode_bwd_layers): a list of L entries,
+        ``d_below[l]`` = d(loss)/d(hidden_states[l]) fp32 [B,S,H] or None; ``d_hidden`` may then be None (a zero gradient
+        at the last slot)."""
         live = getattr(self, "_live_encode", None)
         if live is None:
             raise RuntimeError("encode_bwd: no live encode() on this engine (one backward per encode)")
         ids, lens, packing, B, S = live
-        d = torch.as_tensor(d_hidden)
-        if d.dtype != torch.float32 or d.device != self.device or not d.is_contiguous():
-            d = d.to(device=self.device, dtype=torch.float32).contiguous()
-        if tuple(d.shape) != (B, S, self.cfg.hidden_size):
-            raise ValueError(f"d_hidden must be [{B}, {S}, {self.cfg.hidden_size}], got {tuple(d.shape)}")
+        shape = (B, S, self.cfg.hidden_size)
+
+        def dev(g, what):
+            if g is None:
+                return None
+            d = torch.as_tensor(g)
+            if d.dtype != torch.float32 or d.device != self.device or not d.is_contiguous():
+                d = d.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(d.shape) != shape:
+                raise ValueError(f"{what} must be {list(shape)}, got {tuple(d.shape)}")
+            return d
+
+        d = dev(d_hidden, "d_hidden")
+        if d_below is None and d is None:
+            raise ValueError("encode_bwd: d_hidden is None and no d_below is given")
+        below = None if d_below is None else [dev(g, f"d_below[{l}]") for l, g in enumerate(d_below)]
         self._live_encode = None
         with torch.cuda.device(self.device):
             pk = self._packing(packing, B, S)
-            _lib.check(self.L.plb_encode_bwd(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
-                                             None if pk is None else C.byref(pk), d.data_ptr(), self._stream()),
-                       "plb_encode_bwd")
+            args = (self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
+                    None if pk is None else C.byref(pk), None if d is None else d.data_ptr())
+            if below is None:
+                _lib.check(self.L.plb_encode_bwd(*args, self._stream()), "plb_encode_bwd")
+            else:
+                arr = self._ptr_array(below, self.cfg.num_hidden_layers, "d_below", shape)
+                _lib.check(self.L.plb_encode_bwd_layers(*args, None if arr is None else C.addressof(arr), self._stream()),
+                           "plb_encode_bwd_layers")
 
     def pooler(self, hidden):
         """tanh(pooler(hidden[:, 0])) (modeling_albert.py:403), fp32 [B,H]; ``hidden`` fp32 [B,S,H] on the device."""

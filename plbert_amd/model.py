@@ -23,6 +23,10 @@ returns a ``last_hidden_state`` that requires grad while the module is in traini
 enabled; ``backward()`` runs plb_encode_bwd and hands every encoder Parameter its slice of the
 engine's gradient buffer.  ``pooler_output`` is returned DETACHED (the pooler gets no gradient), and
 ``last_hidden_state`` is zero at pad positions.
+
+``output_hidden_states=True`` / ``output_attentions=True`` (transformers' arguments of ``AlbertModel.forward``) add
+``.hidden_states`` (the model after every application of the shared layer) and ``.attentions``; on the differentiable
+path every hidden state joins the graph (plb_encode_layers / plb_encode_bwd_layers), elsewhere plb_forward_layers runs.
 """
 from __future__ import annotations
 
@@ -42,9 +46,16 @@ _DEFAULT_MAX_BATCH = 32
 class BaseModelOutputWithPooling:
     last_hidden_state: torch.Tensor
     pooler_output: torch.Tensor | None = None
+    hidden_states: tuple | None = None   # output_hidden_states=True: L + 1 tensors, [0] = the map-in output, [-1] IS last_hidden_state
+    attentions: tuple | None = None      # output_attentions=True: L tensors [B,NH,S,S]
+
+    def to_tuple(self):
+        """The fields that are not None, in order (transformers' ModelOutput.to_tuple)."""
+        return tuple(v for v in (self.last_hidden_state, self.pooler_output, self.hidden_states, self.attentions)
+                     if v is not None)
 
     def __getitem__(self, i):
-        return (self.last_hidden_state, self.pooler_output)[i]
+        return self.to_tuple()[i]
 
 
 class _Leaf(nn.Module):
@@ -87,6 +98,31 @@ def _lengths_from_mask(attention_mask, strict=True):
     return lengths
 
 
+def _encode_backward(ctx, d_hidden, d_below):
+    """The backward of a differentiable forward (``ctx``: engine, names, serial): plb_encode_bwd[_layers], then every encoder
+    Parameter's view of its slice of ``engine.grads`` (None for the pooler and the heads)."""
+    eng = ctx.engine
+    gone = "a later engine call overwrote the activations of this forward (the engine keeps one differentiable " \
+           "forward at a time: call backward() before the next forward, loss call or optimizer step)"
+    if eng._live_encode is None or eng._encode_serial != ctx.serial:
+        raise RuntimeError(gone)
+    try:
+        if d_below is None:
+            eng.encode_bwd(d_hidden)
+        else:
+            eng.encode_bwd(d_hidden, d_below=d_below)
+    except RuntimeError as ex:
+        if "no live plb_encode stash" in str(ex):
+            raise RuntimeError(f"{gone}: {ex}") from ex
+        raise
+    end = eng.layout["phoneme_predictor.weight"][0]   # the encoder range of the flat buffers
+    grads = []
+    for n in ctx.names:
+        off, size, shp = eng.layout[n]
+        grads.append(eng.grads[off:off + size].view(shp) if off + size <= end else None)
+    return tuple(grads)
+
+
 class _Encode(torch.autograd.Function):
     """The differentiable forward as one autograd node: forward = plb_encode, backward = plb_encode_bwd on the upstream
     gradient; every encoder Parameter receives the view of its slice of ``engine.grads`` (the scheme of train._FusedLoss),
@@ -102,23 +138,32 @@ class _Encode(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad):
+        return (None,) * 5 + _encode_backward(ctx, grad.contiguous().float(), None)
+
+
+class _EncodeLayers(torch.autograd.Function):
+    """The differentiable forward with per-application outputs as ONE autograd node (plb_encode_layers /
+    plb_encode_bwd_layers). Outputs: the L + 1 hidden states (``want_hs``; else the last hidden state alone), then the L
+    attention maps (``want_at``), which are marked non-differentiable. The backward hands the gradient of the last slot to
+    the engine as d_hidden and those of the slots below as d_below; a slot nothing downstream used arrives as None and
+    goes in as a NULL pointer. Parameter gradients as in _Encode."""
+
+    @staticmethod
+    def forward(ctx, engine, names, ids, lengths, packing, want_hs, want_at, *params):
+        hid, hs, at = engine.encode(ids, lengths, packing, layers=dict(hidden_states=want_hs, attentions=want_at))
+        ctx.engine, ctx.names, ctx.serial, ctx.want_hs = engine, names, engine._encode_serial, want_hs
+        ctx.set_materialize_grads(False)
+        if want_at:
+            ctx.mark_non_differentiable(*at)
+        return (*(hs if want_hs else [hid]), *(at if want_at else []))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
         eng = ctx.engine
-        gone = "a later engine call overwrote the activations of this forward (the engine keeps one differentiable " \
-               "forward at a time: call backward() before the next forward, loss call or optimizer step)"
-        if eng._live_encode is None or eng._encode_serial != ctx.serial:
-            raise RuntimeError(gone)
-        try:
-            eng.encode_bwd(grad.contiguous().float())
-        except RuntimeError as ex:
-            if "no live plb_encode stash" in str(ex):
-                raise RuntimeError(f"{gone}: {ex}") from ex
-            raise
-        end = eng.layout["phoneme_predictor.weight"][0]   # the encoder range of the flat buffers
-        grads = []
-        for n in ctx.names:
-            off, size, shp = eng.layout[n]
-            grads.append(eng.grads[off:off + size].view(shp) if off + size <= end else None)
-        return (None, None, None, None, None, *grads)
+        nl = eng.cfg.num_hidden_layers
+        g = [None if x is None else x.contiguous().float() for x in grads[:nl + 1 if ctx.want_hs else 1]]
+        return (None,) * 7 + _encode_backward(ctx, g[-1], g[:-1] if ctx.want_hs else None)
 
 
 class AlbertModel(nn.Module):
@@ -188,12 +233,20 @@ class AlbertModel(nn.Module):
     def engine(self):
         return self._engine
 
-    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, **unused):
+    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None,
+                output_hidden_states=False, output_attentions=False, **unused):
+        """``output_hidden_states`` / ``output_attentions`` (transformers' arguments): ``.hidden_states`` = L + 1 tensors
+        [B,S,H] (the output of embedding_hidden_mapping_in, then of every application of the shared layer; the last one IS
+        ``last_hidden_state``), ``.attentions`` = L tensors [B,NH,S,S]. Pad positions of the hidden states, pad query rows
+        and pad key columns of the attention maps are ZEROS (transformers leaves values in pad rows). On the differentiable
+        path every hidden state carries gradient; the attention maps never do."""
         if input_ids is None:
             raise ValueError("input_ids is required (inputs_embeds is not supported on the HIP path)")
         if token_type_ids is not None or position_ids is not None:
             raise ValueError("the HIP path implements the reference's implicit token_type_ids=0 / position_ids=arange")
         lengths = _lengths_from_mask(attention_mask)
+        want_hs, want_at = bool(output_hidden_states), bool(output_attentions)
+        nl = self.config.num_hidden_layers
         if getattr(self, "differentiable", False) and self.training and torch.is_grad_enabled():
             # fine-tuning: the forward joins the autograd graph (_Encode); pad positions of last_hidden_state are zeros and
             # pooler_output is DETACHED (the pooler receives no gradient, as in every other call of this library)
@@ -201,9 +254,24 @@ class AlbertModel(nn.Module):
             for n, p in self.named_parameters():
                 names.append("encoder." + n)
                 params.append(p)
+            if want_hs or want_at:
+                outs = _EncodeLayers.apply(self._engine, names, input_ids, lengths,
+                                           _packing_from_lengths(self, lengths, input_ids), want_hs, want_at, *params)
+                hs = tuple(outs[:nl + 1]) if want_hs else None
+                hid = hs[-1] if want_hs else outs[0]
+                return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid.detach()),
+                                                  hidden_states=hs, attentions=tuple(outs[-nl:]) if want_at else None)
             hid = _Encode.apply(self._engine, names, input_ids, lengths, _packing_from_lengths(self, lengths, input_ids),
                                 *params)
             return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid.detach()))
+        if want_hs or want_at:
+            hs, at, hid = self._engine.forward_layers(input_ids, lengths, _packing_from_lengths(self, lengths, input_ids),
+                                                      hidden_states=want_hs, attentions=want_at, want_hidden=True)
+            if want_hs:
+                hid = hs[-1]   # (the same tensor object, as in transformers; unlike `hidden`, zeros at pad positions)
+            return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid),
+                                              hidden_states=tuple(hs) if want_hs else None,
+                                              attentions=tuple(at) if want_at else None)
         hid, _, _ = self._engine.forward(input_ids, lengths, want_hidden=True, want_phoneme=False,
                                          packing=_packing_from_lengths(self, lengths, input_ids))
         # pooler (modeling_albert.py:403): computed for API completeness (plb_pooler), never used by the loss
