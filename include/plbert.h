@@ -210,6 +210,50 @@ int plb_grad_norm(PlbEngine* e, double grad_scale, double max_norm, float* norm_
 int plb_adamw_step_clipped(PlbEngine* e, double lr, double beta1, double beta2, double eps, double weight_decay,
                            int32_t step, double grad_scale, const float* norm_buf, void* stream);
 
+/* ---- AdamW parameter groups and frozen tensors (opt-in: a step that calls none of these launches what it launched
+ * before) ----
+ * Stands in for torch.optim.AdamW([{"params": ..., "lr": ..., "betas": ..., "eps": ..., "weight_decay": ...}, ...]) and for
+ * requires_grad = False: every tensor of the flat layout belongs to one of n_groups hyper-parameter sets or is FROZEN.
+ * group_of: int32 [PLB_NPARAM] on the host, group_of[i] = the group of tensor i (enum PlbParam), -1 = frozen. The update
+ * stays ONE launch per range (the trainable range, the token head), with no further pass over the parameters: the range is
+ * cut into SEGMENTS, each with its own pre-rounded scalars, and the segment table travels as a kernel argument (no device
+ * table, no copy: the calls stay asynchronous and capturable). A frozen tensor is a hole between segments: neither its
+ * parameters nor its moments nor its bf16 copy are loaded or stored, as torch skips such a tensor and leaves its state alone.
+ * plb_adamw_plan (host only, no device access; works on an engine that was created and never bound): the live segments
+ *   the next plb_adamw_step_groups would launch, in flat-buffer order. begin / end: floats from the start of the flat
+ *   buffer, multiples of 4. The scalars are formed in DOUBLE and rounded to fp32 once, exactly as plb_adamw_step forms
+ *   them: decay = 1 - lr * weight_decay, omb1 = 1 - beta1, b2 = beta2, omb2 = 1 - beta2, eps, step_size =
+ *   lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step). Adjacent tensors of the same group whose rounded scalars and
+ *   step agree are merged into one segment. A frozen tensor does not appear; nor does a tensor the engine would not step
+ *   anyway, whatever group it was given (torch skips a parameter whose .grad is None): the pooler, the phoneme head after
+ *   plb_encode_bwd, the token head unless the last loss call was a dual-head one. Segments of the token head carry the token
+ *   head's own next step count (plb_token_head_steps + 1), all others `step`. segs has room for PLB_NPARAM entries.
+ * plb_adamw_step_groups: plb_adamw_step (norm_buf == NULL) or plb_adamw_step_clipped (norm_buf = what plb_grad_norm* wrote)
+ *   over that plan, with all of their bookkeeping: joins pending all-reduce pieces, ends a live plb_encode stash, the final
+ *   state and an accumulation window, refreshes the compute copies, counts a left-out update in word 1 (trainable range) /
+ *   word 2 (token head) of the health word and in norm_buf[3]. One group that holds every tensor gives plb_adamw_step's
+ *   (plb_adamw_step_clipped's) results bit for bit. A range without a live segment launches nothing; the token head's step
+ *   count advances only when the token head is stepped.
+ *   `step` is ONE count for all tensors outside the token head, as in plb_adamw_step. DEVIATION from torch, which keeps a
+ *   count per parameter: a tensor that was frozen for some steps and is thawed later continues with the shared count, not
+ *   with the number of steps it took itself (the deviation plb_encode_bwd documents for the phoneme head).
+ * plb_grad_norm_groups: plb_grad_norm with have_partials = 0, over the tensors with group_of[i] >= 0 only (a select, not a
+ *   product: a NaN in a frozen tensor's gradient does not reach the norm). Same norm_buf layout, same finish.
+ * Refused BEFORE anything is launched, with a text: n_groups < 1; a group_of entry outside [-1, n_groups); lr or eps
+ *   negative or not finite; a beta outside [0, 1); step < 1; optimizer buffers not bound; an inference-only engine. */
+typedef struct { double lr, beta1, beta2, eps, weight_decay; } PlbAdamWGroup;
+typedef struct {
+  int64_t begin, end;
+  int32_t group, step;
+  float decay, omb1, b2, omb2, eps, step_size, bc2_sqrt;
+} PlbAdamWSegment;
+int plb_adamw_plan(const PlbEngine* e, const PlbAdamWGroup* groups, int32_t n_groups, const int32_t* group_of, int32_t step,
+                   PlbAdamWSegment* segs, int32_t* n_segs);
+int plb_adamw_step_groups(PlbEngine* e, const PlbAdamWGroup* groups, int32_t n_groups, const int32_t* group_of, int32_t step,
+                          double grad_scale, const float* norm_buf, void* stream);
+int plb_grad_norm_groups(PlbEngine* e, const int32_t* group_of, double grad_scale, double max_norm, float* norm_buf,
+                         void* stream);
+
 /* fp8 mode (BASELINE.json configs[4]): EVERY projection GEMM of the shared layer runs on OCP fp8 operands with fp32
  * accumulation through the block-scaled MFMA with unit block scales (twice the bf16 MFMA rate) — forward: QKV, dense
  * (+ LayerNorm 1), FFN up (+ gelu_new), FFN output (+ LayerNorm 2); backward: the four dX GEMMs (two of them carrying a

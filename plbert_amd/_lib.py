@@ -115,6 +115,19 @@ class PlbPacking(C.Structure):
     _fields_ = [("row_start", C.c_void_p), ("rows", C.c_int32), ("used", C.c_int32)]
 
 
+class PlbAdamWGroup(C.Structure):
+    """include/plbert.h: one set of AdamW hyper-parameters (doubles, as torch holds them)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double)]
+
+
+class PlbAdamWSegment(C.Structure):
+    """include/plbert.h: one live segment of a grouped AdamW step with its pre-rounded scalars (plb_adamw_plan)."""
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("group", C.c_int32), ("step", C.c_int32),
+                ("decay", C.c_float), ("omb1", C.c_float), ("b2", C.c_float), ("omb2", C.c_float), ("eps", C.c_float),
+                ("step_size", C.c_float), ("bc2_sqrt", C.c_float)]
+
+
 class PlbLayerOutputs(C.Structure):
     """include/plbert.h: per-application outputs of plb_forward_layers / plb_encode_layers — two HOST arrays of device
     pointers (L + 1 hidden-state slots, L attention maps; an entry or a whole array may be NULL)."""
@@ -210,6 +223,9 @@ PUBLIC = {
     "plb_grad_accum_add": (i32, [vp, i32, vp, vp]),
     "plb_grad_norm": (i32, [vp, f64, f64, vp, i32, vp]),
     "plb_adamw_step_clipped": (i32, [vp, f64, f64, f64, f64, f64, i32, f64, vp, vp]),
+    "plb_adamw_plan": (i32, [vp, P(PlbAdamWGroup), i32, P(i32), i32, P(PlbAdamWSegment), P(i32)]),
+    "plb_adamw_step_groups": (i32, [vp, P(PlbAdamWGroup), i32, P(i32), i32, f64, vp, vp]),
+    "plb_grad_norm_groups": (i32, [vp, P(i32), f64, f64, vp, vp]),
     "plb_set_fp8": (i32, [vp, i32, vp]),
     "plb_fp8_state": (i32, [vp, P(i32), P(i32)]),
     "plb_fp8_stats": (i32, [vp, P(f32), P(f32), vp]),
@@ -326,6 +342,8 @@ INTERNAL = {
     "plb_launch_grad_sumsq": (i32, [vp, sz, vp, vp]),
     "plb_launch_grad_norm_finish": (i32, [vp, i32, f64, f64, vp, vp]),
     "plb_launch_adamw_clipped": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i32, f64, vp, i32, vp, i32, vp]),
+    "plb_launch_adamw_segments": (i32, [vp, vp, vp, vp, vp, sz, P(PlbAdamWSegment), i32, f64, vp, i32, vp, i32, vp]),
+    "plb_launch_grad_sumsq_segments": (i32, [vp, sz, P(PlbAdamWSegment), i32, vp, vp]),
     "plb_launch_step_status": (i32, [vp, vp, vp, vp, vp]),
     "plb_launch_status_export": (i32, [vp, vp, vp]),
     "plb_launch_cast_bf16": (i32, [vp, vp, sz, vp]),

@@ -1,8 +1,11 @@
-// Gradient accumulation, the global gradient norm and the clipped AdamW update (include/plbert.h: plb_grad_accum_*,
-// plb_grad_norm, plb_adamw_step_clipped). Host bookkeeping of a window of micro-steps plus launches of optim.hip; no
-// workspace of its own: the accumulator and the norm buffer are the caller's. Only writer of PlbEngine's accumulation
-// block (grads_fresh / norm_nparts are also reset by begin_training_call, engine_calls.cpp); after a LAST add it sets
-// head_grads_live, tok_grads_live and grads_reduced to what the window accumulated.
+// Gradient accumulation, the global gradient norm, the clipped AdamW update and the grouped forms of norm and update
+// (include/plbert.h: plb_grad_accum_*, plb_grad_norm, plb_adamw_step_clipped; plb_adamw_plan, plb_adamw_step_groups,
+// plb_grad_norm_groups). Host bookkeeping of a window of micro-steps plus launches of optim.hip; no workspace of its own:
+// the accumulator and the norm buffer are the caller's. Only writer of PlbEngine's accumulation block (grads_fresh /
+// norm_nparts are also reset by begin_training_call, engine_calls.cpp); after a LAST add it sets head_grads_live,
+// tok_grads_live and grads_reduced to what the window accumulated.
+#include <cmath>
+
 #include "engine_internal.h"
 
 void end_accum_window(PlbEngine* e, const char* by) {
@@ -168,4 +171,170 @@ extern "C" int plb_adamw_step_clipped(PlbEngine* e, double lr, double beta1, dou
                                  e->at<unsigned int>(e->o_lnerr), 2, norm, 0, s));
   }
   return sync_transposes(e, s, false);
+}
+
+// ---- parameter groups and frozen tensors (include/plbert.h: plb_adamw_plan, plb_adamw_step_groups, plb_grad_norm_groups)
+namespace {
+// The tensors the next AdamW entry steps, whatever the caller's groups say: plb_adamw_step's ranges
+bool steps_tensor(const PlbEngine* e, int i) {
+  if (e->psize[i] == 0 || i == PLB_POOL_W || i == PLB_POOL_B) return false;
+  if (i == PLB_HEAD_W || i == PLB_HEAD_B) return e->head_grads_live;
+  if (i == PLB_TOK_W || i == PLB_TOK_B) return e->tok_grads_live && e->NT > 0;
+  return true;
+}
+bool in_token_head(int i) { return i == PLB_TOK_W || i == PLB_TOK_B; }
+
+int check_group_of(const PlbEngine* e, const int32_t* group_of, int32_t n_groups, const char* who) {
+  if (!e) return fail("%s: null engine", who);
+  if (!group_of) return fail("%s: group_of is null", who);
+  if (n_groups < 1) return fail("%s: n_groups %d: there must be at least one group", who, n_groups);
+  for (int i = 0; i < PLB_NPARAM; ++i)
+    if (group_of[i] < -1 || group_of[i] >= n_groups)
+      return fail("%s: group_of[%d] = %d is outside [-1, %d)", who, i, group_of[i], n_groups);
+  return 0;
+}
+
+// The scalars of one group at one step count: formed in double, rounded once (optim.hip: plb_launch_adamw)
+void group_scalars(const PlbAdamWGroup& g, int step, PlbAdamWSegment* s) {
+  const double bc1 = 1.0 - pow(g.beta1, step), bc2 = 1.0 - pow(g.beta2, step);
+  s->step = step;
+  s->decay = (float)(1.0 - g.lr * g.weight_decay);
+  s->omb1 = (float)(1.0 - g.beta1);
+  s->b2 = (float)g.beta2;
+  s->omb2 = (float)(1.0 - g.beta2);
+  s->eps = (float)g.eps;
+  s->step_size = (float)(g.lr / bc1);
+  s->bc2_sqrt = (float)sqrt(bc2);
+}
+bool same_scalars(const PlbAdamWSegment& a, const PlbAdamWSegment& b) {
+  return a.group == b.group && a.step == b.step && !memcmp(&a.decay, &b.decay, 7 * sizeof(float));
+}
+
+// groups == null: the live tensors only (plb_grad_norm_groups), merged wherever they are adjacent
+int plan_segments(const PlbEngine* e, const PlbAdamWGroup* groups, const int32_t* group_of, int32_t step,
+                  PlbAdamWSegment* segs) {
+  int n = 0;
+  for (int i = 0; i < PLB_NPARAM; ++i) {
+    if (group_of[i] < 0 || !steps_tensor(e, i)) continue;
+    PlbAdamWSegment s;
+    memset(&s, 0, sizeof(s));
+    s.begin = e->poff[i];
+    s.end = e->poff[i] + e->psize[i];
+    s.step = 1;
+    if (groups) {
+      s.group = group_of[i];
+      group_scalars(groups[group_of[i]], in_token_head(i) ? e->tok_steps + 1 : step, &s);
+    }
+    // (the pooler lies between the trainable range and the token head: no segment reaches from one launch into the other)
+    if (n && segs[n - 1].end == s.begin && same_scalars(segs[n - 1], s)) segs[n - 1].end = s.end;
+    else segs[n++] = s;
+  }
+  return n;
+}
+
+int check_groups(const PlbAdamWGroup* groups, int32_t n_groups, int32_t step, const char* who) {
+  if (!groups) return fail("%s: groups is null", who);
+  for (int k = 0; k < n_groups; ++k) {
+    const PlbAdamWGroup& g = groups[k];
+    if (!(g.lr >= 0.0) || !std::isfinite(g.lr)) return fail("%s: group %d: lr %g is negative or not finite", who, k, g.lr);
+    if (!(g.eps >= 0.0) || !std::isfinite(g.eps)) return fail("%s: group %d: eps %g is negative or not finite", who, k, g.eps);
+    if (!(g.beta1 >= 0.0 && g.beta1 < 1.0)) return fail("%s: group %d: beta1 %g is outside [0, 1)", who, k, g.beta1);
+    if (!(g.beta2 >= 0.0 && g.beta2 < 1.0)) return fail("%s: group %d: beta2 %g is outside [0, 1)", who, k, g.beta2);
+    if (!std::isfinite(g.weight_decay)) return fail("%s: group %d: weight_decay is not finite", who, k);
+  }
+  if (step < 1) return fail("%s: step counts from 1", who);
+  return 0;
+}
+
+// The segments of [a, b) among segs, rebased to a
+int range_segments(const PlbAdamWSegment* segs, int n, int64_t a, int64_t b, PlbAdamWSegment* out) {
+  int k = 0;
+  for (int i = 0; i < n; ++i)
+    if (segs[i].begin >= a && segs[i].end <= b) {
+      out[k] = segs[i];
+      out[k].begin -= a;
+      out[k++].end -= a;
+    }
+  return k;
+}
+}  // namespace
+
+extern "C" int plb_adamw_plan(const PlbEngine* e, const PlbAdamWGroup* groups, int32_t n_groups, const int32_t* group_of,
+                              int32_t step, PlbAdamWSegment* segs, int32_t* n_segs) {
+  if (check_group_of(e, group_of, n_groups, "plb_adamw_plan")) return 1;
+  if (check_groups(groups, n_groups, step, "plb_adamw_plan")) return 1;
+  if (!segs || !n_segs) return fail("plb_adamw_plan: null output");
+  if (e->infer) return fail("plb_adamw_plan: inference-only engine");
+  *n_segs = plan_segments(e, groups, group_of, step, segs);
+  return 0;
+}
+
+extern "C" int plb_adamw_step_groups(PlbEngine* e, const PlbAdamWGroup* groups, int32_t n_groups, const int32_t* group_of,
+                                     int32_t step, double grad_scale, const float* norm_buf, void* stream) {
+  if (!e || !e->ws || !e->grads || !e->m || !e->v) return fail("plb_adamw_step_groups: optimizer buffers not bound");
+  if (e->infer) return fail("plb_adamw_step_groups: inference-only engine");
+  if (check_group_of(e, group_of, n_groups, "plb_adamw_step_groups")) return 1;
+  if (check_groups(groups, n_groups, step, "plb_adamw_step_groups")) return 1;
+  drop_stash(e, "plb_adamw_step_groups moved the weights since");
+  drop_final(e, "plb_adamw_step_groups moved the weights since: ask between the loss call and the optimizer step");
+  end_accum_window(e, "plb_adamw_step_groups moved the weights");
+  hipStream_t s = (hipStream_t)stream;
+  if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
+    HIPTRY(ev_wait(e, s, e->ev_comm_done));
+    e->comm_pending = false;
+  }
+  float* norm = const_cast<float*>(norm_buf);   // (the launch counts the updates it leaves out in norm[3])
+  HB_R(s, e->grads, e->ptotal * 4, "grouped AdamW (reads the gradient buffer)");
+  if (norm) HB_W(s, norm, 16, "grouped AdamW (reads the coefficient, counts a left-out update)");
+  PlbAdamWSegment all[PLB_NPARAM], part[PLB_NPARAM];
+  const int n = plan_segments(e, groups, group_of, step, all);
+  // the ranges, the step counts and the skip word are plb_adamw_step's; a range without a live segment launches nothing
+  const int n_main = range_segments(all, n, 0, e->ptrain, part);
+  if (n_main)
+    TRY(plb_launch_adamw_segments(e->params, e->grads, e->m, e->v, e->at<bf16_t>(e->o_wbf), (size_t)part[n_main - 1].end, part,
+                                  n_main, grad_scale, e->at<unsigned int>(e->o_lnerr), 1, norm, 1, s));
+  const int64_t o = e->poff[PLB_TOK_W];
+  const int n_tok = range_segments(all, n, o, e->ptotal, part);
+  if (n_tok) {
+    e->tok_steps += 1;   // (the plan gave these segments tok_steps + 1)
+    TRY(plb_launch_adamw_segments(e->params + o, e->grads + o, e->m + o, e->v + o, e->at<bf16_t>(e->o_wbf) + o,
+                                  (size_t)part[n_tok - 1].end, part, n_tok, grad_scale, e->at<unsigned int>(e->o_lnerr), 2, norm,
+                                  0, s));
+  }
+  return sync_transposes(e, s, false);
+}
+
+extern "C" int plb_grad_norm_groups(PlbEngine* e, const int32_t* group_of, double grad_scale, double max_norm, float* norm_buf,
+                                    void* stream) {
+  if (!e) return fail("plb_grad_norm_groups: null engine");
+  if (e->infer) return fail("plb_grad_norm_groups: inference-only engine");
+  if (check_group_of(e, group_of, 1 << 30, "plb_grad_norm_groups")) return 1;
+  if (!norm_buf || ((uintptr_t)norm_buf & 15)) return fail("plb_grad_norm_groups: norm_buf must be a 16-byte aligned device buffer");
+  if (!e->ws || !e->grads) return fail("plb_grad_norm_groups: gradient buffer not bound");
+  hipStream_t s = (hipStream_t)stream;
+  if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
+    HIPTRY(ev_wait(e, s, e->ev_comm_done));
+    e->comm_pending = false;
+  }
+  PlbAdamWSegment all[PLB_NPARAM], part[PLB_NPARAM];
+  const int n = plan_segments(e, nullptr, group_of, 1, all);
+  // plb_grad_norm's ranges, grids and partial slots; holes contribute exact zeros
+  const int64_t nstep = e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W];
+  HB_R(s, e->grads, nstep * 4, "gradient norm (reads the gradient buffer)");
+  HB_W(s, norm_buf + 4, PLB_NORM_PARTS * 4, "gradient norm (writes the partial sums)");
+  TRY(plb_launch_grad_sumsq_segments(e->grads, (size_t)nstep, part, range_segments(all, n, 0, nstep, part), norm_buf + 4, s));
+  int nparts = PLB_NORM_PARTS;
+  if (e->tok_grads_live && e->NT > 0) {
+    const int64_t o = e->poff[PLB_TOK_W];
+    HB_R(s, e->grads + o, (e->ptotal - o) * 4, "gradient norm (reads the token head's gradients)");
+    HB_W(s, norm_buf + 4 + nparts, PLB_NORM_PARTS * 4, "gradient norm (writes the partial sums)");
+    TRY(plb_launch_grad_sumsq_segments(e->grads + o, (size_t)(e->ptotal - o), part, range_segments(all, n, o, e->ptotal, part),
+                                       norm_buf + 4 + nparts, s));
+    nparts += PLB_NORM_PARTS;
+  }
+  e->norm_nparts = 0;   // (these partials are not a LAST add's: a later have_partials call must not take them for such)
+  HB_R(s, norm_buf + 4, (size_t)nparts * 4, "gradient norm (reads the partial sums)");
+  HB_W(s, norm_buf, 16, "gradient norm (writes norm, coefficient and flag)");
+  TRY(plb_launch_grad_norm_finish(norm_buf + 4, nparts, grad_scale, max_norm, norm_buf, s));
+  return 0;
 }

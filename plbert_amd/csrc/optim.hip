@@ -1,5 +1,6 @@
 // Optimizer of the PL-BERT step, gfx950 (A12): AdamW, gradient accumulation, the global gradient norm with the clipped
-// update (include/plbert.h: plb_grad_accum_add, plb_grad_norm, plb_adamw_step_clipped), and the step status word.
+// update (include/plbert.h: plb_grad_accum_add, plb_grad_norm, plb_adamw_step_clipped), their segmented forms for parameter
+// groups and frozen tensors (plb_adamw_step_groups, plb_grad_norm_groups), and the step status word.
 // HBM-bound (30 B/param). Plain float4 loads and stores, no atomics on gradient data, fixed summation order: bitwise
 // reproducible from run to run. adamw_kernel and adamw_clipped_kernel stay two kernels: at coef == 1 their outputs are
 // bit-identical, and tests/test_gpu_grad_accum.py holds one against the other.
@@ -214,6 +215,152 @@ extern "C" int plb_launch_adamw_clipped(float* p, const float* g, float* m, floa
                      (float)(1.0 - lr * wd), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
                      (float)(lr / bc1), (float)sqrt(bc2), (float)grad_scale, skip_if_nonzero, count_skip, norm,
                      count_nonfinite);
+  return LAUNCH_OK();
+}
+
+namespace {
+// ---- segmented AdamW and the masked sum of squares (include/plbert.h: plb_adamw_step_groups, plb_grad_norm_groups).
+// The live segments of one flat range, passed BY VALUE as a kernel argument (about 1 KiB of the kernarg segment: no device
+// table, no copy, the launch stays asynchronous and capturable). Bounds count float4s: every boundary is a multiple of 4
+// floats (checked by the launcher), so a float4 never straddles one. Segments are sorted and disjoint; whatever lies
+// between them is a hole.
+struct AdamWSegTable {
+  int n;
+  unsigned int b4[PLB_NPARAM], e4[PLB_NPARAM];   // [b4, e4) in float4s
+  float sc[PLB_NPARAM][7];                       // decay, 1 - beta1, beta2, 1 - beta2, eps, lr / bc1, sqrt(bc2)
+};
+// The first segment that ends behind float4 q (t.n: none does); q wave-uniform: scalar loads and compares
+DEVI int seg_behind(const AdamWSegTable& t, unsigned int q) {
+  int s = 0;
+  while (s < t.n && t.e4[s] <= q) ++s;
+  return s;
+}
+
+// One pass over [0, n): adamw_clipped_body with the scalars of the segment each float4 lies in; a float4 in a hole is
+// neither loaded nor stored. A 256-thread workgroup covers 1024 floats and bias tensors are 128 to 1024 floats long, so a
+// workgroup can straddle several boundaries: the workgroup looks up the first segment that reaches into it (seg_behind:
+// uniform, scalar loads and compares); if that segment covers all of it the scalars stay uniform, otherwise every lane selects
+// its own among the segments that overlap the workgroup. skip / norm: adamw_clipped_kernel's tests in its order. NORM = false
+// (the launcher's norm == null): coef = 1, no flag test, and only the unclipped body is compiled in. A single segment over
+// [0, n) gives plb_launch_adamw's (with norm: plb_launch_adamw_clipped's) bits.
+template <bool NORM>
+__global__ __launch_bounds__(256) void adamw_segments_kernel(float* p, const float* g, float* m, float* v, bf16_t* pb,
+                                                             AdamWSegTable t, float gscale, unsigned int* skip,
+                                                             int count_skip, float* norm, int count_nonfinite) {
+  if (skip && *skip) {
+    if (count_skip && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(skip + count_skip, 1u);
+    return;
+  }
+  float coef = 1.0f;
+  if (NORM) {
+    if (norm[2] != 0.f) {
+      if (count_nonfinite && blockIdx.x == 0 && threadIdx.x == 0) norm[3] += 1.f;
+      return;
+    }
+    coef = norm[1];
+  }
+  const unsigned int q0 = blockIdx.x * 256u, qend = q0 + 256u, q = q0 + threadIdx.x;   // (the grid ends at the last e4)
+  const int s = seg_behind(t, q0);
+  if (s == t.n || t.b4[s] >= qend) return;   // the whole workgroup lies in a hole
+  float decay = t.sc[s][0], omb1 = t.sc[s][1], b2 = t.sc[s][2], omb2 = t.sc[s][3], eps = t.sc[s][4], step = t.sc[s][5],
+        bc2_sqrt = t.sc[s][6];
+  bool live = q >= t.b4[s] && q < t.e4[s];
+  for (int k = s + 1; k < t.n && t.b4[k] < qend; ++k) {   // (no trip when segment s covers the workgroup)
+    if (q >= t.b4[k] && q < t.e4[k]) {
+      live = true;
+      decay = t.sc[k][0]; omb1 = t.sc[k][1]; b2 = t.sc[k][2]; omb2 = t.sc[k][3]; eps = t.sc[k][4]; step = t.sc[k][5];
+      bc2_sqrt = t.sc[k][6];
+    }
+  }
+  if (!live) return;
+  const size_t i = (size_t)q * 4;
+  if (!NORM || coef == 1.0f) adamw_clipped_body<false>(p, g, m, v, pb, i, decay, omb1, b2, omb2, eps, step, bc2_sqrt, gscale, coef);
+  else adamw_clipped_body<true>(p, g, m, v, pb, i, decay, omb1, b2, omb2, eps, step, bc2_sqrt, gscale, coef);
+}
+
+// grad_accum_kernel's phase 4 (same grid, same chunk, same order of additions) with the float4s of the holes replaced by
+// zeros: a SELECT, not a product — a NaN or Inf in a frozen tensor's gradient never reaches the sum, and since
+// fma(0, 0, s) == s the partials are the bits plb_launch_grad_sumsq gives on a copy whose holes were zero-filled.
+__global__ __launch_bounds__(256) void grad_sumsq_segments_kernel(const float* grads, size_t n, size_t chunk, AdamWSegTable t,
+                                                                  float* partials) {
+  __shared__ float red[4];
+  const size_t begin = (size_t)blockIdx.x * chunk;
+  const size_t end = begin + chunk < n ? begin + chunk : n;
+  float acc = 0.f;
+  int s = begin < end ? seg_behind(t, (unsigned int)(begin / 4)) : t.n;
+  if (s < t.n && t.b4[s] <= begin / 4 && t.e4[s] >= end / 4) {   // one segment covers the chunk: grad_accum_kernel's loop
+    for (size_t i = begin + (size_t)threadIdx.x * 4; i < end; i += 1024) {
+      const float4 r = *(const float4*)(grads + i);
+      acc = __builtin_fmaf(r.x, r.x, acc); acc = __builtin_fmaf(r.y, r.y, acc);
+      acc = __builtin_fmaf(r.z, r.z, acc); acc = __builtin_fmaf(r.w, r.w, acc);
+    }
+  } else if (s < t.n && t.b4[s] < end / 4) {   // (else the chunk is empty or lies in a hole: 0)
+    for (size_t base = begin; base < end; base += 1024) {   // one pass of the workgroup: float4s [q0, qend)
+      const size_t q0 = base / 4, qend = (base + 1024 < end ? base + 1024 : end) / 4, q = q0 + threadIdx.x;
+      while (s < t.n && t.e4[s] <= q0) ++s;
+      bool live = false;
+      for (int k = s; k < t.n && t.b4[k] < qend; ++k) live = live || (q >= t.b4[k] && q < t.e4[k]);
+      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (q < qend) {
+        if (live) r = *(const float4*)(grads + q * 4);
+        acc = __builtin_fmaf(r.x, r.x, acc); acc = __builtin_fmaf(r.y, r.y, acc);
+        acc = __builtin_fmaf(r.z, r.z, acc); acc = __builtin_fmaf(r.w, r.w, acc);
+      }
+    }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// The launchers' checks and the table: at most PLB_NPARAM segments, sorted, disjoint, not empty, inside [0, n), every
+// boundary a multiple of 4 floats, step >= 1. Returns false on a refusal.
+bool seg_table(const PlbAdamWSegment* segs, int n_segs, size_t n, AdamWSegTable* t) {
+  if (n_segs < 0 || n_segs > PLB_NPARAM || (n_segs && !segs) || n % 4 || n / 4 > 0x7fffffffu) return false;
+  *t = AdamWSegTable{};
+  int64_t prev = 0;
+  for (int i = 0; i < n_segs; ++i) {
+    const PlbAdamWSegment& sg = segs[i];
+    if (sg.begin < prev || sg.end <= sg.begin || sg.end > (int64_t)n || sg.begin % 4 || sg.end % 4 || sg.step < 1) return false;
+    prev = sg.end;
+    t->b4[i] = (unsigned int)(sg.begin / 4);
+    t->e4[i] = (unsigned int)(sg.end / 4);
+    const float sc[7] = {sg.decay, sg.omb1, sg.b2, sg.omb2, sg.eps, sg.step_size, sg.bc2_sqrt};
+    for (int j = 0; j < 7; ++j) t->sc[i][j] = sc[j];
+  }
+  t->n = n_segs;
+  return true;
+}
+}  // namespace
+extern "C" int plb_launch_adamw_segments(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, size_t n,
+                                         const PlbAdamWSegment* segs, int n_segs, double grad_scale,
+                                         unsigned int* skip_if_nonzero, int count_skip, float* norm, int count_nonfinite,
+                                         hipStream_t stream) {
+  AdamWSegTable t;
+  if (!seg_table(segs, n_segs, n, &t)) return 1;
+  if (!n_segs) return 0;
+  size_t live = 0;
+  for (int i = 0; i < n_segs; ++i) live += (size_t)(segs[i].end - segs[i].begin);
+  ProfScope ps(PLB_K_ADAMW, stream, 0, (double)live * 30.0);  // p,m,v read+write, g read, bf16 copy: live segments only
+  const dim3 grid((t.e4[n_segs - 1] + 255u) / 256u);
+  if (norm)
+    hipLaunchKernelGGL(adamw_segments_kernel<true>, grid, dim3(256), 0, stream, p, g, m, v, p_bf16, t, (float)grad_scale,
+                       skip_if_nonzero, count_skip, norm, count_nonfinite);
+  else
+    hipLaunchKernelGGL(adamw_segments_kernel<false>, grid, dim3(256), 0, stream, p, g, m, v, p_bf16, t, (float)grad_scale,
+                       skip_if_nonzero, count_skip, norm, count_nonfinite);
+  return LAUNCH_OK();
+}
+extern "C" int plb_launch_grad_sumsq_segments(const float* grads, size_t n, const PlbAdamWSegment* segs, int n_segs,
+                                              float* partials, hipStream_t stream) {
+  AdamWSegTable t;
+  if (!grads || !partials || ((uintptr_t)grads & 15) || !seg_table(segs, n_segs, n, &t)) return 1;
+  size_t live = 0;
+  for (int i = 0; i < n_segs; ++i) live += (size_t)(segs[i].end - segs[i].begin);
+  ProfScope ps(PLB_K_REDUCE, stream, 0, (double)live * 4.0);
+  hipLaunchKernelGGL(grad_sumsq_segments_kernel, dim3(PLB_NORM_PARTS), dim3(256), 0, stream, grads, n, plb_norm_chunk(n), t,
+                     partials);
   return LAUNCH_OK();
 }
 

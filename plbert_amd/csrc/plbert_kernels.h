@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/plbert.h"   // PLB_NPARAM, PlbAdamWSegment (the segmented optimizer launches)
+
 typedef uint16_t bf16_t;
 
 extern "C" {
@@ -421,6 +423,22 @@ int plb_launch_adamw_clipped(float* p, const float* g, float* m, float* v, bf16_
                              double beta2, double eps, double wd, int step, double grad_scale,
                              unsigned int* skip_if_nonzero, int count_skip, float* norm, int count_nonfinite,
                              hipStream_t stream);
+// ---- segmented AdamW and the masked sum of squares (optim.hip; include/plbert.h plb_adamw_step_groups /
+// plb_grad_norm_groups). segs: HOST array of at most PLB_NPARAM live segments of [0, n) (begin / end in floats relative to
+// p, sorted, disjoint, not empty, every boundary a multiple of 4; `group` is not read) with their pre-rounded scalars, as
+// plb_adamw_plan forms them; the launchers copy them into a by-value kernel argument — nothing is read after the call
+// returns. What lies between the segments is a hole: no load and no store of p, m, v or the bf16 copy there.
+// One pass over [0, n) with each float4's own segment's scalars. norm == null: plb_launch_adamw's arithmetic (one live
+// segment over [0, n): its bits); else plb_launch_adamw_clipped's, with its norm[2] / norm[3] semantics. The skip word is
+// tested first, as there. Refused (1): a boundary that is no multiple of 4, unsorted or overlapping segments, more than
+// PLB_NPARAM of them, a segment outside [0, n), step < 1. n_segs == 0 launches nothing.
+int plb_launch_adamw_segments(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, size_t n,
+                              const PlbAdamWSegment* segs, int n_segs, double grad_scale, unsigned int* skip_if_nonzero,
+                              int count_skip, float* norm, int count_nonfinite, hipStream_t stream);
+// plb_launch_grad_sumsq (same grid, chunk and order of additions) with every float4 of a hole taken as zeros (a select: a
+// NaN there does not reach the sum): the partials are bit-identical to plb_launch_grad_sumsq's on a zero-filled copy.
+int plb_launch_grad_sumsq_segments(const float* grads, size_t n, const PlbAdamWSegment* segs, int n_segs, float* partials,
+                                   hipStream_t stream);
 // End of a loss call: mirror the hand-off error word into host-visible memory (host_mirror: device pointer of a pinned
 // host word) and, when it is non-zero, overwrite the loss with NaN — whoever reads the loss sees that the step is invalid
 int plb_launch_step_status(unsigned int* ln_err, float* loss, unsigned int* host_mirror, const float* summed, hipStream_t stream);

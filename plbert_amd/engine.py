@@ -808,6 +808,49 @@ class HipEngine:
                            "plb_adamw_step_clipped")
         self._synced_version = self.params._version
 
+    # ---- parameter groups and frozen tensors (include/plbert.h: plb_adamw_plan, plb_adamw_step_groups) ----
+    @staticmethod
+    def _groups_c(groups, group_of):
+        """The C arrays of ``groups`` (dicts with lr, betas, eps, weight_decay) and ``group_of``: a sequence of
+        PLB_NPARAM group indices in flat-buffer order (-1: frozen), or a dict {state-dict name: index} (absent: frozen)."""
+        garr = (_lib.PlbAdamWGroup * max(1, len(groups)))()
+        for k, g in enumerate(groups):
+            garr[k] = _lib.PlbAdamWGroup(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                         float(g["weight_decay"]))
+        return garr, HipEngine._group_of_c(group_of)
+
+    @staticmethod
+    def _group_of_c(group_of):
+        if isinstance(group_of, dict):
+            unknown = sorted(set(group_of) - set(_lib.PLB_PARAM_NAMES))
+            if unknown:
+                raise ValueError(f"group_of names no tensor of the flat layout: {unknown}")
+            group_of = [group_of.get(n, -1) for n in _lib.PLB_PARAM_NAMES]
+        if len(group_of) != _lib.PLB_NPARAM:
+            raise ValueError(f"group_of needs {_lib.PLB_NPARAM} entries (flat-buffer order), not {len(group_of)}")
+        return (C.c_int32 * _lib.PLB_NPARAM)(*[int(k) for k in group_of])
+
+    def adamw_plan(self, step, groups, group_of):
+        """plb_adamw_plan (host only; the engine need not be bound): the live segments the next ``adamw_step_groups`` with
+        these arguments would launch, as a list of dicts (begin, end, group, step and the seven fp32 scalars)."""
+        garr, gof = self._groups_c(groups, group_of)
+        segs = (_lib.PlbAdamWSegment * _lib.PLB_NPARAM)()
+        n = C.c_int32()
+        _lib.check(self.L.plb_adamw_plan(self.handle, garr, len(groups), gof, int(step), segs, C.byref(n)), "plb_adamw_plan")
+        return [{name: getattr(segs[i], name) for name, _ in _lib.PlbAdamWSegment._fields_} for i in range(n.value)]
+
+    def adamw_step_groups(self, step, groups, group_of, grad_scale=1.0, norm_buf=None):
+        """plb_adamw_step_groups: ``adamw_step`` with one set of hyper-parameters per group and frozen tensors, still one
+        launch per range. ``groups`` / ``group_of``: see ``_groups_c``. ``norm_buf``: what ``grad_norm`` returned (the
+        clipped update), or None."""
+        self._bind()
+        garr, gof = self._groups_c(groups, group_of)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.plb_adamw_step_groups(self.handle, garr, len(groups), gof, int(step), float(grad_scale),
+                                                    None if norm_buf is None else norm_buf.data_ptr(), self._stream()),
+                       "plb_adamw_step_groups")
+        self._synced_version = self.params._version
+
     # ---- gradient accumulation and global-norm clipping (include/plbert.h: plb_grad_accum_add, plb_grad_norm) ----
     GRAD_FIRST, GRAD_ADD, GRAD_LAST = 0, 1, 2
 
@@ -834,13 +877,23 @@ class HipEngine:
             nb = self.norm_buf.data_ptr() if want_partials else None
             _lib.check(self.L.plb_grad_accum_add(self.handle, int(phase), nb, self._stream()), "plb_grad_accum_add")
 
-    def grad_norm(self, grad_scale=1.0, max_norm=0.0, have_partials=False):
+    def grad_norm(self, grad_scale=1.0, max_norm=0.0, have_partials=False, group_of=None):
         """Global norm of the gradients the next ``adamw_step`` covers, times ``grad_scale``, and the coefficient of
         torch.nn.utils.clip_grad_norm_ for ``max_norm`` (<= 0: no clipping), on the device (plb_grad_norm). Returns
-        ``self.norm_buf``; its first four floats are the result. Nothing is read back."""
+        ``self.norm_buf``; its first four floats are the result. Nothing is read back. ``group_of`` (see
+        ``adamw_step_groups``): the norm of the tensors that are not frozen only (plb_grad_norm_groups; one pass over the
+        gradients, ``have_partials`` does not combine with it)."""
         self._bind()
         with torch.cuda.device(self.device):
             nb = self.norm_buf
+            if group_of is not None:
+                if have_partials:
+                    raise ValueError("grad_norm: the partial sums of a LAST add cover frozen tensors too: have_partials "
+                                     "does not combine with group_of")
+                _lib.check(self.L.plb_grad_norm_groups(self.handle, self._group_of_c(group_of), float(grad_scale),
+                                                       float(max_norm or 0.0), nb.data_ptr(), self._stream()),
+                           "plb_grad_norm_groups")
+                return nb
             _lib.check(self.L.plb_grad_norm(self.handle, float(grad_scale), float(max_norm or 0.0), nb.data_ptr(),
                                             int(bool(have_partials)), self._stream()), "plb_grad_norm")
         return nb

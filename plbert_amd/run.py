@@ -24,7 +24,8 @@ import torch
 import torch.distributed as dist
 import yaml
 
-from .checkpoint import find_latest_checkpoint, optimizer_state_from_flat, optimizer_state_to_flat
+from .checkpoint import (find_latest_checkpoint, optimizer_state_from_flat, optimizer_state_to_flat,
+                         reference_param_names)
 from .config import albert_config_from_yaml
 from .data import build_dataloader
 from .dist import init_from_env, shard_batch, world_info
@@ -100,12 +101,23 @@ def _state_for_file(trainer, step, epoch):
             return trainer.step_count
         return eng.token_head_steps if eng.num_tokens and off >= tok0 else 0
 
+    grouped = getattr(trainer, "param_groups", None)
+    if grouped is not None:   # a tensor no grouped step has updated (frozen so far) has no state, as in torch
+        steps_all = steps_of
+        steps_of = lambda name, off, size: steps_all(name, off, size) if name in trainer.stepped else 0
     state, n = optimizer_state_from_flat(eng.layout, eng.exp_avg, eng.exp_avg_sq, steps_of)
-    group = {"lr": trainer.lr, "betas": tuple(trainer.betas), "eps": trainer.eps, "weight_decay": trainer.weight_decay,
-             "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-             "fused": None, "decoupled_weight_decay": True, "params": list(range(n))}
+    extra = {"amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+             "fused": None, "decoupled_weight_decay": True}
+    if grouped is None:
+        groups = [{"lr": trainer.lr, "betas": tuple(trainer.betas), "eps": trainer.eps, "weight_decay": trainer.weight_decay,
+                   **extra, "params": list(range(n))}]
+    else:   # torch's multi-group layout: every group's settings and the indices of its tensors; a frozen tensor is in none
+        index = {name: i for i, name in enumerate(reference_param_names(eng.layout))}
+        groups = [{"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": g["weight_decay"], **extra,
+                   "params": [index[name] for name in tg["names"]]}
+                  for g, tg in zip(trainer.groups_for_step()[0], grouped)]
     return {"net": {k: v.cpu() for k, v in eng.state_dict().items()}, "step": step, "epoch": epoch,
-            "optimizer": {"state": state, "param_groups": [group]}}
+            "optimizer": {"state": state, "param_groups": groups}}
 
 
 def save_checkpoint(trainer, current_step, log_dir, current_epoch, main=True):
@@ -116,13 +128,32 @@ def save_checkpoint(trainer, current_step, log_dir, current_epoch, main=True):
     return path
 
 
-def load_checkpoint(trainer, path):
+def load_checkpoint(trainer, path, restore_groups=True):
     """Weights (``module.`` prefixes stripped, non-strict: train.py:98-100) and, when present, the AdamW state — of a
-    file this driver wrote or of a reference ``step_N.pth`` (indices in ``model.parameters()`` order)."""
+    file this driver wrote or of a reference ``step_N.pth`` (indices in ``model.parameters()`` order).
+    Parameter groups (PLBertTrainer(no_decay=..., frozen=...)): what the trainer was built with always stays — learning
+    rate, betas and eps come from the configuration, as they do without groups. With ``restore_groups`` (a resume) a file that
+    holds several groups gives a trainer built WITHOUT groups its membership and weight decays, and a trainer built WITH
+    groups must agree with it (ValueError otherwise: the run would silently continue under another recipe). A file with the
+    ordinary single group (an ungrouped run, a reference checkpoint) never changes the trainer's groups.
+    ``restore_groups=False`` (``pretrained_model``): the file's groups are not looked at."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     eng = trainer.engine
-    eng.load_state_dict({k.replace("module.", ""): v for k, v in ck["net"].items()}, strict=False)
     opt = ck.get("optimizer")
+    saved = (opt.get("param_groups") or []) if opt else []
+    file_groups = None
+    if restore_groups and len(saved) > 1:
+        names = reference_param_names(eng.layout)
+        file_groups = [{"weight_decay": g["weight_decay"], "names": [names[int(i)] for i in g["params"]]} for g in saved]
+        mine = getattr(trainer, "param_groups", None)
+        if mine is not None:
+            key = lambda gs: sorted((float(g["weight_decay"]), tuple(sorted(g["names"]))) for g in gs)
+            if key(mine) != key(file_groups):
+                raise ValueError(f"{path} was written under other parameter groups than this run is configured with "
+                                 "(training_params.weight_decay / no_decay / frozen): resume with the recipe it was written "
+                                 "under, or load it as model_params.pretrained_model")
+            file_groups = None   # (the same recipe: the trainer's own dicts stay, with whatever else they carry)
+    eng.load_state_dict({k.replace("module.", ""): v for k, v in ck["net"].items()}, strict=False)
     if opt and opt.get("state"):
         tok0 = eng.token_range[0]
 
@@ -135,6 +166,10 @@ def load_checkpoint(trainer, path):
         tok_steps = {v for n, v in steps.items() if is_tok(eng.layout[n][0])}
         trainer.step_count = max(main_steps) if main_steps else 0
         eng.token_head_steps = max(tok_steps) if tok_steps else 0
+        if file_groups is not None:
+            trainer.param_groups = file_groups
+        if getattr(trainer, "param_groups", None) is not None:
+            trainer.mark_stepped(steps, reset=True)   # the tensors that have state in the file, and only they
     print(f"Checkpoint {path} loaded.", flush=True)
     return int(ck.get("step", 0))
 
@@ -152,10 +187,14 @@ def initialize_model(config, log_dir, resuming, device=None, max_batch=None):
                             device=device, packed_dual=tp.get("packed_dual"),      # (None: PLBERT_PACKED_DUAL)
                             packed_fp8=tp.get("packed_fp8"),                       # (None: PLBERT_PACKED_FP8)
                             max_grad_norm=tp.get("max_grad_norm"),                 # (not in the reference's config.yml; absent: off)
-                            track_accuracy=bool(tp.get("eval_accuracy", False)))   # (likewise)
+                            track_accuracy=bool(tp.get("eval_accuracy", False)),   # (likewise)
+                            # (likewise) weight_decay: absent = AdamW's 0.01 on every tensor; no_decay / frozen: lists of
+                            # name substrings, absent = one group and nothing frozen (PLBertTrainer)
+                            weight_decay=float(tp.get("weight_decay", 0.01)), no_decay=tuple(tp.get("no_decay") or ()),
+                            frozen=tuple(tp.get("frozen") or ()))
     if config["model_params"].get("pretrained_model"):
         print(f"Loading pretrained model from: {config['model_params']['pretrained_model']}")
-        load_checkpoint(trainer, config["model_params"]["pretrained_model"])
+        load_checkpoint(trainer, config["model_params"]["pretrained_model"], restore_groups=False)
     found, last = find_latest_checkpoint(log_dir)
     current_step = 0
     if found and resuming:

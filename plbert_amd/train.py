@@ -94,7 +94,25 @@ def _rewind_steps(owner):
         o = ref()
         if o is not None:
             o.step_count = max(0, o.step_count - err.skipped_updates)
+            first = getattr(o, "_first_step", None)
+            if first:   # tensors whose first update was one of the skipped ones were never updated
+                for n in [n for n, at in first.items() if at > o.step_count]:
+                    del first[n]
+                o._noted.clear()
     return cb
+
+
+def _note_stepped(owner, engine, groups, group_of, liveness=None):
+    """Before a grouped update at ``owner.step_count``: remember the tensors it updates for the first time
+    (``owner._first_step``: {state-dict name: step count of its first update}; a tensor that is not in it has no optimizer
+    state). Which of ``group_of``'s tensors the engine steps is the plan's answer (plb_adamw_plan); it is asked once per
+    membership and ``liveness`` (what the caller knows of the engine's has-a-gradient state), not once per step."""
+    key = (frozenset(group_of), liveness)
+    if key in owner._noted:
+        return
+    for n in planned_names(engine, engine.adamw_plan(owner.step_count, groups, group_of)):
+        owner._first_step.setdefault(n, owner.step_count)
+    owner._noted.add(key)
 
 
 class PLBertTrainer:
@@ -105,8 +123,15 @@ class PLBertTrainer:
     def __init__(self, cfg, num_phonemes, max_batch=32, max_seq=512, lr=7e-5, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.01, device=None, seed=0, state_dict=None, process_group=None, force_collectives=False,
                  num_tokens=0, comm="auto", overlap=True, packed=None, packed_dual=None, packed_fp8=None,
-                 max_grad_norm=None, track_accuracy=False):
-        """``track_accuracy`` (default off: a step then launches what it launched before): every ``step`` also launches the
+                 max_grad_norm=None, track_accuracy=False, no_decay=(), frozen=()):
+        """``no_decay`` / ``frozen`` (tuples of substrings matched against state-dict names; both empty, the default: the
+        single plb_adamw_step of before): tensors whose name holds a ``no_decay`` substring are updated with weight decay 0
+        — the usual BERT recipe is ``("bias", "LayerNorm", "layer_norm")`` here: the layer's second LayerNorm is named
+        ``full_layer_layer_norm``, which ``"LayerNorm"`` alone does not match —, tensors whose name holds a ``frozen`` substring are not updated
+        at all and keep their moments, and a clipped step takes its norm over the tensors that are not frozen
+        (plb_adamw_step_groups / plb_grad_norm_groups: still one launch per range). ``param_groups`` then holds the groups'
+        live dicts (``weight_decay``, ``names``, and any of lr / betas / eps that should differ from the trainer's own).
+        ``track_accuracy`` (default off: a step then launches what it launched before): every ``step`` also launches the
         totals-only report on its loss call's masked rows (plb_masked_report) and keeps ``last_accuracy`` — a device int32 [4]:
         masked rows, top-1 correct, top-5 correct, samples that have rows; ``step_accumulated``: summed over its micro-steps —
         the way ``last_grad_norm`` is kept: nothing is read back.
@@ -129,6 +154,12 @@ class PLBertTrainer:
         self.engine = HipEngine(cfg, num_phonemes, num_tokens, max_batch=max_batch, max_seq=max_seq, device=device)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.step_count = 0
+        self.no_decay, self.frozen = tuple(no_decay), tuple(frozen)
+        self.param_groups = None     # parameter groups (no_decay / frozen): a list of live dicts; None: one plb_adamw_step
+        self._first_step = {}        # ... and the tensors a grouped step has updated: {name: step count of the first update}
+        self._noted, self._dual = set(), False   # (_note_stepped's memo; whether the step in hand is a dual-head one)
+        if self.no_decay or self.frozen:
+            self.param_groups = name_param_groups(self.engine.layout, weight_decay, self.no_decay, self.frozen)
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and float(max_grad_norm) > 0 else None
         self.last_grad_norm = None   # the four result floats of the last clipped step (device)
         self.track_accuracy = bool(track_accuracy)
@@ -251,6 +282,7 @@ class PLBertTrainer:
         if batch.n_masked == 0 and self.world == 1 and not dual:
             return loss  # reference: zero-loss fallback has no graph, the optimizer sees no gradients
         self.all_reduce_grads(dual)
+        self._dual = dual
         self._optimizer_step(1.0 / self.world)
         return loss
 
@@ -259,6 +291,14 @@ class PLBertTrainer:
         rank computes the same coefficient) and the clipped update."""
         self.step_count += 1
         norm_buf = None
+        if self.param_groups is not None:
+            groups, group_of = self.groups_for_step()
+            if self.max_grad_norm is not None:   # (a LAST add's partial sums cover frozen tensors too: one pass of its own)
+                norm_buf = self.engine.grad_norm(grad_scale, self.max_grad_norm, group_of=group_of)
+                self.last_grad_norm = norm_buf[:4]
+            _note_stepped(self, self.engine, groups, group_of, liveness=self._dual)
+            self.engine.adamw_step_groups(self.step_count, groups, group_of, grad_scale=grad_scale, norm_buf=norm_buf)
+            return
         if self.max_grad_norm is not None:
             norm_buf = self.engine.grad_norm(grad_scale, self.max_grad_norm, have_partials=have_partials)
             self.last_grad_norm = norm_buf[:4]
@@ -267,6 +307,27 @@ class PLBertTrainer:
         else:
             self.engine.adamw_step(self.step_count, self.lr, self.betas, self.eps, self.weight_decay, grad_scale=grad_scale,
                                    norm_buf=norm_buf)
+
+    @property
+    def stepped(self):
+        """The tensors a grouped step has updated (or a checkpoint brought state for): the others have no optimizer state.
+        An update the device left out (HandoffTimeout) does not count."""
+        return set(self._first_step)
+
+    def mark_stepped(self, names, reset=False):
+        """Count ``names`` as updated before the first step (a checkpoint's tensors with state)."""
+        if reset:
+            self._first_step = {}
+        self._noted.clear()
+        for n in names:
+            self._first_step[n] = 0
+
+    def groups_for_step(self):
+        """(groups, group_of) of a grouped step: every group's hyper-parameters (the trainer's own where its dict names
+        none) and {state-dict name: group index} (a name in no group is frozen)."""
+        base = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
+        groups = [{**base, **{k: v for k, v in g.items() if k != "names"}} for g in self.param_groups]
+        return groups, {n: k for k, g in enumerate(self.param_groups) for n in g["names"]}
 
     def step_accumulated(self, batches):
         """ONE optimizer step over a list of staged batches (gradient accumulation, include/plbert.h plb_grad_accum_add):
@@ -288,7 +349,7 @@ class PLBertTrainer:
         try:
             dual = False
             loss_sum = None
-            clip_local = self.max_grad_norm is not None and not self.reducer.active
+            clip_local = self.max_grad_norm is not None and not self.reducer.active and self.param_groups is None
             for i, b in enumerate(batches):
                 loss = self.loss_and_grads(b)
                 if self.track_accuracy:
@@ -302,11 +363,63 @@ class PLBertTrainer:
             if all(b.n_masked == 0 for b in batches) and self.world == 1 and not dual:
                 return loss_sum
             self.all_reduce_grads(dual)
+            self._dual = dual
             self._optimizer_step(1.0 / (self.world * k), have_partials=clip_local)
         finally:
             if rccl_overlap:
                 eng.set_grad_overlap(True)
         return loss_sum
+
+
+def name_param_groups(layout, weight_decay, no_decay=(), frozen=()):
+    """The groups of PLBertTrainer(no_decay=..., frozen=...) over the state-dict names of ``layout``: [{'weight_decay':
+    weight_decay, 'names': [...]}, {'weight_decay': 0.0, 'names': [...]}] (a group without names is left out); a name that
+    holds a ``frozen`` substring is in no group. ValueError when ``frozen`` leaves nothing to train. Pure: no device, no
+    engine."""
+    decay, plain = [], []
+    for n in layout:
+        if any(f in n for f in frozen):
+            continue
+        (plain if any(d in n for d in no_decay) else decay).append(n)
+    groups = [g for g in ({"weight_decay": weight_decay, "names": decay}, {"weight_decay": 0.0, "names": plain}) if g["names"]]
+    if not groups:
+        raise ValueError(f"frozen={tuple(frozen)!r} matches every parameter name: nothing would be trained")
+    return groups
+
+
+def planned_names(engine, plan):
+    """The state-dict names of the tensors inside the segments of an ``engine.adamw_plan``."""
+    return {n for n, (off, size, _) in engine.layout.items() if any(s["begin"] <= off and off + size <= s["end"] for s in plan)}
+
+
+def resolve_param_groups(layout, named_parameters, groups):
+    """torch's ``param_groups`` (dicts whose 'params' are Parameters of ONE model) -> (group_of, frozen): group_of = {layout
+    name: group index} of every tensor a group holds, frozen = the layout names of the model's parameters that are in no
+    group or have ``requires_grad == False`` (they are not updated and keep their moments). ``layout``: the engine's
+    {state-dict name: ...}; ``named_parameters``: the model's (a stand-alone AlbertModel names its parameters without the
+    "encoder." prefix of the layout). Q, K and V are separate tensors of the layout and may sit in different groups. Pure:
+    no device. Raises ValueError for a parameter in two groups (torch's wording) and for one that is not the model's."""
+    by_id = {}
+    for n, p in named_parameters:
+        by_id[id(p)] = (n if n in layout else "encoder." + n, p)
+    group_of = {}
+    for k, g in enumerate(groups):
+        params = g["params"]
+        params = [params] if isinstance(params, torch.Tensor) else list(params)
+        for p in params:
+            if id(p) not in by_id:
+                raise ValueError(f"param group {k} holds a parameter that is not one of the model's: the fused optimizer "
+                                 "updates the model's flat parameter buffer and nothing else")
+            name = by_id[id(p)][0]
+            if name not in layout:
+                raise ValueError(f"param group {k}: {name!r} is no tensor of the engine's flat layout")
+            if name in group_of:
+                raise ValueError("some parameters appear in more than one parameter group")
+            group_of[name] = k
+    frozen = [n for n, p in by_id.values() if n in layout and (n not in group_of or not p.requires_grad)]
+    for n in frozen:
+        group_of.pop(n, None)
+    return group_of, frozen
 
 
 def own_gpu_per_rank():
@@ -505,13 +618,25 @@ def process_batch(model, batch, criterion=None, accelerator=None):
 class AdamW:
     """``torch.optim.AdamW(model.parameters(), lr=...)`` of train.py:272 as one fused HIP launch over the
     model's flat buffers. ``params`` must be the parameters of ONE plbert_amd model (it identifies the
-    engine); state_dict()/load_state_dict() carry step + both moments (train.py:417-421 'optimizer')."""
+    engine); state_dict()/load_state_dict() carry step + both moments (train.py:417-421 'optimizer').
+    ``params`` may also be torch's iterable of dicts ({"params": [...], "lr": ..., "betas": ..., "eps": ...,
+    "weight_decay": ...}; missing keys inherit the defaults): every group steps with its own hyper-parameters, a model
+    parameter in no group — or with ``requires_grad == False``, or whose ``.grad`` is None at ``step()`` — is frozen (not
+    updated, moments untouched), and the update is still one launch per range (plb_adamw_step_groups). One step count is
+    shared by all tensors outside the token head: a tensor thawed later continues with it (include/plbert.h)."""
+
+    HYPER = ("lr", "betas", "eps", "weight_decay")
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, model=None, max_grad_norm=None):
         """``max_grad_norm`` (None or <= 0: off): ``step`` clips the global norm of the gradients it consumes (times
         ``grad_scale``) as torch.nn.utils.clip_grad_norm_ does, on the device; ``last_grad_norm`` holds [norm, coefficient,
         not-finite flag, updates left out] as a device tensor."""
-        self.param_list = list(params)
+        params = list(params)
+        self._groups = None          # dict groups: torch's live list of dicts; None: one group, today's path
+        if params and isinstance(params[0], dict):
+            self._groups = []
+            pending, params = params, [p for _, p in model.named_parameters()] if model is not None else []
+        self.param_list = params
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and float(max_grad_norm) > 0 else None
         self.last_grad_norm = None
         if model is None:
@@ -525,12 +650,59 @@ class AdamW:
         # (a stand-alone AlbertModel names its parameters without the "encoder." prefix of the engine's layout)
         by_id = {id(p): (n if n in self.engine.layout else "encoder." + n) for n, p in model.named_parameters()}
         self._names = [by_id[id(p)] for p in self.param_list]
+        if self._groups is not None:
+            self._model = model
+            self._first_step = {}    # {name: step count of its first update}: the others have no entry in state_dict()['state']
+            self._resolved = (None, None)   # resolve_param_groups' result for the membership it was made from
+            self._noted = set()             # _note_stepped's memo
+            for g in pending:
+                self.add_param_group(g)
 
     @property
     def param_groups(self):
         """One group, and its dict IS the live ``defaults``: ``for g in optimizer.param_groups: g['lr'] = ...`` (the
-        reference README's fine-tuning set-up) takes effect at the next step."""
-        return [self.defaults]
+        reference README's fine-tuning set-up) takes effect at the next step. Built from dicts: the live list of the
+        groups' dicts, as in torch."""
+        return [self.defaults] if self._groups is None else self._groups
+
+    def add_param_group(self, group):
+        """torch.optim.Optimizer.add_param_group: a further dict of parameters that are in no group yet (it thaws them)."""
+        if self._groups is None:
+            raise ValueError("add_param_group needs an optimizer built from parameter-group dicts")
+        if not isinstance(group, dict) or "params" not in group:
+            raise ValueError("a parameter group is a dict with a 'params' entry")
+        g = dict(group)
+        g["params"] = [g["params"]] if isinstance(g["params"], torch.Tensor) else list(g["params"])
+        for k in self.HYPER:
+            g.setdefault(k, self.defaults[k])
+        resolve_param_groups(self.engine.layout, self._model.named_parameters(), self._groups + [g])   # raises
+        self._groups.append(g)
+
+    def _live_groups(self):
+        """(groups, group_of) of this step: requires_grad and .grad are read now."""
+        key = (tuple(tuple(map(id, g["params"])) for g in self._groups), tuple(p.requires_grad for p in self.param_list))
+        if self._resolved[0] != key:   # (membership changes with the groups and with requires_grad only)
+            self._resolved = (key, resolve_param_groups(self.engine.layout, self._model.named_parameters(), self._groups)[0])
+        group_of = self._resolved[1]
+        grads = {n: p.grad for n, p in zip(self._names, self.param_list)}
+        return self._groups, {n: k for n, k in group_of.items() if grads.get(n) is not None}
+
+    def _step_groups(self):
+        e = self.engine
+        groups, group_of = self._live_groups()
+        if not group_of:
+            return
+        for n, p in zip(self._names, self.param_list):   # (as in step(): whatever .grad holds now is what the update consumes)
+            off, size, shp = e.layout[n]
+            if n in group_of and p.grad.data_ptr() != e.grads.data_ptr() + 4 * off:
+                e.grads[off:off + size].view(shp).copy_(p.grad)
+        self.step_count += 1
+        norm_buf = None
+        if self.max_grad_norm is not None:
+            norm_buf = e.grad_norm(self.grad_scale, self.max_grad_norm, group_of=group_of)
+            self.last_grad_norm = norm_buf[:4]
+        _note_stepped(self, e, groups, group_of)
+        e.adamw_step_groups(self.step_count, groups, group_of, self.grad_scale, norm_buf=norm_buf)
 
     def zero_grad(self, set_to_none=True):
         for p in self.param_list:
@@ -541,6 +713,8 @@ class AdamW:
         # zero-loss fallback) changes nothing; otherwise the trainable range is updated in one launch
         if all(p.grad is None for p in self.param_list):
             return
+        if self._groups is not None:
+            return self._step_groups()
         e = self.engine
         for n, p in zip(self._names, self.param_list):
             # autograd may have handed the Parameter a copy of its gradient slice (or user code replaced
@@ -580,10 +754,19 @@ class AdamW:
                 steps = tok_steps
             else:
                 steps = 0
+            if self._groups is not None and n not in self._first_step:
+                steps = 0   # (frozen so far: torch has no state for a parameter it never stepped)
             if steps > 0:
                 state[i] = {"step": torch.tensor(float(steps)),
                             "exp_avg": e.exp_avg[off:off + size].view(shp).clone(),
                             "exp_avg_sq": e.exp_avg_sq[off:off + size].view(shp).clone()}
+        if self._groups is not None:   # torch's multi-group layout; indices count model.parameters() order
+            index = {id(p): i for i, p in enumerate(self.param_list)}
+            extra = {"amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+                     "fused": None, "decoupled_weight_decay": True}
+            groups = [{**extra, **{k: (tuple(v) if k == "betas" else v) for k, v in g.items() if k != "params"},
+                       "params": [index[id(p)] for p in g["params"]]} for g in self._groups]
+            return {"state": state, "param_groups": groups}
         group = {"lr": d["lr"], "betas": tuple(d["betas"]), "eps": d["eps"], "weight_decay": d["weight_decay"],
                  "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
                  "fused": None, "decoupled_weight_decay": True, "params": list(range(len(self.param_list)))}
@@ -592,6 +775,8 @@ class AdamW:
     def load_state_dict(self, sd):
         e = self.engine
         e._bind()
+        if self._groups is not None:
+            return self._load_groups(sd)
         if "param_groups" in sd:
             g = sd["param_groups"][0]
             for k in ("lr", "betas", "eps", "weight_decay"):
@@ -618,3 +803,49 @@ class AdamW:
         self.step_count = int(sd["step"])  # compact form written by early versions of this class
         e.exp_avg[: e.trainable].copy_(sd["exp_avg"])
         e.exp_avg_sq[: e.trainable].copy_(sd["exp_avg_sq"])
+
+    def _load_groups(self, sd):
+        """A state dict of this class or of torch.optim.AdamW with the same group sizes: every group's settings, and the
+        state of saved parameter k of the groups' chain goes to this optimizer's k-th (torch's positional rule).
+        ONE step count: torch counts steps per parameter, the fused update keeps one count for everything outside the token
+        head (include/plbert.h). A torch state dict in which a tensor sat out a step — frozen for a while, or without a
+        gradient — holds differing counts and is refused (ValueError): loading it would change the bias correction of some
+        tensor. Dicts this class wrote, and torch dicts whose stepped tensors share one count, load."""
+        e = self.engine
+        saved = sd["param_groups"]
+        if [len(g["params"]) for g in saved] != [len(g["params"]) for g in self._groups]:
+            raise ValueError("loaded state dict has parameter groups of other sizes: "
+                             f"{[len(g['params']) for g in saved]} against {[len(g['params']) for g in self._groups]}")
+        name_of = {id(p): n for n, p in zip(self._names, self.param_list)}
+        target = {}
+        for gs, g in zip(saved, self._groups):
+            for i, p in zip(gs["params"], g["params"]):
+                target[int(i)] = name_of[id(p)]
+        ta = e.token_range[0]
+        entries, steps, tok_steps = [], set(), set()
+        for i, st in sd["state"].items():
+            n = target[int(i)]
+            off, size, shp = e.layout[n]
+            is_tok = bool(e.num_tokens) and off >= ta
+            if off + size > e.trainable and not is_tok:
+                continue  # the pooler never trains
+            entries.append((n, st))
+            (tok_steps if is_tok else steps).add(int(float(st["step"])))
+        if len(steps) > 1 or len(tok_steps) > 1:   # (before anything is written)
+            raise ValueError(f"per-parameter step counts differ ({sorted(steps)} / token head {sorted(tok_steps)}): "
+                             "the fused AdamW keeps one step for the encoder + phoneme head and one for the token head")
+        for gs, g in zip(saved, self._groups):
+            for k, v in gs.items():
+                if k != "params":
+                    g[k] = tuple(v) if k == "betas" else v
+        e.exp_avg.zero_()
+        e.exp_avg_sq.zero_()
+        self._first_step = {}
+        self._noted.clear()
+        for n, st in entries:
+            off, size, shp = e.layout[n]
+            e.exp_avg[off:off + size].view(shp).copy_(st["exp_avg"])
+            e.exp_avg_sq[off:off + size].view(shp).copy_(st["exp_avg_sq"])
+            self._first_step[n] = 0
+        self.step_count = steps.pop() if steps else 0
+        e.token_head_steps = tok_steps.pop() if tok_steps else 0
