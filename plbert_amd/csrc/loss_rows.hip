@@ -139,7 +139,8 @@ __device__ __forceinline__ void token_ce_merge_row(const float* pmax, const floa
   for (int i = lane; i < ntiles; i += 64) {
     const float pm = pmax[(size_t)t * ntiles + i], ps = psum[(size_t)t * ntiles + i];
     if (pm > m) { l *= __expf(m - pm); m = pm; }
-    l += ps * __expf(pm - m);
+    // a tile without a real class is (-inf, 0): as a lane's first tile, exp(-inf - -inf) would make its 0 a NaN for good
+    if (pm > -INFINITY) l += ps * __expf(pm - m);
   }
   const float M = wave_max(m);
   l = wave_sum(m == -INFINITY ? 0.f : l * __expf(m - M));

@@ -43,6 +43,10 @@ typedef struct {
   float* ce_tlogit;             // act 3 out: [M] logit of the target class
   const float* ce_lse;          // act 4 in: [M] log-sum-exp of the row
   const float* ce_w;            // act 4 in: [M] row weight (0 on rows without loss)
+  // A row of weight 0 (a pad position, the rest of a packed slot, a row >= B*S) may hold anything: its target may be any
+  // int64 (pass 1 writes ce_tlogit[row] only when the target, converted to int, names one of the N columns; nothing reads
+  // that entry), its row of A may be stale, infinite or NaN, and act 4 still SELECTS exact zeros for its whole gradient
+  // row: nothing of it reaches another row or colpart.
   // fp8 operand mode (plb_launch_gemm_nt_fp8, gemm_fp8.hip): A and B are 1-byte images (lda / ldb / K count elements)
   const float* deq_a; const float* deq_b;  // device scalars: 1 / scale of each operand
   uint8_t* C8; int ldc8;        // optional fp8 copy of the output that feeds the next fp8 GEMM (act 1: of C2 = gelu; else of C)

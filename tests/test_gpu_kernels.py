@@ -520,7 +520,8 @@ def test_colsum():
 def test_fused_gemm_cross_entropy_passes(NT, B, S, lens, tile):
     """The two GEMM passes of the fused token-head CE + the merge kernel against torch: loss rows with weight
     1 / (B * len), gradient (softmax - onehot) * w in bf16, zeros on padded positions, on rows >= B*S and on columns
-    >= NT, and the column-sum partials (bias gradient) of the gradient as stored."""
+    >= NT, and the column-sum partials (bias gradient) of the gradient as stored. (An aggregate on soft rows; per element, on
+    sharp / offset / tied rows and rows of weight 0 with anything in them: tests/test_gpu_token_ce.py.)"""
     L = _lib.lib()
     T, H = B * S, 128
     Tp = (T + 255) // 256 * 256 if tile == 256 else (T + 127) // 128 * 128
