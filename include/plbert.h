@@ -254,6 +254,59 @@ int plb_adamw_step_groups(PlbEngine* e, const PlbAdamWGroup* groups, int32_t n_g
 int plb_grad_norm_groups(PlbEngine* e, const int32_t* group_of, double grad_scale, double max_norm, float* norm_buf,
                          void* stream);
 
+/* ---- LAMB: Adam with a layer-wise trust ratio (opt-in: a step that calls none of these launches what it launched before) ----
+ * The optimizer of ALBERT and of large-batch BERT pre-training (You et al., "Large Batch Optimization for Deep Learning").
+ * torch ships no LAMB, so THIS TEXT IS THE DEFINITION. Per tensor t of the flat layout (one entry of plb_param_layout; tensors
+ * are never merged, even when they are adjacent and share their scalars), in a group with lr, beta1, beta2, eps, weight_decay,
+ * adapt, at step count k:
+ *   g   = (grad * grad_scale) * coef          coef = norm_buf[1] when a norm_buf is given, else 1: plb_adamw_step_clipped's
+ *   m   = m + (1-beta1) * (g - m)             the AdamW kernels' expressions, operation for operation
+ *   v   = beta2 * v + (1-beta2) * (g*g)
+ *   r   = m / (sqrt(v) / sqrt(bc2) + eps)     bc = 1 - beta^k; scalars formed in double on the host and rounded to fp32 once
+ *   u   = r * (1/bc1) + weight_decay * p      the decay is INSIDE the update (LAMB), not decoupled
+ *   wn  = ||p||_2 over t (p BEFORE the update),  un = ||u||_2 over t
+ *   trust = wn / un  if adapt and wn > 0 and un > 0  else 1
+ *   p   = p - (lr * trust) * u                then the bf16 compute copy, as AdamW writes it
+ * Bias correction is on; neither wn nor trust is clamped. adapt = 0 turns the trust ratio off for a group's tensors (the
+ * "exclude from layer adaptation" convention for biases and LayerNorm, which usually have weight_decay = 0 as well). k is
+ * `step` for everything outside the token head and plb_token_head_steps + 1 for the token head, as in plb_adamw_step_groups
+ * (with its DEVIATION from torch: one count for all tensors outside the token head). A tensor in no group (group_of[i] = -1)
+ * or not stepped by this call (the pooler, the phoneme head after plb_encode_bwd, the token head unless the last loss call was
+ * a dual-head one) is a hole: nothing of it is loaded or stored.
+ * exp_avg and exp_avg_sq after a LAMB step are BIT-IDENTICAL to those after plb_adamw_step[_clipped] from the same state with
+ * the same betas, grad_scale and coef: a run may change between the two optimizers without touching its moments.
+ * The norms: fp32 sums of at most 1024 squares per workgroup, added per tensor in double in a fixed order (no atomics on
+ * float data: bitwise reproducible from run to run). Nothing is read back and nothing waits for the host: per range (the
+ * trainable range, the token head) two streaming passes and a one-workgroup-per-tensor finish between them, their tensor table
+ * a kernel argument. The gradient buffer is only read (`.grad` views of it stay what backward left).
+ * plb_lamb_floats: floats of the caller-owned, 16-byte aligned lamb_buf (contents arbitrary). Its first 4 * PLB_NPARAM floats
+ *   are [wn, un, trust, live] per tensor (enum PlbParam order) as the LAST step left them — live = 1: stepped, 0: a hole (wn, un
+ *   and trust are then 0) —, the per-workgroup partial sums follow. The engine's workspace plan does not change.
+ * plb_lamb_plan (host only, like plb_adamw_plan): the per-tensor segments the next plb_lamb_step would launch, in flat-buffer
+ *   order: begin / end in floats, tensor = its enum PlbParam, and the scalars omb1 = 1 - beta1, b2 = beta2, omb2 = 1 - beta2,
+ *   eps, bc2_sqrt = sqrt(1 - beta2^step), inv_bc1 = 1 / (1 - beta1^step), weight_decay, lr. segs has room for PLB_NPARAM entries.
+ * plb_lamb_step: the update over that plan with all the bookkeeping of plb_adamw_step_groups: joins pending all-reduce pieces,
+ *   ends a live plb_encode stash, the final state and an accumulation window, advances the token head's step count when the
+ *   token head is stepped, refreshes the compute copies (bf16, transposed, fp8). HEALTH WORD: tested first by every launch;
+ *   while it is set nothing is stored — m and v are NOT advanced, lamb_buf keeps the last step's results — and the left-out
+ *   update is counted once per range in word 1 / word 2 (plb_status_ex). norm_buf[2] != 0 (a norm that is not finite) leaves
+ *   everything untouched in the same way and norm_buf[3] grows by one.
+ *   Refused BEFORE anything is launched, with a text: what plb_adamw_step_groups refuses, an adapt that is neither 0 nor 1,
+ *   a lamb_buf that is null or not 16-byte aligned.
+ * DATA-PARALLEL RUNS: the sums are taken over all-reduced gradients and replicated parameters, so wn, un and trust are
+ *   identical on every rank: LAMB adds no collective. */
+typedef struct { double lr, beta1, beta2, eps, weight_decay; int32_t adapt; } PlbLambGroup;
+typedef struct {
+  int64_t begin, end;
+  int32_t tensor, group, step, adapt;
+  float omb1, b2, omb2, eps, bc2_sqrt, inv_bc1, weight_decay, lr;
+} PlbLambSegment;
+int64_t plb_lamb_floats(const PlbEngine* e);
+int plb_lamb_plan(const PlbEngine* e, const PlbLambGroup* groups, int32_t n_groups, const int32_t* group_of, int32_t step,
+                  PlbLambSegment* segs, int32_t* n_segs);
+int plb_lamb_step(PlbEngine* e, const PlbLambGroup* groups, int32_t n_groups, const int32_t* group_of, int32_t step,
+                  double grad_scale, const float* norm_buf, float* lamb_buf, void* stream);
+
 /* fp8 mode (BASELINE.json configs[4]): EVERY projection GEMM of the shared layer runs on OCP fp8 operands with fp32
  * accumulation through the block-scaled MFMA with unit block scales (twice the bf16 MFMA rate) — forward: QKV, dense
  * (+ LayerNorm 1), FFN up (+ gelu_new), FFN output (+ LayerNorm 2); backward: the four dX GEMMs (two of them carrying a
@@ -441,7 +494,8 @@ int plb_set_packed_fp8(PlbEngine* e, int32_t on);
  *   order (the head piece carries its zeros, the status all-reduce sits behind it); overlap off: plb_allreduce_grads as
  *   before. plb_comm_pieces and plb_last_call_rows report for these calls too.
  *   A host that steps the parameters with an optimizer of its own (torch.optim.AdamW over the views) must check
- *   plb_poll_status itself: the device-side skip of a poisoned step lives in plb_adamw_step only. */
+ *   plb_poll_status itself: the device-side skip of a poisoned step lives in the fused optimizer entries (plb_adamw_step*,
+ *   plb_lamb_step) only. */
 int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing,
                float* hidden, void* stream);
 int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing,

@@ -14,7 +14,7 @@ def __getattr__(name):
     if name in ("AlbertModel", "PhonemeOnlyModel", "MultiTaskModel", "BaseModelOutputWithPooling"):
         from . import model
         return getattr(model, name)
-    if name in ("PLBertTrainer", "process_batch", "AdamW", "StagedBatch", "stage_reference_batch", "validate_batch",
+    if name in ("PLBertTrainer", "process_batch", "AdamW", "Lamb", "StagedBatch", "stage_reference_batch", "validate_batch",
                 "device_mask_batch", "device_apply_mask"):
         from . import train
         return getattr(train, name)
@@ -34,7 +34,7 @@ def __getattr__(name):
 
 
 __all__ = [
-    "AlbertModel", "PhonemeOnlyModel", "MultiTaskModel", "PLBertTrainer", "process_batch", "AdamW", "HipEngine",
+    "AlbertModel", "PhonemeOnlyModel", "MultiTaskModel", "PLBertTrainer", "process_batch", "AdamW", "Lamb", "HipEngine",
     "save_checkpoint", "load_checkpoint", "find_latest_checkpoint", "export_pretrained", "encoder_state_dict",
     "load_pl_bert_model", "device_mask_batch", "device_apply_mask",
     "AlbertConfig", "albert_config_from_yaml", "load_config",

@@ -128,6 +128,19 @@ class PlbAdamWSegment(C.Structure):
                 ("step_size", C.c_float), ("bc2_sqrt", C.c_float)]
 
 
+class PlbLambGroup(C.Structure):
+    """include/plbert.h: one set of LAMB hyper-parameters; adapt = 0 turns the trust ratio off for the group's tensors."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("adapt", C.c_int32)]
+
+
+class PlbLambSegment(C.Structure):
+    """include/plbert.h: one live tensor of a LAMB step with its pre-rounded scalars (plb_lamb_plan)."""
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("tensor", C.c_int32), ("group", C.c_int32), ("step", C.c_int32),
+                ("adapt", C.c_int32), ("omb1", C.c_float), ("b2", C.c_float), ("omb2", C.c_float), ("eps", C.c_float),
+                ("bc2_sqrt", C.c_float), ("inv_bc1", C.c_float), ("weight_decay", C.c_float), ("lr", C.c_float)]
+
+
 class PlbLayerOutputs(C.Structure):
     """include/plbert.h: per-application outputs of plb_forward_layers / plb_encode_layers — two HOST arrays of device
     pointers (L + 1 hidden-state slots, L attention maps; an entry or a whole array may be NULL)."""
@@ -192,6 +205,9 @@ def norm_chunk(n):
     return (n + PLB_NORM_PARTS * 1024 - 1) // (PLB_NORM_PARTS * 1024) * 1024
 
 
+LAMB_CHAIN = 4 + 6 + 3   # PLB_LAMB_CHAIN: the longest chain of fp32 additions behind one partial sum of LAMB's pass 1
+
+
 def norm_chain(n):
     """PLB_NORM_CHAIN: the longest chain of fp32 additions behind one partial sum of a launch over n floats."""
     return 4 * (norm_chunk(n) // 1024) + 6 + 3
@@ -226,6 +242,9 @@ PUBLIC = {
     "plb_adamw_plan": (i32, [vp, P(PlbAdamWGroup), i32, P(i32), i32, P(PlbAdamWSegment), P(i32)]),
     "plb_adamw_step_groups": (i32, [vp, P(PlbAdamWGroup), i32, P(i32), i32, f64, vp, vp]),
     "plb_grad_norm_groups": (i32, [vp, P(i32), f64, f64, vp, vp]),
+    "plb_lamb_floats": (i64, [vp]),
+    "plb_lamb_plan": (i32, [vp, P(PlbLambGroup), i32, P(i32), i32, P(PlbLambSegment), P(i32)]),
+    "plb_lamb_step": (i32, [vp, P(PlbLambGroup), i32, P(i32), i32, f64, vp, vp, vp]),
     "plb_set_fp8": (i32, [vp, i32, vp]),
     "plb_fp8_state": (i32, [vp, P(i32), P(i32)]),
     "plb_fp8_stats": (i32, [vp, P(f32), P(f32), vp]),
@@ -344,6 +363,10 @@ INTERNAL = {
     "plb_launch_adamw_clipped": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i32, f64, vp, i32, vp, i32, vp]),
     "plb_launch_adamw_segments": (i32, [vp, vp, vp, vp, vp, sz, P(PlbAdamWSegment), i32, f64, vp, i32, vp, i32, vp]),
     "plb_launch_grad_sumsq_segments": (i32, [vp, sz, P(PlbAdamWSegment), i32, vp, vp]),
+    "plb_lamb_workgroups": (i64, [P(PlbLambSegment), i32, sz]),
+    "plb_launch_lamb_pass1": (i32, [vp, vp, vp, vp, sz, P(PlbLambSegment), i32, f64, vp, i32, vp, i32, vp, vp]),
+    "plb_launch_lamb_finish": (i32, [P(PlbLambSegment), i32, sz, i32, i32, vp, vp, vp, vp, vp]),
+    "plb_launch_lamb_pass2": (i32, [vp, vp, vp, vp, sz, P(PlbLambSegment), i32, vp, vp, vp, vp]),
     "plb_launch_step_status": (i32, [vp, vp, vp, vp, vp]),
     "plb_launch_status_export": (i32, [vp, vp, vp]),
     "plb_launch_cast_bf16": (i32, [vp, vp, sz, vp]),

@@ -1,9 +1,9 @@
 // Gradient accumulation, the global gradient norm, the clipped AdamW update and the grouped forms of norm and update
 // (include/plbert.h: plb_grad_accum_*, plb_grad_norm, plb_adamw_step_clipped; plb_adamw_plan, plb_adamw_step_groups,
-// plb_grad_norm_groups). Host bookkeeping of a window of micro-steps plus launches of optim.hip; no workspace of its own:
-// the accumulator and the norm buffer are the caller's. Only writer of PlbEngine's accumulation block (grads_fresh /
-// norm_nparts are also reset by begin_training_call, engine_calls.cpp); after a LAST add it sets head_grads_live,
-// tok_grads_live and grads_reduced to what the window accumulated.
+// plb_grad_norm_groups) and LAMB (plb_lamb_plan, plb_lamb_step). Host bookkeeping of a window of micro-steps plus launches of
+// optim.hip and lamb.hip; no workspace of its own: the accumulator, the norm buffer and the LAMB buffer are the caller's.
+// Only writer of PlbEngine's accumulation block (grads_fresh / norm_nparts are also reset by begin_training_call,
+// engine_calls.cpp); after a LAST add it sets head_grads_live, tok_grads_live and grads_reduced to what the window accumulated.
 #include <cmath>
 
 #include "engine_internal.h"
@@ -337,4 +337,127 @@ extern "C" int plb_grad_norm_groups(PlbEngine* e, const int32_t* group_of, doubl
   HB_W(s, norm_buf, 16, "gradient norm (writes norm, coefficient and flag)");
   TRY(plb_launch_grad_norm_finish(norm_buf + 4, nparts, grad_scale, max_norm, norm_buf, s));
   return 0;
+}
+
+// ---- LAMB (include/plbert.h: plb_lamb_floats, plb_lamb_plan, plb_lamb_step; kernels: lamb.hip)
+namespace {
+// lamb_buf: [4 * PLB_NPARAM results][partials of the trainable range][partials of the token head]. A range of n floats in
+// k tensors has at most n / 1024 + k workgroups (one pair of floats each).
+int64_t lamb_main_pairs(const PlbEngine* e) { return e->ptrain / 1024 + PLB_NPARAM; }
+int64_t lamb_tok_pairs(const PlbEngine* e) { return (e->ptotal - e->poff[PLB_TOK_W]) / 1024 + 2; }
+
+int check_lamb_groups(const PlbLambGroup* groups, int32_t n_groups, int32_t step, const char* who) {
+  if (!groups) return fail("%s: groups is null", who);
+  for (int k = 0; k < n_groups; ++k) {
+    const PlbLambGroup& g = groups[k];
+    if (!(g.lr >= 0.0) || !std::isfinite(g.lr)) return fail("%s: group %d: lr %g is negative or not finite", who, k, g.lr);
+    if (!(g.eps >= 0.0) || !std::isfinite(g.eps)) return fail("%s: group %d: eps %g is negative or not finite", who, k, g.eps);
+    if (!(g.beta1 >= 0.0 && g.beta1 < 1.0)) return fail("%s: group %d: beta1 %g is outside [0, 1)", who, k, g.beta1);
+    if (!(g.beta2 >= 0.0 && g.beta2 < 1.0)) return fail("%s: group %d: beta2 %g is outside [0, 1)", who, k, g.beta2);
+    if (!std::isfinite(g.weight_decay)) return fail("%s: group %d: weight_decay is not finite", who, k);
+    if (g.adapt != 0 && g.adapt != 1) return fail("%s: group %d: adapt %d is neither 0 nor 1", who, k, g.adapt);
+  }
+  if (step < 1) return fail("%s: step counts from 1", who);
+  return 0;
+}
+
+// One segment per live tensor, never merged: the trust ratio is a tensor's own
+int plan_lamb(const PlbEngine* e, const PlbLambGroup* groups, const int32_t* group_of, int32_t step, PlbLambSegment* segs) {
+  int n = 0;
+  for (int i = 0; i < PLB_NPARAM; ++i) {
+    if (group_of[i] < 0 || !steps_tensor(e, i)) continue;
+    const PlbLambGroup& g = groups[group_of[i]];
+    const PlbAdamWGroup a = {g.lr, g.beta1, g.beta2, g.eps, g.weight_decay};
+    PlbAdamWSegment sc;
+    const int k = in_token_head(i) ? e->tok_steps + 1 : step;
+    group_scalars(a, k, &sc);   // the AdamW scalars: omb1, b2, omb2, eps and sqrt(bc2) are shared bit for bit
+    PlbLambSegment s;
+    memset(&s, 0, sizeof(s));
+    s.begin = e->poff[i];
+    s.end = e->poff[i] + e->psize[i];
+    s.tensor = i;
+    s.group = group_of[i];
+    s.step = k;
+    s.adapt = g.adapt;
+    s.omb1 = sc.omb1; s.b2 = sc.b2; s.omb2 = sc.omb2; s.eps = sc.eps; s.bc2_sqrt = sc.bc2_sqrt;
+    s.inv_bc1 = (float)(1.0 / (1.0 - pow(g.beta1, k)));
+    s.weight_decay = (float)g.weight_decay;
+    s.lr = (float)g.lr;
+    segs[n++] = s;
+  }
+  return n;
+}
+
+int lamb_range_segments(const PlbLambSegment* segs, int n, int64_t a, int64_t b, PlbLambSegment* out) {
+  int k = 0;
+  for (int i = 0; i < n; ++i)
+    if (segs[i].begin >= a && segs[i].end <= b) {
+      out[k] = segs[i];
+      out[k].begin -= a;
+      out[k++].end -= a;
+    }
+  return k;
+}
+}  // namespace
+
+extern "C" int64_t plb_lamb_floats(const PlbEngine* e) {
+  return e ? (4 * (int64_t)PLB_NPARAM + 2 * (lamb_main_pairs(e) + lamb_tok_pairs(e)) + 3) / 4 * 4 : -1;
+}
+
+extern "C" int plb_lamb_plan(const PlbEngine* e, const PlbLambGroup* groups, int32_t n_groups, const int32_t* group_of,
+                             int32_t step, PlbLambSegment* segs, int32_t* n_segs) {
+  if (check_group_of(e, group_of, n_groups, "plb_lamb_plan")) return 1;
+  if (check_lamb_groups(groups, n_groups, step, "plb_lamb_plan")) return 1;
+  if (!segs || !n_segs) return fail("plb_lamb_plan: null output");
+  if (e->infer) return fail("plb_lamb_plan: inference-only engine");
+  *n_segs = plan_lamb(e, groups, group_of, step, segs);
+  return 0;
+}
+
+extern "C" int plb_lamb_step(PlbEngine* e, const PlbLambGroup* groups, int32_t n_groups, const int32_t* group_of, int32_t step,
+                             double grad_scale, const float* norm_buf, float* lamb_buf, void* stream) {
+  if (!e || !e->ws || !e->grads || !e->m || !e->v) return fail("plb_lamb_step: optimizer buffers not bound");
+  if (e->infer) return fail("plb_lamb_step: inference-only engine");
+  if (check_group_of(e, group_of, n_groups, "plb_lamb_step")) return 1;
+  if (check_lamb_groups(groups, n_groups, step, "plb_lamb_step")) return 1;
+  if (!lamb_buf || ((uintptr_t)lamb_buf & 15)) return fail("plb_lamb_step: lamb_buf must be a 16-byte aligned device buffer");
+  drop_stash(e, "plb_lamb_step moved the weights since");
+  drop_final(e, "plb_lamb_step moved the weights since: ask between the loss call and the optimizer step");
+  end_accum_window(e, "plb_lamb_step moved the weights");
+  hipStream_t s = (hipStream_t)stream;
+  if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
+    HIPTRY(ev_wait(e, s, e->ev_comm_done));
+    e->comm_pending = false;
+  }
+  float* norm = const_cast<float*>(norm_buf);   // (pass 1 counts the updates it leaves out in norm[3])
+  HB_R(s, e->grads, e->ptotal * 4, "LAMB (reads the gradient buffer)");
+  if (norm) HB_W(s, norm, 16, "LAMB (reads the coefficient, counts a left-out update)");
+  HB_W(s, lamb_buf, plb_lamb_floats(e) * 4, "LAMB (writes the partial sums and the trust ratios)");
+  PlbLambSegment all[PLB_NPARAM], part[PLB_NPARAM];
+  const int n = plan_lamb(e, groups, group_of, step, all);
+  unsigned int* skip = e->at<unsigned int>(e->o_lnerr);
+  bf16_t* wbf = e->at<bf16_t>(e->o_wbf);
+  const int64_t o = e->poff[PLB_TOK_W];
+  const int n_main = lamb_range_segments(all, n, 0, e->ptrain, part);
+  const int n_tok_all = n - n_main;   // (the pooler is never live: what is not in the trainable range is the token head's)
+  // the ranges, the step counts and the skip word are plb_adamw_step's; a range without a live tensor launches nothing, and
+  // the finish of the range that does run marks every other tensor as a hole
+  if (n_main) {
+    const size_t nn = (size_t)part[n_main - 1].end;
+    float* partials = lamb_buf + 4 * PLB_NPARAM;
+    TRY(plb_launch_lamb_pass1(e->params, e->grads, e->m, e->v, nn, part, n_main, grad_scale, skip, 1, norm, 1, partials, s));
+    TRY(plb_launch_lamb_finish(part, n_main, nn, 0, n_tok_all ? (int)PLB_TOK_W : (int)PLB_NPARAM, partials, lamb_buf, skip, norm, s));
+    TRY(plb_launch_lamb_pass2(e->params, e->m, e->v, wbf, nn, part, n_main, lamb_buf, skip, norm, s));
+  }
+  const int n_tok = lamb_range_segments(all, n, o, e->ptotal, part);
+  if (n_tok) {
+    e->tok_steps += 1;   // (the plan gave these tensors tok_steps + 1)
+    const size_t nn = (size_t)part[n_tok - 1].end;
+    float* partials = lamb_buf + 4 * PLB_NPARAM + 2 * lamb_main_pairs(e);
+    TRY(plb_launch_lamb_pass1(e->params + o, e->grads + o, e->m + o, e->v + o, nn, part, n_tok, grad_scale, skip, 2, norm, 0,
+                              partials, s));
+    TRY(plb_launch_lamb_finish(part, n_tok, nn, n_main ? (int)PLB_TOK_W : 0, PLB_NPARAM, partials, lamb_buf, skip, norm, s));
+    TRY(plb_launch_lamb_pass2(e->params + o, e->m + o, e->v + o, wbf + o, nn, part, n_tok, lamb_buf, skip, norm, s));
+  }
+  return sync_transposes(e, s, false);
 }

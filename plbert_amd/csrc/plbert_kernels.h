@@ -443,6 +443,33 @@ int plb_launch_adamw_segments(float* p, const float* g, float* m, float* v, bf16
 // NaN there does not reach the sum): the partials are bit-identical to plb_launch_grad_sumsq's on a zero-filled copy.
 int plb_launch_grad_sumsq_segments(const float* grads, size_t n, const PlbAdamWSegment* segs, int n_segs, float* partials,
                                    hipStream_t stream);
+// ---- LAMB (lamb.hip; include/plbert.h plb_lamb_step holds the definition). segs: HOST array of 1 to PLB_NPARAM live TENSORS
+// of [0, n) (begin / end in floats relative to p, sorted, disjoint, not empty, every boundary a multiple of 4; `tensor` = the
+// result slot, increasing; `group` is not read) with their pre-rounded scalars, as plb_lamb_plan forms them; the launchers copy
+// them into a by-value kernel argument. Workgroups are mapped to tensors: tensor s owns ceil(floats / 1024) consecutive
+// workgroups, each with one piece of 1024 floats counted from the tensor's own start. What lies between the tensors is a hole:
+// no load and no store there. Refused (1): what plb_launch_adamw_segments refuses, an adapt that is neither 0 nor 1, slots that
+// do not increase or leave [0, PLB_NPARAM). n_segs == 0 launches nothing (the finish then writes zeros to its slots).
+// The three launches of one range take the same segs / n_segs / n, skip word and norm. skip_if_nonzero (tested first) or
+// norm[2] != 0: no launch stores anything, pass 1 alone counts (skip[count_skip], norm[3] with count_nonfinite).
+// Longest chain of fp32 additions behind one partial: 4 squares per thread (one fused multiply-add each), 6 steps of the wave
+// reduction, 3 additions over the four waves. The partials of a tensor are added in double.
+#define PLB_LAMB_CHAIN (4 + 6 + 3)
+// workgroups of the passes over these tensors = pairs of floats pass 1 writes to `partials`; -1: the table is refused
+int64_t plb_lamb_workgroups(const PlbLambSegment* segs, int n_segs, size_t n);
+// m, v advanced as plb_launch_adamw_clipped advances them (norm == null: coefficient 1, no flag test), bit for bit;
+// partials[2 b], partials[2 b + 1] = sum of p^2, sum of u^2 over workgroup b's piece. p and g are only read.
+int plb_launch_lamb_pass1(const float* p, const float* g, float* m, float* v, size_t n, const PlbLambSegment* segs, int n_segs,
+                          double grad_scale, unsigned int* skip_if_nonzero, int count_skip, float* norm, int count_nonfinite,
+                          float* partials, hipStream_t stream);
+// results[4 t ..] = wn, un, trust, 1 for every tensor t of segs, and 0, 0, 0, 0 for every other slot of [slot_lo, slot_hi)
+int plb_launch_lamb_finish(const PlbLambSegment* segs, int n_segs, size_t n, int slot_lo, int slot_hi, const float* partials,
+                           float* results, const unsigned int* skip_if_nonzero, const float* norm, hipStream_t stream);
+// p -= (lr * trust) * u with u recomputed from the stored m, v by pass 1's expression, trust = results[4 t + 2]; the bf16
+// copy of the new p (p_bf16 null: none). m, v are only read; the gradient buffer is not an argument.
+int plb_launch_lamb_pass2(float* p, const float* m, const float* v, bf16_t* p_bf16, size_t n, const PlbLambSegment* segs,
+                          int n_segs, const float* results, const unsigned int* skip_if_nonzero, const float* norm,
+                          hipStream_t stream);
 // End of a loss call: mirror the hand-off error word into host-visible memory (host_mirror: device pointer of a pinned
 // host word) and, when it is non-zero, overwrite the loss with NaN — whoever reads the loss sees that the step is invalid
 int plb_launch_step_status(unsigned int* ln_err, float* loss, unsigned int* host_mirror, const float* summed, hipStream_t stream);

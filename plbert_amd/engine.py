@@ -186,7 +186,7 @@ class HipEngine:
     def device_bytes(self):
         """Bytes of device memory this engine holds."""
         ts = [self.params, self._grads, self._exp_avg, self._exp_avg_sq, self.workspace,
-              getattr(self, "_accum", None), getattr(self, "_norm_buf", None)]
+              getattr(self, "_accum", None), getattr(self, "_norm_buf", None), getattr(self, "_lamb_buf", None)]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
     def __del__(self):
@@ -850,6 +850,57 @@ class HipEngine:
                                                     None if norm_buf is None else norm_buf.data_ptr(), self._stream()),
                        "plb_adamw_step_groups")
         self._synced_version = self.params._version
+
+    # ---- LAMB (include/plbert.h: plb_lamb_plan, plb_lamb_step) ----
+    @staticmethod
+    def _lamb_groups_c(groups, group_of):
+        """``_groups_c`` for LAMB: every group dict also carries ``adapt`` (truthy: the trust ratio is on; absent: on)."""
+        garr = (_lib.PlbLambGroup * max(1, len(groups)))()
+        for k, g in enumerate(groups):
+            garr[k] = _lib.PlbLambGroup(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                        float(g["weight_decay"]), int(bool(g.get("adapt", True))))
+        return garr, HipEngine._group_of_c(group_of)
+
+    @property
+    def lamb_buf(self):
+        """The engine's own LAMB buffer (plb_lamb_floats floats): [wn, un, trust, live] per tensor of the flat layout as
+        the last ``lamb_step`` left them, then the partial sums."""
+        if getattr(self, "_lamb_buf", None) is None:
+            with torch.cuda.device(self.device):
+                self._lamb_buf = torch.zeros(int(self.L.plb_lamb_floats(self.handle)), dtype=torch.float32, device=self.device)
+        return self._lamb_buf
+
+    def lamb_plan(self, step, groups, group_of):
+        """plb_lamb_plan (host only; the engine need not be bound): one dict per tensor the next ``lamb_step`` with these
+        arguments would step (begin, end, tensor, group, step, adapt and the eight fp32 scalars), never merged."""
+        garr, gof = self._lamb_groups_c(groups, group_of)
+        segs = (_lib.PlbLambSegment * _lib.PLB_NPARAM)()
+        n = C.c_int32()
+        _lib.check(self.L.plb_lamb_plan(self.handle, garr, len(groups), gof, int(step), segs, C.byref(n)), "plb_lamb_plan")
+        return [{name: getattr(segs[i], name) for name, _ in _lib.PlbLambSegment._fields_} for i in range(n.value)]
+
+    def lamb_step(self, step, groups, group_of, grad_scale=1.0, norm_buf=None):
+        """plb_lamb_step: Adam with a per-tensor trust ratio (the definition: include/plbert.h), two streaming passes and a
+        finish launch per range, nothing read back. ``groups`` / ``group_of``: see ``_groups_c``, every group with its
+        ``adapt``. ``norm_buf``: what ``grad_norm`` returned (the clipped update), or None. The norms and ratios of this
+        step are in ``trust_ratios()``."""
+        self._bind()
+        garr, gof = self._lamb_groups_c(groups, group_of)
+        self._lamb_live = {s["tensor"] for s in self.lamb_plan(step, groups, group_of)}   # (host only: what this step steps)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.plb_lamb_step(self.handle, garr, len(groups), gof, int(step), float(grad_scale),
+                                            None if norm_buf is None else norm_buf.data_ptr(), self.lamb_buf.data_ptr(),
+                                            self._stream()), "plb_lamb_step")
+        self._synced_version = self.params._version
+
+    def trust_ratios(self):
+        """{state-dict name: (wn, un, trust)} of the last ``lamb_step`` — 0-dim DEVICE tensors, views of ``lamb_buf``:
+        nothing is read back unless the caller reads them. Tensors the step left alone (frozen, without a gradient) are
+        absent; which they are is host knowledge (the plan), not a read of the buffer's ``live`` flags."""
+        res = self.lamb_buf[:4 * _lib.PLB_NPARAM].view(_lib.PLB_NPARAM, 4)
+        live = getattr(self, "_lamb_live", None)
+        return {n: (res[i, 0], res[i, 1], res[i, 2]) for i, n in enumerate(_lib.PLB_PARAM_NAMES)
+                if n in self.layout and (live is None or i in live)}
 
     # ---- gradient accumulation and global-norm clipping (include/plbert.h: plb_grad_accum_add, plb_grad_norm) ----
     GRAD_FIRST, GRAD_ADD, GRAD_LAST = 0, 1, 2

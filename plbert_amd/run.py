@@ -114,10 +114,14 @@ def _state_for_file(trainer, step, epoch):
     else:   # torch's multi-group layout: every group's settings and the indices of its tensors; a frozen tensor is in none
         index = {name: i for i, name in enumerate(reference_param_names(eng.layout))}
         groups = [{"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": g["weight_decay"], **extra,
+                   **({"adapt": bool(tg["adapt"])} if "adapt" in tg else {}),   # (LAMB: the group's layer adaptation)
                    "params": [index[name] for name in tg["names"]]}
                   for g, tg in zip(trainer.groups_for_step()[0], grouped)]
-    return {"net": {k: v.cpu() for k, v in eng.state_dict().items()}, "step": step, "epoch": epoch,
-            "optimizer": {"state": state, "param_groups": groups}}
+    out = {"net": {k: v.cpu() for k, v in eng.state_dict().items()}, "step": step, "epoch": epoch,
+           "optimizer": {"state": state, "param_groups": groups}}
+    if getattr(trainer, "optimizer", "adamw") != "adamw":   # (absent = AdamW: the reference's files and every earlier one)
+        out["optimizer_kind"] = trainer.optimizer
+    return out
 
 
 def save_checkpoint(trainer, current_step, log_dir, current_epoch, main=True):
@@ -136,18 +140,27 @@ def load_checkpoint(trainer, path, restore_groups=True):
     holds several groups gives a trainer built WITHOUT groups its membership and weight decays, and a trainer built WITH
     groups must agree with it (ValueError otherwise: the run would silently continue under another recipe). A file with the
     ordinary single group (an ungrouped run, a reference checkpoint) never changes the trainer's groups.
-    ``restore_groups=False`` (``pretrained_model``): the file's groups are not looked at."""
+    ``restore_groups=False`` (``pretrained_model``): the file's groups are not looked at.
+    The optimizer kind (``optimizer_kind`` in the file; absent: AdamW): a resume under the other kind is refused (ValueError)
+    before anything is loaded — the moments would fit, the run would silently continue under another update rule; as a
+    pretrained model the file loads under either."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     eng = trainer.engine
+    kind, mine_kind = ck.get("optimizer_kind", "adamw"), getattr(trainer, "optimizer", "adamw")
+    if restore_groups and kind != mine_kind:
+        raise ValueError(f"{path} was written under optimizer {kind!r} and this run is configured with {mine_kind!r} "
+                         "(training_params.optimizer): resume with the optimizer it was written under, or load it as "
+                         "model_params.pretrained_model")
     opt = ck.get("optimizer")
     saved = (opt.get("param_groups") or []) if opt else []
     file_groups = None
     if restore_groups and len(saved) > 1:
         names = reference_param_names(eng.layout)
-        file_groups = [{"weight_decay": g["weight_decay"], "names": [names[int(i)] for i in g["params"]]} for g in saved]
+        file_groups = [{"weight_decay": g["weight_decay"], "names": [names[int(i)] for i in g["params"]],
+                        **({"adapt": g["adapt"]} if "adapt" in g else {})} for g in saved]
         mine = getattr(trainer, "param_groups", None)
         if mine is not None:
-            key = lambda gs: sorted((float(g["weight_decay"]), tuple(sorted(g["names"]))) for g in gs)
+            key = lambda gs: sorted((float(g["weight_decay"]), bool(g.get("adapt", True)), tuple(sorted(g["names"]))) for g in gs)
             if key(mine) != key(file_groups):
                 raise ValueError(f"{path} was written under other parameter groups than this run is configured with "
                                  "(training_params.weight_decay / no_decay / frozen): resume with the recipe it was written "
@@ -191,7 +204,12 @@ def initialize_model(config, log_dir, resuming, device=None, max_batch=None):
                             # (likewise) weight_decay: absent = AdamW's 0.01 on every tensor; no_decay / frozen: lists of
                             # name substrings, absent = one group and nothing frozen (PLBertTrainer)
                             weight_decay=float(tp.get("weight_decay", 0.01)), no_decay=tuple(tp.get("no_decay") or ()),
-                            frozen=tuple(tp.get("frozen") or ()))
+                            frozen=tuple(tp.get("frozen") or ()),
+                            # (likewise) optimizer: absent = "adamw"; "lamb": plb_lamb_step, with the names excluded from
+                            # the layer adaptation (absent: biases and LayerNorm)
+                            optimizer=str(tp.get("optimizer", "adamw")).lower(),
+                            **({"exclude_from_layer_adaptation": tuple(tp["exclude_from_layer_adaptation"])}
+                               if tp.get("exclude_from_layer_adaptation") is not None else {}))
     if config["model_params"].get("pretrained_model"):
         print(f"Loading pretrained model from: {config['model_params']['pretrained_model']}")
         load_checkpoint(trainer, config["model_params"]["pretrained_model"], restore_groups=False)

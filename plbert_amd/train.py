@@ -123,8 +123,17 @@ class PLBertTrainer:
     def __init__(self, cfg, num_phonemes, max_batch=32, max_seq=512, lr=7e-5, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.01, device=None, seed=0, state_dict=None, process_group=None, force_collectives=False,
                  num_tokens=0, comm="auto", overlap=True, packed=None, packed_dual=None, packed_fp8=None,
-                 max_grad_norm=None, track_accuracy=False, no_decay=(), frozen=()):
-        """``no_decay`` / ``frozen`` (tuples of substrings matched against state-dict names; both empty, the default: the
+                 max_grad_norm=None, track_accuracy=False, no_decay=(), frozen=(), optimizer="adamw",
+                 exclude_from_layer_adaptation=("bias", "LayerNorm", "layer_norm")):
+        """``optimizer``: "adamw" (the default: nothing changes) or "lamb" — Adam with a per-tensor trust ratio, the
+        optimizer of large-batch BERT / ALBERT pre-training (include/plbert.h: plb_lamb_step holds the definition; the
+        weight decay is then INSIDE the update). Every optimizer step is plb_lamb_step: two streaming passes and a finish
+        launch per range, norms and ratios stay on the device (``engine.trust_ratios()``). Tensors whose name holds a
+        substring of ``exclude_from_layer_adaptation`` step with trust ratio 1. Composes with ``no_decay``, ``frozen``,
+        ``max_grad_norm``, ``step_accumulated``, packed and fp8 modes, which all sit before or behind the optimizer step.
+        Data-parallel runs need no further collective: the norms are taken over all-reduced gradients and replicated
+        parameters and are identical on every rank.
+        ``no_decay`` / ``frozen`` (tuples of substrings matched against state-dict names; both empty, the default: the
         single plb_adamw_step of before): tensors whose name holds a ``no_decay`` substring are updated with weight decay 0
         — the usual BERT recipe is ``("bias", "LayerNorm", "layer_norm")`` here: the layer's second LayerNorm is named
         ``full_layer_layer_norm``, which ``"LayerNorm"`` alone does not match —, tensors whose name holds a ``frozen`` substring are not updated
@@ -155,11 +164,18 @@ class PLBertTrainer:
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.step_count = 0
         self.no_decay, self.frozen = tuple(no_decay), tuple(frozen)
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, not {optimizer!r}")
+        self.optimizer = optimizer
+        self.exclude_from_layer_adaptation = tuple(exclude_from_layer_adaptation)
         self.param_groups = None     # parameter groups (no_decay / frozen): a list of live dicts; None: one plb_adamw_step
         self._first_step = {}        # ... and the tensors a grouped step has updated: {name: step count of the first update}
         self._noted, self._dual = set(), False   # (_note_stepped's memo; whether the step in hand is a dual-head one)
         if self.no_decay or self.frozen:
             self.param_groups = name_param_groups(self.engine.layout, weight_decay, self.no_decay, self.frozen)
+        if optimizer == "lamb":   # always grouped: the groups' dicts carry ``adapt`` beside ``weight_decay`` and ``names``
+            self.param_groups = lamb_param_groups(self.engine.layout, weight_decay, self.no_decay, self.frozen,
+                                                  self.exclude_from_layer_adaptation)
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and float(max_grad_norm) > 0 else None
         self.last_grad_norm = None   # the four result floats of the last clipped step (device)
         self.track_accuracy = bool(track_accuracy)
@@ -286,9 +302,20 @@ class PLBertTrainer:
         self._optimizer_step(1.0 / self.world)
         return loss
 
+    def optimizer_entry_points(self):
+        """The C entry points (include/plbert.h) an optimizer step of this trainer calls, in order: host knowledge of
+        ``_optimizer_step``'s dispatch, no device."""
+        grouped = self.param_groups is not None
+        norm = () if self.max_grad_norm is None else ("plb_grad_norm_groups" if grouped else "plb_grad_norm",)
+        if self.optimizer == "lamb":
+            return norm + ("plb_lamb_step",)
+        if grouped:
+            return norm + ("plb_adamw_step_groups",)
+        return norm + ("plb_adamw_step_clipped" if norm else "plb_adamw_step",)
+
     def _optimizer_step(self, grad_scale, have_partials=False):
-        """AdamW on what the gradient buffer holds; with ``max_grad_norm`` the norm (taken after the exchange, so every
-        rank computes the same coefficient) and the clipped update."""
+        """AdamW (or LAMB: ``optimizer``) on what the gradient buffer holds; with ``max_grad_norm`` the norm (taken after
+        the exchange, so every rank computes the same coefficient) and the clipped update."""
         self.step_count += 1
         norm_buf = None
         if self.param_groups is not None:
@@ -297,7 +324,8 @@ class PLBertTrainer:
                 norm_buf = self.engine.grad_norm(grad_scale, self.max_grad_norm, group_of=group_of)
                 self.last_grad_norm = norm_buf[:4]
             _note_stepped(self, self.engine, groups, group_of, liveness=self._dual)
-            self.engine.adamw_step_groups(self.step_count, groups, group_of, grad_scale=grad_scale, norm_buf=norm_buf)
+            step = self.engine.lamb_step if self.optimizer == "lamb" else self.engine.adamw_step_groups
+            step(self.step_count, groups, group_of, grad_scale=grad_scale, norm_buf=norm_buf)
             return
         if self.max_grad_norm is not None:
             norm_buf = self.engine.grad_norm(grad_scale, self.max_grad_norm, have_partials=have_partials)
@@ -385,6 +413,22 @@ def name_param_groups(layout, weight_decay, no_decay=(), frozen=()):
     if not groups:
         raise ValueError(f"frozen={tuple(frozen)!r} matches every parameter name: nothing would be trained")
     return groups
+
+
+OPTIMIZERS = ("adamw", "lamb")
+
+
+def lamb_param_groups(layout, weight_decay, no_decay=(), frozen=(), exclude=()):
+    """``name_param_groups`` for PLBertTrainer(optimizer="lamb"): every group is cut in two by the layer adaptation — a name
+    that holds an ``exclude`` substring steps with trust ratio 1 (``adapt`` False) — so a group's dict is {'weight_decay',
+    'names', 'adapt'}. Pure: no device, no engine."""
+    out = []
+    for g in name_param_groups(layout, weight_decay, no_decay, frozen):
+        off = [n for n in g["names"] if any(x in n for x in exclude)]
+        on = [n for n in g["names"] if n not in off]
+        out += [{"weight_decay": g["weight_decay"], "names": names, "adapt": adapt} for names, adapt in ((on, True), (off, False))
+                if names]
+    return out
 
 
 def planned_names(engine, plan):
@@ -702,7 +746,10 @@ class AdamW:
             norm_buf = e.grad_norm(self.grad_scale, self.max_grad_norm, group_of=group_of)
             self.last_grad_norm = norm_buf[:4]
         _note_stepped(self, e, groups, group_of)
-        e.adamw_step_groups(self.step_count, groups, group_of, self.grad_scale, norm_buf=norm_buf)
+        self._fused_step(groups, group_of, norm_buf)
+
+    def _fused_step(self, groups, group_of, norm_buf):
+        self.engine.adamw_step_groups(self.step_count, groups, group_of, self.grad_scale, norm_buf=norm_buf)
 
     def zero_grad(self, set_to_none=True):
         for p in self.param_list:
@@ -849,3 +896,53 @@ class AdamW:
             self._first_step[n] = 0
         self.step_count = steps.pop() if steps else 0
         e.token_head_steps = tok_steps.pop() if tok_steps else 0
+
+
+class Lamb(AdamW):
+    """LAMB — Adam with a per-tensor trust ratio, the optimizer ALBERT was trained with — over the model's flat buffers:
+    two streaming HIP passes and a finish launch per range (plb_lamb_step; include/plbert.h holds the definition, torch
+    ships none). The surface of ``AdamW`` above: ``params`` (Parameters of ONE plbert_amd model, or torch's iterable of
+    dicts), live ``param_groups`` / ``add_param_group``, ``zero_grad``, ``step``, ``max_grad_norm``, and ``state_dict`` /
+    ``load_state_dict`` in torch's layout (``state[i] = {step, exp_avg, exp_avg_sq}``) with ``adapt`` as a group key. The
+    moments are AdamW's bit for bit, so either class loads the other's state.
+    ``adapt`` of a group: True / False turn the trust ratio on / off for its tensors; None (the default) decides per tensor:
+    a name that holds a substring of ``exclude_from_layer_adaptation`` steps with trust ratio 1. The weight decay is inside
+    the update (u = r / bc1 + weight_decay * p), so it is scaled by the trust ratio like the rest.
+    ``model.engine.trust_ratios()`` has the norms and ratios of the last step as device tensors."""
+
+    HYPER = ("lr", "betas", "eps", "weight_decay", "adapt")
+    _TORCH_ADAMW_KEYS = ("amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused", "decoupled_weight_decay")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, model=None, max_grad_norm=None,
+                 exclude_from_layer_adaptation=("bias", "LayerNorm", "layer_norm")):
+        params = list(params)
+        if not (params and isinstance(params[0], dict)):
+            params = [{"params": params}]   # (always grouped: a parameter that was not passed is not stepped, as in torch)
+        self.exclude = tuple(exclude_from_layer_adaptation)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, model=model,
+                         max_grad_norm=max_grad_norm)
+
+    def add_param_group(self, group):
+        self.defaults.setdefault("adapt", None)
+        super().add_param_group(group)
+
+    def _live_groups(self):
+        """AdamW's (groups, group_of) with every group cut in two where its tensors differ in layer adaptation."""
+        groups, group_of = super()._live_groups()
+        cut, index, cut_of = [], {}, {}
+        for n, k in group_of.items():
+            adapt = groups[k].get("adapt")
+            adapt = not any(x in n for x in self.exclude) if adapt is None else bool(adapt)
+            if (k, adapt) not in index:
+                index[k, adapt] = len(cut)
+                cut.append({**groups[k], "adapt": adapt})
+            cut_of[n] = index[k, adapt]
+        return cut, cut_of
+
+    def _fused_step(self, groups, group_of, norm_buf):
+        self.engine.lamb_step(self.step_count, groups, group_of, self.grad_scale, norm_buf=norm_buf)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["param_groups"] = [{k: v for k, v in g.items() if k not in self._TORCH_ADAMW_KEYS} for g in sd["param_groups"]]
+        return sd
