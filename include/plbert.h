@@ -544,6 +544,48 @@ int plb_encode_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, 
                       float* hidden, const PlbLayerOutputs* layers, void* stream);
 int plb_encode_bwd_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                           const PlbPacking* packing, const float* d_hidden, const float* const* d_below, void* stream);
+/* ---- embedding inputs: token_type_ids / position_ids / inputs_embeds, with gradients (opt-in: a call that passes none
+ * launches what it launched before) ----
+ * Semantics are HuggingFace AlbertEmbeddings.forward (modeling_albert.py:67-106) with dropout 0:
+ *   LN_E( (inputs_embeds[b,s] | word[ids[b,s]]) + type[token_type_ids[b,s]] + pos[position_ids[b,s]] )
+ * with the deviations this library already makes for plb_encode: zeros at pad positions, prefix masks (lengths), word row 0 is
+ * the padding row and gets no gradient.
+ * PlbEmbedInputs: three DEVICE pointers, each optional, each indexed by the padded [B,S] position in the padded and the packed
+ *   layout alike (as ids are); values at pad positions are read by a padded call (as ids are there) and must be in range.
+ *   token_type_ids NULL means row 0 for every token, position_ids NULL means s. Exactly one of ids and inputs_embeds is given;
+ *   inputs_embeds is E = embedding_size wide (the input of the embedding LayerNorm), not hidden_size. The host validates the
+ *   index ranges; an index outside its table reads row 0 on the device, never memory outside the table.
+ * plb_forward_inputs / plb_encode_inputs / plb_encode_bwd_inputs: supersets of plb_forward_layers / plb_encode_layers /
+ *   plb_encode_bwd_layers. With inputs == NULL, or its three pointers NULL, and d_inputs_embeds == NULL each is exactly its
+ *   namesake: the same launches, bit-identical results, and the same engine state afterwards (plb_last_call_rows, the final
+ *   hidden state for plb_token_report, the live stash, the exchange's pieces, the status exchange). With token_type_ids = 0 and
+ *   position_ids = s passed explicitly the forward is bit-equal to the plain call's too (the same arithmetic per row).
+ * plb_encode_bwd_inputs: `inputs` as given to the live plb_encode_inputs call (as ids are passed again). The encoder range of
+ *   the gradient buffer is overwritten as by plb_encode_bwd. EVERY row of the token-type table receives its gradient (the sum
+ *   over the tokens of that type; a plain call trains row 0 only), a position row the sum over the tokens whose position_id it
+ *   is. No atomics: every sum has a fixed order and results are bitwise reproducible from run to run; a row that owns many
+ *   tokens is summed in 512-token chunks by separate workgroups, the partial rows added in chunk order. With inputs_embeds the
+ *   word table's range is written as ZEROS, and the fused optimizer entries (plb_adamw_step*, plb_lamb_step) see a zero
+ *   gradient there: with weight decay the table still decays. A host that wants torch's "no gradient" for that tensor
+ *   freezes it through the `frozen` plan of plb_adamw_step_groups / plb_lamb_step.
+ *   d_inputs_embeds (or NULL): fp32 [B,S,E], the gradient of the pre-LayerNorm sum per token, in the padded layout, every
+ *   element written exactly once, exact zeros at pad positions. Available whether the forward took ids (the per-phoneme
+ *   saliency) or inputs_embeds (its gradient).
+ * Refusals, each before anything is launched and with a text naming the cause: both or neither of ids / inputs_embeds; any of
+ *   the three inputs or d_inputs_embeds while fp8 mode is on; every refusal of the namesake.
+ * Out of scope: the inputs in the pre-training loss calls (plb_loss_*), fp8 mode, non-prefix attention masks, dropout. */
+typedef struct {
+  const int64_t* token_type_ids;  /* device int64 [B,S] or NULL (all 0); values in [0, type_vocab_size) */
+  const int64_t* position_ids;    /* device int64 [B,S] or NULL (s);     values in [0, max_position_embeddings) */
+  const float*   inputs_embeds;   /* device fp32 [B,S,embedding_size] or NULL; given <=> ids == NULL */
+} PlbEmbedInputs;
+int plb_forward_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths, int32_t B, int32_t S,
+                       const PlbPacking* packing, float* hidden, const PlbLayerOutputs* layers, void* stream);
+int plb_encode_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths, int32_t B, int32_t S,
+                      const PlbPacking* packing, float* hidden, const PlbLayerOutputs* layers, void* stream);
+int plb_encode_bwd_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths, int32_t B,
+                          int32_t S, const PlbPacking* packing, const float* d_hidden, const float* const* d_below,
+                          float* d_inputs_embeds, void* stream);
 /* ---- masked-phoneme evaluation: accuracy, top-k and fill-mask from a loss call (opt-in: a step that does not ask launches
  * what it launched before) ----
  * The reference reports the scalar loss only (train.py:288-336, 395-410). A masked LM's users also expect the accuracy at the

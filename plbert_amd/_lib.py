@@ -110,6 +110,20 @@ class PlbEmbed(C.Structure):
     ]
 
 
+class PlbEmbedIn(C.Structure):
+    """csrc/plbert_kernels.h: the embedding launches with per-token sources (base: pointer to a PlbEmbed of the caller)."""
+    _fields_ = [
+        ("base", C.c_void_p), ("token_type_ids", C.c_void_p), ("position_ids", C.c_void_p), ("inputs_embeds", C.c_void_p),
+        ("NTY", C.c_int), ("P", C.c_int), ("dtype_rows", C.c_void_p), ("d_inputs_embeds", C.c_void_p),
+        ("chunk_part", C.c_void_p),
+    ]
+
+
+class PlbEmbedInputs(C.Structure):
+    """include/plbert.h: what a plb_*_inputs call feeds its embeddings beside the ids (device pointers, each optional)."""
+    _fields_ = [("token_type_ids", C.c_void_p), ("position_ids", C.c_void_p), ("inputs_embeds", C.c_void_p)]
+
+
 class PlbPacking(C.Structure):
     """include/plbert.h: the plan of a token-packed call (row_start: device int32 [B+1])."""
     _fields_ = [("row_start", C.c_void_p), ("rows", C.c_int32), ("used", C.c_int32)]
@@ -273,6 +287,9 @@ PUBLIC = {
     "plb_forward_layers": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
     "plb_encode_layers": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
     "plb_encode_bwd_layers": (i32, [vp, vp, vp, i32, i32, P(PlbPacking), vp, vp, vp]),
+    "plb_forward_inputs": (i32, [vp, vp, P(PlbEmbedInputs), vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
+    "plb_encode_inputs": (i32, [vp, vp, P(PlbEmbedInputs), vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
+    "plb_encode_bwd_inputs": (i32, [vp, vp, P(PlbEmbedInputs), vp, i32, i32, P(PlbPacking), vp, vp, vp, vp]),
     "plb_masked_report": (i32, [vp, vp, i32, i32, P(PlbMaskedReport), vp]),
     "plb_token_report": (i32, [vp, vp, vp, vp, i32, i32, i32, P(PlbPacking), vp, i32, P(PlbTokenReport), vp]),
     "plb_comm_pieces": (i32, [vp, P(i32), P(i64)]),
@@ -320,6 +337,10 @@ INTERNAL = {
     "plb_launch_embed_fwd": (i32, [P(PlbEmbed), vp]),
     "plb_launch_embed_bwd": (i32, [P(PlbEmbed), vp]),
     "plb_launch_embed_scatter": (i32, [P(PlbEmbed), i32, vp]),
+    "plb_launch_embed_inputs_fwd": (i32, [P(PlbEmbedIn), vp]),
+    "plb_launch_embed_inputs_bwd": (i32, [P(PlbEmbedIn), vp]),
+    "plb_launch_embed_inputs_scatter": (i32, [P(PlbEmbedIn), vp]),
+    "plb_embed_inputs_part_floats": (sz, [i32, i32, i32, i32]),
     "plb_launch_amax": (i32, [vp, i32, sz, i32, i32, vp, vp]),
     "plb_launch_fp8_scales": (i32, [vp, vp, vp, i32, f32, i32, vp]),
     "plb_launch_fp8_scales2": (i32, [vp, vp, vp, i32, f32, i32, i32, f32, vp, i32, vp]),

@@ -238,6 +238,9 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
     e->o_tr_rows = cv.take(Tp * 4); e->o_tr_tgt = cv.take(Tp * 4);
     e->o_tr_scratch = cv.take((int64_t)plb_token_topk_scratch_bytes((int)Tp));
   }
+  // The partial rows of plb_launch_embed_inputs_scatter (a backward with position_ids / token_type_ids), carved last like the
+  // regions above: one [max_position_embeddings + type_vocab_size][E] block of floats per 512 positions of the capacity.
+  if (tr) e->o_embpart = cv.take((int64_t)plb_embed_inputs_part_floats((int)Tp, e->P, c.type_vocab_size, (int)E) * 4);
   e->ws_bytes = cv.off;
   *out = e;
   return 0;

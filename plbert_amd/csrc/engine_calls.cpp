@@ -1,6 +1,7 @@
 // Call-level stages of the engine: row selection of a padded or token-packed call, the heads, the stages of a loss call and
 // the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd and their
-// *_layers forms (per-application outputs; a gradient at every application boundary). Only
+// *_layers forms (per-application outputs; a gradient at every application boundary) and *_inputs forms (token_type_ids /
+// position_ids / inputs_embeds: one EmbedCall from the entry point to run_encoder and the backward tail). Only
 // writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
 // last_exec_rows, tok_grads_live and head_grads_live (which a LAST add of engine_optim.cpp replaces by its window's union),
 // and of what plb_masked_report reads (rep_*: engine_eval.cpp; plb_bind clears rep_valid) and of the record of the final
@@ -49,14 +50,32 @@ static int pick_rows(PlbEngine* e, const PlbPacking* pk, const int32_t* lengths,
   return 0;
 }
 
+// The embedding inputs of a plb_*_inputs call (in: the caller's struct or null; d_ie: where a backward puts the gradient of the
+// pre-LayerNorm sum, or null), checked before anything is launched. Nothing given: *ec is a plain call's and only the namesake's
+// own refusal (ids is null) applies.
+static int embed_call(const PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* in, float* d_ie, const char* who, EmbedCall* ec) {
+  memset(ec, 0, sizeof(*ec));
+  if (in) ec->in = *in;
+  ec->d_inputs_embeds = d_ie;
+  if (ids && ec->in.inputs_embeds) return fail("%s: both ids and inputs_embeds are given (exactly one of them feeds the embeddings)", who);
+  if (!ids && !ec->in.inputs_embeds)
+    return ec->any() ? fail("%s: neither ids nor inputs_embeds is given (exactly one of them feeds the embeddings)", who)
+                     : fail("%s: ids is null", who);
+  if (ec->any() && e->fp8_on)
+    return fail("%s: fp8 mode is on: token_type_ids / position_ids / inputs_embeds / d_inputs_embeds are bf16-mode inputs (plb_set_fp8(e, 0, stream) first)", who);
+  return 0;
+}
+
 // layers (or null): the per-application outputs of plb_forward_layers, written by run_encoder as the call goes
+// inputs (or null): the embedding inputs of plb_forward_inputs
 static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                         const PlbPacking* pk, float* hidden, float* phoneme_logits, float* token_logits,
-                        const PlbLayerOutputs* layers, const char* who, void* stream) {
+                        const PlbLayerOutputs* layers, const char* who, void* stream, const PlbEmbedInputs* inputs = nullptr) {
   if (check_shape(e, B, S, who)) return 1;
   drop_stash(e, "plb_forward rewrote the workspace since");
   drop_final(e, "the last call that ran the encoder (plb_forward) failed");
-  if (!ids) return fail("%s: ids is null", who);
+  EmbedCall ec;
+  if (embed_call(e, ids, inputs, nullptr, who, &ec)) return 1;
   if (token_logits && !e->NT) return fail("%s: token_logits requested but num_tokens = 0", who);
   hipStream_t s = (hipStream_t)stream;
   const int H = e->H;
@@ -69,7 +88,7 @@ static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths
   const int T = rw.T;
   const int64_t Tp = rw.Tp;
   bf16_t* x = nullptr;
-  if (run_encoder(e, ids, lengths, B, S, rw, false, &x, s, nullptr, layers)) return 1;
+  if (run_encoder(e, ids, lengths, B, S, rw, false, &x, s, nullptr, layers, &ec)) return 1;
   if (rw.row_start) {
     // back to the caller's [B,S,*] layout, zeros at the pad positions
     if (hidden) TRY(plb_launch_unpack_rows(x, 1, H, rw.row_start, lengths, B, S, H, hidden, s));
@@ -114,6 +133,11 @@ extern "C" int plb_forward_packed(PlbEngine* e, const int64_t* ids, const int32_
 extern "C" int plb_forward_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                                   const PlbPacking* packing, float* hidden, const PlbLayerOutputs* layers, void* stream) {
   return forward_impl(e, ids, lengths, B, S, packing, hidden, nullptr, nullptr, layers, "plb_forward_layers", stream);
+}
+// plb_forward_layers with the embedding inputs (include/plbert.h: PlbEmbedInputs); none given: that call
+extern "C" int plb_forward_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths, int32_t B,
+                                  int32_t S, const PlbPacking* packing, float* hidden, const PlbLayerOutputs* layers, void* stream) {
+  return forward_impl(e, ids, lengths, B, S, packing, hidden, nullptr, nullptr, layers, "plb_forward_inputs", stream, inputs);
 }
 
 // ---- stages of a loss call ----------------------------------------------------------------------------------------------
@@ -285,7 +309,7 @@ static int token_head(PlbEngine* e, bool backward, const bf16_t* xL, const int64
 //        (HBM-bound) — with its own slab / scratch so nothing is shared; joined before the first piece that holds
 //        any of its outputs.
 static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const int32_t* lengths, bf16_t* dy, int B, int S,
-                                 const Rows& rw, int du_rows, hipStream_t s, hipStream_t s2, float* scratch2) {
+                                 const Rows& rw, int du_rows, hipStream_t s, hipStream_t s2, float* scratch2, const EmbedCall* ec) {
   const int E = e->E, H = e->H, I = e->I, L = e->L;
   const int T = rw.T;
   const int64_t Tp = rw.Tp;
@@ -312,8 +336,9 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const 
   HB_W(s2, scratch2, 512 * (3 * H > I ? 3 * H : I) * 4, "column-sum scratch of the side stream");
   HB_W(s2, e->grd(PLB_MAP_B), H * 4, "map-in bias gradient");
   TRY(plb_launch_colsum(dy, 1, (size_t)Tp, H, H, e->grd(PLB_MAP_B), H, 0, scratch2, 128, s2));
+  const bool sources = ec && ec->any();   // per-token embedding sources / d_inputs_embeds: the launches of embed_inputs.hip
   HB_W(s2, e->grd(PLB_TYPE_EMB), e->psize[PLB_TYPE_EMB] * 4, "token-type embedding gradient");
-  HIPTRY(hipMemsetAsync(e->grd(PLB_TYPE_EMB), 0, (size_t)e->psize[PLB_TYPE_EMB] * 4, s2));
+  if (!sources) HIPTRY(hipMemsetAsync(e->grd(PLB_TYPE_EMB), 0, (size_t)e->psize[PLB_TYPE_EMB] * 4, s2));
   PlbEmbed em;
   memset(&em, 0, sizeof(em));
   em.ids = masked_ids; em.T = T; em.S = S; em.E = E; em.V = e->V;
@@ -325,11 +350,29 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const 
   if (rw.row_start) { em.row_start = rw.row_start; em.lengths = lengths; em.B = B; }
   HB_W(s2, em.dx, Tp * E * 4, "embedding LayerNorm backward rows"); HB_W(s2, em.partials, (int64_t)e->emb_blocks * 2 * E * 4, "embedding LayerNorm partials");
   HB_W(s2, e->grd(PLB_WORD_EMB), (e->poff[PLB_MAP_W] - e->poff[PLB_WORD_EMB]) * 4, "embedding tables' and embedding LayerNorm's gradients");
+  if (sources) {
+    // every row of the three tables is written by the scatter: word rows as below (zeros with inputs_embeds), position and
+    // token-type rows from the chunk partial rows where position_ids / token_type_ids key them
+    PlbEmbedIn xi;
+    memset(&xi, 0, sizeof(xi));
+    em.lengths = lengths; em.B = B;   // (padded call too: d_inputs_embeds gets its zeros at the pad positions)
+    xi.base = &em;
+    xi.token_type_ids = ec->in.token_type_ids; xi.position_ids = ec->in.position_ids; xi.inputs_embeds = ec->in.inputs_embeds;
+    xi.NTY = e->c.type_vocab_size; xi.P = e->P;
+    xi.dtype_rows = e->grd(PLB_TYPE_EMB); xi.d_inputs_embeds = ec->d_inputs_embeds;
+    xi.chunk_part = e->at<float>(e->o_embpart);
+    if (xi.d_inputs_embeds) HB_W(s2, xi.d_inputs_embeds, (int64_t)B * S * E * 4, "d_inputs_embeds (the caller's buffer)");
+    HB_W(s2, xi.chunk_part, (int64_t)plb_embed_inputs_part_floats(B * S, e->P, xi.NTY, E) * 4, "chunk partial rows of the keyed table sums");
+    TRY(plb_launch_embed_inputs_bwd(&xi, s2));
+    TRY(plb_launch_embed_inputs_scatter(&xi, s2));
+    TRY(plb_launch_colsum(em.partials, 0, (size_t)e->emb_blocks, 2 * E, 2 * E, e->grd(PLB_EMB_LN_W), 2 * E, 0, scratch2, 1, s2));
+  } else {
   TRY(plb_launch_embed_bwd(&em, s2));
   TRY(plb_launch_embed_scatter(&em, e->P, s2));
   TRY(plb_launch_colsum(em.partials, 0, (size_t)e->emb_blocks, 2 * E, 2 * E, e->grd(PLB_EMB_LN_W), 2 * E, 0, scratch2, 1, s2));
   // token_type row 0 receives every token's gradient = the column sums of dpos
   TRY(plb_launch_colsum(e->grd(PLB_POS_EMB), 0, (size_t)e->P, E, E, e->grd(PLB_TYPE_EMB), E, 0, scratch2, 1, s2));
+  }
   // Q/K/V biases: the attention-backward kernels left the column sums of every 32-row patch they stored, per application
   // ([L][B*QT*4][3H])
   HB_R(s2, st.qkvcol, qkvcol_all * 3 * H * 4, "Q/K/V bias partial rows");
@@ -395,7 +438,7 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const 
 }
 
 static int backward_tail(PlbEngine* e, const int64_t* masked_ids, const int32_t* lengths, bf16_t* dy, int B, int S,
-                         const Rows& rw, int du_rows, hipStream_t s) {
+                         const Rows& rw, int du_rows, hipStream_t s, const EmbedCall* ec = nullptr) {
   hipStream_t s2 = s;
   float* scratch2 = e->at<float>(e->o_scratch);
   // the layer loop (all of it on the caller's stream) has written the stash, the partial-row tables, dX: one entry
@@ -407,7 +450,7 @@ static int backward_tail(PlbEngine* e, const int64_t* masked_ids, const int32_t*
     HIPTRY(ev_record(e, e->ev_fork, s));
     HIPTRY(ev_wait(e, s2, e->ev_fork));
   }
-  const int rc = backward_tail_streams(e, masked_ids, lengths, dy, B, S, rw, du_rows, s, s2, scratch2);
+  const int rc = backward_tail_streams(e, masked_ids, lengths, dy, B, S, rw, du_rows, s, s2, scratch2, ec);
   // Whatever happened above, the caller's stream must not run ahead of the side stream's work (also on an error
   // path: the side stream may hold launches that read buffers the caller is about to reuse).
   if (s2 != s) {
@@ -564,13 +607,17 @@ extern "C" int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, cons
 // part: its gradient range is written as zeros (and still travels as the first piece of the exchange, as in
 // zero_loss_call: the collective sequence of a step is the same whatever the step computes).
 // layers (or null): the per-application outputs of plb_encode_layers, written by run_encoder as the call goes.
+// inputs (or null): the embedding inputs of plb_encode_inputs.
 static int encode_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* pk,
-                       float* hidden, const PlbLayerOutputs* layers, const char* who, void* stream) {
+                       float* hidden, const PlbLayerOutputs* layers, const char* who, void* stream,
+                       const PlbEmbedInputs* inputs = nullptr) {
   if (check_shape(e, B, S, who)) return 1;
   if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1): a differentiable forward keeps every application's activations", who);
   if (!e->grads) return fail("%s: no gradient buffer bound", who);
   if (e->fp8_on) return fail("%s: fp8 mode is on (the gradient sites' delayed scales belong to the pre-training loss); call plb_set_fp8(e, 0, stream) first", who);
-  if (!ids || !hidden) return fail("%s: %s is null", who, !ids ? "ids" : "hidden");
+  EmbedCall ec;
+  if (embed_call(e, ids, inputs, nullptr, who, &ec)) return 1;
+  if (!hidden) return fail("%s: hidden is null", who);
   hipStream_t s = (hipStream_t)stream;
   Rows rw;
   if (pick_rows(e, pk, lengths, false, B, S, who, &rw)) return 1;
@@ -580,7 +627,7 @@ static int encode_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
   HB_W(s, e->ws, e->ws_bytes, "plb_encode (whole workspace)");
   e->last_app_rows[0] = e->last_app_rows[1] = rw.Tp;
   bf16_t* x = nullptr;
-  if (run_encoder(e, ids, lengths, B, S, rw, true, &x, s, nullptr, layers)) return 1;
+  if (run_encoder(e, ids, lengths, B, S, rw, true, &x, s, nullptr, layers, &ec)) return 1;
   // .last_hidden_state in the caller's [B,S,H] layout, ZEROS at the pad positions in both layouts: a downstream model must
   // not be handed numbers that carry no gradient
   if (lengths) TRY(plb_launch_unpack_rows(x, 1, e->H, rw.row_start, lengths, B, S, e->H, hidden, s));
@@ -599,6 +646,11 @@ extern "C" int plb_encode_layers(PlbEngine* e, const int64_t* ids, const int32_t
                                  const PlbPacking* pk, float* hidden, const PlbLayerOutputs* layers, void* stream) {
   return encode_impl(e, ids, lengths, B, S, pk, hidden, layers, "plb_encode_layers", stream);
 }
+// plb_encode_layers with the embedding inputs (include/plbert.h: PlbEmbedInputs); none given: that call
+extern "C" int plb_encode_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths, int32_t B,
+                                 int32_t S, const PlbPacking* pk, float* hidden, const PlbLayerOutputs* layers, void* stream) {
+  return encode_impl(e, ids, lengths, B, S, pk, hidden, layers, "plb_encode_inputs", stream, inputs);
+}
 
 // plb_encode_bwd_layers, and plb_encode_bwd as a call of it (layers_call false: its own name in the texts, d_hidden required).
 // d_below[l] (host array of L device pointers, or null): the caller's gradient of hidden_states[l], the input of application
@@ -606,8 +658,9 @@ extern "C" int plb_encode_layers(PlbEngine* e, const int64_t* ids, const int32_t
 // the output gradient of the last application is zero.
 static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                            const PlbPacking* pk, const float* d_hidden, const float* const* d_below, bool layers_call,
-                           void* stream) {
-  const char* who = layers_call ? "plb_encode_bwd_layers" : "plb_encode_bwd";
+                           void* stream, const char* who_inputs = nullptr, const PlbEmbedInputs* inputs = nullptr,
+                           float* d_inputs_embeds = nullptr) {
+  const char* who = who_inputs ? who_inputs : layers_call ? "plb_encode_bwd_layers" : "plb_encode_bwd";
   if (check_shape(e, B, S, who)) return 1;
   if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1)", who);
   if (!e->grads) return fail("%s: no gradient buffer bound", who);
@@ -619,7 +672,8 @@ static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* leng
     for (const float* p : below) any = any || p != nullptr;
     if (!any) below.clear();
   }
-  if (!ids) return fail("%s: ids is null", who);
+  EmbedCall ec;
+  if (embed_call(e, ids, inputs, d_inputs_embeds, who, &ec)) return 1;
   if (!d_hidden && below.empty())
     return layers_call ? fail("%s: nothing to differentiate (d_hidden is null and d_below has no entry)", who)
                        : fail("%s: d_hidden is null", who);
@@ -656,7 +710,7 @@ static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* leng
   int du_rows = 0;
   if (encoder_bwd(e, nullptr, lengths, B, S, rw, &dy, &du_rows, s, below.empty() ? nullptr : below.data())) return 1;
   if (status_exchange(e, s)) return 1;
-  if (backward_tail(e, ids, lengths, dy, B, S, rw, du_rows, s)) return 1;
+  if (backward_tail(e, ids, lengths, dy, B, S, rw, du_rows, s, &ec)) return 1;
   return status_finish(e, nullptr, s);
 }
 extern "C" int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
@@ -666,4 +720,11 @@ extern "C" int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* l
 extern "C" int plb_encode_bwd_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                                      const PlbPacking* pk, const float* d_hidden, const float* const* d_below, void* stream) {
   return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, d_below, true, stream);
+}
+// plb_encode_bwd_layers with the embedding inputs of the live plb_encode_inputs call and, when asked, the gradient of the
+// pre-LayerNorm embedding sum; nothing of the two given: that call
+extern "C" int plb_encode_bwd_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths,
+                                     int32_t B, int32_t S, const PlbPacking* pk, const float* d_hidden, const float* const* d_below,
+                                     float* d_inputs_embeds, void* stream) {
+  return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, d_below, true, stream, "plb_encode_bwd_inputs", inputs, d_inputs_embeds);
 }

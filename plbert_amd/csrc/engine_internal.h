@@ -107,6 +107,7 @@ struct PlbEngine {
   int64_t o_hm, o_logm, o_dlog, o_dhm, o_rows, o_tgt, o_w, o_lrows;
   int64_t o_slab, o_part1, o_part2, o_parte, o_scratch, o_dxe, o_ducol, o_slab2, o_scratch2, o_qkvcol = 0;
   int64_t o_lnx = 0, o_lnerr = 0;
+  int64_t o_embpart = 0;   // chunk partial rows of the table sums keyed by position_ids / token_type_ids (embed_inputs.hip)
   // plb_masked_report's own regions (engine_eval.cpp): ranks and row losses when the caller takes none, the token head's
   // per-block counts. No other entry point reads or writes them.
   int64_t o_rep_rank = 0, o_rep_nll = 0, o_rep_tok = 0;
@@ -296,6 +297,16 @@ struct Bwd {
   hipStream_t s;
 };
 
+// What a call feeds its embeddings beside the ids (include/plbert.h: PlbEmbedInputs) and, in a backward, where the gradient of
+// the pre-LayerNorm sum goes (fp32 [B,S,E], or null). One struct from the entry point down to the embedding forward
+// (run_encoder) and the backward tail; a null pointer to it, or one whose members are all null, is a plain call: the launches of
+// embed.hip, as before.
+struct EmbedCall {
+  PlbEmbedInputs in;
+  float* d_inputs_embeds;
+  bool any() const { return in.token_type_ids || in.position_ids || in.inputs_embeds || d_inputs_embeds; }
+};
+
 // The pieces of the overlapped exchange in issue order (engine_comm.cpp: kPieces)
 enum { kPieceHead = 0, kPieceQkvW, kPieceFfnW, kPieceSmall, kPieceFfnoW = kPieceSmall + 5, kPieceDenseW, kNPieces };
 
@@ -325,7 +336,8 @@ int qkvcol_rows(int B, int S);
 Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int prows = 0, int du_rows = 0);
 bool prune_enabled();
 int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B, int S, const Rows& rw, bool stash,
-                bf16_t** xout, hipStream_t s, const Prune* pr = nullptr, const PlbLayerOutputs* taps = nullptr);
+                bf16_t** xout, hipStream_t s, const Prune* pr = nullptr, const PlbLayerOutputs* taps = nullptr,
+                const EmbedCall* ec = nullptr);
 int tn_splits(int64_t Mtot, int N, int K, int* rows_per_split);
 int weight_grad(PlbEngine* e, const bf16_t* A, int lda, int Ncols, const bf16_t* Bm, int ldb, int64_t Mtot, int N,
                 int K, float* out, hipStream_t s, bool side_slab = false);

@@ -260,6 +260,7 @@ static int tap_hidden(PlbEngine* e, const PlbLayerOutputs* taps, int slot, const
 
 // Embeddings + L applications of the shared layer. stash: keep every layer's activations (training)
 // or reuse the layer-0 slots (inference). Returns the final hidden buffer in *xout.
+// ec (or null): what the embeddings read beside the ids (EmbedCall); ids is null with inputs_embeds.
 // taps (or null; never with a pruned last application): the per-application outputs the caller asked for — the map-in
 // output and every application's output as they are written, the attention probabilities from the qkv rows and the
 // log-sum-exp of the attention forward that has just run (without a stash the next application reuses that slot: stream
@@ -271,7 +272,7 @@ static int tap_hidden(PlbEngine* e, const PlbLayerOutputs* taps, int slot, const
 // call: the weight-gradient GEMMs read them all at the end of the backward. A calibration call (the first after
 // plb_set_fp8, and a training call whose gradient sites have not been seen yet) runs in bf16 and only records the maxima.
 int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B, int S, const Rows& rw, bool stash,
-                       bf16_t** xout, hipStream_t s, const Prune* pr, const PlbLayerOutputs* taps) {
+                       bf16_t** xout, hipStream_t s, const Prune* pr, const PlbLayerOutputs* taps, const EmbedCall* ec) {
   const int E = e->E, H = e->H, I = e->I, L = e->L;
   const int T = rw.T;
   const int64_t Tp = rw.Tp;
@@ -295,7 +296,16 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
     // maxima — taken over every row of the slots — are those of the padded call on the batch trimmed to its slots
     em.fill_slots = e->fp8_on;
   }
-  TRY(plb_launch_embed_fwd(&em, s));
+  if (ec && ec->any()) {   // per-token sources (plb_*_inputs): the row kernel of embed_inputs.hip
+    PlbEmbedIn xi;
+    memset(&xi, 0, sizeof(xi));
+    xi.base = &em;
+    xi.token_type_ids = ec->in.token_type_ids; xi.position_ids = ec->in.position_ids; xi.inputs_embeds = ec->in.inputs_embeds;
+    xi.NTY = e->c.type_vocab_size; xi.P = e->P;
+    TRY(plb_launch_embed_inputs_fwd(&xi, s));
+  } else {
+    TRY(plb_launch_embed_fwd(&em, s));
+  }
 
   const Slots first = slots(e, Tp, B, S, 0, stash);
   PlbGemmNT g = nt_desc(em.out, e->wbf(PLB_MAP_W), Tp, H, E);

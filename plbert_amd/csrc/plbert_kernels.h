@@ -143,6 +143,34 @@ int plb_launch_embed_fwd(const PlbEmbed* p, hipStream_t stream);
 int plb_launch_embed_bwd(const PlbEmbed* p, hipStream_t stream);  // grid = p->nblocks; writes dx + partials
 int plb_launch_embed_scatter(const PlbEmbed* p, int P, hipStream_t stream);  // dx -> dword [V,E], dpos [P,E]
 
+// Embeddings with per-token sources (embed_inputs.hip): e = LN_E((inputs_embeds[b,s] | word[ids[b,s]]) + type[token_type_ids[b,s]]
+// + pos[position_ids[b,s]]). base (HOST pointer, read by the launcher) carries everything the plain launchers read: shapes,
+// tables (type0 = row 0 of the token-type table), LayerNorm, outputs, the packing plan; base->lengths may be set in a padded call
+// too (B with it) — then d_inputs_embeds gets its zeros at the pad positions. Exactly one of base->ids and inputs_embeds is given.
+// The three per-token sources are indexed like ids, by the padded [B,S] position, also in a token-packed call. An index outside
+// its table reads row 0 (the host validates).
+typedef struct {
+  const PlbEmbed* base;
+  const int64_t* token_type_ids;  // [B,S] or NULL: row 0
+  const int64_t* position_ids;    // [B,S] or NULL: s
+  const float* inputs_embeds;     // fp32 [B,S,E] or NULL
+  int NTY, P;                     // rows of the token-type and of the position table
+  // backward
+  float* dtype_rows;              // fp32 [NTY,E]: written by embed_inputs_scatter (every row)
+  float* d_inputs_embeds;         // fp32 [B,S,E] or NULL: embed_inputs_bwd unpacks dx into it (zeros at pad positions)
+  // embed_inputs_scatter: plb_embed_inputs_part_floats(...) floats — the partial rows of the 512-token chunks, summed in chunk order
+  float* chunk_part;
+} PlbEmbedIn;
+int plb_launch_embed_inputs_fwd(const PlbEmbedIn* p, hipStream_t stream);
+int plb_launch_embed_inputs_bwd(const PlbEmbedIn* p, hipStream_t stream);  // grid = base->nblocks; dx + partials (+ d_inputs_embeds)
+// dx -> dword [V,E] (zeros with inputs_embeds), dpos [P,E], dtype_rows [NTY,E]. Word rows, and position rows without position_ids,
+// are summed by plb_launch_embed_scatter's kernel as in a plain call. A row keyed by position_ids / token_type_ids may own every
+// token of the call: the padded token range is cut into chunks of 512, workgroup (row, chunk) sums the chunk's tokens of that row
+// in token order into a partial row, and the partial rows are added in chunk order. No atomics; fixed order.
+int plb_launch_embed_inputs_scatter(const PlbEmbedIn* p, hipStream_t stream);
+// floats of chunk_part for a call of `tokens` padded positions (B*S)
+size_t plb_embed_inputs_part_floats(int tokens, int P, int NTY, int E);
+
 // LayerNorm over rows of width H (H%4==0, H<=1024): y = LN(x)*g+b ; stats saved for the backward
 typedef struct {
   const bf16_t* x; int ldx;

@@ -429,13 +429,64 @@ class HipEngine:
             t = t.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous()
         return t
 
-    def forward(self, ids, lengths=None, want_hidden=False, want_phoneme=True, want_token=False, packing=None):
+    # ---- embedding inputs (include/plbert.h: PlbEmbedInputs) ----
+    def _embed_inputs(self, ids, token_type_ids, position_ids, inputs_embeds):
+        """(ids | None, B, S, PlbEmbedInputs | None, the tensors it points to). Exactly one of ``ids`` and
+        ``inputs_embeds``; ``position_ids`` [B,S] or [1,S] (broadcast); index ranges are checked here, on the host side of
+        the call, with the argument and its bound in the text."""
+        if (ids is None) == (inputs_embeds is None):
+            raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
+        E = self.cfg.embedding_size
+        xe = None
+        if ids is not None:
+            ids = self._dev_i64(ids)
+            B, S = ids.shape
+        else:
+            xe = torch.as_tensor(inputs_embeds)
+            if xe.dim() != 3 or xe.shape[-1] != E:
+                raise ValueError(f"inputs_embeds must be [B,S,embedding_size={E}], got {tuple(xe.shape)}")
+            xe = xe.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            B, S = int(xe.shape[0]), int(xe.shape[1])
+
+        def index(t, what, bound, bound_name):
+            if t is None:
+                return None
+            t = torch.as_tensor(t)
+            if what == "position_ids" and t.dim() == 2 and t.shape[0] == 1 and B > 1:
+                t = t.expand(B, -1)
+            if tuple(t.shape) != (B, S):
+                raise ValueError(f"{what} must be [{B},{S}]{' or [1,' + str(S) + ']' if what == 'position_ids' else ''}, got {tuple(t.shape)}")
+            t = t.to(device=self.device, dtype=torch.int64).contiguous()
+            lo, hi = int(t.min()), int(t.max())
+            if lo < 0 or hi >= bound:
+                raise ValueError(f"{what} has values in [{lo}, {hi}]: they must be in [0, {bound_name} = {bound})")
+            return t
+
+        tt = index(token_type_ids, "token_type_ids", self.cfg.type_vocab_size, "type_vocab_size")
+        pid = index(position_ids, "position_ids", self.cfg.max_position_embeddings, "max_position_embeddings")
+        if tt is None and pid is None and xe is None:
+            return ids, int(B), int(S), None, None
+        p = lambda t: None if t is None else t.data_ptr()
+        return ids, int(B), int(S), _lib.PlbEmbedInputs(p(tt), p(pid), p(xe)), (tt, pid, xe)
+
+    def forward(self, ids, lengths=None, want_hidden=False, want_phoneme=True, want_token=False, packing=None,
+                token_type_ids=None, position_ids=None, inputs_embeds=None):
         """ids int64 [B,S]; lengths per-sample valid-token counts (None = no padding).
         Returns (hidden | None, phoneme_logits | None, token_logits | None), fp32 on the device.
         ``packing`` (PackingPlan of these lengths): token-packed execution; pad positions of the outputs are zeros.
         With all three ``want_*`` False the call outputs nothing: it runs the encoder and leaves the final hidden state
-        on the device for ``token_report``."""
+        on the device for ``token_report``.
+        ``token_type_ids`` / ``position_ids`` / ``inputs_embeds`` (plb_forward_inputs; ``ids`` is None with
+        ``inputs_embeds``): the hidden state only — pass want_phoneme=False (the logits of such a call are not computed)."""
         self._ensure_synced()
+        if token_type_ids is not None or position_ids is not None or inputs_embeds is not None:
+            if want_phoneme or want_token:
+                raise ValueError("forward: token_type_ids / position_ids / inputs_embeds give the hidden state only "
+                                 "(want_phoneme=False, want_token=False)")
+            hs, at, hid = self.forward_layers(ids, lengths, packing, hidden_states=False, attentions=False, want_hidden=True,
+                                              token_type_ids=token_type_ids, position_ids=position_ids,
+                                              inputs_embeds=inputs_embeds)
+            return (hid if want_hidden else None), None, None
         ids = self._dev_i64(ids)
         B, S = ids.shape
         lens = self._dev_i32(lengths)
@@ -505,50 +556,68 @@ class HipEngine:
         return lo, (ha, aa)
 
     def forward_layers(self, ids, lengths=None, packing=None, hidden_states=True, attentions=False, want_hidden=False,
-                       out=None):
+                       out=None, token_type_ids=None, position_ids=None, inputs_embeds=None):
         """The encoder's per-application outputs (plb_forward_layers): ``hidden_states`` / ``attentions`` = True (every
         slot), False, or a list of slots. Returns ``(hidden_states, attentions)``: lists of L + 1 fp32 [B,S,H] and of L
         fp32 [B,NH,S,S] tensors with None in the slots not asked for; ``hidden_states[0]`` is the output of
         embedding_hidden_mapping_in, ``hidden_states[l]`` the output of application l. Pad positions of every hidden
         state and pad query rows / key columns of every attention map are zeros. ``want_hidden``: a third element, the
         ``hidden`` of ``forward`` itself. ``out`` = (hidden-state list, attention list): the caller's tensors (None = slot
-        not wanted) instead of new ones. Works on inference-only engines, with a plan, and in fp8 mode."""
+        not wanted) instead of new ones. Works on inference-only engines, with a plan, and in fp8 mode.
+        ``token_type_ids`` / ``position_ids`` / ``inputs_embeds`` (plb_forward_inputs, not in fp8 mode): the embedding
+        inputs of transformers' AlbertModel; ``ids`` is None with ``inputs_embeds`` [B,S,embedding_size]."""
         self._ensure_synced()
-        ids = self._dev_i64(ids)
-        B, S = ids.shape
+        ids, B, S, ein, keep_in = self._embed_inputs(ids, token_type_ids, position_ids, inputs_embeds)
         lens = self._dev_i32(lengths)
         with torch.cuda.device(self.device):
             hs, at = self._alloc_layer_outputs(B, S, hidden_states, attentions) if out is None else (list(out[0]), list(out[1]))
             hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device) if want_hidden else None
             lo, keep = self._layer_outputs(hs, at, B, S)
             pk = self._packing(packing, B, S)
-            _lib.check(self.L.plb_forward_layers(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
-                                                 None if pk is None else C.byref(pk), None if hid is None else hid.data_ptr(),
-                                                 None if lo is None else C.byref(lo), self._stream()), "plb_forward_layers")
-            del keep
+            if ein is None:
+                _lib.check(self.L.plb_forward_layers(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
+                                                     None if pk is None else C.byref(pk), None if hid is None else hid.data_ptr(),
+                                                     None if lo is None else C.byref(lo), self._stream()), "plb_forward_layers")
+            else:
+                _lib.check(self.L.plb_forward_inputs(self.handle, None if ids is None else ids.data_ptr(), C.byref(ein),
+                                                     None if lens is None else lens.data_ptr(), B, S,
+                                                     None if pk is None else C.byref(pk), None if hid is None else hid.data_ptr(),
+                                                     None if lo is None else C.byref(lo), self._stream()), "plb_forward_inputs")
+            del keep, keep_in
         self._last_encoder_call = (int(B), int(S), lens, packing)
         return (hs, at, hid) if want_hidden else (hs, at)
 
-    def encode(self, ids, lengths=None, packing=None, layers=None):
+    def encode(self, ids, lengths=None, packing=None, layers=None, token_type_ids=None, position_ids=None, inputs_embeds=None):
         """Differentiable forward (include/plbert.h: plb_encode): ``.last_hidden_state`` fp32 [B,S,H] with every
         application's activations kept for ``encode_bwd``; ZEROS at pad positions. Training engines only, not in fp8
         mode. The ids, lengths and plan are remembered for the backward; any other computing call on this engine in
         between (forward, a loss call, another encode, an optimizer step) ends the life of the kept activations.
         ``layers`` = dict(hidden_states=True | False | slots, attentions=...) (plb_encode_layers): returns
-        ``(hidden, hidden_states, attentions)`` as ``forward_layers`` does."""
+        ``(hidden, hidden_states, attentions)`` as ``forward_layers`` does.
+        ``token_type_ids`` / ``position_ids`` / ``inputs_embeds`` (plb_encode_inputs): the embedding inputs of
+        transformers' AlbertModel, remembered for the backward like the ids; ``ids`` is None with ``inputs_embeds``."""
         if not self.train_mode:
             raise RuntimeError("this HipEngine was built with train=False (inference / validation only): encode() keeps "
                                "the activations of every layer for a backward")
         self.raise_if_failed()
         self._ensure_synced()
-        ids = self._dev_i64(ids)
-        B, S = ids.shape
+        ids, B, S, ein, keep_in = self._embed_inputs(ids, token_type_ids, position_ids, inputs_embeds)
         lens = self._dev_i32(lengths)
         self._live_encode = None
         with torch.cuda.device(self.device):
             hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device)
             pk = self._packing(packing, B, S)
-            if layers is None:
+            hs = at = None
+            if ein is not None:
+                if layers is not None:
+                    hs, at = self._alloc_layer_outputs(B, S, layers.get("hidden_states", False), layers.get("attentions", False))
+                lo, keep = self._layer_outputs(hs, at, B, S)
+                _lib.check(self.L.plb_encode_inputs(self.handle, None if ids is None else ids.data_ptr(), C.byref(ein),
+                                                    None if lens is None else lens.data_ptr(), B, S,
+                                                    None if pk is None else C.byref(pk), hid.data_ptr(),
+                                                    None if lo is None else C.byref(lo), self._stream()), "plb_encode_inputs")
+                del keep
+            elif layers is None:
                 _lib.check(self.L.plb_encode(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
                                              None if pk is None else C.byref(pk), hid.data_ptr(), self._stream()), "plb_encode")
             else:
@@ -559,20 +628,22 @@ class HipEngine:
                                                     None if lo is None else C.byref(lo), self._stream()), "plb_encode_layers")
                 del keep
         self._encode_serial = getattr(self, "_encode_serial", 0) + 1
-        self._live_encode = (ids, lens, packing, B, S)   # (holds the tensors the backward reads again)
+        self._live_encode = (ids, lens, packing, B, S, ein, keep_in)   # (holds the tensors the backward reads again)
         self._last_encoder_call = (int(B), int(S), lens, packing)
         return hid if layers is None else (hid, hs, at)
 
-    def encode_bwd(self, d_hidden, d_below=None):
+    def encode_bwd(self, d_hidden, d_below=None, want_d_inputs_embeds=False):
         """Backward of the live ``encode`` from ``d_hidden`` = d(loss)/d(hidden), fp32 [B,S,H] (values at pad positions
         are ignored): the encoder range of ``self.grads`` is overwritten, the phoneme head's is zeroed and the next
         ``adamw_step`` leaves the head alone (plb_encode_bwd). ``d_below`` (plb_encode_bwd_layers): a list of L entries,
         ``d_below[l]`` = d(loss)/d(hidden_states[l]) fp32 [B,S,H] or None; ``d_hidden`` may then be None (a zero gradient
-        at the last slot)."""
+        at the last slot). ``want_d_inputs_embeds`` (plb_encode_bwd_inputs): returns fp32 [B,S,embedding_size], the gradient
+        of the pre-LayerNorm embedding sum per token (zeros at pad positions) — the gradient of ``inputs_embeds``, or the
+        per-phoneme saliency of a call that took ids."""
         live = getattr(self, "_live_encode", None)
         if live is None:
             raise RuntimeError("encode_bwd: no live encode() on this engine (one backward per encode)")
-        ids, lens, packing, B, S = live
+        ids, lens, packing, B, S, ein, keep_in = live
         shape = (B, S, self.cfg.hidden_size)
 
         def dev(g, what):
@@ -592,8 +663,19 @@ class HipEngine:
         self._live_encode = None
         with torch.cuda.device(self.device):
             pk = self._packing(packing, B, S)
-            args = (self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
+            args = (self.handle, None if ids is None else ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
                     None if pk is None else C.byref(pk), None if d is None else d.data_ptr())
+            if ein is not None or want_d_inputs_embeds:
+                arr = None if below is None else self._ptr_array(below, self.cfg.num_hidden_layers, "d_below", shape)
+                die = (torch.empty((B, S, self.cfg.embedding_size), dtype=torch.float32, device=self.device)
+                       if want_d_inputs_embeds else None)
+                _lib.check(self.L.plb_encode_bwd_inputs(self.handle, None if ids is None else ids.data_ptr(),
+                                                        None if ein is None else C.byref(ein), *args[2:],
+                                                        None if arr is None else C.addressof(arr),
+                                                        None if die is None else die.data_ptr(), self._stream()),
+                           "plb_encode_bwd_inputs")
+                del keep_in
+                return die
             if below is None:
                 _lib.check(self.L.plb_encode_bwd(*args, self._stream()), "plb_encode_bwd")
             else:

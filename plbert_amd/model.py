@@ -98,16 +98,20 @@ def _lengths_from_mask(attention_mask, strict=True):
     return lengths
 
 
-def _encode_backward(ctx, d_hidden, d_below):
+def _encode_backward(ctx, d_hidden, d_below, want_d_inputs_embeds=None, without=()):
     """The backward of a differentiable forward (``ctx``: engine, names, serial): plb_encode_bwd[_layers], then every encoder
-    Parameter's view of its slice of ``engine.grads`` (None for the pooler and the heads)."""
+    Parameter's view of its slice of ``engine.grads`` (None for the pooler, the heads and the names in ``without``).
+    ``want_d_inputs_embeds`` True / False (a forward with embedding inputs: plb_encode_bwd_inputs): the result is then
+    ``(gradient of the pre-LayerNorm embedding sum | None, parameter gradients)``."""
     eng = ctx.engine
     gone = "a later engine call overwrote the activations of this forward (the engine keeps one differentiable " \
            "forward at a time: call backward() before the next forward, loss call or optimizer step)"
     if eng._live_encode is None or eng._encode_serial != ctx.serial:
         raise RuntimeError(gone)
     try:
-        if d_below is None:
+        if want_d_inputs_embeds is not None:
+            die = eng.encode_bwd(d_hidden, d_below=d_below, want_d_inputs_embeds=want_d_inputs_embeds)
+        elif d_below is None:
             eng.encode_bwd(d_hidden)
         else:
             eng.encode_bwd(d_hidden, d_below=d_below)
@@ -119,8 +123,8 @@ def _encode_backward(ctx, d_hidden, d_below):
     grads = []
     for n in ctx.names:
         off, size, shp = eng.layout[n]
-        grads.append(eng.grads[off:off + size].view(shp) if off + size <= end else None)
-    return tuple(grads)
+        grads.append(eng.grads[off:off + size].view(shp) if off + size <= end and n not in without else None)
+    return tuple(grads) if want_d_inputs_embeds is None else (die, tuple(grads))
 
 
 class _Encode(torch.autograd.Function):
@@ -164,6 +168,35 @@ class _EncodeLayers(torch.autograd.Function):
         nl = eng.cfg.num_hidden_layers
         g = [None if x is None else x.contiguous().float() for x in grads[:nl + 1 if ctx.want_hs else 1]]
         return (None,) * 7 + _encode_backward(ctx, g[-1], g[:-1] if ctx.want_hs else None)
+
+
+class _EncodeInputs(torch.autograd.Function):
+    """_EncodeLayers with the embedding inputs of transformers' AlbertModel (plb_encode_inputs / plb_encode_bwd_inputs).
+    ``inputs_embeds`` (or None) is an input of the node: when it requires grad it receives the gradient of the pre-LayerNorm
+    embedding sum, and the word table — which took no part — receives None, as in torch. The token-type and position tables
+    receive their views of the gradient buffer like every other encoder Parameter."""
+
+    @staticmethod
+    def forward(ctx, engine, names, ids, lengths, packing, want_hs, want_at, token_type_ids, position_ids, inputs_embeds,
+                *params):
+        hid, hs, at = engine.encode(ids, lengths, packing, layers=dict(hidden_states=want_hs, attentions=want_at),
+                                    token_type_ids=token_type_ids, position_ids=position_ids, inputs_embeds=inputs_embeds)
+        ctx.engine, ctx.names, ctx.serial, ctx.want_hs = engine, names, engine._encode_serial, want_hs
+        ctx.embeds = inputs_embeds is not None
+        ctx.set_materialize_grads(False)
+        if want_at:
+            ctx.mark_non_differentiable(*at)
+        return (*(hs if want_hs else [hid]), *(at if want_at else []))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        nl = ctx.engine.cfg.num_hidden_layers
+        g = [None if x is None else x.contiguous().float() for x in grads[:nl + 1 if ctx.want_hs else 1]]
+        die, pg = _encode_backward(ctx, g[-1], g[:-1] if ctx.want_hs else None,
+                                   want_d_inputs_embeds=ctx.embeds and ctx.needs_input_grad[9],
+                                   without=("encoder.embeddings.word_embeddings.weight",) if ctx.embeds else ())
+        return (None,) * 9 + (die,) + pg
 
 
 class AlbertModel(nn.Module):
@@ -234,19 +267,22 @@ class AlbertModel(nn.Module):
         return self._engine
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None,
-                output_hidden_states=False, output_attentions=False, **unused):
+                output_hidden_states=False, output_attentions=False, inputs_embeds=None, **unused):
         """``output_hidden_states`` / ``output_attentions`` (transformers' arguments): ``.hidden_states`` = L + 1 tensors
         [B,S,H] (the output of embedding_hidden_mapping_in, then of every application of the shared layer; the last one IS
         ``last_hidden_state``), ``.attentions`` = L tensors [B,NH,S,S]. Pad positions of the hidden states, pad query rows
         and pad key columns of the attention maps are ZEROS (transformers leaves values in pad rows). On the differentiable
-        path every hidden state carries gradient; the attention maps never do."""
-        if input_ids is None:
-            raise ValueError("input_ids is required (inputs_embeds is not supported on the HIP path)")
-        if token_type_ids is not None or position_ids is not None:
-            raise ValueError("the HIP path implements the reference's implicit token_type_ids=0 / position_ids=arange")
+        path every hidden state carries gradient; the attention maps never do.
+        ``token_type_ids`` [B,S], ``position_ids`` [B,S] or [1,S], ``inputs_embeds`` [B,S,embedding_size] instead of
+        ``input_ids`` (transformers' arguments and rules; AlbertEmbeddings.forward with dropout 0): on the differentiable
+        path an ``inputs_embeds`` that requires grad receives its gradient, and the word table's ``.grad`` stays None."""
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
         lengths = _lengths_from_mask(attention_mask)
         want_hs, want_at = bool(output_hidden_states), bool(output_attentions)
         nl = self.config.num_hidden_layers
+        if token_type_ids is not None or position_ids is not None or inputs_embeds is not None:
+            return self._forward_inputs(input_ids, lengths, token_type_ids, position_ids, inputs_embeds, want_hs, want_at)
         if getattr(self, "differentiable", False) and self.training and torch.is_grad_enabled():
             # fine-tuning: the forward joins the autograd graph (_Encode); pad positions of last_hidden_state are zeros and
             # pooler_output is DETACHED (the pooler receives no gradient, as in every other call of this library)
@@ -276,6 +312,32 @@ class AlbertModel(nn.Module):
                                          packing=_packing_from_lengths(self, lengths, input_ids))
         # pooler (modeling_albert.py:403): computed for API completeness (plb_pooler), never used by the loss
         return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid))
+
+    def _forward_inputs(self, input_ids, lengths, token_type_ids, position_ids, inputs_embeds, want_hs, want_at):
+        """AlbertModel.forward with any of the embedding inputs: HipEngine.forward_layers / encode with them (the engine checks
+        shapes and index ranges), outputs as in the plain call."""
+        nl = self.config.num_hidden_layers
+        shaped = input_ids if input_ids is not None else inputs_embeds
+        packing = _packing_from_lengths(self, lengths, shaped)
+        if getattr(self, "differentiable", False) and self.training and torch.is_grad_enabled():
+            names, params = [], []
+            for n, p in self.named_parameters():
+                names.append("encoder." + n)
+                params.append(p)
+            outs = _EncodeInputs.apply(self._engine, names, input_ids, lengths, packing, want_hs, want_at, token_type_ids,
+                                       position_ids, inputs_embeds, *params)
+            hs = tuple(outs[:nl + 1]) if want_hs else None
+            hid = hs[-1] if want_hs else outs[0]
+            return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid.detach()),
+                                              hidden_states=hs, attentions=tuple(outs[-nl:]) if want_at else None)
+        hs, at, hid = self._engine.forward_layers(input_ids, lengths, packing, hidden_states=want_hs, attentions=want_at,
+                                                  want_hidden=True, token_type_ids=token_type_ids, position_ids=position_ids,
+                                                  inputs_embeds=inputs_embeds)
+        if want_hs:
+            hid = hs[-1]
+        return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid),
+                                          hidden_states=tuple(hs) if want_hs else None,
+                                          attentions=tuple(at) if want_at else None)
 
 
 class _HeadModel(nn.Module):
