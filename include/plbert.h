@@ -573,7 +573,8 @@ int plb_encode_bwd_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengt
  *   saliency) or inputs_embeds (its gradient).
  * Refusals, each before anything is launched and with a text naming the cause: both or neither of ids / inputs_embeds; any of
  *   the three inputs or d_inputs_embeds while fp8 mode is on; every refusal of the namesake.
- * Out of scope: the inputs in the pre-training loss calls (plb_loss_*), fp8 mode, non-prefix attention masks, dropout. */
+ * Out of scope: the inputs in the pre-training loss calls (plb_loss_*), fp8 mode, dropout. (Non-prefix attention masks: the
+ *   plb_*_masked calls below.) */
 typedef struct {
   const int64_t* token_type_ids;  /* device int64 [B,S] or NULL (all 0); values in [0, type_vocab_size) */
   const int64_t* position_ids;    /* device int64 [B,S] or NULL (s);     values in [0, max_position_embeddings) */
@@ -586,6 +587,39 @@ int plb_encode_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* in
 int plb_encode_bwd_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths, int32_t B,
                           int32_t S, const PlbPacking* packing, const float* d_hidden, const float* const* d_below,
                           float* d_inputs_embeds, void* stream);
+/* ---- key masks: attention masks that are no prefix, with gradients (opt-in: a call that passes none launches what it
+ * launched before) ----
+ * key_mask: DEVICE int32 [B,S], nonzero = attend, indexed by the padded position in the padded and the packed layout alike.
+ *   HuggingFace's 2-D key-padding rule: key j of sample b takes part in the softmax of EVERY query of b iff key_mask[b,j] != 0.
+ *   `lengths` is the EXTENT of each sample, 1 + the last position whose key_mask is nonzero (NULL: S); bits at and past
+ *   lengths[b] are ignored. Positions at and past the extent are pad positions exactly as in every other call: zeros in
+ *   `hidden` / hidden_states / attentions, never read by the backward, skipped by token packing (the plan is made from the
+ *   extents; holes stay inside their slot). A position below the extent whose key_mask is 0 is a HOLE: it is removed as a KEY
+ *   only. It stays a query like any other — it attends to the valid keys, has a hidden state, receives and carries gradient
+ *   (as in HuggingFace) — and attentions[l][b,h,i,j] is exactly 0 in its column j; rows i below the extent sum to 1.
+ * plb_forward_masked / plb_encode_masked / plb_encode_bwd_masked: supersets of plb_forward_inputs / plb_encode_inputs /
+ *   plb_encode_bwd_inputs. With key_mask == NULL each is exactly its namesake: the same launches, bit-identical results, the
+ *   same engine state afterwards (plb_last_call_rows, the final hidden state for plb_token_report, the live stash, the
+ *   exchange's pieces, the status exchange). With a key mask the call packs it into one bit per key in the workspace (one small
+ *   launch) and every attention launch runs the masked instantiation of its kernel (plbert_kernels.h: PlbAttn.key_words); the
+ *   backward then runs in the two-kernel form, whatever plb_set_attn_bwd_fused / PLBERT_ATTN_BWD say. A key mask that is a
+ *   prefix of ones gives the results of the call without it bit for bit (the same arithmetic per row).
+ * plb_encode_bwd_masked: key_mask as given to the live plb_encode_masked call (as ids and inputs are passed again).
+ * A sample without a single nonzero key_mask entry below its length is the host's to reject: on the device its own rows are
+ *   not finite; nothing outside the sample is affected and nothing outside its rows is read.
+ * Refusals, each before anything is launched and with a text naming the cause: key_mask while fp8 mode is on; key_mask with
+ *   S > 2048; plb_encode_bwd_masked with a key mask when the live forward had none, or without one when it had; every
+ *   refusal of the namesake.
+ * Out of scope: the pre-training loss calls (plb_loss_*), the logits of plb_forward, fp8 mode, 3-D / 4-D masks, dropout. */
+int plb_forward_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
+                       const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing, float* hidden,
+                       const PlbLayerOutputs* layers, void* stream);
+int plb_encode_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
+                      const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing, float* hidden,
+                      const PlbLayerOutputs* layers, void* stream);
+int plb_encode_bwd_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
+                          const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing, const float* d_hidden,
+                          const float* const* d_below, float* d_inputs_embeds, void* stream);
 /* ---- masked-phoneme evaluation: accuracy, top-k and fill-mask from a loss call (opt-in: a step that does not ask launches
  * what it launched before) ----
  * The reference reports the scalar loss only (train.py:288-336, 395-410). A masked LM's users also expect the accuracy at the

@@ -97,6 +97,7 @@ class PlbAttn(C.Structure):
         ("qoff", C.c_void_p), ("q", C.c_void_p), ("ldq", C.c_int), ("nq_total", C.c_int), ("dq", C.c_void_p), ("lddq", C.c_int),
         ("dq8", C.c_void_p), ("lddq8", C.c_int),
         ("row_start", C.c_void_p),
+        ("key_words", C.c_void_p), ("ldkw", C.c_int),
     ]
 
 
@@ -290,6 +291,9 @@ PUBLIC = {
     "plb_forward_inputs": (i32, [vp, vp, P(PlbEmbedInputs), vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
     "plb_encode_inputs": (i32, [vp, vp, P(PlbEmbedInputs), vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
     "plb_encode_bwd_inputs": (i32, [vp, vp, P(PlbEmbedInputs), vp, i32, i32, P(PlbPacking), vp, vp, vp, vp]),
+    "plb_forward_masked": (i32, [vp, vp, P(PlbEmbedInputs), vp, vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
+    "plb_encode_masked": (i32, [vp, vp, P(PlbEmbedInputs), vp, vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
+    "plb_encode_bwd_masked": (i32, [vp, vp, P(PlbEmbedInputs), vp, vp, i32, i32, P(PlbPacking), vp, vp, vp, vp]),
     "plb_masked_report": (i32, [vp, vp, i32, i32, P(PlbMaskedReport), vp]),
     "plb_token_report": (i32, [vp, vp, vp, vp, i32, i32, i32, P(PlbPacking), vp, i32, P(PlbTokenReport), vp]),
     "plb_comm_pieces": (i32, [vp, P(i32), P(i64)]),
@@ -361,6 +365,8 @@ INTERNAL = {
     "plb_launch_unpack_rows": (i32, [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
     "plb_launch_seed_dy": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "plb_launch_attn_probs": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, f32, vp, vp]),
+    "plb_launch_attn_probs_masked": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
+    "plb_launch_key_mask_words": (i32, [vp, vp, i32, i32, vp, i32, vp]),
     "plb_launch_add_row_grad": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "plb_launch_ce_fwd_bwd": (i32, [vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, vp]),
     "plb_launch_sum_rows": (i32, [vp, i32, vp, vp]),

@@ -241,6 +241,8 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
   // The partial rows of plb_launch_embed_inputs_scatter (a backward with position_ids / token_type_ids), carved last like the
   // regions above: one [max_position_embeddings + type_vocab_size][E] block of floats per 512 positions of the capacity.
   if (tr) e->o_embpart = cv.take((int64_t)plb_embed_inputs_part_floats((int)Tp, e->P, c.type_vocab_size, (int)E) * 4);
+  // The key-mask words of a plb_*_masked call (key_mask.hip), carved last like the regions above: two words per 64 keys.
+  e->o_keywords = cv.take((int64_t)c.max_batch * 2 * ((c.max_seq + 63) / 64) * 4);
   e->ws_bytes = cv.off;
   *out = e;
   return 0;

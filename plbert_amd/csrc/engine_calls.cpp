@@ -66,16 +66,37 @@ static int embed_call(const PlbEngine* e, const int64_t* ids, const PlbEmbedInpu
   return 0;
 }
 
+// The key mask of a plb_*_masked call (int32 [B,S] on the device, or null: nothing to check), refused before anything is launched.
+static int key_mask_check(const PlbEngine* e, const int32_t* key_mask, int S, const char* who) {
+  if (!key_mask) return 0;
+  if (e->fp8_on)
+    return fail("%s: fp8 mode is on: key_mask is a bf16-mode input (plb_set_fp8(e, 0, stream) first)", who);
+  if (S > 2048) return fail("%s: key_mask with seq %d: the masked attention kernels take S <= 2048", who, S);
+  return 0;
+}
+// ... and packed into the words the attention launches of the call read (key_mask.hip), first launch of the call
+static int key_mask_words(PlbEngine* e, const int32_t* key_mask, const int32_t* lengths, int B, int S, Rows* rw, hipStream_t s) {
+  if (!key_mask) return 0;
+  uint32_t* const words = e->at<uint32_t>(e->o_keywords);
+  const int ldkw = 2 * ((S + 63) / 64);
+  HB_W(s, words, (int64_t)B * ldkw * 4, "key-mask words of the call");
+  TRY(plb_launch_key_mask_words(key_mask, lengths, B, S, words, ldkw, s));
+  rw->key_words = words; rw->ldkw = ldkw;
+  return 0;
+}
+
 // layers (or null): the per-application outputs of plb_forward_layers, written by run_encoder as the call goes
-// inputs (or null): the embedding inputs of plb_forward_inputs
+// inputs (or null): the embedding inputs of plb_forward_inputs; key_mask (or null): the key mask of plb_forward_masked
 static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                         const PlbPacking* pk, float* hidden, float* phoneme_logits, float* token_logits,
-                        const PlbLayerOutputs* layers, const char* who, void* stream, const PlbEmbedInputs* inputs = nullptr) {
+                        const PlbLayerOutputs* layers, const char* who, void* stream, const PlbEmbedInputs* inputs = nullptr,
+                        const int32_t* key_mask = nullptr) {
   if (check_shape(e, B, S, who)) return 1;
   drop_stash(e, "plb_forward rewrote the workspace since");
   drop_final(e, "the last call that ran the encoder (plb_forward) failed");
   EmbedCall ec;
   if (embed_call(e, ids, inputs, nullptr, who, &ec)) return 1;
+  if (key_mask_check(e, key_mask, S, who)) return 1;
   if (token_logits && !e->NT) return fail("%s: token_logits requested but num_tokens = 0", who);
   hipStream_t s = (hipStream_t)stream;
   const int H = e->H;
@@ -88,6 +109,7 @@ static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths
   const int T = rw.T;
   const int64_t Tp = rw.Tp;
   bf16_t* x = nullptr;
+  if (key_mask_words(e, key_mask, lengths, B, S, &rw, s)) return 1;
   if (run_encoder(e, ids, lengths, B, S, rw, false, &x, s, nullptr, layers, &ec)) return 1;
   if (rw.row_start) {
     // back to the caller's [B,S,*] layout, zeros at the pad positions
@@ -138,6 +160,13 @@ extern "C" int plb_forward_layers(PlbEngine* e, const int64_t* ids, const int32_
 extern "C" int plb_forward_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths, int32_t B,
                                   int32_t S, const PlbPacking* packing, float* hidden, const PlbLayerOutputs* layers, void* stream) {
   return forward_impl(e, ids, lengths, B, S, packing, hidden, nullptr, nullptr, layers, "plb_forward_inputs", stream, inputs);
+}
+// plb_forward_inputs with a key mask (include/plbert.h); key_mask == NULL: that call
+extern "C" int plb_forward_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
+                                  const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing, float* hidden,
+                                  const PlbLayerOutputs* layers, void* stream) {
+  return forward_impl(e, ids, lengths, B, S, packing, hidden, nullptr, nullptr, layers,
+                      key_mask ? "plb_forward_masked" : "plb_forward_inputs", stream, inputs, key_mask);
 }
 
 // ---- stages of a loss call ----------------------------------------------------------------------------------------------
@@ -610,13 +639,14 @@ extern "C" int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, cons
 // inputs (or null): the embedding inputs of plb_encode_inputs.
 static int encode_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* pk,
                        float* hidden, const PlbLayerOutputs* layers, const char* who, void* stream,
-                       const PlbEmbedInputs* inputs = nullptr) {
+                       const PlbEmbedInputs* inputs = nullptr, const int32_t* key_mask = nullptr) {
   if (check_shape(e, B, S, who)) return 1;
   if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1): a differentiable forward keeps every application's activations", who);
   if (!e->grads) return fail("%s: no gradient buffer bound", who);
   if (e->fp8_on) return fail("%s: fp8 mode is on (the gradient sites' delayed scales belong to the pre-training loss); call plb_set_fp8(e, 0, stream) first", who);
   EmbedCall ec;
   if (embed_call(e, ids, inputs, nullptr, who, &ec)) return 1;
+  if (key_mask_check(e, key_mask, S, who)) return 1;
   if (!hidden) return fail("%s: hidden is null", who);
   hipStream_t s = (hipStream_t)stream;
   Rows rw;
@@ -627,6 +657,7 @@ static int encode_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
   HB_W(s, e->ws, e->ws_bytes, "plb_encode (whole workspace)");
   e->last_app_rows[0] = e->last_app_rows[1] = rw.Tp;
   bf16_t* x = nullptr;
+  if (key_mask_words(e, key_mask, lengths, B, S, &rw, s)) return 1;
   if (run_encoder(e, ids, lengths, B, S, rw, true, &x, s, nullptr, layers, &ec)) return 1;
   // .last_hidden_state in the caller's [B,S,H] layout, ZEROS at the pad positions in both layouts: a downstream model must
   // not be handed numbers that carry no gradient
@@ -635,6 +666,7 @@ static int encode_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths,
   TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), nullptr, e->host_err_dev, nullptr, s));
   e->stash_live = true;
   e->stash_B = B; e->stash_S = S; e->stash_rows = rw.Tp; e->stash_used = rw.T; e->stash_row_start = rw.row_start;
+  e->stash_masked = key_mask != nullptr;
   note_final(e, x, B, S, rw);
   return 0;
 }
@@ -651,6 +683,13 @@ extern "C" int plb_encode_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbe
                                  int32_t S, const PlbPacking* pk, float* hidden, const PlbLayerOutputs* layers, void* stream) {
   return encode_impl(e, ids, lengths, B, S, pk, hidden, layers, "plb_encode_inputs", stream, inputs);
 }
+// plb_encode_inputs with a key mask (include/plbert.h); key_mask == NULL: that call
+extern "C" int plb_encode_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
+                                 const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* pk, float* hidden,
+                                 const PlbLayerOutputs* layers, void* stream) {
+  return encode_impl(e, ids, lengths, B, S, pk, hidden, layers, key_mask ? "plb_encode_masked" : "plb_encode_inputs", stream, inputs,
+                     key_mask);
+}
 
 // plb_encode_bwd_layers, and plb_encode_bwd as a call of it (layers_call false: its own name in the texts, d_hidden required).
 // d_below[l] (host array of L device pointers, or null): the caller's gradient of hidden_states[l], the input of application
@@ -659,7 +698,7 @@ extern "C" int plb_encode_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbe
 static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                            const PlbPacking* pk, const float* d_hidden, const float* const* d_below, bool layers_call,
                            void* stream, const char* who_inputs = nullptr, const PlbEmbedInputs* inputs = nullptr,
-                           float* d_inputs_embeds = nullptr) {
+                           float* d_inputs_embeds = nullptr, const int32_t* key_mask = nullptr) {
   const char* who = who_inputs ? who_inputs : layers_call ? "plb_encode_bwd_layers" : "plb_encode_bwd";
   if (check_shape(e, B, S, who)) return 1;
   if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1)", who);
@@ -674,12 +713,16 @@ static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* leng
   }
   EmbedCall ec;
   if (embed_call(e, ids, inputs, d_inputs_embeds, who, &ec)) return 1;
+  if (key_mask_check(e, key_mask, S, who)) return 1;
   if (!d_hidden && below.empty())
     return layers_call ? fail("%s: nothing to differentiate (d_hidden is null and d_below has no entry)", who)
                        : fail("%s: d_hidden is null", who);
   if (!e->stash_live) return fail("%s: no live plb_encode stash: %s", who, e->stash_dead_by);
   if (B != e->stash_B || S != e->stash_S)
     return fail("%s: batch %d x seq %d differs from the plb_encode call's %d x %d", who, B, S, e->stash_B, e->stash_S);
+  if ((key_mask != nullptr) != e->stash_masked)
+    return fail("%s: %s, the live plb_encode call ran %s one (the backward takes the key mask of its forward again)", who,
+                key_mask ? "a key mask is given" : "no key mask is given", e->stash_masked ? "with" : "without");
   hipStream_t s = (hipStream_t)stream;
   Rows rw;
   // (a call that fails launches nothing and leaves what plb_last_call_rows reports alone)
@@ -701,6 +744,7 @@ static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* leng
   const int64_t Tp = rw.Tp;
   bf16_t* dy = e->at<bf16_t>(e->o_dy0);
   HB_W(s, dy, Tp * e->H * 2, "output gradient of the last application, seeded from d_hidden");
+  if (key_mask_words(e, key_mask, lengths, B, S, &rw, s)) return 1;
   if (d_hidden) TRY(plb_launch_seed_dy(d_hidden, lengths, rw.row_start, B, S, e->H, (int)Tp, dy, s));
   else HIPTRY(hipMemsetAsync(dy, 0, (size_t)Tp * e->H * 2, s));   // (no gradient at the last slot: every row zero)
   // the phoneme head took no part: zeros, final before the layer loop — its piece travels where a regular step's does
@@ -727,4 +771,11 @@ extern "C" int plb_encode_bwd_inputs(PlbEngine* e, const int64_t* ids, const Plb
                                      int32_t B, int32_t S, const PlbPacking* pk, const float* d_hidden, const float* const* d_below,
                                      float* d_inputs_embeds, void* stream) {
   return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, d_below, true, stream, "plb_encode_bwd_inputs", inputs, d_inputs_embeds);
+}
+// plb_encode_bwd_inputs with the key mask of the live plb_encode_masked call; key_mask == NULL: that call
+extern "C" int plb_encode_bwd_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
+                                     const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* pk, const float* d_hidden,
+                                     const float* const* d_below, float* d_inputs_embeds, void* stream) {
+  return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, d_below, true, stream,
+                         key_mask ? "plb_encode_bwd_masked" : "plb_encode_bwd_inputs", inputs, d_inputs_embeds, key_mask);
 }

@@ -108,6 +108,7 @@ struct PlbEngine {
   int64_t o_slab, o_part1, o_part2, o_parte, o_scratch, o_dxe, o_ducol, o_slab2, o_scratch2, o_qkvcol = 0;
   int64_t o_lnx = 0, o_lnerr = 0;
   int64_t o_embpart = 0;   // chunk partial rows of the table sums keyed by position_ids / token_type_ids (embed_inputs.hip)
+  int64_t o_keywords = 0;  // key-mask words of a plb_*_masked call (key_mask.hip): [max_batch][2 * ceil(max_seq / 64)] uint32
   // plb_masked_report's own regions (engine_eval.cpp): ranks and row losses when the caller takes none, the token head's
   // per-block counts. No other entry point reads or writes them.
   int64_t o_rep_rank = 0, o_rep_nll = 0, o_rep_tok = 0;
@@ -179,6 +180,7 @@ struct PlbEngine {
   int stash_B = 0, stash_S = 0;
   int64_t stash_rows = 0, stash_used = 0;       // Tp and T of the plb_encode call
   const int32_t* stash_row_start = nullptr;     // its plan's table (null: it ran padded)
+  bool stash_masked = false;                    // it ran with a key mask (plb_encode_masked): its backward takes the mask again
   // ---- exchange, status and trace: engine_comm.cpp (begin_training_call in engine_calls.cpp resets the per-call counters) ----
   // data-parallel exchange (plb_comm_*): RCCL communicator, its stream, and the join event of the pieces in flight
   RcclComm comm = nullptr;
@@ -237,6 +239,8 @@ enum { F8W_QKV = 0, F8W_D, F8W_1, F8W_2, F8W_2T, F8W_1T, F8W_QKVT, F8W_DT, F8W_N
 struct Rows {
   const int32_t* row_start;   // device, or null: padded
   int T; int64_t Tp;
+  // key-mask words of a plb_*_masked call (PlbAttn.key_words / ldkw), or null: every attention launch of the call takes them
+  const uint32_t* key_words = nullptr; int ldkw = 0;
 };
 
 // One fp8 operand site of one application: the delayed scale its images are written with, the running maximum the writing
@@ -288,6 +292,7 @@ struct Prune { const int32_t* rows; int n; int Mc; };
 struct Bwd {
   const int32_t* lengths;
   const int32_t* row_start;   // token-packed call (Rows), or null
+  const uint32_t* key_words; int ldkw;   // key-mask words (Rows), or null
   int B, S, T;
   int64_t Tp;
   bool f8, calib;   // fp8 operands | an fp8-mode call that only records the maxima

@@ -339,6 +339,7 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
     memset(&at, 0, sizeof(at));
     at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H;
     at.row_start = rw.row_start;
+    at.key_words = rw.key_words; at.ldkw = rw.ldkw;
     // pruned last application: the attention output of ALL rows goes to a buffer of its own (training: a backward temporary
     // that the attention backward of this application reads again — its slot holds the compact rows), then only the masked
     // rows continue
@@ -356,7 +357,8 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
     }
     TRY(plb_launch_attn_fwd(&at, s));
     if (float* const probs = (taps && taps->attentions) ? taps->attentions[l] : nullptr)
-      TRY(plb_launch_attn_probs(sl.qkv, 3 * H, sl.lse, lengths, rw.row_start, B, S, e->NH, at.scale, probs, s));
+      TRY(plb_launch_attn_probs_masked(sl.qkv, 3 * H, sl.lse, lengths, rw.row_start, rw.key_words, rw.ldkw, B, S, e->NH, at.scale,
+                                       probs, s));
     // packed: the tail behind the last slot (up to 1,023 rows) is written by no attention workgroup, and what sits there
     // goes through dense / LayerNorm / FFN into the stash the weight-gradient GEMMs read: zeros, not whatever was there
     if (rw.row_start && Tp > T) {
@@ -554,6 +556,7 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
   memset(&at, 0, sizeof(at));
   at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = c.lengths; at.B = c.B; at.S = c.S; at.NH = e->NH; at.H = H; at.scale = 0.125f;
   at.row_start = c.row_start;
+  at.key_words = c.key_words; at.ldkw = c.ldkw;
   at.ctx = ctx; at.ldctx = H; at.lse = sl.lse;
   at.dctx = e->at<bf16_t>(e->o_dctx); at.lddctx = H; at.delta = e->at<float>(e->o_delta); at.dqkv = sl.dqkv; at.lddqkv = 3 * H;
   at.colpart = sl.qkvcol; at.colpart_accumulate = 0;
@@ -595,7 +598,7 @@ int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, in
                        int* du_rows, hipStream_t s, const float* const* d_below) {
   const int I = e->I, L = e->L;
   Bwd c;
-  c.lengths = lengths; c.row_start = rw.row_start; c.B = B; c.S = S; c.T = rw.T; c.Tp = rw.Tp; c.s = s;
+  c.lengths = lengths; c.row_start = rw.row_start; c.key_words = rw.key_words; c.ldkw = rw.ldkw; c.B = B; c.S = S; c.T = rw.T; c.Tp = rw.Tp; c.s = s;
   const int Tp = (int)c.Tp;
   c.f8 = f8_call(e, Tp, true);
   c.calib = e->fp8_on && !c.f8;

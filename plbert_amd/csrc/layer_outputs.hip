@@ -42,9 +42,11 @@ DEVI void probs_store_rows(const float* patch, float* out_bh, int S, int q0, int
   }
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void attn_probs_kernel(const bf16_t* qkv, int ld, const float* lse, const int32_t* lengths,
-                                                         const int32_t* row_start, int S, int NH, float scale, float* out) {
+// KM: key masks (PlbAttn.key_words; kw = the words, ldkw their row stride): a masked key's column is zeros in every row.
+// Both forms of the body are instantiated under kernel symbols of their own; KM = false is the code as it always was.
+template <bool VEC, bool KM>
+DEVI void attn_probs_body(const bf16_t* qkv, int ld, const float* lse, const int32_t* lengths, const int32_t* row_start, int S,
+                          int NH, float scale, float* out, const uint32_t* kw, int ldkw) {
   __shared__ __attribute__((aligned(16))) bf16_t smem[2][64 * 64];   // [stage] K row image, 16 KiB
   __shared__ __attribute__((aligned(16))) float spatch[4][32 * PPS];  // per-wave transpose patches, 34 KiB
   const int tid = threadIdx.x, lane = tid & 63;
@@ -99,9 +101,12 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const bf16_t* qkv, int 
 
   int kqo[4];
   row_frag_offsets(lane, kqo);
+  uint32_t kwl = 0;   // KM: word i of the sample's row on lane i (S <= 2048), as in the forward
+  if constexpr (KM) kwl = lane < 2 * ((S + 63) >> 6) ? kw[(size_t)b * ldkw + lane] : 0u;
   K_STAGE(0, 0);
   DMA_WAIT();
   __syncthreads();
+  if constexpr (KM) asm volatile("" : "+v"(kwl));   // (the word's load is consumed before the loop: attn_kernels.h, the forward)
   // One tile of 64 keys out of LDS stage CUR (a literal, as in the forward: every LDS address is a lane constant + an
   // immediate). Register r of s0 is key kt*64 + 4h + (r & 3) + 8 (r >> 2), s1 the same + 32: register group rg holds the
   // four consecutive keys 8 rg + 4h .. + 3 of this lane's query.
@@ -115,11 +120,21 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const bf16_t* qkv, int 
       s0 = MFMA32(ROW_FRAG(sK, 0, ks, kqo), qf[ks], s0);                                                 \
       s1 = MFMA32(ROW_FRAG(sK, 1, ks, kqo), qf[ks], s1);                                                 \
     }                                                                                                    \
+    uint32_t b0 = ~0u, b1 = ~0u; /* KM: register r = bit 4h + (r & 3) + 8 (r >> 2) of the tile's two words */ \
+    if constexpr (KM) {                                                                                  \
+      b0 = (uint32_t)__builtin_amdgcn_readlane((int)kwl, 2 * kt) >> (4 * h);                             \
+      b1 = (uint32_t)__builtin_amdgcn_readlane((int)kwl, 2 * kt + 1) >> (4 * h);                         \
+    }                                                                                                    \
     _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                     \
       const int key = kt * 64 + 4 * h + (r & 3) + 8 * (r >> 2);                                          \
       const float p0 = EXP2(__builtin_fmaf(s0[r], sl2, lse2)), p1 = EXP2(__builtin_fmaf(s1[r], sl2, lse2)); \
-      s0[r] = (qok && key < len) ? p0 : 0.f;                                                             \
-      s1[r] = (qok && key + 32 < len) ? p1 : 0.f;                                                        \
+      if constexpr (KM) { /* (bits at or past the length are clear) */                                   \
+        s0[r] = (qok && ((b0 >> ((r & 3) + 8 * (r >> 2))) & 1u)) ? p0 : 0.f;                             \
+        s1[r] = (qok && ((b1 >> ((r & 3) + 8 * (r >> 2))) & 1u)) ? p1 : 0.f;                             \
+      } else {                                                                                           \
+        s0[r] = (qok && key < len) ? p0 : 0.f;                                                           \
+        s1[r] = (qok && key + 32 < len) ? p1 : 0.f;                                                      \
+      }                                                                                                  \
     }                                                                                                    \
     if (q0 < S) { /* (wave-uniform) */                                                                   \
       __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): the previous tile's patch reads have landed */  \
@@ -145,13 +160,31 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const bf16_t* qkv, int 
   if (q0 < S)
     for (int kt = nkt; kt < nct; ++kt) probs_store_rows<VEC, true>(patch, out_bh, S, q0, kt * 64, lane);
 }
+template <bool VEC>
+__global__ __launch_bounds__(256) void attn_probs_kernel(const bf16_t* qkv, int ld, const float* lse, const int32_t* lengths,
+                                                         const int32_t* row_start, int S, int NH, float scale, float* out) {
+  attn_probs_body<VEC, false>(qkv, ld, lse, lengths, row_start, S, NH, scale, out, nullptr, 0);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void attn_probs_km_kernel(const bf16_t* qkv, int ld, const float* lse, const int32_t* lengths,
+                                                            const int32_t* row_start, int S, int NH, float scale, float* out,
+                                                            const uint32_t* kw, int ldkw) {
+  attn_probs_body<VEC, true>(qkv, ld, lse, lengths, row_start, S, NH, scale, out, kw, ldkw);
+}
 
 }  // namespace
 
 extern "C" int plb_launch_attn_probs(const bf16_t* qkv, int ldqkv, const float* lse, const int32_t* lengths,
                                      const int32_t* row_start, int B, int S, int NH, float scale, float* out,
                                      hipStream_t stream) {
+  return plb_launch_attn_probs_masked(qkv, ldqkv, lse, lengths, row_start, nullptr, 0, B, S, NH, scale, out, stream);
+}
+
+extern "C" int plb_launch_attn_probs_masked(const bf16_t* qkv, int ldqkv, const float* lse, const int32_t* lengths,
+                                            const int32_t* row_start, const uint32_t* key_words, int ldkw, int B, int S, int NH,
+                                            float scale, float* out, hipStream_t stream) {
   if (!qkv || !lse || !out || B < 1 || S < 1 || NH < 1) return 1;
+  if (key_words && (S > 2048 || ldkw < 2 * ((S + 63) / 64))) return 1;
   if (ldqkv < 3 * NH * 64 || ldqkv % 8 || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 3)) return 1;
   if (row_start && !lengths) return 1;   // token-packed rows are defined by the lengths
   if ((int64_t)S * ldqkv * 2 >= ((int64_t)1 << 32)) return 1;   // (the staging's 32-bit byte offsets count from the sample's first row)
@@ -159,6 +192,15 @@ extern "C" int plb_launch_attn_probs(const bf16_t* qkv, int ldqkv, const float* 
   if (grid >= ((int64_t)1 << 31)) return 1;
   const double elems = (double)B * NH * (double)S * S;
   ProfScope ps(PLB_K_ROWS, stream, 2.0 * elems * 64.0, 4.0 * elems);
+  if (key_words) {
+    if (S % 4 == 0 && !((uintptr_t)out & 15))
+      hipLaunchKernelGGL(attn_probs_km_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, qkv, ldqkv, lse, lengths, row_start,
+                         S, NH, scale, out, key_words, ldkw);
+    else
+      hipLaunchKernelGGL(attn_probs_km_kernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, qkv, ldqkv, lse, lengths, row_start,
+                         S, NH, scale, out, key_words, ldkw);
+    return LAUNCH_OK();
+  }
   if (S % 4 == 0 && !((uintptr_t)out & 15))
     hipLaunchKernelGGL(attn_probs_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, qkv, ldqkv, lse, lengths, row_start, S, NH,
                        scale, out);

@@ -254,6 +254,13 @@ typedef struct {
   // at or past the length return before any barrier (their colpart rows are zeroed unless accumulating) and nothing
   // outside the slot is read or written. lse / delta / colpart keep their (b, S) indexing.
   const int32_t* row_start;
+  // Key masks (key_words != NULL; plb_launch_key_mask_words writes them): bit j & 31 of word j >> 5 of row b (row stride
+  // ldkw >= 2 * ceil(S / 64) words: every 64-key tile owns two whole words) says whether key j of sample b takes part in the
+  // softmax of the sample's queries; bits at or past lengths[b] are clear. A masked key below the length (a hole) stays a
+  // query like any other: it has a context row, a statistic and a dQ row; its dK / dV rows are exact zeros. NULL selects
+  // the kernels without the mask; a row of all-ones bits below the length gives their results bit for bit. S <= 2048; not
+  // with compact queries; the backward runs in the two-kernel form whatever plb_set_attn_bwd_fused says.
+  const uint32_t* key_words; int ldkw;
 } PlbAttn;
 int plb_launch_attn_fwd(const PlbAttn* p, hipStream_t stream);
 // Default: the two-kernel form, dq (+delta) then dk,dv. plb_set_attn_bwd_fused(1) / PLBERT_ATTN_BWD=fused: ONE kernel for
@@ -304,6 +311,17 @@ int plb_launch_seed_dy(const float* d_hidden, const int32_t* lengths, const int3
 // indexing. lengths == NULL: S. Any S >= 1; 16-byte stores when S % 4 == 0 and out is 16-byte aligned.
 int plb_launch_attn_probs(const bf16_t* qkv, int ldqkv, const float* lse, const int32_t* lengths, const int32_t* row_start,
                           int B, int S, int NH, float scale, float* out, hipStream_t stream);
+// The same with key masks (key_words / ldkw as PlbAttn.key_words, or NULL: the launch above): the column of a masked key is
+// exact zeros in every row; a masked key below the length keeps its own row (it is a query like any other). Every element
+// is still written exactly once.
+int plb_launch_attn_probs_masked(const bf16_t* qkv, int ldqkv, const float* lse, const int32_t* lengths, const int32_t* row_start,
+                                 const uint32_t* key_words, int ldkw, int B, int S, int NH, float scale, float* out,
+                                 hipStream_t stream);
+// ---- key masks (key_mask.hip): words [B][ldkw] (ldkw >= 2 * ceil(S / 64)) from mask int32 [B,S] (nonzero = the key takes
+// part) and lengths ([B], or NULL: S; clamped to [1, S] as everywhere): bit j & 31 of word j >> 5 = key j, clear at and past
+// the length; the words of a row past 2 * ceil(S / 64) are not written. One wave per 64-key tile, one ballot, two stores.
+int plb_launch_key_mask_words(const int32_t* mask, const int32_t* lengths, int B, int S, uint32_t* words, int ldkw,
+                              hipStream_t stream);
 // A caller's fp32 gradient joins a bf16 residual operand: every one of the Tp rows of out [Tp,H] is written exactly once —
 // bf16(float(res[r,:]) + g[b,s,:]), rounded to nearest even, on row r = row_start[b] + s (row_start == NULL: b*S + s) for
 // s < lengths[b] (lengths == NULL, padded only: every position), res[r,:] unchanged on every other row: pad positions, the

@@ -469,6 +469,15 @@ class HipEngine:
         p = lambda t: None if t is None else t.data_ptr()
         return ids, int(B), int(S), _lib.PlbEmbedInputs(p(tt), p(pid), p(xe)), (tt, pid, xe)
 
+    def _key_mask(self, key_mask, B, S):
+        """A key mask (include/plbert.h: plb_*_masked) as the int32 [B,S] device tensor the calls take, or None."""
+        if key_mask is None:
+            return None
+        m = torch.as_tensor(key_mask)
+        if tuple(m.shape) != (B, S):
+            raise ValueError(f"key_mask must be [{B},{S}], got {tuple(m.shape)}")
+        return (m != 0).to(device=self.device, dtype=torch.int32).contiguous()
+
     def forward(self, ids, lengths=None, want_hidden=False, want_phoneme=True, want_token=False, packing=None,
                 token_type_ids=None, position_ids=None, inputs_embeds=None):
         """ids int64 [B,S]; lengths per-sample valid-token counts (None = no padding).
@@ -556,7 +565,7 @@ class HipEngine:
         return lo, (ha, aa)
 
     def forward_layers(self, ids, lengths=None, packing=None, hidden_states=True, attentions=False, want_hidden=False,
-                       out=None, token_type_ids=None, position_ids=None, inputs_embeds=None):
+                       out=None, token_type_ids=None, position_ids=None, inputs_embeds=None, key_mask=None):
         """The encoder's per-application outputs (plb_forward_layers): ``hidden_states`` / ``attentions`` = True (every
         slot), False, or a list of slots. Returns ``(hidden_states, attentions)``: lists of L + 1 fp32 [B,S,H] and of L
         fp32 [B,NH,S,S] tensors with None in the slots not asked for; ``hidden_states[0]`` is the output of
@@ -565,16 +574,26 @@ class HipEngine:
         ``hidden`` of ``forward`` itself. ``out`` = (hidden-state list, attention list): the caller's tensors (None = slot
         not wanted) instead of new ones. Works on inference-only engines, with a plan, and in fp8 mode.
         ``token_type_ids`` / ``position_ids`` / ``inputs_embeds`` (plb_forward_inputs, not in fp8 mode): the embedding
-        inputs of transformers' AlbertModel; ``ids`` is None with ``inputs_embeds`` [B,S,embedding_size]."""
+        inputs of transformers' AlbertModel; ``ids`` is None with ``inputs_embeds`` [B,S,embedding_size].
+        ``key_mask`` [B,S], nonzero = attend (plb_forward_masked, not in fp8 mode): a mask that need not be a prefix;
+        ``lengths`` is then each sample's extent, 1 + its last valid position. A masked position below the extent (a hole)
+        is removed as a key only: its column of every attention map is zeros, its own row and hidden state are computed."""
         self._ensure_synced()
         ids, B, S, ein, keep_in = self._embed_inputs(ids, token_type_ids, position_ids, inputs_embeds)
         lens = self._dev_i32(lengths)
+        km = self._key_mask(key_mask, B, S)
         with torch.cuda.device(self.device):
             hs, at = self._alloc_layer_outputs(B, S, hidden_states, attentions) if out is None else (list(out[0]), list(out[1]))
             hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device) if want_hidden else None
             lo, keep = self._layer_outputs(hs, at, B, S)
             pk = self._packing(packing, B, S)
-            if ein is None:
+            if km is not None:
+                _lib.check(self.L.plb_forward_masked(self.handle, None if ids is None else ids.data_ptr(),
+                                                     None if ein is None else C.byref(ein), km.data_ptr(),
+                                                     None if lens is None else lens.data_ptr(), B, S,
+                                                     None if pk is None else C.byref(pk), None if hid is None else hid.data_ptr(),
+                                                     None if lo is None else C.byref(lo), self._stream()), "plb_forward_masked")
+            elif ein is None:
                 _lib.check(self.L.plb_forward_layers(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
                                                      None if pk is None else C.byref(pk), None if hid is None else hid.data_ptr(),
                                                      None if lo is None else C.byref(lo), self._stream()), "plb_forward_layers")
@@ -587,7 +606,8 @@ class HipEngine:
         self._last_encoder_call = (int(B), int(S), lens, packing)
         return (hs, at, hid) if want_hidden else (hs, at)
 
-    def encode(self, ids, lengths=None, packing=None, layers=None, token_type_ids=None, position_ids=None, inputs_embeds=None):
+    def encode(self, ids, lengths=None, packing=None, layers=None, token_type_ids=None, position_ids=None, inputs_embeds=None,
+               key_mask=None):
         """Differentiable forward (include/plbert.h: plb_encode): ``.last_hidden_state`` fp32 [B,S,H] with every
         application's activations kept for ``encode_bwd``; ZEROS at pad positions. Training engines only, not in fp8
         mode. The ids, lengths and plan are remembered for the backward; any other computing call on this engine in
@@ -595,7 +615,8 @@ class HipEngine:
         ``layers`` = dict(hidden_states=True | False | slots, attentions=...) (plb_encode_layers): returns
         ``(hidden, hidden_states, attentions)`` as ``forward_layers`` does.
         ``token_type_ids`` / ``position_ids`` / ``inputs_embeds`` (plb_encode_inputs): the embedding inputs of
-        transformers' AlbertModel, remembered for the backward like the ids; ``ids`` is None with ``inputs_embeds``."""
+        transformers' AlbertModel, remembered for the backward like the ids; ``ids`` is None with ``inputs_embeds``.
+        ``key_mask`` [B,S] (plb_encode_masked): as in ``forward_layers``; remembered for the backward like the ids."""
         if not self.train_mode:
             raise RuntimeError("this HipEngine was built with train=False (inference / validation only): encode() keeps "
                                "the activations of every layer for a backward")
@@ -603,12 +624,23 @@ class HipEngine:
         self._ensure_synced()
         ids, B, S, ein, keep_in = self._embed_inputs(ids, token_type_ids, position_ids, inputs_embeds)
         lens = self._dev_i32(lengths)
+        km = self._key_mask(key_mask, B, S)
         self._live_encode = None
         with torch.cuda.device(self.device):
             hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device)
             pk = self._packing(packing, B, S)
             hs = at = None
-            if ein is not None:
+            if km is not None:
+                if layers is not None:
+                    hs, at = self._alloc_layer_outputs(B, S, layers.get("hidden_states", False), layers.get("attentions", False))
+                lo, keep = self._layer_outputs(hs, at, B, S)
+                _lib.check(self.L.plb_encode_masked(self.handle, None if ids is None else ids.data_ptr(),
+                                                    None if ein is None else C.byref(ein), km.data_ptr(),
+                                                    None if lens is None else lens.data_ptr(), B, S,
+                                                    None if pk is None else C.byref(pk), hid.data_ptr(),
+                                                    None if lo is None else C.byref(lo), self._stream()), "plb_encode_masked")
+                del keep
+            elif ein is not None:
                 if layers is not None:
                     hs, at = self._alloc_layer_outputs(B, S, layers.get("hidden_states", False), layers.get("attentions", False))
                 lo, keep = self._layer_outputs(hs, at, B, S)
@@ -628,7 +660,7 @@ class HipEngine:
                                                     None if lo is None else C.byref(lo), self._stream()), "plb_encode_layers")
                 del keep
         self._encode_serial = getattr(self, "_encode_serial", 0) + 1
-        self._live_encode = (ids, lens, packing, B, S, ein, keep_in)   # (holds the tensors the backward reads again)
+        self._live_encode = (ids, lens, packing, B, S, ein, keep_in, km)   # (holds the tensors the backward reads again)
         self._last_encoder_call = (int(B), int(S), lens, packing)
         return hid if layers is None else (hid, hs, at)
 
@@ -639,11 +671,12 @@ class HipEngine:
         ``d_below[l]`` = d(loss)/d(hidden_states[l]) fp32 [B,S,H] or None; ``d_hidden`` may then be None (a zero gradient
         at the last slot). ``want_d_inputs_embeds`` (plb_encode_bwd_inputs): returns fp32 [B,S,embedding_size], the gradient
         of the pre-LayerNorm embedding sum per token (zeros at pad positions) — the gradient of ``inputs_embeds``, or the
-        per-phoneme saliency of a call that took ids."""
+        per-phoneme saliency of a call that took ids. The key mask of an ``encode(key_mask=...)`` is taken from the live
+        record (plb_encode_bwd_masked)."""
         live = getattr(self, "_live_encode", None)
         if live is None:
             raise RuntimeError("encode_bwd: no live encode() on this engine (one backward per encode)")
-        ids, lens, packing, B, S, ein, keep_in = live
+        ids, lens, packing, B, S, ein, keep_in, km = live
         shape = (B, S, self.cfg.hidden_size)
 
         def dev(g, what):
@@ -665,6 +698,17 @@ class HipEngine:
             pk = self._packing(packing, B, S)
             args = (self.handle, None if ids is None else ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
                     None if pk is None else C.byref(pk), None if d is None else d.data_ptr())
+            if km is not None:
+                arr = None if below is None else self._ptr_array(below, self.cfg.num_hidden_layers, "d_below", shape)
+                die = (torch.empty((B, S, self.cfg.embedding_size), dtype=torch.float32, device=self.device)
+                       if want_d_inputs_embeds else None)
+                _lib.check(self.L.plb_encode_bwd_masked(self.handle, None if ids is None else ids.data_ptr(),
+                                                        None if ein is None else C.byref(ein), km.data_ptr(), *args[2:],
+                                                        None if arr is None else C.addressof(arr),
+                                                        None if die is None else die.data_ptr(), self._stream()),
+                           "plb_encode_bwd_masked")
+                del keep_in
+                return die
             if ein is not None or want_d_inputs_embeds:
                 arr = None if below is None else self._ptr_array(below, self.cfg.num_hidden_layers, "d_below", shape)
                 die = (torch.empty((B, S, self.cfg.embedding_size), dtype=torch.float32, device=self.device)

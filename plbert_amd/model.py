@@ -24,6 +24,13 @@ enabled; ``backward()`` runs plb_encode_bwd and hands every encoder Parameter it
 engine's gradient buffer.  ``pooler_output`` is returned DETACHED (the pooler gets no gradient), and
 ``last_hidden_state`` is zero at pad positions.
 
+``attention_mask`` of ``AlbertModel.forward`` follows transformers' 2-D rule and need not be a prefix (left padding, keys
+knocked out, a sub-span of a buffer): key j of a sample takes part in the softmax of all its queries iff its entry is nonzero.
+A prefix mask runs the lengths-only kernels as before; any other mask goes through plb_forward_masked / plb_encode_masked /
+plb_encode_bwd_masked with the sample's EXTENT (1 + its last valid position) as its length. Positions at or past the extent
+are pad positions (zeros); a masked position below it is a hole, removed as a key only — it has a hidden state and carries
+gradient, as in transformers. The head wrappers, ``fill_mask``, ``predict_tokens`` and the trainer take prefix masks only.
+
 ``output_hidden_states=True`` / ``output_attentions=True`` (transformers' arguments of ``AlbertModel.forward``) add
 ``.hidden_states`` (the model after every application of the shared layer) and ``.attentions``; on the differentiable
 path every hidden state joins the graph (plb_encode_layers / plb_encode_bwd_layers), elsewhere plb_forward_layers runs.
@@ -96,6 +103,30 @@ def _lengths_from_mask(attention_mask, strict=True):
         if bool((lengths < 1).any()):
             raise ValueError("attention_mask has a row with no valid token")
     return lengths
+
+
+def _extent_from_mask(attention_mask):
+    """int [B,S], nonzero = attend -> (extent int32 [B] = 1 + the last valid position of each row, whether every row is a
+    prefix 1...1 0...0). torch ops on the mask's device, one read-back for the two flags. A row without a valid token
+    raises ValueError."""
+    am = attention_mask != 0
+    if am.dim() != 2:
+        raise ValueError(f"attention_mask must be [B,S], got {tuple(am.shape)}")
+    S = am.shape[1]
+    extent = (am * torch.arange(1, S + 1, device=am.device)[None, :]).amax(dim=1).to(torch.int32)
+    empty, prefix = torch.stack([(extent < 1).any(), (am.sum(dim=1) == extent).all()]).tolist()
+    if empty:
+        raise ValueError("attention_mask has a row with no valid token")
+    return extent, bool(prefix)
+
+
+def _lengths_and_key_mask(attention_mask):
+    """AlbertModel.forward's reading of its mask: (lengths | None, key mask | None). A prefix mask gives the lengths alone
+    (the path without a key mask); any other mask gives its extents and itself."""
+    if attention_mask is None:
+        return None, None
+    extent, prefix = _extent_from_mask(attention_mask)
+    return extent, (None if prefix else attention_mask)
 
 
 def _encode_backward(ctx, d_hidden, d_below, want_d_inputs_embeds=None, without=()):
@@ -174,13 +205,15 @@ class _EncodeInputs(torch.autograd.Function):
     """_EncodeLayers with the embedding inputs of transformers' AlbertModel (plb_encode_inputs / plb_encode_bwd_inputs).
     ``inputs_embeds`` (or None) is an input of the node: when it requires grad it receives the gradient of the pre-LayerNorm
     embedding sum, and the word table — which took no part — receives None, as in torch. The token-type and position tables
-    receive their views of the gradient buffer like every other encoder Parameter."""
+    receive their views of the gradient buffer like every other encoder Parameter. ``key_mask`` (or None): a mask that is
+    no prefix (plb_encode_masked / plb_encode_bwd_masked; the engine's live record hands it to the backward)."""
 
     @staticmethod
     def forward(ctx, engine, names, ids, lengths, packing, want_hs, want_at, token_type_ids, position_ids, inputs_embeds,
-                *params):
+                key_mask, *params):
         hid, hs, at = engine.encode(ids, lengths, packing, layers=dict(hidden_states=want_hs, attentions=want_at),
-                                    token_type_ids=token_type_ids, position_ids=position_ids, inputs_embeds=inputs_embeds)
+                                    token_type_ids=token_type_ids, position_ids=position_ids, inputs_embeds=inputs_embeds,
+                                    key_mask=key_mask)
         ctx.engine, ctx.names, ctx.serial, ctx.want_hs = engine, names, engine._encode_serial, want_hs
         ctx.embeds = inputs_embeds is not None
         ctx.set_materialize_grads(False)
@@ -196,7 +229,7 @@ class _EncodeInputs(torch.autograd.Function):
         die, pg = _encode_backward(ctx, g[-1], g[:-1] if ctx.want_hs else None,
                                    want_d_inputs_embeds=ctx.embeds and ctx.needs_input_grad[9],
                                    without=("encoder.embeddings.word_embeddings.weight",) if ctx.embeds else ())
-        return (None,) * 9 + (die,) + pg
+        return (None,) * 9 + (die, None) + pg
 
 
 class AlbertModel(nn.Module):
@@ -275,14 +308,19 @@ class AlbertModel(nn.Module):
         path every hidden state carries gradient; the attention maps never do.
         ``token_type_ids`` [B,S], ``position_ids`` [B,S] or [1,S], ``inputs_embeds`` [B,S,embedding_size] instead of
         ``input_ids`` (transformers' arguments and rules; AlbertEmbeddings.forward with dropout 0): on the differentiable
-        path an ``inputs_embeds`` that requires grad receives its gradient, and the word table's ``.grad`` stays None."""
+        path an ``inputs_embeds`` that requires grad receives its gradient, and the word table's ``.grad`` stays None.
+        ``attention_mask`` [B,S], nonzero = attend (transformers' 2-D key-padding rule): a prefix mask runs as it always
+        did; any other mask — left padding, holes — runs the masked attention kernels (module docstring). Positions at or
+        past a row's last valid token are pad positions (zeros); a hole below it keeps its hidden state and its gradient and
+        has an all-zero column in every attention map. A row without a valid token raises ValueError."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
-        lengths = _lengths_from_mask(attention_mask)
+        lengths, key_mask = _lengths_and_key_mask(attention_mask)
         want_hs, want_at = bool(output_hidden_states), bool(output_attentions)
         nl = self.config.num_hidden_layers
-        if token_type_ids is not None or position_ids is not None or inputs_embeds is not None:
-            return self._forward_inputs(input_ids, lengths, token_type_ids, position_ids, inputs_embeds, want_hs, want_at)
+        if token_type_ids is not None or position_ids is not None or inputs_embeds is not None or key_mask is not None:
+            return self._forward_inputs(input_ids, lengths, token_type_ids, position_ids, inputs_embeds, want_hs, want_at,
+                                        key_mask)
         if getattr(self, "differentiable", False) and self.training and torch.is_grad_enabled():
             # fine-tuning: the forward joins the autograd graph (_Encode); pad positions of last_hidden_state are zeros and
             # pooler_output is DETACHED (the pooler receives no gradient, as in every other call of this library)
@@ -313,9 +351,10 @@ class AlbertModel(nn.Module):
         # pooler (modeling_albert.py:403): computed for API completeness (plb_pooler), never used by the loss
         return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid))
 
-    def _forward_inputs(self, input_ids, lengths, token_type_ids, position_ids, inputs_embeds, want_hs, want_at):
-        """AlbertModel.forward with any of the embedding inputs: HipEngine.forward_layers / encode with them (the engine checks
-        shapes and index ranges), outputs as in the plain call."""
+    def _forward_inputs(self, input_ids, lengths, token_type_ids, position_ids, inputs_embeds, want_hs, want_at, key_mask=None):
+        """AlbertModel.forward with any of the embedding inputs or a mask that is no prefix (``key_mask``; ``lengths`` = its
+        extents): HipEngine.forward_layers / encode with them (the engine checks shapes and index ranges), outputs as in the
+        plain call. ``pooler_output`` is the pooler of position 0, hole or not, as in transformers."""
         nl = self.config.num_hidden_layers
         shaped = input_ids if input_ids is not None else inputs_embeds
         packing = _packing_from_lengths(self, lengths, shaped)
@@ -325,14 +364,14 @@ class AlbertModel(nn.Module):
                 names.append("encoder." + n)
                 params.append(p)
             outs = _EncodeInputs.apply(self._engine, names, input_ids, lengths, packing, want_hs, want_at, token_type_ids,
-                                       position_ids, inputs_embeds, *params)
+                                       position_ids, inputs_embeds, key_mask, *params)
             hs = tuple(outs[:nl + 1]) if want_hs else None
             hid = hs[-1] if want_hs else outs[0]
             return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid.detach()),
                                               hidden_states=hs, attentions=tuple(outs[-nl:]) if want_at else None)
         hs, at, hid = self._engine.forward_layers(input_ids, lengths, packing, hidden_states=want_hs, attentions=want_at,
                                                   want_hidden=True, token_type_ids=token_type_ids, position_ids=position_ids,
-                                                  inputs_embeds=inputs_embeds)
+                                                  inputs_embeds=inputs_embeds, key_mask=key_mask)
         if want_hs:
             hid = hs[-1]
         return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid),
