@@ -1,7 +1,10 @@
 // Call-level stages of the engine: row selection of a padded or token-packed call, the heads, the stages of a loss call and
 // the two-stream tail of its backward, and the entry points plb_forward*, plb_loss_*, plb_encode, plb_encode_bwd and their
-// *_layers forms (per-application outputs; a gradient at every application boundary) and *_inputs forms (token_type_ids /
-// position_ids / inputs_embeds: one EmbedCall from the entry point to run_encoder and the backward tail). Only
+// *_layers forms (per-application outputs; a gradient at every application boundary), *_inputs forms (token_type_ids /
+// position_ids / inputs_embeds) and *_masked forms (key masks). Every entry point is one statement that names itself and fills
+// the arguments of its family's implementation (EncArgs; loss_impl's in place); the implementation builds ONE Call
+// (engine_internal.h) behind its refusals, and every stage below — run_encoder, token_head, encoder_bwd, the backward tail —
+// takes that and nothing else about the call. Only
 // writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
 // last_exec_rows, tok_grads_live and head_grads_live (which a LAST add of engine_optim.cpp replaces by its window's union),
 // and of what plb_masked_report reads (rep_*: engine_eval.cpp; plb_bind clears rep_valid) and of the record of the final
@@ -18,9 +21,9 @@ void drop_stash(PlbEngine* e, const char* by) {
 void drop_final(PlbEngine* e, const char* by) {
   if (e) { e->fin_live = false; e->fin_dead_by = by; }
 }
-static void note_final(PlbEngine* e, const bf16_t* x, int B, int S, const Rows& rw) {
-  e->fin_live = true; e->fin_x = x; e->fin_B = B; e->fin_S = S;
-  e->fin_rows = rw.Tp; e->fin_used = rw.T; e->fin_row_start = rw.row_start;
+static void note_final(PlbEngine* e, const bf16_t* x, const Call& c) {
+  e->fin_live = true; e->fin_x = x; e->fin_B = c.B; e->fin_S = c.S;
+  e->fin_rows = c.rw.Tp; e->fin_used = c.rw.T; e->fin_row_start = c.rw.row_start;
 }
 
 static int check_shape(const PlbEngine* e, int B, int S, const char* who) {
@@ -75,59 +78,60 @@ static int key_mask_check(const PlbEngine* e, const int32_t* key_mask, int S, co
   return 0;
 }
 // ... and packed into the words the attention launches of the call read (key_mask.hip), first launch of the call
-static int key_mask_words(PlbEngine* e, const int32_t* key_mask, const int32_t* lengths, int B, int S, Rows* rw, hipStream_t s) {
+static int key_mask_words(PlbEngine* e, const int32_t* key_mask, Call* c) {
   if (!key_mask) return 0;
   uint32_t* const words = e->at<uint32_t>(e->o_keywords);
-  const int ldkw = 2 * ((S + 63) / 64);
-  HB_W(s, words, (int64_t)B * ldkw * 4, "key-mask words of the call");
-  TRY(plb_launch_key_mask_words(key_mask, lengths, B, S, words, ldkw, s));
-  rw->key_words = words; rw->ldkw = ldkw;
+  const int ldkw = 2 * ((c->S + 63) / 64);
+  HB_W(c->s, words, (int64_t)c->B * ldkw * 4, "key-mask words of the call");
+  TRY(plb_launch_key_mask_words(key_mask, c->lengths, c->B, c->S, words, ldkw, c->s));
+  c->rw.key_words = words; c->rw.ldkw = ldkw;
   return 0;
 }
 
-// layers (or null): the per-application outputs of plb_forward_layers, written by run_encoder as the call goes
-// inputs (or null): the embedding inputs of plb_forward_inputs; key_mask (or null): the key mask of plb_forward_masked
-static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
-                        const PlbPacking* pk, float* hidden, float* phoneme_logits, float* token_logits,
-                        const PlbLayerOutputs* layers, const char* who, void* stream, const PlbEmbedInputs* inputs = nullptr,
-                        const int32_t* key_mask = nullptr) {
-  if (check_shape(e, B, S, who)) return 1;
+// What a plb_forward* / plb_encode* / plb_encode_bwd* entry point was given beside its outputs (null: not given, or a rung
+// below the one that takes it). inputs: the embedding inputs of plb_*_inputs; key_mask: the key mask of plb_*_masked; layers:
+// the per-application outputs of plb_*_layers, written by run_encoder as the call goes.
+struct EncArgs {
+  const int64_t* ids; const PlbEmbedInputs* inputs; const int32_t* key_mask; const int32_t* lengths;
+  int32_t B, S;
+  const PlbPacking* packing; const PlbLayerOutputs* layers; void* stream;
+};
+
+static int forward_impl(PlbEngine* e, const char* who, const EncArgs& a, float* hidden, float* phoneme_logits,
+                        float* token_logits) {
+  if (check_shape(e, a.B, a.S, who)) return 1;
   drop_stash(e, "plb_forward rewrote the workspace since");
   drop_final(e, "the last call that ran the encoder (plb_forward) failed");
   EmbedCall ec;
-  if (embed_call(e, ids, inputs, nullptr, who, &ec)) return 1;
-  if (key_mask_check(e, key_mask, S, who)) return 1;
+  if (embed_call(e, a.ids, a.inputs, nullptr, who, &ec)) return 1;
+  if (key_mask_check(e, a.key_mask, a.S, who)) return 1;
   if (token_logits && !e->NT) return fail("%s: token_logits requested but num_tokens = 0", who);
-  hipStream_t s = (hipStream_t)stream;
   const int H = e->H;
   Rows rw;
   // (token logits: a full [B,S,NT] fp32 output is a debugging output and runs padded, whatever plb_set_packed_dual says.
   // Phoneme logits of a packed call pass, as [Tp][NP] fp32, through a slot
   // of the forward-only call that is free once the encoder is done: QKV (6H bytes per row) or the FFN's u (2I))
   const int64_t lg_off = 4 * e->NP <= 6 * H ? e->o_qkv : 4 * e->NP <= 2 * e->I ? e->o_u : -1;
-  if (pick_rows(e, pk, lengths, token_logits != nullptr || lg_off < 0, B, S, who, &rw)) return 1;
+  if (pick_rows(e, a.packing, a.lengths, token_logits != nullptr || lg_off < 0, a.B, a.S, who, &rw)) return 1;
+  Call c = {who, a.ids, a.lengths, a.B, a.S, rw, ec, a.layers, (hipStream_t)a.stream};
+  hipStream_t s = c.s;
   const int T = rw.T;
   const int64_t Tp = rw.Tp;
   bf16_t* x = nullptr;
-  if (key_mask_words(e, key_mask, lengths, B, S, &rw, s)) return 1;
-  if (run_encoder(e, ids, lengths, B, S, rw, false, &x, s, nullptr, layers, &ec)) return 1;
-  if (rw.row_start) {
-    // back to the caller's [B,S,*] layout, zeros at the pad positions
-    if (hidden) TRY(plb_launch_unpack_rows(x, 1, H, rw.row_start, lengths, B, S, H, hidden, s));
-    if (phoneme_logits) {
-      float* lg = e->at<float>(lg_off);
-      PlbGemmNT g = nt_desc(x, e->wbf(PLB_HEAD_W), Tp, e->NP, H);
-      g.Mstore = T; g.bias = e->par(PLB_HEAD_B); g.Cf = lg; g.ldcf = e->NP;
-      TRY(plb_launch_gemm_nt(&g, 0, 1, s));
-      TRY(plb_launch_unpack_rows(lg, 0, e->NP, rw.row_start, lengths, B, S, e->NP, phoneme_logits, s));
-    }
-  } else {
-  if (hidden) TRY(plb_launch_bf16_to_f32(x, H, hidden, H, T, H, s));
-  if (phoneme_logits) {
-    PlbGemmNT g = nt_desc(x, e->wbf(PLB_HEAD_W), Tp, e->NP, H);
-    g.Mstore = T; g.bias = e->par(PLB_HEAD_B); g.Cf = phoneme_logits; g.ldcf = e->NP;
-    TRY(plb_launch_gemm_nt(&g, 0, 1, s));
+  if (key_mask_words(e, a.key_mask, &c)) return 1;
+  if (run_encoder(e, c, false, &x, nullptr)) return 1;
+  // packed: back to the caller's [B,S,*] layout, zeros at the pad positions (by row_start, not by lengths: a padded call
+  // leaves values at the pad positions of hidden)
+  if (hidden) {
+    if (rw.row_start) TRY(plb_launch_unpack_rows(x, 1, H, rw.row_start, a.lengths, a.B, a.S, H, hidden, s));
+    else TRY(plb_launch_bf16_to_f32(x, H, hidden, H, T, H, s));
   }
+  if (phoneme_logits) {
+    float* const lg = rw.row_start ? e->at<float>(lg_off) : phoneme_logits;
+    PlbGemmNT g = nt_desc(x, e->wbf(PLB_HEAD_W), Tp, e->NP, H);
+    g.Mstore = T; g.bias = e->par(PLB_HEAD_B); g.Cf = lg; g.ldcf = e->NP;
+    TRY(plb_launch_gemm_nt(&g, 0, 1, s));
+    if (rw.row_start) TRY(plb_launch_unpack_rows(lg, 0, e->NP, rw.row_start, a.lengths, a.B, a.S, e->NP, phoneme_logits, s));
   }
   if (token_logits) {
     PlbGemmNT g = nt_desc(x, e->wbf(PLB_TOK_W), Tp, e->NT, H);
@@ -139,34 +143,38 @@ static int forward_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths
     e->fp8_ready = true;
   }
   TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), nullptr, e->host_err_dev, nullptr, s));
-  note_final(e, x, B, S, rw);
+  note_final(e, x, c);
   return 0;
 }
 extern "C" int plb_forward(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, float* hidden,
                            float* phoneme_logits, float* token_logits, void* stream) {
-  return forward_impl(e, ids, lengths, B, S, nullptr, hidden, phoneme_logits, token_logits, nullptr, "plb_forward", stream);
+  return forward_impl(e, "plb_forward", {ids, nullptr, nullptr, lengths, B, S, nullptr, nullptr, stream}, hidden, phoneme_logits,
+                      token_logits);
 }
 extern "C" int plb_forward_packed(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                                   const PlbPacking* packing, float* hidden, float* phoneme_logits, float* token_logits,
                                   void* stream) {
-  return forward_impl(e, ids, lengths, B, S, packing, hidden, phoneme_logits, token_logits, nullptr, "plb_forward", stream);
+  return forward_impl(e, "plb_forward", {ids, nullptr, nullptr, lengths, B, S, packing, nullptr, stream}, hidden, phoneme_logits,
+                      token_logits);
 }
 // plb_forward_packed(hidden, no logits) plus the per-application outputs (include/plbert.h: PlbLayerOutputs)
 extern "C" int plb_forward_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                                   const PlbPacking* packing, float* hidden, const PlbLayerOutputs* layers, void* stream) {
-  return forward_impl(e, ids, lengths, B, S, packing, hidden, nullptr, nullptr, layers, "plb_forward_layers", stream);
+  return forward_impl(e, "plb_forward_layers", {ids, nullptr, nullptr, lengths, B, S, packing, layers, stream}, hidden, nullptr,
+                      nullptr);
 }
 // plb_forward_layers with the embedding inputs (include/plbert.h: PlbEmbedInputs); none given: that call
 extern "C" int plb_forward_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths, int32_t B,
                                   int32_t S, const PlbPacking* packing, float* hidden, const PlbLayerOutputs* layers, void* stream) {
-  return forward_impl(e, ids, lengths, B, S, packing, hidden, nullptr, nullptr, layers, "plb_forward_inputs", stream, inputs);
+  return forward_impl(e, "plb_forward_inputs", {ids, inputs, nullptr, lengths, B, S, packing, layers, stream}, hidden, nullptr,
+                      nullptr);
 }
 // plb_forward_inputs with a key mask (include/plbert.h); key_mask == NULL: that call
 extern "C" int plb_forward_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
                                   const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing, float* hidden,
                                   const PlbLayerOutputs* layers, void* stream) {
-  return forward_impl(e, ids, lengths, B, S, packing, hidden, nullptr, nullptr, layers,
-                      key_mask ? "plb_forward_masked" : "plb_forward_inputs", stream, inputs, key_mask);
+  return forward_impl(e, key_mask ? "plb_forward_masked" : "plb_forward_inputs",
+                      {ids, inputs, key_mask, lengths, B, S, packing, layers, stream}, hidden, nullptr, nullptr);
 }
 
 // ---- stages of a loss call ----------------------------------------------------------------------------------------------
@@ -271,23 +279,25 @@ static int phoneme_head(PlbEngine* e, bool backward, bool prune, const bf16_t* x
 // log-sum-exp, weight and loss; pass 2 recomputes the logits and writes the gradient (softmax - onehot) * w in
 // bf16 [Tp][NTp] (2.1 GB at 16384 x 64000), the operand of dWt = dlogits^T · H and dH = dlogits · Wt, and the
 // column-sum partials that give the bias gradient.
-// Token-packed call (rw.row_start): the row axis is the plan's — Tp = rw.Tp rows, the targets and the row weights placed by
+// Token-packed call (c.rw.row_start): the row axis is the plan's — Tp = rw.Tp rows, the targets and the row weights placed by
 // the plan, zeros on the rows that hold no token: pass 2 selects an exact 0 for a row of weight 0, so those rows add nothing
 // to the head's gradients or to dH.
-static int token_head(PlbEngine* e, bool backward, const bf16_t* xL, const int64_t* token_targets, const int32_t* lengths,
-                      int B, int S, const Rows& rw, bf16_t* dy, float* loss, float* loss_parts, hipStream_t s) {
-  const int H = e->H, NT = e->NT, NTp = e->NTp, T = B * S;
+static int token_head(PlbEngine* e, const Call& c, bool backward, const bf16_t* xL, const int64_t* token_targets, bf16_t* dy,
+                      float* loss, float* loss_parts) {
+  const int H = e->H, NT = e->NT, NTp = e->NTp, B = c.B, S = c.S, T = B * S;
+  const Rows& rw = c.rw;
   const int64_t Tp = rw.Tp;
+  hipStream_t s = c.s;
   const int tile = (Tp % 256 == 0) ? 256 : 1256;          // 256x256 or 128x256: both 256 columns wide
   const int ntile = NTp / 256, cprows = tile == 256 ? 2 * (int)(Tp / 256) : 2 * (int)(Tp / 128);
   float* tlrows = e->at<float>(e->o_tlrows);
   float* tloss = e->at<float>(e->o_tloss);
   int64_t* ttgt = e->at<int64_t>(e->o_ttgt);
   if (rw.row_start) {
-    TRY(plb_launch_pack_token_targets(token_targets, lengths, rw.row_start, B, S, (int)Tp, ttgt, s));
+    TRY(plb_launch_pack_token_targets(token_targets, c.lengths, rw.row_start, B, S, (int)Tp, ttgt, s));
   } else {
-  HIPTRY(hipMemcpyAsync(ttgt, token_targets, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
-  if (Tp > T) HIPTRY(hipMemsetAsync(ttgt + T, 0, (size_t)(Tp - T) * 8, s));
+    HIPTRY(hipMemcpyAsync(ttgt, token_targets, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
+    if (Tp > T) HIPTRY(hipMemsetAsync(ttgt + T, 0, (size_t)(Tp - T) * 8, s));
   }
   PlbGemmNT g = nt_desc(xL, e->wbf(PLB_TOK_W), Tp, NTp, H);
   g.bias = e->at<float>(e->o_bt);
@@ -298,13 +308,13 @@ static int token_head(PlbEngine* e, bool backward, const bf16_t* xL, const int64
   TRY(plb_launch_gemm_nt_big(&g, tile, 3, 0, s));
   plb_prof_end(tok, s);
   if (rw.row_start) {
-    TRY(plb_launch_token_ce_combine_packed(g.ce_pmax, g.ce_psum, ntile, g.ce_tlogit, lengths, rw.row_start, B, S, (int)Tp,
+    TRY(plb_launch_token_ce_combine_packed(g.ce_pmax, g.ce_psum, ntile, g.ce_tlogit, c.lengths, rw.row_start, B, S, (int)Tp,
                                            e->at<float>(e->o_tlse), e->at<float>(e->o_tw), tlrows, s));
     TRY(plb_launch_sum_rows(tlrows, (int)Tp, tloss, s));
   } else {
-  TRY(plb_launch_token_ce_combine(g.ce_pmax, g.ce_psum, ntile, g.ce_tlogit, lengths, B, S, (int)Tp,
-                                  e->at<float>(e->o_tlse), e->at<float>(e->o_tw), tlrows, s));
-  TRY(plb_launch_sum_rows(tlrows, T, tloss, s));
+    TRY(plb_launch_token_ce_combine(g.ce_pmax, g.ce_psum, ntile, g.ce_tlogit, c.lengths, B, S, (int)Tp,
+                                    e->at<float>(e->o_tlse), e->at<float>(e->o_tw), tlrows, s));
+    TRY(plb_launch_sum_rows(tlrows, T, tloss, s));
   }
   TRY(plb_launch_add_scalar(loss, loss, tloss, s));
   if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts + 1, tloss, sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -337,11 +347,10 @@ static int token_head(PlbEngine* e, bool backward, const bf16_t* xL, const int64
 //  side: everything else that only needs finished gradients — embedding chain, bias and LayerNorm-affine column sums
 //        (HBM-bound) — with its own slab / scratch so nothing is shared; joined before the first piece that holds
 //        any of its outputs.
-static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const int32_t* lengths, bf16_t* dy, int B, int S,
-                                 const Rows& rw, int du_rows, hipStream_t s, hipStream_t s2, float* scratch2, const EmbedCall* ec) {
-  const int E = e->E, H = e->H, I = e->I, L = e->L;
-  const int T = rw.T;
-  const int64_t Tp = rw.Tp;
+static int backward_tail_streams(PlbEngine* e, const Call& c, bf16_t* dy, int du_rows, hipStream_t s2, float* scratch2) {
+  const int E = e->E, H = e->H, I = e->I, L = e->L, B = c.B, S = c.S;
+  const int64_t Tp = c.rw.Tp;
+  hipStream_t s = c.s;
   const int64_t Mtot = (int64_t)L * Tp;
   // stacked rows of the operands whose last application ran on its masked rows only (ffn.weight, ffn_output.weight,
   // dense.weight: their slots of application L-1 hold Mc compact rows); the Q/K/V weights' operands are always full
@@ -365,30 +374,21 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const 
   HB_W(s2, scratch2, 512 * (3 * H > I ? 3 * H : I) * 4, "column-sum scratch of the side stream");
   HB_W(s2, e->grd(PLB_MAP_B), H * 4, "map-in bias gradient");
   TRY(plb_launch_colsum(dy, 1, (size_t)Tp, H, H, e->grd(PLB_MAP_B), H, 0, scratch2, 128, s2));
-  const bool sources = ec && ec->any();   // per-token embedding sources / d_inputs_embeds: the launches of embed_inputs.hip
+  const bool sources = c.ec.any();   // per-token embedding sources / d_inputs_embeds: the launches of embed_inputs.hip
   HB_W(s2, e->grd(PLB_TYPE_EMB), e->psize[PLB_TYPE_EMB] * 4, "token-type embedding gradient");
   if (!sources) HIPTRY(hipMemsetAsync(e->grd(PLB_TYPE_EMB), 0, (size_t)e->psize[PLB_TYPE_EMB] * 4, s2));
-  PlbEmbed em;
-  memset(&em, 0, sizeof(em));
-  em.ids = masked_ids; em.T = T; em.S = S; em.E = E; em.V = e->V;
-  em.word = e->par(PLB_WORD_EMB); em.pos = e->par(PLB_POS_EMB); em.type0 = e->par(PLB_TYPE_EMB);
-  em.gamma = e->par(PLB_EMB_LN_W); em.beta = e->par(PLB_EMB_LN_B); em.eps = e->c.layer_norm_eps;
+  PlbEmbed em = embed_desc(e, c);
   em.dout = de; em.lddo = E; em.dword = e->grd(PLB_WORD_EMB); em.dpos = e->grd(PLB_POS_EMB);
   em.dx = e->at<float>(e->o_dxe);
   em.partials = e->at<float>(e->o_parte); em.nblocks = e->emb_blocks;
-  if (rw.row_start) { em.row_start = rw.row_start; em.lengths = lengths; em.B = B; }
   HB_W(s2, em.dx, Tp * E * 4, "embedding LayerNorm backward rows"); HB_W(s2, em.partials, (int64_t)e->emb_blocks * 2 * E * 4, "embedding LayerNorm partials");
   HB_W(s2, e->grd(PLB_WORD_EMB), (e->poff[PLB_MAP_W] - e->poff[PLB_WORD_EMB]) * 4, "embedding tables' and embedding LayerNorm's gradients");
   if (sources) {
     // every row of the three tables is written by the scatter: word rows as below (zeros with inputs_embeds), position and
     // token-type rows from the chunk partial rows where position_ids / token_type_ids key them
-    PlbEmbedIn xi;
-    memset(&xi, 0, sizeof(xi));
-    em.lengths = lengths; em.B = B;   // (padded call too: d_inputs_embeds gets its zeros at the pad positions)
-    xi.base = &em;
-    xi.token_type_ids = ec->in.token_type_ids; xi.position_ids = ec->in.position_ids; xi.inputs_embeds = ec->in.inputs_embeds;
-    xi.NTY = e->c.type_vocab_size; xi.P = e->P;
-    xi.dtype_rows = e->grd(PLB_TYPE_EMB); xi.d_inputs_embeds = ec->d_inputs_embeds;
+    em.lengths = c.lengths; em.B = B;   // (padded call too: d_inputs_embeds gets its zeros at the pad positions)
+    PlbEmbedIn xi = embed_in_desc(e, c.ec, &em);
+    xi.dtype_rows = e->grd(PLB_TYPE_EMB); xi.d_inputs_embeds = c.ec.d_inputs_embeds;
     xi.chunk_part = e->at<float>(e->o_embpart);
     if (xi.d_inputs_embeds) HB_W(s2, xi.d_inputs_embeds, (int64_t)B * S * E * 4, "d_inputs_embeds (the caller's buffer)");
     HB_W(s2, xi.chunk_part, (int64_t)plb_embed_inputs_part_floats(B * S, e->P, xi.NTY, E) * 4, "chunk partial rows of the keyed table sums");
@@ -396,11 +396,11 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const 
     TRY(plb_launch_embed_inputs_scatter(&xi, s2));
     TRY(plb_launch_colsum(em.partials, 0, (size_t)e->emb_blocks, 2 * E, 2 * E, e->grd(PLB_EMB_LN_W), 2 * E, 0, scratch2, 1, s2));
   } else {
-  TRY(plb_launch_embed_bwd(&em, s2));
-  TRY(plb_launch_embed_scatter(&em, e->P, s2));
-  TRY(plb_launch_colsum(em.partials, 0, (size_t)e->emb_blocks, 2 * E, 2 * E, e->grd(PLB_EMB_LN_W), 2 * E, 0, scratch2, 1, s2));
-  // token_type row 0 receives every token's gradient = the column sums of dpos
-  TRY(plb_launch_colsum(e->grd(PLB_POS_EMB), 0, (size_t)e->P, E, E, e->grd(PLB_TYPE_EMB), E, 0, scratch2, 1, s2));
+    TRY(plb_launch_embed_bwd(&em, s2));
+    TRY(plb_launch_embed_scatter(&em, e->P, s2));
+    TRY(plb_launch_colsum(em.partials, 0, (size_t)e->emb_blocks, 2 * E, 2 * E, e->grd(PLB_EMB_LN_W), 2 * E, 0, scratch2, 1, s2));
+    // token_type row 0 receives every token's gradient = the column sums of dpos
+    TRY(plb_launch_colsum(e->grd(PLB_POS_EMB), 0, (size_t)e->P, E, E, e->grd(PLB_TYPE_EMB), E, 0, scratch2, 1, s2));
   }
   // Q/K/V biases: the attention-backward kernels left the column sums of every 32-row patch they stored, per application
   // ([L][B*QT*4][3H])
@@ -466,9 +466,8 @@ static int backward_tail_streams(PlbEngine* e, const int64_t* masked_ids, const 
   return 0;
 }
 
-static int backward_tail(PlbEngine* e, const int64_t* masked_ids, const int32_t* lengths, bf16_t* dy, int B, int S,
-                         const Rows& rw, int du_rows, hipStream_t s, const EmbedCall* ec = nullptr) {
-  hipStream_t s2 = s;
+static int backward_tail(PlbEngine* e, const Call& c, bf16_t* dy, int du_rows) {
+  hipStream_t s = c.s, s2 = s;
   float* scratch2 = e->at<float>(e->o_scratch);
   // the layer loop (all of it on the caller's stream) has written the stash, the partial-row tables, dX: one entry
   HB_W(s, e->ws, e->ws_bytes, "layer loop (whole workspace)");
@@ -479,7 +478,7 @@ static int backward_tail(PlbEngine* e, const int64_t* masked_ids, const int32_t*
     HIPTRY(ev_record(e, e->ev_fork, s));
     HIPTRY(ev_wait(e, s2, e->ev_fork));
   }
-  const int rc = backward_tail_streams(e, masked_ids, lengths, dy, B, S, rw, du_rows, s, s2, scratch2, ec);
+  const int rc = backward_tail_streams(e, c, dy, du_rows, s2, scratch2);
   // Whatever happened above, the caller's stream must not run ahead of the side stream's work (also on an error
   // path: the side stream may hold launches that read buffers the caller is about to reuse).
   if (s2 != s) {
@@ -520,6 +519,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   // from here on the call launches: what plb_masked_report reads is this call's, once it has gone through
   e->rep_valid = false;
   e->rep_n = n_masked; e->rep_B = B; e->rep_dual = token_targets != nullptr; e->rep_tok_rows = token_targets ? Tp : 0;
+  const Call c = {who, masked_ids, lengths, B, S, rw, {}, nullptr, s};
   if (backward && begin_training_call(e, token_targets != nullptr, s)) return 1;
   if (n_masked == 0 && !token_targets) {
     drop_final(e, "the last loss call had no masked position and no token targets: it did not run the encoder");
@@ -544,11 +544,11 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   if (backward) e->pruned_rows = prune ? NM : 0;
   e->last_app_rows[0] = prune ? NM : Tp; e->last_app_rows[1] = Tp;
   bf16_t* xL = nullptr;
-  if (run_encoder(e, masked_ids, lengths, B, S, rw, backward, &xL, s, prune ? &pr : nullptr)) return 1;
+  if (run_encoder(e, c, backward, &xL, prune ? &pr : nullptr)) return 1;
   bf16_t* dy = backward ? e->at<bf16_t>(e->o_dy0) : nullptr;
   if (phoneme_head(e, backward, prune, xL, n_masked, Tp, dy, loss, s)) return 1;
   if (loss_parts) HIPTRY(hipMemcpyAsync(loss_parts, loss, sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (token_targets && token_head(e, backward, xL, token_targets, lengths, B, S, rw, dy, loss, loss_parts, s)) return 1;
+  if (token_targets && token_head(e, c, backward, xL, token_targets, dy, loss, loss_parts)) return 1;
   if (!backward) {
     if (e->fp8_on) {  // forward-only call in fp8 mode: activation sites only (gradient sites saw nothing and keep theirs)
       TRY(fp8_update_scales(e, s));
@@ -559,15 +559,15 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
     e->last_loss = loss;
     TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), loss, e->host_err_dev, nullptr, s));
     e->rep_valid = true;
-    if (prune) drop_final(e, kPrunedText); else note_final(e, xL, B, S, rw);
+    if (prune) drop_final(e, kPrunedText); else note_final(e, xL, c);
     return 0;
   }
 
   int du_rows = 0;
-  if (encoder_bwd(e, prune ? &pr : nullptr, lengths, B, S, rw, &dy, &du_rows, s)) return 1;
+  if (encoder_bwd(e, c, prune ? &pr : nullptr, &dy, &du_rows, nullptr)) return 1;
   // the last launch that can raise the hand-off error word is behind us: the word travels now (beside the tail)
   if (status_exchange(e, s)) return 1;
-  if (backward_tail(e, masked_ids, lengths, dy, B, S, rw, du_rows, s)) return 1;
+  if (backward_tail(e, c, dy, du_rows)) return 1;
   if (e->fp8_on) {
     // This call's maxima become the next call's scales; a calibration call arms the fp8 path. AFTER the tail: the weight-
     // gradient GEMMs dequantise this call's images with the scales they were written with (updated before the tail, a
@@ -580,7 +580,7 @@ static int loss_impl(PlbEngine* e, bool backward, const int64_t* masked_ids, con
   // NaN and shows in plb_poll_status; plb_adamw_step skips on the same word. No host round trip anywhere.
   if (status_finish(e, loss, s)) return 1;
   e->rep_valid = true;
-  if (prune) drop_final(e, kPrunedText); else note_final(e, xL, B, S, rw);
+  if (prune) drop_final(e, kPrunedText); else note_final(e, xL, c);
   return 0;
 }
 
@@ -635,72 +635,66 @@ extern "C" int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, cons
 // application (plb_launch_seed_dy) and runs the stages of a loss call's backward behind it. The phoneme head takes no
 // part: its gradient range is written as zeros (and still travels as the first piece of the exchange, as in
 // zero_loss_call: the collective sequence of a step is the same whatever the step computes).
-// layers (or null): the per-application outputs of plb_encode_layers, written by run_encoder as the call goes.
-// inputs (or null): the embedding inputs of plb_encode_inputs.
-static int encode_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* pk,
-                       float* hidden, const PlbLayerOutputs* layers, const char* who, void* stream,
-                       const PlbEmbedInputs* inputs = nullptr, const int32_t* key_mask = nullptr) {
-  if (check_shape(e, B, S, who)) return 1;
+static int encode_impl(PlbEngine* e, const char* who, const EncArgs& a, float* hidden) {
+  if (check_shape(e, a.B, a.S, who)) return 1;
   if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1): a differentiable forward keeps every application's activations", who);
   if (!e->grads) return fail("%s: no gradient buffer bound", who);
   if (e->fp8_on) return fail("%s: fp8 mode is on (the gradient sites' delayed scales belong to the pre-training loss); call plb_set_fp8(e, 0, stream) first", who);
   EmbedCall ec;
-  if (embed_call(e, ids, inputs, nullptr, who, &ec)) return 1;
-  if (key_mask_check(e, key_mask, S, who)) return 1;
+  if (embed_call(e, a.ids, a.inputs, nullptr, who, &ec)) return 1;
+  if (key_mask_check(e, a.key_mask, a.S, who)) return 1;
   if (!hidden) return fail("%s: hidden is null", who);
-  hipStream_t s = (hipStream_t)stream;
   Rows rw;
-  if (pick_rows(e, pk, lengths, false, B, S, who, &rw)) return 1;
+  if (pick_rows(e, a.packing, a.lengths, false, a.B, a.S, who, &rw)) return 1;
   drop_stash(e, "a plb_encode call that failed rewrote the workspace since");
   drop_final(e, "the last call that ran the encoder (plb_encode) failed");
+  Call c = {who, a.ids, a.lengths, a.B, a.S, rw, ec, a.layers, (hipStream_t)a.stream};
+  hipStream_t s = c.s;
   // (whatever an earlier call left on the side / communication stream was joined by that call's tail; audit on: checked)
   HB_W(s, e->ws, e->ws_bytes, "plb_encode (whole workspace)");
   e->last_app_rows[0] = e->last_app_rows[1] = rw.Tp;
   bf16_t* x = nullptr;
-  if (key_mask_words(e, key_mask, lengths, B, S, &rw, s)) return 1;
-  if (run_encoder(e, ids, lengths, B, S, rw, true, &x, s, nullptr, layers, &ec)) return 1;
-  // .last_hidden_state in the caller's [B,S,H] layout, ZEROS at the pad positions in both layouts: a downstream model must
-  // not be handed numbers that carry no gradient
-  if (lengths) TRY(plb_launch_unpack_rows(x, 1, e->H, rw.row_start, lengths, B, S, e->H, hidden, s));
+  if (key_mask_words(e, a.key_mask, &c)) return 1;
+  if (run_encoder(e, c, true, &x, nullptr)) return 1;
+  // .last_hidden_state in the caller's [B,S,H] layout, ZEROS at the pad positions in both layouts (by lengths, as tap_hidden
+  // does): a downstream model must not be handed numbers that carry no gradient
+  if (a.lengths) TRY(plb_launch_unpack_rows(x, 1, e->H, rw.row_start, a.lengths, a.B, a.S, e->H, hidden, s));
   else TRY(plb_launch_bf16_to_f32(x, e->H, hidden, e->H, rw.T, e->H, s));
   TRY(plb_launch_step_status(e->at<unsigned int>(e->o_lnerr), nullptr, e->host_err_dev, nullptr, s));
   e->stash_live = true;
-  e->stash_B = B; e->stash_S = S; e->stash_rows = rw.Tp; e->stash_used = rw.T; e->stash_row_start = rw.row_start;
-  e->stash_masked = key_mask != nullptr;
-  note_final(e, x, B, S, rw);
+  e->stash_B = a.B; e->stash_S = a.S; e->stash_rows = rw.Tp; e->stash_used = rw.T; e->stash_row_start = rw.row_start;
+  e->stash_masked = a.key_mask != nullptr;
+  note_final(e, x, c);
   return 0;
 }
 extern "C" int plb_encode(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                           const PlbPacking* pk, float* hidden, void* stream) {
-  return encode_impl(e, ids, lengths, B, S, pk, hidden, nullptr, "plb_encode", stream);
+  return encode_impl(e, "plb_encode", {ids, nullptr, nullptr, lengths, B, S, pk, nullptr, stream}, hidden);
 }
 extern "C" int plb_encode_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                                  const PlbPacking* pk, float* hidden, const PlbLayerOutputs* layers, void* stream) {
-  return encode_impl(e, ids, lengths, B, S, pk, hidden, layers, "plb_encode_layers", stream);
+  return encode_impl(e, "plb_encode_layers", {ids, nullptr, nullptr, lengths, B, S, pk, layers, stream}, hidden);
 }
 // plb_encode_layers with the embedding inputs (include/plbert.h: PlbEmbedInputs); none given: that call
 extern "C" int plb_encode_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths, int32_t B,
                                  int32_t S, const PlbPacking* pk, float* hidden, const PlbLayerOutputs* layers, void* stream) {
-  return encode_impl(e, ids, lengths, B, S, pk, hidden, layers, "plb_encode_inputs", stream, inputs);
+  return encode_impl(e, "plb_encode_inputs", {ids, inputs, nullptr, lengths, B, S, pk, layers, stream}, hidden);
 }
 // plb_encode_inputs with a key mask (include/plbert.h); key_mask == NULL: that call
 extern "C" int plb_encode_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
                                  const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* pk, float* hidden,
                                  const PlbLayerOutputs* layers, void* stream) {
-  return encode_impl(e, ids, lengths, B, S, pk, hidden, layers, key_mask ? "plb_encode_masked" : "plb_encode_inputs", stream, inputs,
-                     key_mask);
+  return encode_impl(e, key_mask ? "plb_encode_masked" : "plb_encode_inputs", {ids, inputs, key_mask, lengths, B, S, pk, layers, stream},
+                     hidden);
 }
 
-// plb_encode_bwd_layers, and plb_encode_bwd as a call of it (layers_call false: its own name in the texts, d_hidden required).
+// plb_encode_bwd_layers, and plb_encode_bwd as a call of it (layers_call false: d_hidden required, with its own text).
 // d_below[l] (host array of L device pointers, or null): the caller's gradient of hidden_states[l], the input of application
 // l; it joins the residual operand of the dX GEMM that produces that state's gradient (attention_bwd_dx). d_hidden == NULL:
 // the output gradient of the last application is zero.
-static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
-                           const PlbPacking* pk, const float* d_hidden, const float* const* d_below, bool layers_call,
-                           void* stream, const char* who_inputs = nullptr, const PlbEmbedInputs* inputs = nullptr,
-                           float* d_inputs_embeds = nullptr, const int32_t* key_mask = nullptr) {
-  const char* who = who_inputs ? who_inputs : layers_call ? "plb_encode_bwd_layers" : "plb_encode_bwd";
-  if (check_shape(e, B, S, who)) return 1;
+static int encode_bwd_impl(PlbEngine* e, const char* who, const EncArgs& a, const float* d_hidden, const float* const* d_below,
+                           float* d_inputs_embeds, bool layers_call) {
+  if (check_shape(e, a.B, a.S, who)) return 1;
   if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1)", who);
   if (!e->grads) return fail("%s: no gradient buffer bound", who);
   // the pointer array is read here, on the host: a copy without its NULL-only form
@@ -712,22 +706,21 @@ static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* leng
     if (!any) below.clear();
   }
   EmbedCall ec;
-  if (embed_call(e, ids, inputs, d_inputs_embeds, who, &ec)) return 1;
-  if (key_mask_check(e, key_mask, S, who)) return 1;
+  if (embed_call(e, a.ids, a.inputs, d_inputs_embeds, who, &ec)) return 1;
+  if (key_mask_check(e, a.key_mask, a.S, who)) return 1;
   if (!d_hidden && below.empty())
     return layers_call ? fail("%s: nothing to differentiate (d_hidden is null and d_below has no entry)", who)
                        : fail("%s: d_hidden is null", who);
   if (!e->stash_live) return fail("%s: no live plb_encode stash: %s", who, e->stash_dead_by);
-  if (B != e->stash_B || S != e->stash_S)
-    return fail("%s: batch %d x seq %d differs from the plb_encode call's %d x %d", who, B, S, e->stash_B, e->stash_S);
-  if ((key_mask != nullptr) != e->stash_masked)
+  if (a.B != e->stash_B || a.S != e->stash_S)
+    return fail("%s: batch %d x seq %d differs from the plb_encode call's %d x %d", who, a.B, a.S, e->stash_B, e->stash_S);
+  if ((a.key_mask != nullptr) != e->stash_masked)
     return fail("%s: %s, the live plb_encode call ran %s one (the backward takes the key mask of its forward again)", who,
-                key_mask ? "a key mask is given" : "no key mask is given", e->stash_masked ? "with" : "without");
-  hipStream_t s = (hipStream_t)stream;
+                a.key_mask ? "a key mask is given" : "no key mask is given", e->stash_masked ? "with" : "without");
   Rows rw;
   // (a call that fails launches nothing and leaves what plb_last_call_rows reports alone)
   const int64_t exec_rows[2] = {e->last_exec_rows[0], e->last_exec_rows[1]};
-  const bool plan_ok = pick_rows(e, pk, lengths, false, B, S, who, &rw) == 0;   // (its own text names the plan)
+  const bool plan_ok = pick_rows(e, a.packing, a.lengths, false, a.B, a.S, who, &rw) == 0;   // (its own text names the plan)
   const bool same = plan_ok && rw.Tp == e->stash_rows && rw.T == e->stash_used && rw.row_start == e->stash_row_start;
   if (!same) {
     e->last_exec_rows[0] = exec_rows[0]; e->last_exec_rows[1] = exec_rows[1];
@@ -736,6 +729,8 @@ static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* leng
                 who, (long long)rw.Tp, (long long)rw.T, rw.row_start ? "packed" : "padded", (long long)e->stash_rows,
                 (long long)e->stash_used, e->stash_row_start ? "packed" : "padded");
   }
+  Call c = {who, a.ids, a.lengths, a.B, a.S, rw, ec, nullptr, (hipStream_t)a.stream};
+  hipStream_t s = c.s;
   if (begin_training_call(e, false, s)) return 1;
   e->stash_live = false;
   e->stash_dead_by = "plb_encode_bwd has consumed it (one backward per plb_encode)";
@@ -744,38 +739,41 @@ static int encode_bwd_impl(PlbEngine* e, const int64_t* ids, const int32_t* leng
   const int64_t Tp = rw.Tp;
   bf16_t* dy = e->at<bf16_t>(e->o_dy0);
   HB_W(s, dy, Tp * e->H * 2, "output gradient of the last application, seeded from d_hidden");
-  if (key_mask_words(e, key_mask, lengths, B, S, &rw, s)) return 1;
-  if (d_hidden) TRY(plb_launch_seed_dy(d_hidden, lengths, rw.row_start, B, S, e->H, (int)Tp, dy, s));
+  if (key_mask_words(e, a.key_mask, &c)) return 1;
+  if (d_hidden) TRY(plb_launch_seed_dy(d_hidden, a.lengths, rw.row_start, a.B, a.S, e->H, (int)Tp, dy, s));
   else HIPTRY(hipMemsetAsync(dy, 0, (size_t)Tp * e->H * 2, s));   // (no gradient at the last slot: every row zero)
   // the phoneme head took no part: zeros, final before the layer loop — its piece travels where a regular step's does
   HB_W(s, e->grd(PLB_HEAD_W), (e->ptrain - e->poff[PLB_HEAD_W]) * 4, "phoneme head gradients (zeros: plb_encode_bwd)");
   HIPTRY(hipMemsetAsync(e->grd(PLB_HEAD_W), 0, (size_t)(e->ptrain - e->poff[PLB_HEAD_W]) * 4, s));
   if (overlapping(e) && reduce_pieces(e, kPieceHead, kPieceHead + 1, s)) return 1;
   int du_rows = 0;
-  if (encoder_bwd(e, nullptr, lengths, B, S, rw, &dy, &du_rows, s, below.empty() ? nullptr : below.data())) return 1;
+  if (encoder_bwd(e, c, nullptr, &dy, &du_rows, below.empty() ? nullptr : below.data())) return 1;
   if (status_exchange(e, s)) return 1;
-  if (backward_tail(e, ids, lengths, dy, B, S, rw, du_rows, s, &ec)) return 1;
+  if (backward_tail(e, c, dy, du_rows)) return 1;
   return status_finish(e, nullptr, s);
 }
 extern "C" int plb_encode_bwd(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                               const PlbPacking* pk, const float* d_hidden, void* stream) {
-  return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, nullptr, false, stream);
+  return encode_bwd_impl(e, "plb_encode_bwd", {ids, nullptr, nullptr, lengths, B, S, pk, nullptr, stream}, d_hidden, nullptr, nullptr,
+                         false);
 }
 extern "C" int plb_encode_bwd_layers(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int32_t B, int32_t S,
                                      const PlbPacking* pk, const float* d_hidden, const float* const* d_below, void* stream) {
-  return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, d_below, true, stream);
+  return encode_bwd_impl(e, "plb_encode_bwd_layers", {ids, nullptr, nullptr, lengths, B, S, pk, nullptr, stream}, d_hidden, d_below,
+                         nullptr, true);
 }
 // plb_encode_bwd_layers with the embedding inputs of the live plb_encode_inputs call and, when asked, the gradient of the
 // pre-LayerNorm embedding sum; nothing of the two given: that call
 extern "C" int plb_encode_bwd_inputs(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* lengths,
                                      int32_t B, int32_t S, const PlbPacking* pk, const float* d_hidden, const float* const* d_below,
                                      float* d_inputs_embeds, void* stream) {
-  return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, d_below, true, stream, "plb_encode_bwd_inputs", inputs, d_inputs_embeds);
+  return encode_bwd_impl(e, "plb_encode_bwd_inputs", {ids, inputs, nullptr, lengths, B, S, pk, nullptr, stream}, d_hidden, d_below,
+                         d_inputs_embeds, true);
 }
 // plb_encode_bwd_inputs with the key mask of the live plb_encode_masked call; key_mask == NULL: that call
 extern "C" int plb_encode_bwd_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
                                      const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* pk, const float* d_hidden,
                                      const float* const* d_below, float* d_inputs_embeds, void* stream) {
-  return encode_bwd_impl(e, ids, lengths, B, S, pk, d_hidden, d_below, true, stream,
-                         key_mask ? "plb_encode_bwd_masked" : "plb_encode_bwd_inputs", inputs, d_inputs_embeds, key_mask);
+  return encode_bwd_impl(e, key_mask ? "plb_encode_bwd_masked" : "plb_encode_bwd_inputs",
+                         {ids, inputs, key_mask, lengths, B, S, pk, nullptr, stream}, d_hidden, d_below, d_inputs_embeds, true);
 }

@@ -288,28 +288,35 @@ struct LnSlot { const float* gamma; const float* beta; const bf16_t* pre; float*
 // The masked rows a pruned last application runs on (engine_layers.cpp: last_application_fwd_pruned): n rows, Mc = n padded to 128
 struct Prune { const int32_t* rows; int n; int Mc; };
 
-// What the backward stages of one call share: its shape, its precision mode, the partial-row layout of its layer loop.
-struct Bwd {
-  const int32_t* lengths;
-  const int32_t* row_start;   // token-packed call (Rows), or null
-  const uint32_t* key_words; int ldkw;   // key-mask words (Rows), or null
-  int B, S, T;
-  int64_t Tp;
-  bool f8, calib;   // fp8 operands | an fp8-mode call that only records the maxima
-  bool fuse_b;      // LayerNorm backward in the epilogue of the dX GEMM that produces its output gradient
-  int prows;        // LayerNorm-backward partial rows per application
-  int du_rows;      // ffn.bias partial rows per application (0: the tail sums dU itself)
-  hipStream_t s;
-};
-
 // What a call feeds its embeddings beside the ids (include/plbert.h: PlbEmbedInputs) and, in a backward, where the gradient of
-// the pre-LayerNorm sum goes (fp32 [B,S,E], or null). One struct from the entry point down to the embedding forward
-// (run_encoder) and the backward tail; a null pointer to it, or one whose members are all null, is a plain call: the launches of
-// embed.hip, as before.
+// the pre-LayerNorm sum goes (fp32 [B,S,E], or null). All members null: a plain call — the launches of embed.hip, as before.
 struct EmbedCall {
   PlbEmbedInputs in;
   float* d_inputs_embeds;
   bool any() const { return in.token_type_ids || in.position_ids || in.inputs_embeds || d_inputs_embeds; }
+};
+
+// One encoder call, as every stage from its entry point down to the launches sees it. The implementation of the entry point
+// builds it once, behind its refusals (a loss call too: ids = masked_ids, an empty EmbedCall, no taps); the stages take it by
+// const reference and nothing else about the call. Nothing in it is derived from another member.
+struct Call {
+  const char* who;                // the entry point, as its texts name it
+  const int64_t* ids;             // [B,S], or null with ec.in.inputs_embeds
+  const int32_t* lengths;         // [B], or null: every sample is full
+  int B, S;
+  Rows rw;                        // its rows and, in a plb_*_masked call, its key-mask words
+  EmbedCall ec;
+  const PlbLayerOutputs* taps;    // per-application outputs the caller asked for (include/plbert.h), or null
+  hipStream_t s;
+};
+
+// What the backward stages of one call share beside the call: its precision mode, the partial-row layout of its layer loop.
+struct Bwd {
+  const Call& call;
+  bool f8, calib;   // fp8 operands | an fp8-mode call that only records the maxima
+  bool fuse_b;      // LayerNorm backward in the epilogue of the dX GEMM that produces its output gradient
+  int prows;        // LayerNorm-backward partial rows per application
+  int du_rows;      // ffn.bias partial rows per application (0: the tail sums dU itself)
 };
 
 // The pieces of the overlapped exchange in issue order (engine_comm.cpp: kPieces)
@@ -340,16 +347,15 @@ PlbGemmNT nt_desc(const bf16_t* A, const bf16_t* B, int64_t M, int N, int K);
 int qkvcol_rows(int B, int S);
 Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int prows = 0, int du_rows = 0);
 bool prune_enabled();
-int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B, int S, const Rows& rw, bool stash,
-                bf16_t** xout, hipStream_t s, const Prune* pr = nullptr, const PlbLayerOutputs* taps = nullptr,
-                const EmbedCall* ec = nullptr);
+int run_encoder(PlbEngine* e, const Call& c, bool stash, bf16_t** xout, const Prune* pr);
+PlbEmbed embed_desc(const PlbEngine* e, const Call& c);
+PlbEmbedIn embed_in_desc(const PlbEngine* e, const EmbedCall& ec, const PlbEmbed* base);
 int tn_splits(int64_t Mtot, int N, int K, int* rows_per_split);
 int weight_grad(PlbEngine* e, const bf16_t* A, int lda, int Ncols, const bf16_t* Bm, int ldb, int64_t Mtot, int N,
                 int K, float* out, hipStream_t s, bool side_slab = false);
 int weight_grad8(PlbEngine* e, const uint8_t* A8, const uint8_t* B8, int64_t Mtot, int N, int K, int site_a, int site_b,
                  float* out, hipStream_t s);
-int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, int S, const Rows& rw, bf16_t** dy,
-                int* du_rows, hipStream_t s, const float* const* d_below = nullptr);
+int encoder_bwd(PlbEngine* e, const Call& c, const Prune* pr, bf16_t** dy, int* du_rows, const float* const* d_below);
 // engine_calls.cpp
 void drop_stash(PlbEngine* e, const char* by);
 void drop_final(PlbEngine* e, const char* by);

@@ -249,19 +249,40 @@ static int last_application_fwd_pruned(PlbEngine* e, const Prune* pr, bool stash
 
 // Hidden-state slot `slot` of a call's taps (include/plbert.h: PlbLayerOutputs), when wanted: the fp32 image of the bf16 rows
 // x in the caller's [B,S,H] layout, zeros at the pad positions in both layouts (plb_encode's conversion pass).
-static int tap_hidden(PlbEngine* e, const PlbLayerOutputs* taps, int slot, const bf16_t* x, const int32_t* lengths, int B, int S,
-                      const Rows& rw, hipStream_t s) {
-  float* const out = (taps && taps->hidden_states) ? taps->hidden_states[slot] : nullptr;
+static int tap_hidden(PlbEngine* e, const Call& c, int slot, const bf16_t* x) {
+  float* const out = (c.taps && c.taps->hidden_states) ? c.taps->hidden_states[slot] : nullptr;
   if (!out) return 0;
-  if (lengths) TRY(plb_launch_unpack_rows(x, 1, e->H, rw.row_start, lengths, B, S, e->H, out, s));
-  else TRY(plb_launch_bf16_to_f32(x, e->H, out, e->H, rw.T, e->H, s));
+  if (c.lengths) TRY(plb_launch_unpack_rows(x, 1, e->H, c.rw.row_start, c.lengths, c.B, c.S, e->H, out, c.s));
+  else TRY(plb_launch_bf16_to_f32(x, e->H, out, e->H, c.rw.T, e->H, c.s));
   return 0;
+}
+
+// The embedding descriptors of a call. PlbEmbed from the engine: tables, LayerNorm affine, eps, the call's shapes and, in a
+// packed call, its plan; the forward and the backward tail add what is their own (out, fill_slots | the gradient outputs).
+PlbEmbed embed_desc(const PlbEngine* e, const Call& c) {
+  PlbEmbed em;
+  memset(&em, 0, sizeof(em));
+  em.ids = c.ids; em.T = c.rw.T; em.S = c.S; em.E = e->E; em.V = e->V;
+  em.word = e->par(PLB_WORD_EMB); em.pos = e->par(PLB_POS_EMB); em.type0 = e->par(PLB_TYPE_EMB);
+  em.gamma = e->par(PLB_EMB_LN_W); em.beta = e->par(PLB_EMB_LN_B); em.eps = e->c.layer_norm_eps;
+  if (c.rw.row_start) { em.row_start = c.rw.row_start; em.lengths = c.lengths; em.B = c.B; }
+  return em;
+}
+// PlbEmbedIn over `base` from the per-token sources of an EmbedCall (plb_*_inputs): the launches of embed_inputs.hip
+PlbEmbedIn embed_in_desc(const PlbEngine* e, const EmbedCall& ec, const PlbEmbed* base) {
+  PlbEmbedIn xi;
+  memset(&xi, 0, sizeof(xi));
+  xi.base = base;
+  xi.token_type_ids = ec.in.token_type_ids; xi.position_ids = ec.in.position_ids; xi.inputs_embeds = ec.in.inputs_embeds;
+  xi.NTY = e->c.type_vocab_size; xi.P = e->P;
+  return xi;
 }
 
 // Embeddings + L applications of the shared layer. stash: keep every layer's activations (training)
 // or reuse the layer-0 slots (inference). Returns the final hidden buffer in *xout.
-// ec (or null): what the embeddings read beside the ids (EmbedCall); ids is null with inputs_embeds.
-// taps (or null; never with a pruned last application): the per-application outputs the caller asked for — the map-in
+// c: the call (Call) — c.ec is what the embeddings read beside the ids (ids is null with inputs_embeds); pr (or null): the
+// masked rows a pruned last application runs on.
+// c.taps (or null; never with a pruned last application): the per-application outputs the caller asked for — the map-in
 // output and every application's output as they are written, the attention probabilities from the qkv rows and the
 // log-sum-exp of the attention forward that has just run (without a stash the next application reuses that slot: stream
 // order protects it).
@@ -271,9 +292,10 @@ static int tap_hidden(PlbEngine* e, const PlbLayerOutputs* taps, int slot, const
 // attention kernel; the standalone LayerNorm kernels on shapes without a fused form), one image per layer in a training
 // call: the weight-gradient GEMMs read them all at the end of the backward. A calibration call (the first after
 // plb_set_fp8, and a training call whose gradient sites have not been seen yet) runs in bf16 and only records the maxima.
-int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B, int S, const Rows& rw, bool stash,
-                       bf16_t** xout, hipStream_t s, const Prune* pr, const PlbLayerOutputs* taps, const EmbedCall* ec) {
-  const int E = e->E, H = e->H, I = e->I, L = e->L;
+int run_encoder(PlbEngine* e, const Call& c, bool stash, bf16_t** xout, const Prune* pr) {
+  const int E = e->E, H = e->H, I = e->I, L = e->L, B = c.B, S = c.S;
+  const Rows& rw = c.rw;
+  hipStream_t s = c.s;
   const int T = rw.T;
   const int64_t Tp = rw.Tp;
   const bool f8 = f8_call(e, Tp, stash);
@@ -284,24 +306,16 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
   // tail rows are those of zero embeddings behind a zero attention output: the same in every call.
   const int T8 = (f8 && rw.row_start) ? (int)Tp : T;
   if (e->fp8_on && e->fp8_wstale) TRY(fp8_quantize_weights(e, s));
-  PlbEmbed em;
-  memset(&em, 0, sizeof(em));
-  em.ids = ids; em.T = T; em.S = S; em.E = E; em.V = e->V;
-  em.word = e->par(PLB_WORD_EMB); em.pos = e->par(PLB_POS_EMB); em.type0 = e->par(PLB_TYPE_EMB);
-  em.gamma = e->par(PLB_EMB_LN_W); em.beta = e->par(PLB_EMB_LN_B); em.eps = e->c.layer_norm_eps;
+  PlbEmbed em = embed_desc(e, c);
   em.out = e->at<bf16_t>(e->o_e); em.ldo = E;
   if (rw.row_start) {   // packed: every row of the call gets a value (zeros where no token sits), the tail included
-    em.row_start = rw.row_start; em.lengths = lengths; em.B = B; em.T = (int)Tp;
+    em.T = (int)Tp;
     // fp8 mode (plb_set_packed_fp8): the rest of a slot is embedded like the pad positions of a padded call, so the sites'
     // maxima — taken over every row of the slots — are those of the padded call on the batch trimmed to its slots
     em.fill_slots = e->fp8_on;
   }
-  if (ec && ec->any()) {   // per-token sources (plb_*_inputs): the row kernel of embed_inputs.hip
-    PlbEmbedIn xi;
-    memset(&xi, 0, sizeof(xi));
-    xi.base = &em;
-    xi.token_type_ids = ec->in.token_type_ids; xi.position_ids = ec->in.position_ids; xi.inputs_embeds = ec->in.inputs_embeds;
-    xi.NTY = e->c.type_vocab_size; xi.P = e->P;
+  if (c.ec.any()) {   // per-token sources (plb_*_inputs): the row kernel of embed_inputs.hip
+    const PlbEmbedIn xi = embed_in_desc(e, c.ec, &em);
     TRY(plb_launch_embed_inputs_fwd(&xi, s));
   } else {
     TRY(plb_launch_embed_fwd(&em, s));
@@ -311,7 +325,7 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
   PlbGemmNT g = nt_desc(em.out, e->wbf(PLB_MAP_W), Tp, H, E);
   g.bias = e->par(PLB_MAP_B); g.C = first.x; g.ldc = H;
   TRY(plb_launch_gemm_nt(&g, 0, 0, s));
-  if (tap_hidden(e, taps, 0, first.x, lengths, B, S, rw, s)) return 1;
+  if (tap_hidden(e, c, 0, first.x)) return 1;
   if (f8) {  // layer 0 reads the map-in output, which no LayerNorm produced: one quantisation pass
     // (image and the site's maximum in one pass: the rows are contiguous)
     const F8Site sX(e, F8_X, 0);
@@ -337,7 +351,7 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
     TRY(gemm_nt_any(&g, 0, f8 ? &oq : nullptr, s));
     PlbAttn at;
     memset(&at, 0, sizeof(at));
-    at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H;
+    at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = c.lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H;
     at.row_start = rw.row_start;
     at.key_words = rw.key_words; at.ldkw = rw.ldkw;
     // pruned last application: the attention output of ALL rows goes to a buffer of its own (training: a backward temporary
@@ -356,8 +370,8 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
       if (at.ctx8) HIPTRY(hipMemsetAsync(sl.c8, 0, (size_t)T * H, s));
     }
     TRY(plb_launch_attn_fwd(&at, s));
-    if (float* const probs = (taps && taps->attentions) ? taps->attentions[l] : nullptr)
-      TRY(plb_launch_attn_probs_masked(sl.qkv, 3 * H, sl.lse, lengths, rw.row_start, rw.key_words, rw.ldkw, B, S, e->NH, at.scale,
+    if (float* const probs = (c.taps && c.taps->attentions) ? c.taps->attentions[l] : nullptr)
+      TRY(plb_launch_attn_probs_masked(sl.qkv, 3 * H, sl.lse, c.lengths, rw.row_start, rw.key_words, rw.ldkw, B, S, e->NH, at.scale,
                                        probs, s));
     // packed: the tail behind the last slot (up to 1,023 rows) is written by no attention workgroup, and what sits there
     // goes through dense / LayerNorm / FFN into the stash the weight-gradient GEMMs read: zeros, not whatever was there
@@ -401,7 +415,7 @@ int run_encoder(PlbEngine* e, const int64_t* ids, const int32_t* lengths, int B,
     if (gemm_ln_fwd(e, &g, f8 ? &o2 : nullptr, fuse_f, ln2_slot(e, sl), sl.y, T8, next8 ? sl.x8n : nullptr,
                     next8 ? F8Site(e, F8_X, l + 1) : F8Site(), s))
       return 1;
-    if (tap_hidden(e, taps, l + 1, sl.y, lengths, B, S, rw, s)) return 1;
+    if (tap_hidden(e, c, l + 1, sl.y)) return 1;
     *xout = sl.y;
   }
   return 0;
@@ -454,8 +468,8 @@ int weight_grad8(PlbEngine* e, const uint8_t* A8, const uint8_t* B8, int64_t Mto
 // gradient (read by the LayerNorm-2 backward of the last application only: for the others, the dX GEMM of application l+1
 // ran it — attention_bwd_dx).
 static int post_attention_bwd(PlbEngine* e, const Bwd& c, int l, const Slots& sl, const bf16_t* dy) {
-  const int H = e->H, I = e->I, T = c.T, Tp = (int)c.Tp;
-  hipStream_t s = c.s;
+  const int H = e->H, I = e->I, T = c.call.rw.T, Tp = (int)c.call.rw.Tp;
+  hipStream_t s = c.call.s;
   const F8Site sDP(e, F8_DP, l), sDU(e, F8_DU, l), sDP1(e, F8_DP1, l);
   if (l == e->L - 1 && ln_bwd(e, ln2_slot(e, sl), c.prows, dy, sl.dpre2, T, Tp, c.f8 ? sl.dp8 : nullptr, sDP, s)) return 1;
   if (c.calib) TRY(plb_launch_amax(sl.dpre2, 1, (size_t)T, H, H, sDP.amax, s));
@@ -495,7 +509,8 @@ static int post_attention_bwd(PlbEngine* e, const Bwd& c, int l, const Slots& sl
 // there) for the attention backward and the dX GEMM, which run on all rows: dCtx into o_dctx, dpre1 into o_da.
 static int last_application_bwd_pruned(PlbEngine* e, const Bwd& c, const Slots& sl, const Prune* pr) {
   const int H = e->H, I = e->I, L = e->L, Mc = pr->Mc, n = pr->n;
-  hipStream_t s = c.s;
+  const int64_t Tp = c.call.rw.Tp;
+  hipStream_t s = c.call.s;
   const F8Site sDP(e, F8_DP, L - 1), sDU(e, F8_DU, L - 1), sDP1(e, F8_DP1, L - 1);
   bf16_t* const dac = e->at<bf16_t>(e->o_da);       // dA of the compact rows, then (full) dpre1 scattered to token rows
   bf16_t* const dctxc = e->at<bf16_t>(e->o_dy0);    // dCtx of the compact rows (dy is not used by this application)
@@ -526,9 +541,9 @@ static int last_application_bwd_pruned(PlbEngine* e, const Bwd& c, const Slots& 
   g.C = dctxc; g.ldc = H;
   TRY(plb_launch_gemm_nt(&g, 0, 0, s));
   // back to token rows: dCtx and dpre1 are zero wherever no masked position sits
-  HIPTRY(hipMemsetAsync(dctx, 0, (size_t)c.Tp * H * 2, s));
+  HIPTRY(hipMemsetAsync(dctx, 0, (size_t)Tp * H * 2, s));
   TRY(plb_launch_scatter_rows(dctxc, H, pr->rows, n, H, dctx, H, s));
-  HIPTRY(hipMemsetAsync(dac, 0, (size_t)c.Tp * H * 2, s));   // (dA has been consumed by the LayerNorm backward above)
+  HIPTRY(hipMemsetAsync(dac, 0, (size_t)Tp * H * 2, s));   // (dA has been consumed by the LayerNorm backward above)
   TRY(plb_launch_scatter_rows(sl.dpre1, H, pr->rows, n, H, dac, H, s));
   return 0;
 }
@@ -541,22 +556,25 @@ static int last_application_bwd_pruned(PlbEngine* e, const Bwd& c, const Slots& 
 // res' = res + d_in goes to o_da, which is dead here (dA of this application was consumed by its LayerNorm-1 backward; the
 // pruned path uses the buffer the same way); res itself (dpre1: the weight-gradient GEMMs read it) is left alone.
 static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, bf16_t* ctx, const bf16_t* res,
-                            bf16_t* dx, const float* d_in = nullptr) {
-  const int H = e->H, T = c.T;
-  hipStream_t s = c.s;
+                            bf16_t* dx, const float* d_in) {
+  const Call& call = c.call;
+  const Rows& rw = call.rw;
+  const int H = e->H, T = rw.T;
+  const int64_t Tp = rw.Tp;
+  hipStream_t s = call.s;
   if (d_in) {
     bf16_t* const res_in = e->at<bf16_t>(e->o_da);
-    HB_R(s, res, c.Tp * H * 2, "residual operand of the dX GEMM");
-    HB_W(s, res_in, c.Tp * H * 2, "residual operand + the caller's gradient of this application's input");
-    TRY(plb_launch_add_row_grad(res, d_in, c.lengths, c.row_start, c.B, c.S, H, (int)c.Tp, res_in, s));
+    HB_R(s, res, Tp * H * 2, "residual operand of the dX GEMM");
+    HB_W(s, res_in, Tp * H * 2, "residual operand + the caller's gradient of this application's input");
+    TRY(plb_launch_add_row_grad(res, d_in, call.lengths, rw.row_start, call.B, call.S, H, (int)Tp, res_in, s));
     res = res_in;
   }
   const F8Site sDQ(e, F8_DQ, l);
   PlbAttn at;
   memset(&at, 0, sizeof(at));
-  at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = c.lengths; at.B = c.B; at.S = c.S; at.NH = e->NH; at.H = H; at.scale = 0.125f;
-  at.row_start = c.row_start;
-  at.key_words = c.key_words; at.ldkw = c.ldkw;
+  at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = call.lengths; at.B = call.B; at.S = call.S; at.NH = e->NH; at.H = H; at.scale = 0.125f;
+  at.row_start = rw.row_start;
+  at.key_words = rw.key_words; at.ldkw = rw.ldkw;
   at.ctx = ctx; at.ldctx = H; at.lse = sl.lse;
   at.dctx = e->at<bf16_t>(e->o_dctx); at.lddctx = H; at.delta = e->at<float>(e->o_delta); at.dqkv = sl.dqkv; at.lddqkv = 3 * H;
   at.colpart = sl.qkvcol; at.colpart_accumulate = 0;
@@ -567,24 +585,24 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
   // packed, S no multiple of 128: the backward kernels store no row of a sample at or past position S, and the slot of a
   // full-length sample runs on to the next multiple of 128 — rows no launch of this call writes, which the weight-gradient
   // GEMMs read: zeros (their true value: no token sits there), not what an earlier call left
-  if (c.row_start && c.S % 128 && at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv, 0, (size_t)T * 3 * H * 2, s));
+  if (rw.row_start && call.S % 128 && at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv, 0, (size_t)T * 3 * H * 2, s));
   // (their e5m2 image likewise: a stale byte there can be a NaN encoding, and 0 x NaN in the stacked weight-gradient GEMM is NaN)
-  if (c.row_start && c.S % 128 && at.dqkv8) HIPTRY(hipMemsetAsync(sl.dq8, 0, (size_t)T * 3 * H, s));
+  if (rw.row_start && call.S % 128 && at.dqkv8) HIPTRY(hipMemsetAsync(sl.dq8, 0, (size_t)T * 3 * H, s));
   TRY(plb_launch_attn_bwd(&at, s));
-  if (c.Tp > T) {
-    if (at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv + (int64_t)T * 3 * H, 0, (size_t)(c.Tp - T) * 3 * H * 2, s));
-    if (c.f8) HIPTRY(hipMemsetAsync(sl.dq8 + (int64_t)T * 3 * H, 0, (size_t)(c.Tp - T) * 3 * H, s));
+  if (Tp > T) {
+    if (at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv + (int64_t)T * 3 * H, 0, (size_t)(Tp - T) * 3 * H * 2, s));
+    if (c.f8) HIPTRY(hipMemsetAsync(sl.dq8 + (int64_t)T * 3 * H, 0, (size_t)(Tp - T) * 3 * H, s));
   }
   if (c.calib) TRY(plb_launch_amax(sl.dqkv, 1, (size_t)T, 3 * H, 3 * H, sDQ.amax, s));
-  PlbGemmNT g = nt_desc(sl.dqkv, e->at<bf16_t>(e->o_wqkvT), c.Tp, H, 3 * H);
+  PlbGemmNT g = nt_desc(sl.dqkv, e->at<bf16_t>(e->o_wqkvT), Tp, H, 3 * H);
   g.res = res; g.ldr = H; g.C = dx; g.ldc = H;
   const F8Op ox = f8_op(sl.dq8, sDQ, F8Weight(e, F8W_QKVT), 1);
   if (l == 0) {   // the gradient of the embeddings' map-in output: the tail takes it
     TRY(gemm_nt_any(&g, 0, c.f8 ? &ox : nullptr, s));
     return 0;
   }
-  const Slots below = slots(e, c.Tp, c.B, c.S, l - 1, true, c.prows, c.du_rows);
-  return gemm_ln_bwd(e, &g, c.f8 ? &ox : nullptr, c.fuse_b, ln2_slot(e, below), c.prows, below.dpre2, T, (int)c.Tp,
+  const Slots below = slots(e, Tp, call.B, call.S, l - 1, true, c.prows, c.du_rows);
+  return gemm_ln_bwd(e, &g, c.f8 ? &ox : nullptr, c.fuse_b, ln2_slot(e, below), c.prows, below.dpre2, T, (int)Tp,
                      c.f8 ? below.dp8 : nullptr, F8Site(e, F8_DP, l - 1), s);
 }
 
@@ -594,12 +612,10 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
 // backward), dCtx = dpre1·Wd, dX = dQKV·Wqkv (+ LayerNorm 2 backward of the layer below) — written by the launch that
 // produces the gradient (fused LayerNorm-backward / gelu-backward epilogues, the attention-backward kernels, the
 // standalone LayerNorm backward), one image per layer for the weight-gradient GEMMs at the end.
-int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, int S, const Rows& rw, bf16_t** dy,
-                       int* du_rows, hipStream_t s, const float* const* d_below) {
+int encoder_bwd(PlbEngine* e, const Call& call, const Prune* pr, bf16_t** dy, int* du_rows, const float* const* d_below) {
   const int I = e->I, L = e->L;
-  Bwd c;
-  c.lengths = lengths; c.row_start = rw.row_start; c.key_words = rw.key_words; c.ldkw = rw.ldkw; c.B = B; c.S = S; c.T = rw.T; c.Tp = rw.Tp; c.s = s;
-  const int Tp = (int)c.Tp;
+  Bwd c = {call};
+  const int Tp = (int)call.rw.Tp;
   c.f8 = f8_call(e, Tp, true);
   c.calib = e->fp8_on && !c.f8;
   // ffn.bias gradient from the dU GEMM's epilogue: 2 partial rows per row tile of the kernel that runs it
@@ -613,11 +629,11 @@ int encoder_bwd(PlbEngine* e, const Prune* pr, const int32_t* lengths, int B, in
   e->part_rows_used = c.prows;
   bf16_t* dx = e->at<bf16_t>(e->o_dy1);
   for (int l = L - 1; l >= 0; --l) {
-    const Slots sl = slots(e, c.Tp, B, S, l, true, c.prows, c.du_rows);
+    const Slots sl = slots(e, call.rw.Tp, call.B, call.S, l, true, c.prows, c.du_rows);
     if (pr && l == L - 1) {
       // the attention output of all rows is the backward temporary o_dy1 (the ctx slot holds the compact rows)
       if (last_application_bwd_pruned(e, c, sl, pr)) return 1;
-      if (attention_bwd_dx(e, c, l, sl, e->at<bf16_t>(e->o_dy1), e->at<bf16_t>(e->o_da), dx)) return 1;
+      if (attention_bwd_dx(e, c, l, sl, e->at<bf16_t>(e->o_dy1), e->at<bf16_t>(e->o_da), dx, nullptr)) return 1;
     } else {
       if (post_attention_bwd(e, c, l, sl, *dy)) return 1;
       if (attention_bwd_dx(e, c, l, sl, sl.ctx, sl.dpre1, dx, d_below ? d_below[l] : nullptr)) return 1;

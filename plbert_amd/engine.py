@@ -89,6 +89,54 @@ def packed_fp8_default():
     return os.environ.get("PLBERT_PACKED_FP8", "0").strip() == "1"
 
 
+# ---- the encoder and loss entry points (include/plbert.h): which one a call reaches, and its parameters in order ------------
+# A call reaches the NARROWEST rung that carries what the caller gave: the error texts name the rung, and a library named
+# by PLBERT_HIP_LIB that predates a rung keeps serving the calls that do not need it.
+def encoder_entry(family, layers, inputs, key_mask, d_below=None, want_d_inputs_embeds=False):
+    """The symbol of ``family`` ("forward", "encode", "encode_bwd") for a call with per-application outputs (``layers``),
+    embedding inputs (``inputs``) and a key mask (``key_mask``): given or not. "encode_bwd" takes the inputs and the mask of
+    its live encode, and ``d_below`` (a list, or None) / ``want_d_inputs_embeds`` in place of ``layers``. The plain
+    "forward" rung is HipEngine.forward's (with a plan: that name + "_packed"); forward_layers starts at the layers rung."""
+    if family == "encode_bwd":
+        layers, inputs = d_below is not None, inputs or want_d_inputs_embeds
+    return "plb_" + family + ("_masked" if key_mask else "_inputs" if inputs else "_layers" if layers else "")
+
+
+def loss_entry(backward, dual, packed):
+    """The symbol of a loss call: with the backward or not, dual-head (token_ids given) or not, with a plan or not."""
+    return "plb_loss_fwd" + (("_bwd_dual" if dual else "_bwd") if backward else "") + ("_packed" if packed else "")
+
+
+_ENC = ("e", "ids", "lengths", "B", "S", "packing")
+_ENC_IN = ("e", "ids", "inputs", "lengths", "B", "S", "packing")
+_ENC_KM = ("e", "ids", "inputs", "key_mask", "lengths", "B", "S", "packing")
+_LOSS = ("e", "masked_ids", "labels", "token_ids", "lengths", "idx_offsets", "idx_flat", "n_masked", "B", "S")
+_LOSS1 = tuple(n for n in _LOSS if n != "token_ids")   # the phoneme-only training calls take no token_ids
+# symbol -> its parameter names as the header has them (tests/test_entry_table_host.py holds the two together):
+# HipEngine._entry passes every argument through c_void_p, so nothing else guards the order
+ENTRY_ARGS = {
+    "plb_forward": _ENC[:-1] + ("hidden", "phoneme_logits", "token_logits", "stream"),
+    "plb_forward_packed": _ENC + ("hidden", "phoneme_logits", "token_logits", "stream"),
+    "plb_forward_layers": _ENC + ("hidden", "layers", "stream"),
+    "plb_forward_inputs": _ENC_IN + ("hidden", "layers", "stream"),
+    "plb_forward_masked": _ENC_KM + ("hidden", "layers", "stream"),
+    "plb_encode": _ENC + ("hidden", "stream"),
+    "plb_encode_layers": _ENC + ("hidden", "layers", "stream"),
+    "plb_encode_inputs": _ENC_IN + ("hidden", "layers", "stream"),
+    "plb_encode_masked": _ENC_KM + ("hidden", "layers", "stream"),
+    "plb_encode_bwd": _ENC + ("d_hidden", "stream"),
+    "plb_encode_bwd_layers": _ENC + ("d_hidden", "d_below", "stream"),
+    "plb_encode_bwd_inputs": _ENC_IN + ("d_hidden", "d_below", "d_inputs_embeds", "stream"),
+    "plb_encode_bwd_masked": _ENC_KM + ("d_hidden", "d_below", "d_inputs_embeds", "stream"),
+    "plb_loss_fwd": _LOSS + ("loss", "loss_parts", "stream"),
+    "plb_loss_fwd_packed": _LOSS + ("packing", "loss", "loss_parts", "stream"),
+    "plb_loss_fwd_bwd": _LOSS1 + ("loss", "stream"),
+    "plb_loss_fwd_bwd_packed": _LOSS1 + ("packing", "loss", "stream"),
+    "plb_loss_fwd_bwd_dual": _LOSS + ("loss", "loss_parts", "stream"),
+    "plb_loss_fwd_bwd_dual_packed": _LOSS + ("packing", "loss", "loss_parts", "stream"),
+}
+
+
 class HipEngine:
     def __init__(self, cfg, num_phonemes, num_tokens=0, max_batch=32, max_seq=512, device=None, train=True):
         """``train=False``: inference / validation engine (README.md:91, train.py:288-304) — no gradient, moment or
@@ -503,16 +551,24 @@ class HipEngine:
             hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device) if want_hidden else None
             ph = torch.empty((B, S, self.num_phonemes), dtype=torch.float32, device=self.device) if want_phoneme else None
             tk = torch.empty((B, S, self.num_tokens), dtype=torch.float32, device=self.device) if want_token else None
-            p = lambda t: None if t is None else t.data_ptr()
             pk = self._packing(packing, B, S)
-            if pk is None:
-                _lib.check(self.L.plb_forward(self.handle, ids.data_ptr(), p(lens), B, S, p(hid), p(ph), p(tk), self._stream()),
-                           "plb_forward")
-            else:
-                _lib.check(self.L.plb_forward_packed(self.handle, ids.data_ptr(), p(lens), B, S, C.byref(pk), p(hid), p(ph),
-                                                     p(tk), self._stream()), "plb_forward_packed")
+            self._entry(encoder_entry("forward", False, False, False) + ("" if pk is None else "_packed"),
+                        dict(ids=ids, lengths=lens, B=B, S=S, packing=pk, hidden=hid, phoneme_logits=ph, token_logits=tk))
         self._last_encoder_call = (int(B), int(S), lens, packing)
         return hid, ph, tk
+
+    def _entry(self, name, pieces):
+        """Call the entry point ``name`` with its ENTRY_ARGS out of ``pieces`` (the handle and the current stream are added
+        here): a device tensor goes in as its pointer, a ctypes struct by reference, a ctypes pointer array by address, an
+        int as it is and None as NULL."""
+        def arg(v):
+            if v is None or isinstance(v, (int, C.c_void_p)):
+                return v
+            if torch.is_tensor(v):
+                return v.data_ptr()
+            return C.byref(v) if isinstance(v, C.Structure) else C.addressof(v)
+        pieces = dict(pieces, e=self.handle, stream=self._stream())
+        _lib.check(getattr(self.L, name)(*[arg(pieces[k]) for k in ENTRY_ARGS[name]]), name)
 
     # ---- per-application outputs (include/plbert.h: PlbLayerOutputs) ----
     @staticmethod
@@ -586,22 +642,9 @@ class HipEngine:
             hs, at = self._alloc_layer_outputs(B, S, hidden_states, attentions) if out is None else (list(out[0]), list(out[1]))
             hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device) if want_hidden else None
             lo, keep = self._layer_outputs(hs, at, B, S)
-            pk = self._packing(packing, B, S)
-            if km is not None:
-                _lib.check(self.L.plb_forward_masked(self.handle, None if ids is None else ids.data_ptr(),
-                                                     None if ein is None else C.byref(ein), km.data_ptr(),
-                                                     None if lens is None else lens.data_ptr(), B, S,
-                                                     None if pk is None else C.byref(pk), None if hid is None else hid.data_ptr(),
-                                                     None if lo is None else C.byref(lo), self._stream()), "plb_forward_masked")
-            elif ein is None:
-                _lib.check(self.L.plb_forward_layers(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
-                                                     None if pk is None else C.byref(pk), None if hid is None else hid.data_ptr(),
-                                                     None if lo is None else C.byref(lo), self._stream()), "plb_forward_layers")
-            else:
-                _lib.check(self.L.plb_forward_inputs(self.handle, None if ids is None else ids.data_ptr(), C.byref(ein),
-                                                     None if lens is None else lens.data_ptr(), B, S,
-                                                     None if pk is None else C.byref(pk), None if hid is None else hid.data_ptr(),
-                                                     None if lo is None else C.byref(lo), self._stream()), "plb_forward_inputs")
+            self._entry(encoder_entry("forward", True, ein is not None, km is not None),
+                        dict(ids=ids, inputs=ein, key_mask=km, lengths=lens, B=B, S=S, packing=self._packing(packing, B, S),
+                             hidden=hid, layers=lo))
             del keep, keep_in
         self._last_encoder_call = (int(B), int(S), lens, packing)
         return (hs, at, hid) if want_hidden else (hs, at)
@@ -630,35 +673,12 @@ class HipEngine:
             hid = torch.empty((B, S, self.cfg.hidden_size), dtype=torch.float32, device=self.device)
             pk = self._packing(packing, B, S)
             hs = at = None
-            if km is not None:
-                if layers is not None:
-                    hs, at = self._alloc_layer_outputs(B, S, layers.get("hidden_states", False), layers.get("attentions", False))
-                lo, keep = self._layer_outputs(hs, at, B, S)
-                _lib.check(self.L.plb_encode_masked(self.handle, None if ids is None else ids.data_ptr(),
-                                                    None if ein is None else C.byref(ein), km.data_ptr(),
-                                                    None if lens is None else lens.data_ptr(), B, S,
-                                                    None if pk is None else C.byref(pk), hid.data_ptr(),
-                                                    None if lo is None else C.byref(lo), self._stream()), "plb_encode_masked")
-                del keep
-            elif ein is not None:
-                if layers is not None:
-                    hs, at = self._alloc_layer_outputs(B, S, layers.get("hidden_states", False), layers.get("attentions", False))
-                lo, keep = self._layer_outputs(hs, at, B, S)
-                _lib.check(self.L.plb_encode_inputs(self.handle, None if ids is None else ids.data_ptr(), C.byref(ein),
-                                                    None if lens is None else lens.data_ptr(), B, S,
-                                                    None if pk is None else C.byref(pk), hid.data_ptr(),
-                                                    None if lo is None else C.byref(lo), self._stream()), "plb_encode_inputs")
-                del keep
-            elif layers is None:
-                _lib.check(self.L.plb_encode(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
-                                             None if pk is None else C.byref(pk), hid.data_ptr(), self._stream()), "plb_encode")
-            else:
+            if layers is not None:
                 hs, at = self._alloc_layer_outputs(B, S, layers.get("hidden_states", False), layers.get("attentions", False))
-                lo, keep = self._layer_outputs(hs, at, B, S)
-                _lib.check(self.L.plb_encode_layers(self.handle, ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
-                                                    None if pk is None else C.byref(pk), hid.data_ptr(),
-                                                    None if lo is None else C.byref(lo), self._stream()), "plb_encode_layers")
-                del keep
+            lo, keep = self._layer_outputs(hs, at, B, S)
+            self._entry(encoder_entry("encode", layers is not None, ein is not None, km is not None),
+                        dict(ids=ids, inputs=ein, key_mask=km, lengths=lens, B=B, S=S, packing=pk, hidden=hid, layers=lo))
+            del keep
         self._encode_serial = getattr(self, "_encode_serial", 0) + 1
         self._live_encode = (ids, lens, packing, B, S, ein, keep_in, km)   # (holds the tensors the backward reads again)
         self._last_encoder_call = (int(B), int(S), lens, packing)
@@ -696,36 +716,14 @@ class HipEngine:
         self._live_encode = None
         with torch.cuda.device(self.device):
             pk = self._packing(packing, B, S)
-            args = (self.handle, None if ids is None else ids.data_ptr(), None if lens is None else lens.data_ptr(), B, S,
-                    None if pk is None else C.byref(pk), None if d is None else d.data_ptr())
-            if km is not None:
-                arr = None if below is None else self._ptr_array(below, self.cfg.num_hidden_layers, "d_below", shape)
-                die = (torch.empty((B, S, self.cfg.embedding_size), dtype=torch.float32, device=self.device)
-                       if want_d_inputs_embeds else None)
-                _lib.check(self.L.plb_encode_bwd_masked(self.handle, None if ids is None else ids.data_ptr(),
-                                                        None if ein is None else C.byref(ein), km.data_ptr(), *args[2:],
-                                                        None if arr is None else C.addressof(arr),
-                                                        None if die is None else die.data_ptr(), self._stream()),
-                           "plb_encode_bwd_masked")
-                del keep_in
-                return die
-            if ein is not None or want_d_inputs_embeds:
-                arr = None if below is None else self._ptr_array(below, self.cfg.num_hidden_layers, "d_below", shape)
-                die = (torch.empty((B, S, self.cfg.embedding_size), dtype=torch.float32, device=self.device)
-                       if want_d_inputs_embeds else None)
-                _lib.check(self.L.plb_encode_bwd_inputs(self.handle, None if ids is None else ids.data_ptr(),
-                                                        None if ein is None else C.byref(ein), *args[2:],
-                                                        None if arr is None else C.addressof(arr),
-                                                        None if die is None else die.data_ptr(), self._stream()),
-                           "plb_encode_bwd_inputs")
-                del keep_in
-                return die
-            if below is None:
-                _lib.check(self.L.plb_encode_bwd(*args, self._stream()), "plb_encode_bwd")
-            else:
-                arr = self._ptr_array(below, self.cfg.num_hidden_layers, "d_below", shape)
-                _lib.check(self.L.plb_encode_bwd_layers(*args, None if arr is None else C.addressof(arr), self._stream()),
-                           "plb_encode_bwd_layers")
+            arr = None if below is None else self._ptr_array(below, self.cfg.num_hidden_layers, "d_below", shape)
+            die = (torch.empty((B, S, self.cfg.embedding_size), dtype=torch.float32, device=self.device)
+                   if want_d_inputs_embeds else None)
+            self._entry(encoder_entry("encode_bwd", None, ein is not None, km is not None, below, want_d_inputs_embeds),
+                        dict(ids=ids, inputs=ein, key_mask=km, lengths=lens, B=B, S=S, packing=pk, d_hidden=d, d_below=arr,
+                             d_inputs_embeds=die))
+            del keep_in
+        return die
 
     def pooler(self, hidden):
         """tanh(pooler(hidden[:, 0])) (modeling_albert.py:403), fp32 [B,H]; ``hidden`` fp32 [B,S,H] on the device."""
@@ -770,40 +768,12 @@ class HipEngine:
             tok = self._dev_i64(token_ids)
             if tok.shape != masked_ids.shape:
                 raise ValueError("token_ids must have the shape of the phoneme batch")
-        p = lambda t: None if t is None else t.data_ptr()
-        flat_p = flat.data_ptr() if n_masked else None
         with torch.cuda.device(self.device):
             pk = self._packing(packing, B, S)
-            if pk is not None and not backward:
-                _lib.check(self.L.plb_loss_fwd_packed(self.handle, masked_ids.data_ptr(), labels.data_ptr(), p(tok), p(lens),
-                                                      offs.data_ptr(), flat_p, int(n_masked), B, S, C.byref(pk),
-                                                      self._loss.data_ptr(),
-                                                      self._loss_parts.data_ptr() if tok is not None else None,
-                                                      self._stream()), "plb_loss_fwd_packed")
-            elif pk is not None and tok is not None:
-                _lib.check(self.L.plb_loss_fwd_bwd_dual_packed(self.handle, masked_ids.data_ptr(), labels.data_ptr(),
-                                                               tok.data_ptr(), p(lens), offs.data_ptr(), flat_p, int(n_masked),
-                                                               B, S, C.byref(pk), self._loss.data_ptr(),
-                                                               self._loss_parts.data_ptr(), self._stream()),
-                           "plb_loss_fwd_bwd_dual_packed")
-            elif pk is not None:
-                _lib.check(self.L.plb_loss_fwd_bwd_packed(self.handle, masked_ids.data_ptr(), labels.data_ptr(), p(lens),
-                                                          offs.data_ptr(), flat_p, int(n_masked), B, S, C.byref(pk),
-                                                          self._loss.data_ptr(), self._stream()), "plb_loss_fwd_bwd_packed")
-            elif not backward:
-                _lib.check(self.L.plb_loss_fwd(self.handle, masked_ids.data_ptr(), labels.data_ptr(), p(tok), p(lens),
-                                               offs.data_ptr(), flat_p, int(n_masked), B, S, self._loss.data_ptr(),
-                                               self._loss_parts.data_ptr() if tok is not None else None, self._stream()),
-                           "plb_loss_fwd")
-            elif tok is not None:
-                _lib.check(self.L.plb_loss_fwd_bwd_dual(self.handle, masked_ids.data_ptr(), labels.data_ptr(), tok.data_ptr(),
-                                                        p(lens), offs.data_ptr(), flat_p, int(n_masked), B, S,
-                                                        self._loss.data_ptr(), self._loss_parts.data_ptr(), self._stream()),
-                           "plb_loss_fwd_bwd_dual")
-            else:
-                _lib.check(self.L.plb_loss_fwd_bwd(self.handle, masked_ids.data_ptr(), labels.data_ptr(), p(lens),
-                                                   offs.data_ptr(), flat_p, int(n_masked), B, S, self._loss.data_ptr(),
-                                                   self._stream()), "plb_loss_fwd_bwd")
+            self._entry(loss_entry(backward, tok is not None, pk is not None),
+                        dict(masked_ids=masked_ids, labels=labels, token_ids=tok, lengths=lens, idx_offsets=offs,
+                             idx_flat=flat if n_masked else None, n_masked=int(n_masked), B=B, S=S, packing=pk, loss=self._loss,
+                             loss_parts=self._loss_parts if tok is not None else None))
         self._last_loss_call = (int(B), int(n_masked), tok is not None)
         self._last_encoder_call = (int(B), int(S), lens, packing)   # (token_report: the tensors that call was given)
         return self._loss

@@ -129,64 +129,27 @@ def _lengths_and_key_mask(attention_mask):
     return extent, (None if prefix else attention_mask)
 
 
-def _encode_backward(ctx, d_hidden, d_below, want_d_inputs_embeds=None, without=()):
-    """The backward of a differentiable forward (``ctx``: engine, names, serial): plb_encode_bwd[_layers], then every encoder
-    Parameter's view of its slice of ``engine.grads`` (None for the pooler, the heads and the names in ``without``).
-    ``want_d_inputs_embeds`` True / False (a forward with embedding inputs: plb_encode_bwd_inputs): the result is then
-    ``(gradient of the pre-LayerNorm embedding sum | None, parameter gradients)``."""
-    eng = ctx.engine
-    gone = "a later engine call overwrote the activations of this forward (the engine keeps one differentiable " \
-           "forward at a time: call backward() before the next forward, loss call or optimizer step)"
-    if eng._live_encode is None or eng._encode_serial != ctx.serial:
-        raise RuntimeError(gone)
-    try:
-        if want_d_inputs_embeds is not None:
-            die = eng.encode_bwd(d_hidden, d_below=d_below, want_d_inputs_embeds=want_d_inputs_embeds)
-        elif d_below is None:
-            eng.encode_bwd(d_hidden)
-        else:
-            eng.encode_bwd(d_hidden, d_below=d_below)
-    except RuntimeError as ex:
-        if "no live plb_encode stash" in str(ex):
-            raise RuntimeError(f"{gone}: {ex}") from ex
-        raise
-    end = eng.layout["phoneme_predictor.weight"][0]   # the encoder range of the flat buffers
-    grads = []
-    for n in ctx.names:
-        off, size, shp = eng.layout[n]
-        grads.append(eng.grads[off:off + size].view(shp) if off + size <= end and n not in without else None)
-    return tuple(grads) if want_d_inputs_embeds is None else (die, tuple(grads))
-
-
 class _Encode(torch.autograd.Function):
-    """The differentiable forward as one autograd node: forward = plb_encode, backward = plb_encode_bwd on the upstream
-    gradient; every encoder Parameter receives the view of its slice of ``engine.grads`` (the scheme of train._FusedLoss),
-    the pooler and the heads receive None. The engine keeps ONE forward's activations: the backward of a forward that a
-    later engine call has overwritten raises."""
+    """The differentiable forward as ONE autograd node, whatever the call carries: HipEngine.encode / encode_bwd choose the
+    entry points (plb_encode / plb_encode_bwd for the plain call, the _layers / _inputs / _masked rungs for the rest). The
+    engine keeps ONE forward's activations: the backward of a forward that a later engine call has overwritten raises.
+    Outputs: the L + 1 hidden states (``want_hs``; else the last hidden state alone), then the L attention maps (``want_at``),
+    which are marked non-differentiable. The backward hands the gradient of the last slot to the engine as d_hidden and those
+    of the slots below as d_below; a slot nothing downstream used arrives as None and goes in as a NULL pointer. Every encoder
+    Parameter receives the view of its slice of ``engine.grads`` (the scheme of train._FusedLoss), the pooler and the heads
+    receive None. ``inputs_embeds`` (or None) is an input of the node: when it requires grad it receives the gradient of the
+    pre-LayerNorm embedding sum, and the word table — which took no part — receives None, as in torch. ``key_mask`` (or
+    None): a mask that is no prefix (the engine's live record hands it to the backward)."""
 
     @staticmethod
-    def forward(ctx, engine, names, ids, lengths, packing, *params):
-        hid = engine.encode(ids, lengths, packing)
-        ctx.engine, ctx.names, ctx.serial = engine, names, engine._encode_serial
-        return hid
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        return (None,) * 5 + _encode_backward(ctx, grad.contiguous().float(), None)
-
-
-class _EncodeLayers(torch.autograd.Function):
-    """The differentiable forward with per-application outputs as ONE autograd node (plb_encode_layers /
-    plb_encode_bwd_layers). Outputs: the L + 1 hidden states (``want_hs``; else the last hidden state alone), then the L
-    attention maps (``want_at``), which are marked non-differentiable. The backward hands the gradient of the last slot to
-    the engine as d_hidden and those of the slots below as d_below; a slot nothing downstream used arrives as None and
-    goes in as a NULL pointer. Parameter gradients as in _Encode."""
-
-    @staticmethod
-    def forward(ctx, engine, names, ids, lengths, packing, want_hs, want_at, *params):
-        hid, hs, at = engine.encode(ids, lengths, packing, layers=dict(hidden_states=want_hs, attentions=want_at))
+    def forward(ctx, engine, names, ids, lengths, packing, want_hs, want_at, token_type_ids, position_ids, inputs_embeds,
+                key_mask, *params):
+        layers = dict(hidden_states=want_hs, attentions=want_at) if want_hs or want_at else None
+        out = engine.encode(ids, lengths, packing, layers=layers, token_type_ids=token_type_ids, position_ids=position_ids,
+                            inputs_embeds=inputs_embeds, key_mask=key_mask)
+        hid, hs, at = (out, None, None) if layers is None else out
         ctx.engine, ctx.names, ctx.serial, ctx.want_hs = engine, names, engine._encode_serial, want_hs
+        ctx.embeds = inputs_embeds is not None
         ctx.set_materialize_grads(False)
         if want_at:
             ctx.mark_non_differentiable(*at)
@@ -198,38 +161,24 @@ class _EncodeLayers(torch.autograd.Function):
         eng = ctx.engine
         nl = eng.cfg.num_hidden_layers
         g = [None if x is None else x.contiguous().float() for x in grads[:nl + 1 if ctx.want_hs else 1]]
-        return (None,) * 7 + _encode_backward(ctx, g[-1], g[:-1] if ctx.want_hs else None)
-
-
-class _EncodeInputs(torch.autograd.Function):
-    """_EncodeLayers with the embedding inputs of transformers' AlbertModel (plb_encode_inputs / plb_encode_bwd_inputs).
-    ``inputs_embeds`` (or None) is an input of the node: when it requires grad it receives the gradient of the pre-LayerNorm
-    embedding sum, and the word table — which took no part — receives None, as in torch. The token-type and position tables
-    receive their views of the gradient buffer like every other encoder Parameter. ``key_mask`` (or None): a mask that is
-    no prefix (plb_encode_masked / plb_encode_bwd_masked; the engine's live record hands it to the backward)."""
-
-    @staticmethod
-    def forward(ctx, engine, names, ids, lengths, packing, want_hs, want_at, token_type_ids, position_ids, inputs_embeds,
-                key_mask, *params):
-        hid, hs, at = engine.encode(ids, lengths, packing, layers=dict(hidden_states=want_hs, attentions=want_at),
-                                    token_type_ids=token_type_ids, position_ids=position_ids, inputs_embeds=inputs_embeds,
-                                    key_mask=key_mask)
-        ctx.engine, ctx.names, ctx.serial, ctx.want_hs = engine, names, engine._encode_serial, want_hs
-        ctx.embeds = inputs_embeds is not None
-        ctx.set_materialize_grads(False)
-        if want_at:
-            ctx.mark_non_differentiable(*at)
-        return (*(hs if want_hs else [hid]), *(at if want_at else []))
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grads):
-        nl = ctx.engine.cfg.num_hidden_layers
-        g = [None if x is None else x.contiguous().float() for x in grads[:nl + 1 if ctx.want_hs else 1]]
-        die, pg = _encode_backward(ctx, g[-1], g[:-1] if ctx.want_hs else None,
-                                   want_d_inputs_embeds=ctx.embeds and ctx.needs_input_grad[9],
-                                   without=("encoder.embeddings.word_embeddings.weight",) if ctx.embeds else ())
-        return (None,) * 9 + (die, None) + pg
+        gone = "a later engine call overwrote the activations of this forward (the engine keeps one differentiable " \
+               "forward at a time: call backward() before the next forward, loss call or optimizer step)"
+        if eng._live_encode is None or eng._encode_serial != ctx.serial:
+            raise RuntimeError(gone)
+        try:
+            die = eng.encode_bwd(g[-1], d_below=g[:-1] if ctx.want_hs else None,
+                                 want_d_inputs_embeds=ctx.embeds and ctx.needs_input_grad[9])
+        except RuntimeError as ex:
+            if "no live plb_encode stash" in str(ex):
+                raise RuntimeError(f"{gone}: {ex}") from ex
+            raise
+        end = eng.layout["phoneme_predictor.weight"][0]   # the encoder range of the flat buffers
+        without = ("encoder.embeddings.word_embeddings.weight",) if ctx.embeds else ()
+        pg = []
+        for n in ctx.names:
+            off, size, shp = eng.layout[n]
+            pg.append(eng.grads[off:off + size].view(shp) if off + size <= end and n not in without else None)
+        return (None,) * 9 + (die, None) + tuple(pg)
 
 
 class AlbertModel(nn.Module):
@@ -317,10 +266,10 @@ class AlbertModel(nn.Module):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
         lengths, key_mask = _lengths_and_key_mask(attention_mask)
         want_hs, want_at = bool(output_hidden_states), bool(output_attentions)
-        nl = self.config.num_hidden_layers
-        if token_type_ids is not None or position_ids is not None or inputs_embeds is not None or key_mask is not None:
-            return self._forward_inputs(input_ids, lengths, token_type_ids, position_ids, inputs_embeds, want_hs, want_at,
-                                        key_mask)
+        nl, eng = self.config.num_hidden_layers, self._engine
+        given = {k: v for k, v in dict(token_type_ids=token_type_ids, position_ids=position_ids, inputs_embeds=inputs_embeds,
+                                       key_mask=key_mask).items() if v is not None}
+        packing = _packing_from_lengths(self, lengths, input_ids if input_ids is not None else inputs_embeds)
         if getattr(self, "differentiable", False) and self.training and torch.is_grad_enabled():
             # fine-tuning: the forward joins the autograd graph (_Encode); pad positions of last_hidden_state are zeros and
             # pooler_output is DETACHED (the pooler receives no gradient, as in every other call of this library)
@@ -328,55 +277,25 @@ class AlbertModel(nn.Module):
             for n, p in self.named_parameters():
                 names.append("encoder." + n)
                 params.append(p)
-            if want_hs or want_at:
-                outs = _EncodeLayers.apply(self._engine, names, input_ids, lengths,
-                                           _packing_from_lengths(self, lengths, input_ids), want_hs, want_at, *params)
-                hs = tuple(outs[:nl + 1]) if want_hs else None
-                hid = hs[-1] if want_hs else outs[0]
-                return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid.detach()),
-                                                  hidden_states=hs, attentions=tuple(outs[-nl:]) if want_at else None)
-            hid = _Encode.apply(self._engine, names, input_ids, lengths, _packing_from_lengths(self, lengths, input_ids),
-                                *params)
-            return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid.detach()))
-        if want_hs or want_at:
-            hs, at, hid = self._engine.forward_layers(input_ids, lengths, _packing_from_lengths(self, lengths, input_ids),
-                                                      hidden_states=want_hs, attentions=want_at, want_hidden=True)
+            outs = _Encode.apply(eng, names, input_ids, lengths, packing, want_hs, want_at, token_type_ids, position_ids,
+                                 inputs_embeds, key_mask, *params)
+            hs = tuple(outs[:nl + 1]) if want_hs else None
+            at = tuple(outs[-nl:]) if want_at else None
+            hid = hs[-1] if want_hs else outs[0]
+        elif want_hs or want_at or given:
+            # (the engine checks shapes and index ranges of the embedding inputs; ``lengths`` of a mask that is no prefix are
+            # its extents)
+            hs, at, hid = eng.forward_layers(input_ids, lengths, packing, hidden_states=want_hs, attentions=want_at,
+                                             want_hidden=True, **given)
             if want_hs:
                 hid = hs[-1]   # (the same tensor object, as in transformers; unlike `hidden`, zeros at pad positions)
-            return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid),
-                                              hidden_states=tuple(hs) if want_hs else None,
-                                              attentions=tuple(at) if want_at else None)
-        hid, _, _ = self._engine.forward(input_ids, lengths, want_hidden=True, want_phoneme=False,
-                                         packing=_packing_from_lengths(self, lengths, input_ids))
-        # pooler (modeling_albert.py:403): computed for API completeness (plb_pooler), never used by the loss
-        return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid))
-
-    def _forward_inputs(self, input_ids, lengths, token_type_ids, position_ids, inputs_embeds, want_hs, want_at, key_mask=None):
-        """AlbertModel.forward with any of the embedding inputs or a mask that is no prefix (``key_mask``; ``lengths`` = its
-        extents): HipEngine.forward_layers / encode with them (the engine checks shapes and index ranges), outputs as in the
-        plain call. ``pooler_output`` is the pooler of position 0, hole or not, as in transformers."""
-        nl = self.config.num_hidden_layers
-        shaped = input_ids if input_ids is not None else inputs_embeds
-        packing = _packing_from_lengths(self, lengths, shaped)
-        if getattr(self, "differentiable", False) and self.training and torch.is_grad_enabled():
-            names, params = [], []
-            for n, p in self.named_parameters():
-                names.append("encoder." + n)
-                params.append(p)
-            outs = _EncodeInputs.apply(self._engine, names, input_ids, lengths, packing, want_hs, want_at, token_type_ids,
-                                       position_ids, inputs_embeds, key_mask, *params)
-            hs = tuple(outs[:nl + 1]) if want_hs else None
-            hid = hs[-1] if want_hs else outs[0]
-            return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid.detach()),
-                                              hidden_states=hs, attentions=tuple(outs[-nl:]) if want_at else None)
-        hs, at, hid = self._engine.forward_layers(input_ids, lengths, packing, hidden_states=want_hs, attentions=want_at,
-                                                  want_hidden=True, token_type_ids=token_type_ids, position_ids=position_ids,
-                                                  inputs_embeds=inputs_embeds, key_mask=key_mask)
-        if want_hs:
-            hid = hs[-1]
-        return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=self._engine.pooler(hid),
-                                          hidden_states=tuple(hs) if want_hs else None,
-                                          attentions=tuple(at) if want_at else None)
+            hs, at = tuple(hs) if want_hs else None, tuple(at) if want_at else None
+        else:
+            (hid, _, _), hs, at = eng.forward(input_ids, lengths, want_hidden=True, want_phoneme=False, packing=packing), None, None
+        # pooler (modeling_albert.py:403): computed for API completeness (plb_pooler), never used by the loss; the pooler of
+        # position 0, hole or not, as in transformers
+        return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=eng.pooler(hid.detach()), hidden_states=hs,
+                                          attentions=at)
 
 
 class _HeadModel(nn.Module):
