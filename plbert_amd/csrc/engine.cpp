@@ -9,9 +9,10 @@
 // reference's autograd into ONE token-major GEMM per weight with reduction length L*Tp, which is
 // split over the grid into fp32 slabs and reduced in fixed order (deterministic, no atomics).
 //
-// This unit: the parameter layout, the workspace carve (plb_create / plb_bind), the weight copies (plb_sync_weights,
-// plb_adamw_step) and the entry points that are one launch. Only writer of PlbEngine's layout and capacity block, the
-// workspace offsets, the bound buffers, the side stream and its events, tok_pad_zeroed and (with plb_status) tok_steps.
+// This unit: the parameter layout, the workspace carve (plb_create / plb_bind), the weight copies (plb_sync_weights;
+// sync_transposes also ends every update of engine_optim.cpp) and the entry points that are one launch. Only writer of
+// PlbEngine's layout and capacity block, the workspace offsets, the bound buffers, the side stream and its events and
+// tok_pad_zeroed; tok_steps is written here (plb_set_token_head_steps), by plb_status and by the updates of engine_optim.cpp.
 // The other units: engine_prof.cpp, engine_comm.cpp, engine_fp8.cpp, engine_layers.cpp, engine_calls.cpp, engine_eval.cpp,
 // engine_optim.cpp.
 #include <stdarg.h>
@@ -463,35 +464,4 @@ extern "C" int plb_mask_batch(const int64_t* labels, const int32_t* lengths, int
   m.masked = masked; m.counts = scratch; m.idx_padded = scratch + B; m.offsets = idx_offsets; m.flat = idx_flat;
   TRY(plb_launch_mask(&m, (hipStream_t)stream));
   return 0;
-}
-
-extern "C" int plb_adamw_step(PlbEngine* e, double lr, double beta1, double beta2, double eps, double weight_decay,
-                              int32_t step, double grad_scale, void* stream) {
-  if (!e || !e->ws || !e->grads || !e->m || !e->v) return fail("plb_adamw_step: optimizer buffers not bound");
-  if (e->infer) return fail("plb_adamw_step: inference-only engine");
-  if (step < 1) return fail("plb_adamw_step: step counts from 1");
-  drop_stash(e, "plb_adamw_step moved the weights since");
-  drop_final(e, "plb_adamw_step moved the weights since: ask between the loss call and the optimizer step");
-  end_accum_window(e, "plb_adamw_step moved the weights");
-  hipStream_t s = (hipStream_t)stream;
-  if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
-    HIPTRY(ev_wait(e, s, e->ev_comm_done));
-    e->comm_pending = false;
-  }
-  HB_R(s, e->grads, e->ptotal * 4, "AdamW (reads the gradient buffer)");
-  // after plb_encode_bwd the phoneme head has no gradient: no update, as torch skips a parameter whose .grad is None
-  // (parameters, both moments and the bf16 copy of the head stay as they are; the rule of the token head and the pooler)
-  const int64_t nstep = e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W];
-  TRY(plb_launch_adamw(e->params, e->grads, e->m, e->v, e->at<bf16_t>(e->o_wbf), (size_t)nstep, lr, beta1, beta2, eps,
-                       weight_decay, step, grad_scale, e->at<unsigned int>(e->o_lnerr), 1, s));
-  if (e->tok_grads_live) {
-    // token head: trained only by dual-head steps (no gradient, no update — as the pooler), with its OWN step count:
-    // torch.optim.AdamW keeps one per parameter, so a head that starts training late gets its own bias correction
-    const int64_t o = e->poff[PLB_TOK_W];
-    e->tok_steps += 1;
-    TRY(plb_launch_adamw(e->params + o, e->grads + o, e->m + o, e->v + o, e->at<bf16_t>(e->o_wbf) + o,
-                         (size_t)(e->ptotal - o), lr, beta1, beta2, eps, weight_decay, e->tok_steps, grad_scale,
-                         e->at<unsigned int>(e->o_lnerr), 2, s));
-  }
-  return sync_transposes(e, s, false);   // fp8 copies: delayed scaling from here on (the weights moved by one AdamW step)
 }

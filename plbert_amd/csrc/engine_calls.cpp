@@ -183,10 +183,9 @@ static int begin_training_call(PlbEngine* e, bool dual, hipStream_t s) {
   // All-reduce pieces of a PREVIOUS backward that nobody joined (two plb_loss_fwd_bwd calls with no plb_allreduce_grads /
   // plb_adamw_step between them: gradient probing, a caller that skips a step on a bad loss) still read and write the
   // gradient buffer on the communication stream: this call's kernels must not touch it before they have finished.
-  if (e->comm && e->comm_pending) HIPTRY(ev_wait(e, s, e->ev_comm_done));
+  if (join_comm(e, s)) return 1;
   e->tok_grads_live = dual;
   e->head_grads_live = true;
-  e->comm_pending = false;
   e->grads_reduced = false;
   e->grads_fresh = true;   // (plb_grad_accum_add: these gradients have not been added yet; partials of older ones are void)
   e->norm_nparts = 0;

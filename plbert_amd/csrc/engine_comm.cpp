@@ -132,6 +132,14 @@ int reduce_piece(PlbEngine* e, int64_t a, int64_t b, hipStream_t after) {
   return 0;
 }
 bool overlapping(const PlbEngine* e) { return e->comm && e->overlap; }
+// All-reduce pieces still in flight on the communication stream read and write the gradient buffer: `s` waits for them.
+// (comm_pending implies a communicator: only reduce_piece sets it, behind its own e->comm test, and plb_comm_destroy clears it)
+int join_comm(PlbEngine* e, hipStream_t s) {
+  if (!e->comm_pending) return 0;
+  HIPTRY(ev_wait(e, s, e->ev_comm_done));
+  e->comm_pending = false;
+  return 0;
+}
 // Close the pieces issued so far: later joins wait on ev_comm_done.
 int pieces_done(PlbEngine* e) {
   if (e->hb.on && e->hb.violations)
@@ -389,11 +397,7 @@ extern "C" int plb_allreduce_grads(PlbEngine* e, void* stream) {
   if (!e->comm) return 0;
   if (!e->grads) return fail("plb_allreduce_grads: no gradient buffer bound");
   hipStream_t s = (hipStream_t)stream;
-  if (e->comm_pending) {  // the loss call issued the pieces: join them
-    HIPTRY(ev_wait(e, s, e->ev_comm_done));
-    e->comm_pending = false;
-    return 0;
-  }
+  if (e->comm_pending) return join_comm(e, s);   // the loss call issued the pieces: join them
   if (e->grads_reduced) return 0;
   HB_W(s, e->grads, e->ptotal * 4, "in-stream all-reduce of the gradient buffer");
   int rc = g_rccl.AllReduce(e->grads, e->grads, (size_t)e->ptrain, kNcclFloat32, kNcclSum, e->comm, s);

@@ -132,7 +132,7 @@ struct PlbEngine {
   bool u_is_derivative = false; // what the "u" slots hold after the last forward
   bool tn8_call = false;        // ... decided per training call by its forward (shapes), read by its backward
   int part_rows_used = 0;       // rows per layer the last backward wrote
-  // ---- what a call leaves for the next one: engine_calls.cpp (tok_steps, tok_pad_zeroed: engine.cpp) ----
+  // ---- what a call leaves for the next one: engine_calls.cpp (tok_pad_zeroed: engine.cpp; tok_steps: engine_optim.cpp) ----
   // Last application on the masked rows only (a phoneme-only loss call: nothing but the masked positions' final hidden
   // states reaches the loss, so behind the attention of application L-1 only those rows are computed): decided by the
   // forward of a call, read by its backward. pruned_rows = the compact row count (a multiple of 128), 0 = the call was full.
@@ -188,7 +188,7 @@ struct PlbEngine {
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_piece = nullptr, ev_comm_done = nullptr;
   bool overlap = true;          // issue the all-reduce piecewise inside plb_loss_fwd_bwd
-  bool comm_pending = false;    // pieces were issued: plb_allreduce_grads / plb_adamw_step must join ev_comm_done
+  bool comm_pending = false;    // pieces were issued: whoever touches the gradient buffer next joins ev_comm_done (join_comm)
   bool grads_reduced = false;   // the gradients of the last loss call have been all-reduced
   int64_t piece_floats = 0;     // floats submitted as pieces by the current loss call (must add up to the gradient range)
   int32_t piece_count = 0;      // collectives the last step issued (pieces by the loss call + in-stream all-reduces)
@@ -329,6 +329,7 @@ hipError_t ev_record(PlbEngine* e, hipEvent_t ev, hipStream_t s);
 hipError_t ev_wait(PlbEngine* e, hipStream_t s, hipEvent_t ev);
 int reduce_piece(PlbEngine* e, int64_t a, int64_t b, hipStream_t after);
 bool overlapping(const PlbEngine* e);
+int join_comm(PlbEngine* e, hipStream_t s);
 int pieces_done(PlbEngine* e);
 int64_t piece_begin(const PlbEngine* e, int i);
 int64_t piece_end(const PlbEngine* e, int i);

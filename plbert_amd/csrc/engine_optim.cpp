@@ -1,9 +1,11 @@
-// Gradient accumulation, the global gradient norm, the clipped AdamW update and the grouped forms of norm and update
-// (include/plbert.h: plb_grad_accum_*, plb_grad_norm, plb_adamw_step_clipped; plb_adamw_plan, plb_adamw_step_groups,
-// plb_grad_norm_groups) and LAMB (plb_lamb_plan, plb_lamb_step). Host bookkeeping of a window of micro-steps plus launches of
+// The optimizer path: gradient accumulation, the global gradient norm and every update entry point (include/plbert.h:
+// plb_grad_accum_*, plb_grad_norm, plb_grad_norm_groups; plb_adamw_step, plb_adamw_step_clipped, plb_adamw_plan,
+// plb_adamw_step_groups; plb_lamb_plan, plb_lamb_step). Host bookkeeping of a window of micro-steps plus launches of
 // optim.hip and lamb.hip; no workspace of its own: the accumulator, the norm buffer and the LAMB buffer are the caller's.
 // Only writer of PlbEngine's accumulation block (grads_fresh / norm_nparts are also reset by begin_training_call,
 // engine_calls.cpp); after a LAST add it sets head_grads_live, tok_grads_live and grads_reduced to what the window accumulated.
+// The four update entries share one preamble (begin_update) and, with the two norm entries, one description of the ranges a
+// step covers (step_ranges); the hyper-parameter refusals are written once (check_groups).
 #include <cmath>
 
 #include "engine_internal.h"
@@ -11,6 +13,86 @@
 void end_accum_window(PlbEngine* e, const char* by) {
   if (e && e->win_open) { e->win_open = false; e->win_closed_by = by; }
 }
+
+namespace {
+// ---- what the update and norm entries share --------------------------------------------------------------------------------
+// The texts an update entry leaves behind. drop_stash, drop_final and end_accum_window keep them by pointer: literals only.
+struct Update { const char *who, *stash, *final_state, *window, *reads; };
+#define UPDATE_ENTRY(fn, label)                                                                                      \
+  {fn, fn " moved the weights since", fn " moved the weights since: ask between the loss call and the optimizer step", \
+   fn " moved the weights", label " (reads the gradient buffer)"}
+
+// The preamble of an update: bound, training engine, the entry's own refusals (`own`: 0 or what fail returned), and only
+// then what changes state: the stash, the final hidden state and an open accumulation window end, the exchange is joined.
+template <class Own>
+int begin_update(PlbEngine* e, const Update& u, hipStream_t s, Own own) {
+  if (!e || !e->ws || !e->grads || !e->m || !e->v) return fail("%s: optimizer buffers not bound", u.who);
+  if (e->infer) return fail("%s: inference-only engine", u.who);
+  if (own()) return 1;
+  drop_stash(e, u.stash);
+  drop_final(e, u.final_state);
+  end_accum_window(e, u.window);
+  if (join_comm(e, s)) return 1;
+  HB_R(s, e->grads, e->ptotal * 4, u.reads);
+  return 0;
+}
+
+// One range of the flat buffers that a step covers with a launch of its own. There are at most two: the trainable range up
+// to the phoneme head (after plb_encode_bwd the head has no gradient: no update, as torch skips a parameter whose .grad is
+// None; parameters, both moments and the bf16 copy of the head stay as they are), and the token head, which only dual-head
+// steps train (no gradient, no update, as the pooler between the two) and which keeps its OWN step count: torch.optim.AdamW
+// keeps one per parameter, so a head that starts training late gets its own bias correction.
+struct StepRange {
+  int64_t a, b;          // [a, b); a is also the offset into params / grads / exp_avg / exp_avg_sq / the bf16 copy
+  int step;              // the range's step count
+  int skip_slot;         // which of the step's launches this is to the skip word
+  int count_nonfinite;   // 1: the launch that counts an update left out for a non-finite norm (once per step)
+  int part;              // where its partial sums of squares go behind the four result floats of a norm buffer
+  bool token;
+  size_t n() const { return (size_t)(b - a); }
+};
+// (tok_grads_live implies NT > 0: a dual-head call on an engine without a token head is refused before it sets the flag, and
+// a LAST add sets it from a window that formed it with NT > 0)
+template <class Launch>
+int step_ranges(PlbEngine* e, int step, Launch launch) {
+  const StepRange enc = {0, e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W], step, 1, 1, 0, false};
+  if (launch(enc)) return 1;
+  if (!e->tok_grads_live || e->NT <= 0) return 0;
+  const StepRange tok = {e->poff[PLB_TOK_W], e->ptotal, e->tok_steps + 1, 2, 0, PLB_NORM_PARTS, true};
+  return launch(tok) ? 1 : 0;
+}
+// An update launch of the token head counts its step: exactly where the launch is made, not where the range is described
+void count_step(PlbEngine* e, const StepRange& r) { if (r.token) e->tok_steps = r.step; }
+
+struct Bufs { float *p, *g, *m, *v; bf16_t* w; unsigned int* skip; };
+Bufs bufs(const PlbEngine* e, const StepRange& r) {
+  return {e->params + r.a, e->grads + r.a, e->m + r.a, e->v + r.a, e->at<bf16_t>(e->o_wbf) + r.a, e->at<unsigned int>(e->o_lnerr)};
+}
+
+// The norm of the ranges plb_adamw_step is about to step: one sum-of-squares launch per range (`sumsq`), each into its own
+// slot of partials, or the partials a LAST add left (have_partials); then the finish launch.
+template <class Sumsq>
+int grad_norm(PlbEngine* e, bool have_partials, double grad_scale, double max_norm, float* norm_buf, hipStream_t s, Sumsq sumsq) {
+  int nparts = e->norm_nparts;
+  if (!have_partials) {
+    if (join_comm(e, s)) return 1;
+    nparts = 0;
+    if (step_ranges(e, 1, [&](const StepRange& r) {
+          HB_R(s, e->grads + r.a, r.n() * 4, r.token ? "gradient norm (reads the token head's gradients)"
+                                                     : "gradient norm (reads the gradient buffer)");
+          HB_W(s, norm_buf + 4 + r.part, PLB_NORM_PARTS * 4, "gradient norm (writes the partial sums)");
+          nparts += PLB_NORM_PARTS;
+          return sumsq(r, norm_buf + 4 + r.part);
+        }))
+      return 1;
+    e->norm_nparts = 0;   // (these partials are not a LAST add's: a later have_partials call must not take them for such)
+  }
+  HB_R(s, norm_buf + 4, (size_t)nparts * 4, "gradient norm (reads the partial sums)");
+  HB_W(s, norm_buf, 16, "gradient norm (writes norm, coefficient and flag)");
+  TRY(plb_launch_grad_norm_finish(norm_buf + 4, nparts, grad_scale, max_norm, norm_buf, s));
+  return 0;
+}
+}  // namespace
 
 extern "C" int64_t plb_grad_norm_floats(const PlbEngine* e) {
   // 4 result floats + one set of partials per range a launch can cover on its own: encoder, phoneme head, token head
@@ -46,10 +128,7 @@ extern "C" int plb_grad_accum_add(PlbEngine* e, int32_t phase, float* norm_buf, 
     return fail("plb_grad_accum_add: this micro-step's gradients are %s, the window's are %s", e->grads_reduced ? "all-reduced" : "local",
                 e->win_reduced ? "all-reduced" : "local");
   hipStream_t s = (hipStream_t)stream;
-  if (e->comm_pending) {  // this micro-step's all-reduce pieces are still in flight on the communication stream
-    HIPTRY(ev_wait(e, s, e->ev_comm_done));
-    e->comm_pending = false;
-  }
+  if (join_comm(e, s)) return 1;   // this micro-step's all-reduce pieces
   // What this micro-step produced | what the window holds so far. The encoder range is always both.
   const bool head = e->head_grads_live, tok = e->tok_grads_live && e->NT > 0;
   const bool uhead = phase == 0 ? false : e->win_head, utok = phase == 0 ? false : e->win_tok;
@@ -115,61 +194,48 @@ extern "C" int plb_grad_norm(PlbEngine* e, double grad_scale, double max_norm, f
   }
   if (!e->ws || !e->grads) return fail("plb_grad_norm: gradient buffer not bound");
   hipStream_t s = (hipStream_t)stream;
-  int nparts = e->norm_nparts;
-  if (!have_partials) {
-    if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
-      HIPTRY(ev_wait(e, s, e->ev_comm_done));
-      e->comm_pending = false;
-    }
-    // the ranges plb_adamw_step is about to step
-    const int64_t nstep = e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W];
-    HB_R(s, e->grads, nstep * 4, "gradient norm (reads the gradient buffer)");
-    HB_W(s, norm_buf + 4, PLB_NORM_PARTS * 4, "gradient norm (writes the partial sums)");
-    TRY(plb_launch_grad_sumsq(e->grads, (size_t)nstep, norm_buf + 4, s));
-    nparts = PLB_NORM_PARTS;
-    if (e->tok_grads_live && e->NT > 0) {
-      const int64_t o = e->poff[PLB_TOK_W];
-      HB_R(s, e->grads + o, (e->ptotal - o) * 4, "gradient norm (reads the token head's gradients)");
-      HB_W(s, norm_buf + 4 + nparts, PLB_NORM_PARTS * 4, "gradient norm (writes the partial sums)");
-      TRY(plb_launch_grad_sumsq(e->grads + o, (size_t)(e->ptotal - o), norm_buf + 4 + nparts, s));
-      nparts += PLB_NORM_PARTS;
-    }
-    e->norm_nparts = 0;   // (these partials are not a LAST add's: a later have_partials call must not take them for such)
-  }
-  HB_R(s, norm_buf + 4, (size_t)nparts * 4, "gradient norm (reads the partial sums)");
-  HB_W(s, norm_buf, 16, "gradient norm (writes norm, coefficient and flag)");
-  TRY(plb_launch_grad_norm_finish(norm_buf + 4, nparts, grad_scale, max_norm, norm_buf, s));
-  return 0;
+  return grad_norm(e, have_partials != 0, grad_scale, max_norm, norm_buf, s, [&](const StepRange& r, float* partials) {
+    TRY(plb_launch_grad_sumsq(e->grads + r.a, r.n(), partials, s));
+    return 0;
+  });
+}
+
+// ---- the plain and the clipped update (include/plbert.h: plb_adamw_step, plb_adamw_step_clipped) ---------------------------
+extern "C" int plb_adamw_step(PlbEngine* e, double lr, double beta1, double beta2, double eps, double weight_decay,
+                              int32_t step, double grad_scale, void* stream) {
+  static const Update u = UPDATE_ENTRY("plb_adamw_step", "AdamW");
+  hipStream_t s = (hipStream_t)stream;
+  if (begin_update(e, u, s, [&] { return step < 1 ? fail("plb_adamw_step: step counts from 1") : 0; })) return 1;
+  if (step_ranges(e, step, [&](const StepRange& r) {
+        const Bufs x = bufs(e, r);
+        count_step(e, r);
+        TRY(plb_launch_adamw(x.p, x.g, x.m, x.v, x.w, r.n(), lr, beta1, beta2, eps, weight_decay, r.step, grad_scale, x.skip,
+                             r.skip_slot, s));
+        return 0;
+      }))
+    return 1;
+  return sync_transposes(e, s, false);   // fp8 copies: delayed scaling from here on (the weights moved by one AdamW step)
 }
 
 extern "C" int plb_adamw_step_clipped(PlbEngine* e, double lr, double beta1, double beta2, double eps, double weight_decay,
                                       int32_t step, double grad_scale, const float* norm_buf, void* stream) {
-  if (!e || !e->ws || !e->grads || !e->m || !e->v) return fail("plb_adamw_step_clipped: optimizer buffers not bound");
-  if (e->infer) return fail("plb_adamw_step_clipped: inference-only engine");
-  if (step < 1) return fail("plb_adamw_step_clipped: step counts from 1");
-  if (!norm_buf) return fail("plb_adamw_step_clipped: norm_buf is null (plb_grad_norm writes it)");
-  drop_stash(e, "plb_adamw_step_clipped moved the weights since");
-  drop_final(e, "plb_adamw_step_clipped moved the weights since: ask between the loss call and the optimizer step");
-  end_accum_window(e, "plb_adamw_step_clipped moved the weights");
+  static const Update u = UPDATE_ENTRY("plb_adamw_step_clipped", "clipped AdamW");
   hipStream_t s = (hipStream_t)stream;
-  if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
-    HIPTRY(ev_wait(e, s, e->ev_comm_done));
-    e->comm_pending = false;
-  }
+  if (begin_update(e, u, s, [&] {
+        if (step < 1) return fail("plb_adamw_step_clipped: step counts from 1");
+        return norm_buf ? 0 : fail("plb_adamw_step_clipped: norm_buf is null (plb_grad_norm writes it)");
+      }))
+    return 1;
   float* norm = const_cast<float*>(norm_buf);   // (the launch counts the updates it leaves out in norm[3])
-  HB_R(s, e->grads, e->ptotal * 4, "clipped AdamW (reads the gradient buffer)");
   HB_W(s, norm, 16, "clipped AdamW (reads the coefficient, counts a left-out update)");
-  // the ranges, the step counts and the skip word are plb_adamw_step's
-  const int64_t nstep = e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W];
-  TRY(plb_launch_adamw_clipped(e->params, e->grads, e->m, e->v, e->at<bf16_t>(e->o_wbf), (size_t)nstep, lr, beta1, beta2,
-                               eps, weight_decay, step, grad_scale, e->at<unsigned int>(e->o_lnerr), 1, norm, 1, s));
-  if (e->tok_grads_live) {
-    const int64_t o = e->poff[PLB_TOK_W];
-    e->tok_steps += 1;
-    TRY(plb_launch_adamw_clipped(e->params + o, e->grads + o, e->m + o, e->v + o, e->at<bf16_t>(e->o_wbf) + o,
-                                 (size_t)(e->ptotal - o), lr, beta1, beta2, eps, weight_decay, e->tok_steps, grad_scale,
-                                 e->at<unsigned int>(e->o_lnerr), 2, norm, 0, s));
-  }
+  if (step_ranges(e, step, [&](const StepRange& r) {
+        const Bufs x = bufs(e, r);
+        count_step(e, r);
+        TRY(plb_launch_adamw_clipped(x.p, x.g, x.m, x.v, x.w, r.n(), lr, beta1, beta2, eps, weight_decay, r.step, grad_scale,
+                                     x.skip, r.skip_slot, norm, r.count_nonfinite, s));
+        return 0;
+      }))
+    return 1;
   return sync_transposes(e, s, false);
 }
 
@@ -232,22 +298,30 @@ int plan_segments(const PlbEngine* e, const PlbAdamWGroup* groups, const int32_t
   return n;
 }
 
-int check_groups(const PlbAdamWGroup* groups, int32_t n_groups, int32_t step, const char* who) {
+// The hyper-parameter refusals of both group types; LAMB's adapt is checked on top, group by group
+int check_adapt(const PlbAdamWGroup&, int, const char*) { return 0; }
+int check_adapt(const PlbLambGroup& g, int k, const char* who) {
+  return g.adapt != 0 && g.adapt != 1 ? fail("%s: group %d: adapt %d is neither 0 nor 1", who, k, g.adapt) : 0;
+}
+template <class Group>
+int check_groups(const Group* groups, int32_t n_groups, int32_t step, const char* who) {
   if (!groups) return fail("%s: groups is null", who);
   for (int k = 0; k < n_groups; ++k) {
-    const PlbAdamWGroup& g = groups[k];
+    const Group& g = groups[k];
     if (!(g.lr >= 0.0) || !std::isfinite(g.lr)) return fail("%s: group %d: lr %g is negative or not finite", who, k, g.lr);
     if (!(g.eps >= 0.0) || !std::isfinite(g.eps)) return fail("%s: group %d: eps %g is negative or not finite", who, k, g.eps);
     if (!(g.beta1 >= 0.0 && g.beta1 < 1.0)) return fail("%s: group %d: beta1 %g is outside [0, 1)", who, k, g.beta1);
     if (!(g.beta2 >= 0.0 && g.beta2 < 1.0)) return fail("%s: group %d: beta2 %g is outside [0, 1)", who, k, g.beta2);
     if (!std::isfinite(g.weight_decay)) return fail("%s: group %d: weight_decay is not finite", who, k);
+    if (check_adapt(g, k, who)) return 1;
   }
   if (step < 1) return fail("%s: step counts from 1", who);
   return 0;
 }
 
 // The segments of [a, b) among segs, rebased to a
-int range_segments(const PlbAdamWSegment* segs, int n, int64_t a, int64_t b, PlbAdamWSegment* out) {
+template <class Segment>
+int range_segments(const Segment* segs, int n, int64_t a, int64_t b, Segment* out) {
   int k = 0;
   for (int i = 0; i < n; ++i)
     if (segs[i].begin >= a && segs[i].end <= b) {
@@ -271,36 +345,24 @@ extern "C" int plb_adamw_plan(const PlbEngine* e, const PlbAdamWGroup* groups, i
 
 extern "C" int plb_adamw_step_groups(PlbEngine* e, const PlbAdamWGroup* groups, int32_t n_groups, const int32_t* group_of,
                                      int32_t step, double grad_scale, const float* norm_buf, void* stream) {
-  if (!e || !e->ws || !e->grads || !e->m || !e->v) return fail("plb_adamw_step_groups: optimizer buffers not bound");
-  if (e->infer) return fail("plb_adamw_step_groups: inference-only engine");
-  if (check_group_of(e, group_of, n_groups, "plb_adamw_step_groups")) return 1;
-  if (check_groups(groups, n_groups, step, "plb_adamw_step_groups")) return 1;
-  drop_stash(e, "plb_adamw_step_groups moved the weights since");
-  drop_final(e, "plb_adamw_step_groups moved the weights since: ask between the loss call and the optimizer step");
-  end_accum_window(e, "plb_adamw_step_groups moved the weights");
+  static const Update u = UPDATE_ENTRY("plb_adamw_step_groups", "grouped AdamW");
   hipStream_t s = (hipStream_t)stream;
-  if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
-    HIPTRY(ev_wait(e, s, e->ev_comm_done));
-    e->comm_pending = false;
-  }
+  if (begin_update(e, u, s, [&] { return check_group_of(e, group_of, n_groups, u.who) || check_groups(groups, n_groups, step, u.who); }))
+    return 1;
   float* norm = const_cast<float*>(norm_buf);   // (the launch counts the updates it leaves out in norm[3])
-  HB_R(s, e->grads, e->ptotal * 4, "grouped AdamW (reads the gradient buffer)");
   if (norm) HB_W(s, norm, 16, "grouped AdamW (reads the coefficient, counts a left-out update)");
   PlbAdamWSegment all[PLB_NPARAM], part[PLB_NPARAM];
   const int n = plan_segments(e, groups, group_of, step, all);
-  // the ranges, the step counts and the skip word are plb_adamw_step's; a range without a live segment launches nothing
-  const int n_main = range_segments(all, n, 0, e->ptrain, part);
-  if (n_main)
-    TRY(plb_launch_adamw_segments(e->params, e->grads, e->m, e->v, e->at<bf16_t>(e->o_wbf), (size_t)part[n_main - 1].end, part,
-                                  n_main, grad_scale, e->at<unsigned int>(e->o_lnerr), 1, norm, 1, s));
-  const int64_t o = e->poff[PLB_TOK_W];
-  const int n_tok = range_segments(all, n, o, e->ptotal, part);
-  if (n_tok) {
-    e->tok_steps += 1;   // (the plan gave these segments tok_steps + 1)
-    TRY(plb_launch_adamw_segments(e->params + o, e->grads + o, e->m + o, e->v + o, e->at<bf16_t>(e->o_wbf) + o,
-                                  (size_t)part[n_tok - 1].end, part, n_tok, grad_scale, e->at<unsigned int>(e->o_lnerr), 2, norm,
-                                  0, s));
-  }
+  if (step_ranges(e, step, [&](const StepRange& r) {
+        const int k = range_segments(all, n, r.a, r.b, part);
+        if (!k) return 0;   // a range without a live segment launches nothing
+        const Bufs x = bufs(e, r);
+        count_step(e, r);   // (the plan gave the token head's segments this count)
+        TRY(plb_launch_adamw_segments(x.p, x.g, x.m, x.v, x.w, (size_t)part[k - 1].end, part, k, grad_scale, x.skip,
+                                      r.skip_slot, norm, r.count_nonfinite, s));
+        return 0;
+      }))
+    return 1;
   return sync_transposes(e, s, false);
 }
 
@@ -312,31 +374,13 @@ extern "C" int plb_grad_norm_groups(PlbEngine* e, const int32_t* group_of, doubl
   if (!norm_buf || ((uintptr_t)norm_buf & 15)) return fail("plb_grad_norm_groups: norm_buf must be a 16-byte aligned device buffer");
   if (!e->ws || !e->grads) return fail("plb_grad_norm_groups: gradient buffer not bound");
   hipStream_t s = (hipStream_t)stream;
-  if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
-    HIPTRY(ev_wait(e, s, e->ev_comm_done));
-    e->comm_pending = false;
-  }
   PlbAdamWSegment all[PLB_NPARAM], part[PLB_NPARAM];
   const int n = plan_segments(e, nullptr, group_of, 1, all);
   // plb_grad_norm's ranges, grids and partial slots; holes contribute exact zeros
-  const int64_t nstep = e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W];
-  HB_R(s, e->grads, nstep * 4, "gradient norm (reads the gradient buffer)");
-  HB_W(s, norm_buf + 4, PLB_NORM_PARTS * 4, "gradient norm (writes the partial sums)");
-  TRY(plb_launch_grad_sumsq_segments(e->grads, (size_t)nstep, part, range_segments(all, n, 0, nstep, part), norm_buf + 4, s));
-  int nparts = PLB_NORM_PARTS;
-  if (e->tok_grads_live && e->NT > 0) {
-    const int64_t o = e->poff[PLB_TOK_W];
-    HB_R(s, e->grads + o, (e->ptotal - o) * 4, "gradient norm (reads the token head's gradients)");
-    HB_W(s, norm_buf + 4 + nparts, PLB_NORM_PARTS * 4, "gradient norm (writes the partial sums)");
-    TRY(plb_launch_grad_sumsq_segments(e->grads + o, (size_t)(e->ptotal - o), part, range_segments(all, n, o, e->ptotal, part),
-                                       norm_buf + 4 + nparts, s));
-    nparts += PLB_NORM_PARTS;
-  }
-  e->norm_nparts = 0;   // (these partials are not a LAST add's: a later have_partials call must not take them for such)
-  HB_R(s, norm_buf + 4, (size_t)nparts * 4, "gradient norm (reads the partial sums)");
-  HB_W(s, norm_buf, 16, "gradient norm (writes norm, coefficient and flag)");
-  TRY(plb_launch_grad_norm_finish(norm_buf + 4, nparts, grad_scale, max_norm, norm_buf, s));
-  return 0;
+  return grad_norm(e, false, grad_scale, max_norm, norm_buf, s, [&](const StepRange& r, float* partials) {
+    TRY(plb_launch_grad_sumsq_segments(e->grads + r.a, r.n(), part, range_segments(all, n, r.a, r.b, part), partials, s));
+    return 0;
+  });
 }
 
 // ---- LAMB (include/plbert.h: plb_lamb_floats, plb_lamb_plan, plb_lamb_step; kernels: lamb.hip)
@@ -345,21 +389,6 @@ namespace {
 // k tensors has at most n / 1024 + k workgroups (one pair of floats each).
 int64_t lamb_main_pairs(const PlbEngine* e) { return e->ptrain / 1024 + PLB_NPARAM; }
 int64_t lamb_tok_pairs(const PlbEngine* e) { return (e->ptotal - e->poff[PLB_TOK_W]) / 1024 + 2; }
-
-int check_lamb_groups(const PlbLambGroup* groups, int32_t n_groups, int32_t step, const char* who) {
-  if (!groups) return fail("%s: groups is null", who);
-  for (int k = 0; k < n_groups; ++k) {
-    const PlbLambGroup& g = groups[k];
-    if (!(g.lr >= 0.0) || !std::isfinite(g.lr)) return fail("%s: group %d: lr %g is negative or not finite", who, k, g.lr);
-    if (!(g.eps >= 0.0) || !std::isfinite(g.eps)) return fail("%s: group %d: eps %g is negative or not finite", who, k, g.eps);
-    if (!(g.beta1 >= 0.0 && g.beta1 < 1.0)) return fail("%s: group %d: beta1 %g is outside [0, 1)", who, k, g.beta1);
-    if (!(g.beta2 >= 0.0 && g.beta2 < 1.0)) return fail("%s: group %d: beta2 %g is outside [0, 1)", who, k, g.beta2);
-    if (!std::isfinite(g.weight_decay)) return fail("%s: group %d: weight_decay is not finite", who, k);
-    if (g.adapt != 0 && g.adapt != 1) return fail("%s: group %d: adapt %d is neither 0 nor 1", who, k, g.adapt);
-  }
-  if (step < 1) return fail("%s: step counts from 1", who);
-  return 0;
-}
 
 // One segment per live tensor, never merged: the trust ratio is a tensor's own
 int plan_lamb(const PlbEngine* e, const PlbLambGroup* groups, const int32_t* group_of, int32_t step, PlbLambSegment* segs) {
@@ -387,17 +416,6 @@ int plan_lamb(const PlbEngine* e, const PlbLambGroup* groups, const int32_t* gro
   }
   return n;
 }
-
-int lamb_range_segments(const PlbLambSegment* segs, int n, int64_t a, int64_t b, PlbLambSegment* out) {
-  int k = 0;
-  for (int i = 0; i < n; ++i)
-    if (segs[i].begin >= a && segs[i].end <= b) {
-      out[k] = segs[i];
-      out[k].begin -= a;
-      out[k++].end -= a;
-    }
-  return k;
-}
 }  // namespace
 
 extern "C" int64_t plb_lamb_floats(const PlbEngine* e) {
@@ -407,7 +425,7 @@ extern "C" int64_t plb_lamb_floats(const PlbEngine* e) {
 extern "C" int plb_lamb_plan(const PlbEngine* e, const PlbLambGroup* groups, int32_t n_groups, const int32_t* group_of,
                              int32_t step, PlbLambSegment* segs, int32_t* n_segs) {
   if (check_group_of(e, group_of, n_groups, "plb_lamb_plan")) return 1;
-  if (check_lamb_groups(groups, n_groups, step, "plb_lamb_plan")) return 1;
+  if (check_groups(groups, n_groups, step, "plb_lamb_plan")) return 1;
   if (!segs || !n_segs) return fail("plb_lamb_plan: null output");
   if (e->infer) return fail("plb_lamb_plan: inference-only engine");
   *n_segs = plan_lamb(e, groups, group_of, step, segs);
@@ -416,48 +434,34 @@ extern "C" int plb_lamb_plan(const PlbEngine* e, const PlbLambGroup* groups, int
 
 extern "C" int plb_lamb_step(PlbEngine* e, const PlbLambGroup* groups, int32_t n_groups, const int32_t* group_of, int32_t step,
                              double grad_scale, const float* norm_buf, float* lamb_buf, void* stream) {
-  if (!e || !e->ws || !e->grads || !e->m || !e->v) return fail("plb_lamb_step: optimizer buffers not bound");
-  if (e->infer) return fail("plb_lamb_step: inference-only engine");
-  if (check_group_of(e, group_of, n_groups, "plb_lamb_step")) return 1;
-  if (check_lamb_groups(groups, n_groups, step, "plb_lamb_step")) return 1;
-  if (!lamb_buf || ((uintptr_t)lamb_buf & 15)) return fail("plb_lamb_step: lamb_buf must be a 16-byte aligned device buffer");
-  drop_stash(e, "plb_lamb_step moved the weights since");
-  drop_final(e, "plb_lamb_step moved the weights since: ask between the loss call and the optimizer step");
-  end_accum_window(e, "plb_lamb_step moved the weights");
+  static const Update u = UPDATE_ENTRY("plb_lamb_step", "LAMB");
   hipStream_t s = (hipStream_t)stream;
-  if (e->comm_pending) {  // all-reduce pieces still in flight on the communication stream
-    HIPTRY(ev_wait(e, s, e->ev_comm_done));
-    e->comm_pending = false;
-  }
+  if (begin_update(e, u, s, [&] {
+        if (check_group_of(e, group_of, n_groups, u.who) || check_groups(groups, n_groups, step, u.who)) return 1;
+        return !lamb_buf || ((uintptr_t)lamb_buf & 15) ? fail("plb_lamb_step: lamb_buf must be a 16-byte aligned device buffer") : 0;
+      }))
+    return 1;
   float* norm = const_cast<float*>(norm_buf);   // (pass 1 counts the updates it leaves out in norm[3])
-  HB_R(s, e->grads, e->ptotal * 4, "LAMB (reads the gradient buffer)");
   if (norm) HB_W(s, norm, 16, "LAMB (reads the coefficient, counts a left-out update)");
   HB_W(s, lamb_buf, plb_lamb_floats(e) * 4, "LAMB (writes the partial sums and the trust ratios)");
   PlbLambSegment all[PLB_NPARAM], part[PLB_NPARAM];
   const int n = plan_lamb(e, groups, group_of, step, all);
-  unsigned int* skip = e->at<unsigned int>(e->o_lnerr);
-  bf16_t* wbf = e->at<bf16_t>(e->o_wbf);
-  const int64_t o = e->poff[PLB_TOK_W];
-  const int n_main = lamb_range_segments(all, n, 0, e->ptrain, part);
-  const int n_tok_all = n - n_main;   // (the pooler is never live: what is not in the trainable range is the token head's)
-  // the ranges, the step counts and the skip word are plb_adamw_step's; a range without a live tensor launches nothing, and
-  // the finish of the range that does run marks every other tensor as a hole
-  if (n_main) {
-    const size_t nn = (size_t)part[n_main - 1].end;
-    float* partials = lamb_buf + 4 * PLB_NPARAM;
-    TRY(plb_launch_lamb_pass1(e->params, e->grads, e->m, e->v, nn, part, n_main, grad_scale, skip, 1, norm, 1, partials, s));
-    TRY(plb_launch_lamb_finish(part, n_main, nn, 0, n_tok_all ? (int)PLB_TOK_W : (int)PLB_NPARAM, partials, lamb_buf, skip, norm, s));
-    TRY(plb_launch_lamb_pass2(e->params, e->m, e->v, wbf, nn, part, n_main, lamb_buf, skip, norm, s));
-  }
-  const int n_tok = lamb_range_segments(all, n, o, e->ptotal, part);
-  if (n_tok) {
-    e->tok_steps += 1;   // (the plan gave these tensors tok_steps + 1)
-    const size_t nn = (size_t)part[n_tok - 1].end;
-    float* partials = lamb_buf + 4 * PLB_NPARAM + 2 * lamb_main_pairs(e);
-    TRY(plb_launch_lamb_pass1(e->params + o, e->grads + o, e->m + o, e->v + o, nn, part, n_tok, grad_scale, skip, 2, norm, 0,
-                              partials, s));
-    TRY(plb_launch_lamb_finish(part, n_tok, nn, n_main ? (int)PLB_TOK_W : 0, PLB_NPARAM, partials, lamb_buf, skip, norm, s));
-    TRY(plb_launch_lamb_pass2(e->params + o, e->m + o, e->v + o, wbf + o, nn, part, n_tok, lamb_buf, skip, norm, s));
-  }
+  // a range without a live tensor launches nothing, and the finish of the range that does run marks every other tensor as a hole
+  if (step_ranges(e, step, [&](const StepRange& r) {
+        const int k = range_segments(all, n, r.a, r.b, part);
+        if (!k) return 0;
+        const int other = n - k;   // (the pooler is never live: what is not in this range is in the other one)
+        const int lo = r.token && other ? (int)PLB_TOK_W : 0, hi = !r.token && other ? (int)PLB_TOK_W : (int)PLB_NPARAM;
+        const Bufs x = bufs(e, r);
+        const size_t nn = (size_t)part[k - 1].end;
+        float* partials = lamb_buf + 4 * PLB_NPARAM + (r.token ? 2 * lamb_main_pairs(e) : 0);
+        count_step(e, r);   // (the plan gave the token head's tensors this count)
+        TRY(plb_launch_lamb_pass1(x.p, x.g, x.m, x.v, nn, part, k, grad_scale, x.skip, r.skip_slot, norm, r.count_nonfinite,
+                                  partials, s));
+        TRY(plb_launch_lamb_finish(part, k, nn, lo, hi, partials, lamb_buf, x.skip, norm, s));
+        TRY(plb_launch_lamb_pass2(x.p, x.m, x.v, x.w, nn, part, k, lamb_buf, x.skip, norm, s));
+        return 0;
+      }))
+    return 1;
   return sync_transposes(e, s, false);
 }

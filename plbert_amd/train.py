@@ -115,6 +115,48 @@ def _note_stepped(owner, engine, groups, group_of, liveness=None):
     owner._noted.add(key)
 
 
+def _clip_norm(owner, engine, grad_scale, **which):
+    """With ``owner.max_grad_norm``: the norm and clipping coefficient of the gradients the next update consumes, on the
+    device (``engine.grad_norm``; ``which``: have_partials or group_of). Returns the norm buffer for the update and keeps
+    its four result floats as ``owner.last_grad_norm``; None when clipping is off."""
+    if owner.max_grad_norm is None:
+        return None
+    norm_buf = engine.grad_norm(grad_scale, owner.max_grad_norm, **which)
+    owner.last_grad_norm = norm_buf[:4]
+    return norm_buf
+
+
+# torch.optim.AdamW's group keys beside the hyper-parameters, at its defaults: what its state_dict carries in every group
+TORCH_ADAMW_EXTRA = {"amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+                     "fused": None, "decoupled_weight_decay": True}
+
+
+def _scatter_state(engine, selection):
+    """``selection`` ({state-dict name: torch's {step, exp_avg, exp_avg_sq}}) into the flat moment buffers, zeroed first; the
+    pooler never trains and is left out. Returns (names written, step count outside the token head, the token head's; 0:
+    none). The fused update keeps ONE count each: differing counts are refused before anything is written."""
+    e = engine
+    ta = e.token_range[0]
+    kept, steps, tok_steps = [], set(), set()
+    for n, st in selection.items():
+        off, size, _ = e.layout[n]
+        is_tok = bool(e.num_tokens) and off >= ta
+        if off + size > e.trainable and not is_tok:
+            continue
+        kept.append(n)
+        (tok_steps if is_tok else steps).add(int(float(st["step"])))
+    if len(steps) > 1 or len(tok_steps) > 1:
+        raise ValueError(f"per-parameter step counts differ ({sorted(steps)} / token head {sorted(tok_steps)}): "
+                         "the fused AdamW keeps one step for the encoder + phoneme head and one for the token head")
+    e.exp_avg.zero_()
+    e.exp_avg_sq.zero_()
+    for n in kept:
+        off, size, shp = e.layout[n]
+        e.exp_avg[off:off + size].view(shp).copy_(selection[n]["exp_avg"])
+        e.exp_avg_sq[off:off + size].view(shp).copy_(selection[n]["exp_avg_sq"])
+    return kept, (steps.pop() if steps else 0), (tok_steps.pop() if tok_steps else 0)
+
+
 class PLBertTrainer:
     """PhonemeOnlyModel + AdamW(lr) of train.py:266-272 on one GPU, optionally data parallel.
     ``num_tokens > 0`` builds MultiTaskModel's second head (model.py:11); batches staged with ``token_ids``
@@ -219,21 +261,10 @@ class PLBertTrainer:
         return batch.packing if self.packed else None
 
     def stage_batch(self, labels, masked, lengths, masked_indices, validate=True, token_ids=None, packed=None):
-        if validate:
-            validate_batch(labels, masked, lengths, masked_indices, self.engine.cfg.vocab_size)
-            if token_ids is not None:
-                validate_token_ids(token_ids, np.asarray(masked).shape, lengths, self.engine.num_tokens)
-        dev = self.engine.device
-        masked_t = torch.as_tensor(np.asarray(masked), dtype=torch.int64).to(dev)
-        labels_t = torch.as_tensor(np.asarray(labels), dtype=torch.int64).to(dev)
-        B, S = masked_t.shape
-        lens = np.asarray(lengths, dtype=np.int32)
-        lengths_t = None if (lens == S).all() else torch.from_numpy(lens).to(dev)
-        off, flat = masked_indices_to_csr(masked_indices)
-        tok_t = None if token_ids is None else torch.as_tensor(np.asarray(token_ids), dtype=torch.int64).to(dev)
-        plan = None if lengths_t is None else make_packing(lens, S, dev, self.packed if packed is None else packed)
-        return StagedBatch(masked_t, labels_t, lengths_t, torch.from_numpy(off).to(dev), torch.from_numpy(flat).to(dev),
-                           int(off[-1]), int(lens.sum()), tok_t, plan, lens)
+        """``stage_reference_batch`` on this trainer's engine; ``packed`` None: the trainer's own setting."""
+        batch = (labels, masked, lengths, masked_indices)
+        return stage_reference_batch(self.engine, batch if token_ids is None else (token_ids, *batch), validate,
+                                     self.packed if packed is None else packed)
 
     def loss_and_grads(self, batch: StagedBatch):
         return self.engine.loss_fwd_bwd(batch.masked, batch.labels, batch.lengths, batch.offsets, batch.flat,
@@ -317,24 +348,17 @@ class PLBertTrainer:
         """AdamW (or LAMB: ``optimizer``) on what the gradient buffer holds; with ``max_grad_norm`` the norm (taken after
         the exchange, so every rank computes the same coefficient) and the clipped update."""
         self.step_count += 1
-        norm_buf = None
         if self.param_groups is not None:
             groups, group_of = self.groups_for_step()
-            if self.max_grad_norm is not None:   # (a LAST add's partial sums cover frozen tensors too: one pass of its own)
-                norm_buf = self.engine.grad_norm(grad_scale, self.max_grad_norm, group_of=group_of)
-                self.last_grad_norm = norm_buf[:4]
+            # (a LAST add's partial sums cover frozen tensors too: the grouped norm is one pass of its own)
+            norm_buf = _clip_norm(self, self.engine, grad_scale, group_of=group_of)
             _note_stepped(self, self.engine, groups, group_of, liveness=self._dual)
             step = self.engine.lamb_step if self.optimizer == "lamb" else self.engine.adamw_step_groups
             step(self.step_count, groups, group_of, grad_scale=grad_scale, norm_buf=norm_buf)
             return
-        if self.max_grad_norm is not None:
-            norm_buf = self.engine.grad_norm(grad_scale, self.max_grad_norm, have_partials=have_partials)
-            self.last_grad_norm = norm_buf[:4]
-        if norm_buf is None:
-            self.engine.adamw_step(self.step_count, self.lr, self.betas, self.eps, self.weight_decay, grad_scale=grad_scale)
-        else:
-            self.engine.adamw_step(self.step_count, self.lr, self.betas, self.eps, self.weight_decay, grad_scale=grad_scale,
-                                   norm_buf=norm_buf)
+        norm_buf = _clip_norm(self, self.engine, grad_scale, have_partials=have_partials)
+        self.engine.adamw_step(self.step_count, self.lr, self.betas, self.eps, self.weight_decay, grad_scale=grad_scale,
+                               norm_buf=norm_buf)
 
     @property
     def stepped(self):
@@ -741,10 +765,7 @@ class AdamW:
             if n in group_of and p.grad.data_ptr() != e.grads.data_ptr() + 4 * off:
                 e.grads[off:off + size].view(shp).copy_(p.grad)
         self.step_count += 1
-        norm_buf = None
-        if self.max_grad_norm is not None:
-            norm_buf = e.grad_norm(self.grad_scale, self.max_grad_norm, group_of=group_of)
-            self.last_grad_norm = norm_buf[:4]
+        norm_buf = _clip_norm(self, e, self.grad_scale, group_of=group_of)
         _note_stepped(self, e, groups, group_of)
         self._fused_step(groups, group_of, norm_buf)
 
@@ -772,15 +793,8 @@ class AdamW:
                 e.grads[off:off + size].view(shp).copy_(p.grad)
         self.step_count += 1
         d = self.defaults
-        norm_buf = None
-        if self.max_grad_norm is not None:
-            norm_buf = e.grad_norm(self.grad_scale, self.max_grad_norm)
-            self.last_grad_norm = norm_buf[:4]
-        if norm_buf is None:
-            self.engine.adamw_step(self.step_count, d["lr"], d["betas"], d["eps"], d["weight_decay"], self.grad_scale)
-        else:
-            self.engine.adamw_step(self.step_count, d["lr"], d["betas"], d["eps"], d["weight_decay"], self.grad_scale,
-                                   norm_buf=norm_buf)
+        e.adamw_step(self.step_count, d["lr"], d["betas"], d["eps"], d["weight_decay"], self.grad_scale,
+                     norm_buf=_clip_norm(self, e, self.grad_scale))
 
     def state_dict(self):
         """torch.optim.AdamW layout ({'state': {index: {step, exp_avg, exp_avg_sq}}, 'param_groups': [...]}) with
@@ -809,14 +823,11 @@ class AdamW:
                             "exp_avg_sq": e.exp_avg_sq[off:off + size].view(shp).clone()}
         if self._groups is not None:   # torch's multi-group layout; indices count model.parameters() order
             index = {id(p): i for i, p in enumerate(self.param_list)}
-            extra = {"amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-                     "fused": None, "decoupled_weight_decay": True}
-            groups = [{**extra, **{k: (tuple(v) if k == "betas" else v) for k, v in g.items() if k != "params"},
+            groups = [{**TORCH_ADAMW_EXTRA, **{k: (tuple(v) if k == "betas" else v) for k, v in g.items() if k != "params"},
                        "params": [index[id(p)] for p in g["params"]]} for g in self._groups]
             return {"state": state, "param_groups": groups}
         group = {"lr": d["lr"], "betas": tuple(d["betas"]), "eps": d["eps"], "weight_decay": d["weight_decay"],
-                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-                 "fused": None, "decoupled_weight_decay": True, "params": list(range(len(self.param_list)))}
+                 **TORCH_ADAMW_EXTRA, "params": list(range(len(self.param_list)))}
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
@@ -829,23 +840,7 @@ class AdamW:
             for k in ("lr", "betas", "eps", "weight_decay"):
                 if k in g:
                     self.defaults[k] = tuple(g[k]) if k == "betas" else g[k]
-            steps, tok_steps = set(), set()
-            e.exp_avg.zero_()
-            e.exp_avg_sq.zero_()
-            ta = e.token_range[0]
-            for i, st in sd["state"].items():
-                off, size, shp = e.layout[self._names[int(i)]]
-                is_tok = bool(e.num_tokens) and off >= ta
-                if off + size > e.trainable and not is_tok:
-                    continue  # the pooler never trains
-                e.exp_avg[off:off + size].view(shp).copy_(st["exp_avg"])
-                e.exp_avg_sq[off:off + size].view(shp).copy_(st["exp_avg_sq"])
-                (tok_steps if is_tok else steps).add(int(float(st["step"])))
-            if len(steps) > 1 or len(tok_steps) > 1:
-                raise ValueError(f"per-parameter step counts differ ({sorted(steps)} / token head {sorted(tok_steps)}): "
-                                 "the fused AdamW keeps one step for the encoder + phoneme head and one for the token head")
-            self.step_count = steps.pop() if steps else 0
-            e.token_head_steps = tok_steps.pop() if tok_steps else 0
+            _, self.step_count, e.token_head_steps = _scatter_state(e, {self._names[int(i)]: st for i, st in sd["state"].items()})
             return
         self.step_count = int(sd["step"])  # compact form written by early versions of this class
         e.exp_avg[: e.trainable].copy_(sd["exp_avg"])
@@ -868,34 +863,14 @@ class AdamW:
         for gs, g in zip(saved, self._groups):
             for i, p in zip(gs["params"], g["params"]):
                 target[int(i)] = name_of[id(p)]
-        ta = e.token_range[0]
-        entries, steps, tok_steps = [], set(), set()
-        for i, st in sd["state"].items():
-            n = target[int(i)]
-            off, size, shp = e.layout[n]
-            is_tok = bool(e.num_tokens) and off >= ta
-            if off + size > e.trainable and not is_tok:
-                continue  # the pooler never trains
-            entries.append((n, st))
-            (tok_steps if is_tok else steps).add(int(float(st["step"])))
-        if len(steps) > 1 or len(tok_steps) > 1:   # (before anything is written)
-            raise ValueError(f"per-parameter step counts differ ({sorted(steps)} / token head {sorted(tok_steps)}): "
-                             "the fused AdamW keeps one step for the encoder + phoneme head and one for the token head")
+        # (differing step counts are refused here, before anything is written: the groups' settings included)
+        kept, self.step_count, e.token_head_steps = _scatter_state(e, {target[int(i)]: st for i, st in sd["state"].items()})
         for gs, g in zip(saved, self._groups):
             for k, v in gs.items():
                 if k != "params":
                     g[k] = tuple(v) if k == "betas" else v
-        e.exp_avg.zero_()
-        e.exp_avg_sq.zero_()
-        self._first_step = {}
+        self._first_step = {n: 0 for n in kept}
         self._noted.clear()
-        for n, st in entries:
-            off, size, shp = e.layout[n]
-            e.exp_avg[off:off + size].view(shp).copy_(st["exp_avg"])
-            e.exp_avg_sq[off:off + size].view(shp).copy_(st["exp_avg_sq"])
-            self._first_step[n] = 0
-        self.step_count = steps.pop() if steps else 0
-        e.token_head_steps = tok_steps.pop() if tok_steps else 0
 
 
 class Lamb(AdamW):
@@ -911,7 +886,6 @@ class Lamb(AdamW):
     ``model.engine.trust_ratios()`` has the norms and ratios of the last step as device tensors."""
 
     HYPER = ("lr", "betas", "eps", "weight_decay", "adapt")
-    _TORCH_ADAMW_KEYS = ("amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused", "decoupled_weight_decay")
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, model=None, max_grad_norm=None,
                  exclude_from_layer_adaptation=("bias", "LayerNorm", "layer_norm")):
@@ -944,5 +918,5 @@ class Lamb(AdamW):
 
     def state_dict(self):
         sd = super().state_dict()
-        sd["param_groups"] = [{k: v for k, v in g.items() if k not in self._TORCH_ADAMW_KEYS} for g in sd["param_groups"]]
+        sd["param_groups"] = [{k: v for k, v in g.items() if k not in TORCH_ADAMW_EXTRA} for g in sd["param_groups"]]
         return sd

@@ -49,7 +49,7 @@ class _StubEngine:
         self._on_handoff_timeout = []
         self.calls = []
 
-    def adamw_step(self, step, lr, betas, eps, weight_decay, grad_scale=1.0):
+    def adamw_step(self, step, lr, betas, eps, weight_decay, grad_scale=1.0, norm_buf=None):
         self.calls.append(dict(step=step, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
 
 
