@@ -225,7 +225,8 @@ int plb_adamw_step_clipped(PlbEngine* e, double lr, double beta1, double beta2, 
  *   them: decay = 1 - lr * weight_decay, omb1 = 1 - beta1, b2 = beta2, omb2 = 1 - beta2, eps, step_size =
  *   lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step). Adjacent tensors of the same group whose rounded scalars and
  *   step agree are merged into one segment. A frozen tensor does not appear; nor does a tensor the engine would not step
- *   anyway, whatever group it was given (torch skips a parameter whose .grad is None): the pooler, the phoneme head after
+ *   anyway, whatever group it was given (torch skips a parameter whose .grad is None): the pooler unless the last backward
+ *   call was a plb_encode_bwd_pooled with a d_pooled, the phoneme head after
  *   plb_encode_bwd, the token head unless the last loss call was a dual-head one. Segments of the token head carry the token
  *   head's own next step count (plb_token_head_steps + 1), all others `step`. segs has room for PLB_NPARAM entries.
  * plb_adamw_step_groups: plb_adamw_step (norm_buf == NULL) or plb_adamw_step_clipped (norm_buf = what plb_grad_norm* wrote)
@@ -271,7 +272,7 @@ int plb_grad_norm_groups(PlbEngine* e, const int32_t* group_of, double grad_scal
  * "exclude from layer adaptation" convention for biases and LayerNorm, which usually have weight_decay = 0 as well). k is
  * `step` for everything outside the token head and plb_token_head_steps + 1 for the token head, as in plb_adamw_step_groups
  * (with its DEVIATION from torch: one count for all tensors outside the token head). A tensor in no group (group_of[i] = -1)
- * or not stepped by this call (the pooler, the phoneme head after plb_encode_bwd, the token head unless the last loss call was
+ * or not stepped by this call (the pooler without a gradient, the phoneme head after plb_encode_bwd, the token head unless the last loss call was
  * a dual-head one) is a hole: nothing of it is loaded or stored.
  * exp_avg and exp_avg_sq after a LAMB step are BIT-IDENTICAL to those after plb_adamw_step[_clipped] from the same state with
  * the same betas, grad_scale and coef: a run may change between the two optimizers without touching its moments.
@@ -485,7 +486,8 @@ int plb_set_packed_fp8(PlbEngine* e, int32_t on);
  *   plb_broadcast_params. Without a live stash, or with another B, S or plan, the call fails with a text that says which,
  *   launches nothing and leaves the gradient buffer alone.
  *   Gradient buffer: the encoder range [0, offset of PLB_HEAD_W) is overwritten (not accumulated) as by a loss call; the
- *   phoneme head's range is written as ZEROS and the head — like the token head and the pooler after a phoneme-only call —
+ *   phoneme head's range is written as ZEROS and the head — like the token head after a phoneme-only call, and like the pooler
+ *   after every call but a plb_encode_bwd_pooled that was given a d_pooled (below) —
  *   is marked as having no gradient: the plb_adamw_step that follows updates [0, PLB_HEAD_W) only and leaves the head's
  *   parameters, both moments and bf16 copies bit-unchanged, as torch skips a parameter whose .grad is None. The head does
  *   NOT get a step count of its own: it keeps sharing the engine's (`step` of plb_adamw_step), so after k fine-tuning steps
@@ -620,6 +622,39 @@ int plb_encode_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* in
 int plb_encode_bwd_masked(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
                           const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing, const float* d_hidden,
                           const float* const* d_below, float* d_inputs_embeds, void* stream);
+/* ---- differentiable pooler_output (opt-in: a call without d_pooled launches what it launched before) ----
+ * pooled[b,:] = tanh(pooler.weight · h[b,0,:] + pooler.bias) (plb_pooler; modeling_albert.py:403), h the last hidden state;
+ * position 0 is used whether or not a key mask makes it a hole. A sentence-level head on pooler_output trains the pooler and
+ * the encoder through this call.
+ * plb_encode_bwd_pooled: superset of plb_encode_bwd_masked. d_pooled (or NULL): fp32 [B,H] = d(loss)/d(pooled), 16-byte
+ *   aligned. With d_pooled == NULL the call is exactly its namesake: the same launches, the gradient buffer bit for bit, the
+ *   same engine state afterwards. With d_pooled the pooler backward runs first in the call, from the bf16 rows of the final
+ *   hidden state the live stash holds and the fp32 parameters:
+ *     y = pooled, recomputed with plb_pooler's arithmetic (its bits);  dpre = d_pooled * (1 - y*y)
+ *     d(pooler.weight) = sum_b dpre[b,:]^T h[b,0,:]    d(pooler.bias) = sum_b dpre[b,:]    dh0[b,:] = dpre[b,:] · pooler.weight
+ *   all in fp32, every sum in a fixed order without atomics (bitwise reproducible from run to run). The pooler's range of the
+ *   gradient buffer is overwritten, and the output gradient of the last application at position 0 of sample b becomes
+ *   bf16(d_hidden[b,0,:] + dh0[b,:]) (one fp32 add, one round to nearest even; d_hidden == NULL: a zero addend, every other
+ *   row zero). Nothing else in the backward changes. "Nothing to differentiate" means that d_hidden, d_below and d_pooled are
+ *   all absent.
+ *   The pooler is then marked as having a gradient, by the scheme of the phoneme head: every optimizer and norm entry
+ *   (plb_adamw_step, _clipped, _groups, plb_adamw_plan, plb_lamb_plan, plb_lamb_step, plb_grad_norm, plb_grad_norm_groups)
+ *   covers [PLB_POOL_W, end of PLB_POOL_B) with one more launch, with the engine's step count (the pooler has none of its own);
+ *   groups and `frozen` apply to the two tensors as to any other. The mark is cleared by every later backward call: a loss
+ *   call, or a plb_encode_bwd* call without d_pooled, leaves the pooler without gradient and its parameters, moments and bf16
+ *   copy bit-unchanged by the step that follows.
+ *   plb_grad_accum_add carries the pooler through a window like the phoneme head (live after the LAST add iff a micro-step of
+ *   the window produced it). A window that would hold both the token head's and the pooler's gradients is refused before
+ *   anything is launched: in a norm buffer the two share one set of partial sums.
+ *   Data-parallel runs: the pooler range lies right behind the phoneme head's; when it is live the head piece of the overlapped
+ *   exchange, and the first collective of plb_allreduce_grads, reach to its end. The number and order of collectives stay as
+ *   they are; plb_comm_pieces reports the grown float count.
+ * Refusals, each before anything is launched and with a text: nothing to differentiate; a d_pooled that is not 16-byte
+ *   aligned; every refusal of the namesake (no live stash, another B, S, plan or key mask, fp8 mode through plb_encode).
+ * Out of scope: the pre-training loss calls, fp8 mode, dropout, a pooler step count of its own. */
+int plb_encode_bwd_pooled(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
+                          const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* packing, const float* d_hidden,
+                          const float* const* d_below, float* d_inputs_embeds, const float* d_pooled, void* stream);
 /* ---- masked-phoneme evaluation: accuracy, top-k and fill-mask from a loss call (opt-in: a step that does not ask launches
  * what it launched before) ----
  * The reference reports the scalar loss only (train.py:288-336, 395-410). A masked LM's users also expect the accuracy at the

@@ -294,6 +294,7 @@ PUBLIC = {
     "plb_forward_masked": (i32, [vp, vp, P(PlbEmbedInputs), vp, vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
     "plb_encode_masked": (i32, [vp, vp, P(PlbEmbedInputs), vp, vp, i32, i32, P(PlbPacking), vp, P(PlbLayerOutputs), vp]),
     "plb_encode_bwd_masked": (i32, [vp, vp, P(PlbEmbedInputs), vp, vp, i32, i32, P(PlbPacking), vp, vp, vp, vp]),
+    "plb_encode_bwd_pooled": (i32, [vp, vp, P(PlbEmbedInputs), vp, vp, i32, i32, P(PlbPacking), vp, vp, vp, vp, vp]),
     "plb_masked_report": (i32, [vp, vp, i32, i32, P(PlbMaskedReport), vp]),
     "plb_token_report": (i32, [vp, vp, vp, vp, i32, i32, i32, P(PlbPacking), vp, i32, P(PlbTokenReport), vp]),
     "plb_comm_pieces": (i32, [vp, P(i32), P(i64)]),
@@ -364,6 +365,8 @@ INTERNAL = {
     "plb_launch_ce_prepare_packed": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "plb_launch_unpack_rows": (i32, [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
     "plb_launch_seed_dy": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "plb_launch_pooler_bwd": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "plb_launch_seed_dy_first_rows": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
     "plb_launch_attn_probs": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, f32, vp, vp]),
     "plb_launch_attn_probs_masked": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "plb_launch_key_mask_words": (i32, [vp, vp, i32, i32, vp, i32, vp]),

@@ -244,6 +244,8 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
   if (tr) e->o_embpart = cv.take((int64_t)plb_embed_inputs_part_floats((int)Tp, e->P, c.type_vocab_size, (int)E) * 4);
   // The key-mask words of a plb_*_masked call (key_mask.hip), carved last like the regions above: two words per 64 keys.
   e->o_keywords = cv.take((int64_t)c.max_batch * 2 * ((c.max_seq + 63) / 64) * 4);
+  // dpre and dh0 of the pooler backward (plb_encode_bwd_pooled; pooler_bwd.hip), carved last like the regions above
+  if (tr) { e->o_pool_dpre = cv.take((int64_t)c.max_batch * H * 4); e->o_pool_dh0 = cv.take((int64_t)c.max_batch * H * 4); }
   e->ws_bytes = cv.off;
   *out = e;
   return 0;

@@ -6,7 +6,8 @@
 // (engine_internal.h) behind its refusals, and every stage below — run_encoder, token_head, encoder_bwd, the backward tail —
 // takes that and nothing else about the call. Only
 // writer of the encode stash (stash_*: every unit ends its life through drop_stash), pruned_rows, last_app_rows,
-// last_exec_rows, tok_grads_live and head_grads_live (which a LAST add of engine_optim.cpp replaces by its window's union),
+// last_exec_rows, tok_grads_live, head_grads_live and pool_grads_live (which a LAST add of engine_optim.cpp replaces by its
+// window's union),
 // and of what plb_masked_report reads (rep_*: engine_eval.cpp; plb_bind clears rep_valid) and of the record of the final
 // hidden state plb_token_report reads (fin_*: note_final here; ended through drop_final by the calls that move the weights).
 // (packed_dual, packed_fp8: plb_set_packed_dual / _fp8, engine.cpp.)
@@ -186,6 +187,7 @@ static int begin_training_call(PlbEngine* e, bool dual, hipStream_t s) {
   if (join_comm(e, s)) return 1;
   e->tok_grads_live = dual;
   e->head_grads_live = true;
+  e->pool_grads_live = false;   // (only plb_encode_bwd_pooled with a d_pooled sets it, behind this)
   e->grads_reduced = false;
   e->grads_fresh = true;   // (plb_grad_accum_add: these gradients have not been added yet; partials of older ones are void)
   e->norm_nparts = 0;
@@ -633,7 +635,9 @@ extern "C" int plb_loss_fwd_packed(PlbEngine* e, const int64_t* masked_ids, cons
 // downstream model runs. plb_encode_bwd turns the caller's d(last_hidden_state) into the output gradient of the last
 // application (plb_launch_seed_dy) and runs the stages of a loss call's backward behind it. The phoneme head takes no
 // part: its gradient range is written as zeros (and still travels as the first piece of the exchange, as in
-// zero_loss_call: the collective sequence of a step is the same whatever the step computes).
+// zero_loss_call: the collective sequence of a step is the same whatever the step computes). The pooler takes part only when
+// plb_encode_bwd_pooled brings a gradient of pooler_output: its backward (pooler_bwd.hip) then runs first, writes the pooler's
+// range — which travels with the head's piece — and adds its share to row (b, 0) of the seeded output gradient.
 static int encode_impl(PlbEngine* e, const char* who, const EncArgs& a, float* hidden) {
   if (check_shape(e, a.B, a.S, who)) return 1;
   if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1): a differentiable forward keeps every application's activations", who);
@@ -690,9 +694,11 @@ extern "C" int plb_encode_masked(PlbEngine* e, const int64_t* ids, const PlbEmbe
 // plb_encode_bwd_layers, and plb_encode_bwd as a call of it (layers_call false: d_hidden required, with its own text).
 // d_below[l] (host array of L device pointers, or null): the caller's gradient of hidden_states[l], the input of application
 // l; it joins the residual operand of the dX GEMM that produces that state's gradient (attention_bwd_dx). d_hidden == NULL:
-// the output gradient of the last application is zero.
+// the output gradient of the last application is zero. d_pooled (fp32 [B,H], or null; pooled_call: the entry that takes one): the
+// caller's gradient of pooler_output — the pooler backward (pooler_bwd.hip) runs first, from the final hidden state of the
+// stash and the fp32 parameters: it writes the pooler range of the gradient buffer and dh0, which joins row (b, 0) of dy.
 static int encode_bwd_impl(PlbEngine* e, const char* who, const EncArgs& a, const float* d_hidden, const float* const* d_below,
-                           float* d_inputs_embeds, bool layers_call) {
+                           float* d_inputs_embeds, bool layers_call, const float* d_pooled = nullptr, bool pooled_call = false) {
   if (check_shape(e, a.B, a.S, who)) return 1;
   if (e->infer) return fail("%s: inference-only engine (PlbConfig.inference_only = 1)", who);
   if (!e->grads) return fail("%s: no gradient buffer bound", who);
@@ -707,9 +713,11 @@ static int encode_bwd_impl(PlbEngine* e, const char* who, const EncArgs& a, cons
   EmbedCall ec;
   if (embed_call(e, a.ids, a.inputs, d_inputs_embeds, who, &ec)) return 1;
   if (key_mask_check(e, a.key_mask, a.S, who)) return 1;
-  if (!d_hidden && below.empty())
-    return layers_call ? fail("%s: nothing to differentiate (d_hidden is null and d_below has no entry)", who)
+  if (!d_hidden && below.empty() && !d_pooled)
+    return pooled_call ? fail("%s: nothing to differentiate (d_hidden and d_pooled are null and d_below has no entry)", who) :
+           layers_call ? fail("%s: nothing to differentiate (d_hidden is null and d_below has no entry)", who)
                        : fail("%s: d_hidden is null", who);
+  if ((uintptr_t)d_pooled & 15) return fail("%s: d_pooled must be 16-byte aligned", who);
   if (!e->stash_live) return fail("%s: no live plb_encode stash: %s", who, e->stash_dead_by);
   if (a.B != e->stash_B || a.S != e->stash_S)
     return fail("%s: batch %d x seq %d differs from the plb_encode call's %d x %d", who, a.B, a.S, e->stash_B, e->stash_S);
@@ -736,15 +744,29 @@ static int encode_bwd_impl(PlbEngine* e, const char* who, const EncArgs& a, cons
   e->head_grads_live = false;
   e->pruned_rows = 0;
   const int64_t Tp = rw.Tp;
+  float* const dh0 = e->at<float>(e->o_pool_dh0);
+  if (d_pooled) {
+    e->pool_grads_live = true;
+    const bf16_t* const xL = slots(e, Tp, a.B, a.S, e->L - 1, true).y;   // the output of the last application
+    float* const dpre = e->at<float>(e->o_pool_dpre);
+    HB_R(s, xL, Tp * e->H * 2, "final hidden state (pooler backward)");
+    HB_W(s, dpre, (int64_t)a.B * e->H * 4, "dpre of the pooler backward"); HB_W(s, dh0, (int64_t)a.B * e->H * 4, "dh0 of the pooler backward");
+    HB_W(s, e->grd(PLB_POOL_W), (pool_end(e) - e->poff[PLB_POOL_W]) * 4, "pooler gradients");
+    TRY(plb_launch_pooler_bwd(xL, e->H, rw.row_start, a.B, a.S, e->H, e->par(PLB_POOL_W), e->par(PLB_POOL_B), d_pooled, dpre,
+                              e->grd(PLB_POOL_W), e->grd(PLB_POOL_B), dh0, s));
+  }
   bf16_t* dy = e->at<bf16_t>(e->o_dy0);
   HB_W(s, dy, Tp * e->H * 2, "output gradient of the last application, seeded from d_hidden");
   if (key_mask_words(e, a.key_mask, &c)) return 1;
   if (d_hidden) TRY(plb_launch_seed_dy(d_hidden, a.lengths, rw.row_start, a.B, a.S, e->H, (int)Tp, dy, s));
   else HIPTRY(hipMemsetAsync(dy, 0, (size_t)Tp * e->H * 2, s));   // (no gradient at the last slot: every row zero)
+  if (d_pooled) TRY(plb_launch_seed_dy_first_rows(d_hidden, dh0, rw.row_start, a.B, a.S, e->H, dy, s));   // row (b, 0) += dh0[b]
   // the phoneme head took no part: zeros, final before the layer loop — its piece travels where a regular step's does
   HB_W(s, e->grd(PLB_HEAD_W), (e->ptrain - e->poff[PLB_HEAD_W]) * 4, "phoneme head gradients (zeros: plb_encode_bwd)");
   HIPTRY(hipMemsetAsync(e->grd(PLB_HEAD_W), 0, (size_t)(e->ptrain - e->poff[PLB_HEAD_W]) * 4, s));
-  if (overlapping(e) && reduce_pieces(e, kPieceHead, kPieceHead + 1, s)) return 1;
+  // (with a d_pooled the pooler range, adjacent and final too, travels in the same collective)
+  if (overlapping(e) && (d_pooled ? reduce_piece(e, e->poff[PLB_HEAD_W], pool_end(e), s) : reduce_pieces(e, kPieceHead, kPieceHead + 1, s)))
+    return 1;
   int du_rows = 0;
   if (encoder_bwd(e, c, nullptr, &dy, &du_rows, below.empty() ? nullptr : below.data())) return 1;
   if (status_exchange(e, s)) return 1;
@@ -775,4 +797,12 @@ extern "C" int plb_encode_bwd_masked(PlbEngine* e, const int64_t* ids, const Plb
                                      const float* const* d_below, float* d_inputs_embeds, void* stream) {
   return encode_bwd_impl(e, key_mask ? "plb_encode_bwd_masked" : "plb_encode_bwd_inputs",
                          {ids, inputs, key_mask, lengths, B, S, pk, nullptr, stream}, d_hidden, d_below, d_inputs_embeds, true);
+}
+// plb_encode_bwd_masked with the caller's gradient of pooler_output; d_pooled == NULL: that call
+extern "C" int plb_encode_bwd_pooled(PlbEngine* e, const int64_t* ids, const PlbEmbedInputs* inputs, const int32_t* key_mask,
+                                     const int32_t* lengths, int32_t B, int32_t S, const PlbPacking* pk, const float* d_hidden,
+                                     const float* const* d_below, float* d_inputs_embeds, const float* d_pooled, void* stream) {
+  return encode_bwd_impl(e, d_pooled ? "plb_encode_bwd_pooled" : key_mask ? "plb_encode_bwd_masked" : "plb_encode_bwd_inputs",
+                         {ids, inputs, key_mask, lengths, B, S, pk, nullptr, stream}, d_hidden, d_below, d_inputs_embeds, true, d_pooled,
+                         true);
 }

@@ -147,7 +147,7 @@ int pieces_done(PlbEngine* e) {
   if (!e->comm_pending) return 0;
   // the pieces are disjoint by construction; together they must be exactly the range AdamW is about to consume (a
   // one-rank communicator would not show a forgotten tensor: its all-reduce is the identity)
-  const int64_t want = e->ptrain + (e->tok_grads_live ? e->ptotal - e->poff[PLB_TOK_W] : 0);
+  const int64_t want = (e->pool_grads_live ? pool_end(e) : e->ptrain) + (e->tok_grads_live ? e->ptotal - e->poff[PLB_TOK_W] : 0);
   if (e->piece_floats != want)
     return fail("gradient exchange covered %lld of %lld floats", (long long)e->piece_floats, (long long)want);
   HIPTRY(ev_record(e, e->ev_comm_done, e->comm_stream));
@@ -400,9 +400,11 @@ extern "C" int plb_allreduce_grads(PlbEngine* e, void* stream) {
   if (e->comm_pending) return join_comm(e, s);   // the loss call issued the pieces: join them
   if (e->grads_reduced) return 0;
   HB_W(s, e->grads, e->ptotal * 4, "in-stream all-reduce of the gradient buffer");
-  int rc = g_rccl.AllReduce(e->grads, e->grads, (size_t)e->ptrain, kNcclFloat32, kNcclSum, e->comm, s);
+  // (live pooler gradients lie right behind the trainable range: the same collective covers them)
+  const int64_t first = e->pool_grads_live ? pool_end(e) : e->ptrain;
+  int rc = g_rccl.AllReduce(e->grads, e->grads, (size_t)first, kNcclFloat32, kNcclSum, e->comm, s);
   e->piece_count = 1;
-  e->piece_floats = e->ptrain;
+  e->piece_floats = first;
   if (rc == kNcclSuccess && e->tok_grads_live) {
     const int64_t o = e->poff[PLB_TOK_W];
     rc = g_rccl.AllReduce(e->grads + o, e->grads + o, (size_t)(e->ptotal - o), kNcclFloat32, kNcclSum, e->comm, s);

@@ -109,6 +109,7 @@ struct PlbEngine {
   int64_t o_lnx = 0, o_lnerr = 0;
   int64_t o_embpart = 0;   // chunk partial rows of the table sums keyed by position_ids / token_type_ids (embed_inputs.hip)
   int64_t o_keywords = 0;  // key-mask words of a plb_*_masked call (key_mask.hip): [max_batch][2 * ceil(max_seq / 64)] uint32
+  int64_t o_pool_dpre = 0, o_pool_dh0 = 0;   // pooler backward of plb_encode_bwd_pooled (pooler_bwd.hip): fp32 [max_batch][H] each
   // plb_masked_report's own regions (engine_eval.cpp): ranks and row losses when the caller takes none, the token head's
   // per-block counts. No other entry point reads or writes them.
   int64_t o_rep_rank = 0, o_rep_nll = 0, o_rep_tok = 0;
@@ -141,6 +142,7 @@ struct PlbEngine {
   int64_t last_exec_rows[2] = {0, 0};   // token rows the last forward / loss call executed | the B*S it stood for (plb_last_call_rows)
   bool tok_grads_live = false;  // the last loss call produced token-head gradients (AdamW then steps them)
   bool head_grads_live = true;  // ... phoneme-head gradients (false after plb_encode_bwd: AdamW then stops at PLB_HEAD_W)
+  bool pool_grads_live = false; // the last plb_encode_bwd_pooled call took a d_pooled: the pooler range holds gradients
   bool tok_pad_zeroed = false;  // pad columns of the transposed copy are zeroed once
   int tok_steps = 0;            // AdamW steps the token head has taken (its own bias correction)
   // ---- what the last loss call left for plb_masked_report (engine_eval.cpp): set by loss_impl in engine_calls.cpp, cleared by
@@ -167,7 +169,7 @@ struct PlbEngine {
   bool grads_fresh = false;     // a backward entry point wrote the gradient buffer and no add has consumed it yet
   bool win_open = false;        // between a FIRST add and its LAST
   const char* win_closed_by = "no FIRST add has opened one";
-  bool win_head = false, win_tok = false;   // union of what the window's micro-steps produced (the encoder range always is)
+  bool win_head = false, win_tok = false, win_pool = false;   // union of what the window's micro-steps produced (the encoder range always is)
   bool win_reduced = false;     // the window's micro-steps came in all-reduced (overlap on) or not: they must agree
   const float* norm_src = nullptr;   // the LAST add left norm_nparts partials behind the four result floats of this buffer
   int norm_nparts = 0;
@@ -363,6 +365,7 @@ void drop_final(PlbEngine* e, const char* by);
 // engine.cpp
 int sync_transposes(PlbEngine* e, hipStream_t s, bool exact_fp8 = true);
 // engine_optim.cpp
+inline int64_t pool_end(const PlbEngine* e) { return e->poff[PLB_POOL_B] + e->psize[PLB_POOL_B]; }   // end of the pooler range
 void end_accum_window(PlbEngine* e, const char* by);
 
 #pragma GCC visibility pop

@@ -3,7 +3,8 @@
 // plb_adamw_step_groups; plb_lamb_plan, plb_lamb_step). Host bookkeeping of a window of micro-steps plus launches of
 // optim.hip and lamb.hip; no workspace of its own: the accumulator, the norm buffer and the LAMB buffer are the caller's.
 // Only writer of PlbEngine's accumulation block (grads_fresh / norm_nparts are also reset by begin_training_call,
-// engine_calls.cpp); after a LAST add it sets head_grads_live, tok_grads_live and grads_reduced to what the window accumulated.
+// engine_calls.cpp); after a LAST add it sets head_grads_live, tok_grads_live, pool_grads_live and grads_reduced to what the
+// window accumulated.
 // The four update entries share one preamble (begin_update) and, with the two norm entries, one description of the ranges a
 // step covers (step_ranges); the hyper-parameter refusals are written once (check_groups).
 #include <cmath>
@@ -37,11 +38,15 @@ int begin_update(PlbEngine* e, const Update& u, hipStream_t s, Own own) {
   return 0;
 }
 
-// One range of the flat buffers that a step covers with a launch of its own. There are at most two: the trainable range up
+// One range of the flat buffers that a step covers with a launch of its own. There are at most three: the trainable range up
 // to the phoneme head (after plb_encode_bwd the head has no gradient: no update, as torch skips a parameter whose .grad is
-// None; parameters, both moments and the bf16 copy of the head stay as they are), and the token head, which only dual-head
-// steps train (no gradient, no update, as the pooler between the two) and which keeps its OWN step count: torch.optim.AdamW
-// keeps one per parameter, so a head that starts training late gets its own bias correction.
+// None; parameters, both moments and the bf16 copy of the head stay as they are); the pooler, which only a
+// plb_encode_bwd_pooled call with a d_pooled (or a window of such calls) gives a gradient, and which shares the engine's step
+// count as the phoneme head does; and the token head, which only dual-head steps train and which keeps its OWN step count:
+// torch.optim.AdamW keeps one per parameter, so a head that starts training late gets its own bias correction. The pooler and
+// the token head are never live together (plb_encode_bwd* clears tok_grads_live, a loss call clears pool_grads_live, an
+// accumulation window that would hold both is refused), so the pooler takes the token head's slot of partial sums. It counts
+// no left-out update of its own: word 1 counts the step for the engine's count, word 2 rewinds the token head's.
 struct StepRange {
   int64_t a, b;          // [a, b); a is also the offset into params / grads / exp_avg / exp_avg_sq / the bf16 copy
   int step;              // the range's step count
@@ -57,6 +62,10 @@ template <class Launch>
 int step_ranges(PlbEngine* e, int step, Launch launch) {
   const StepRange enc = {0, e->head_grads_live ? e->ptrain : e->poff[PLB_HEAD_W], step, 1, 1, 0, false};
   if (launch(enc)) return 1;
+  if (e->pool_grads_live) {
+    const StepRange pool = {e->poff[PLB_POOL_W], pool_end(e), step, 0, 0, PLB_NORM_PARTS, false};
+    if (launch(pool)) return 1;
+  }
   if (!e->tok_grads_live || e->NT <= 0) return 0;
   const StepRange tok = {e->poff[PLB_TOK_W], e->ptotal, e->tok_steps + 1, 2, 0, PLB_NORM_PARTS, true};
   return launch(tok) ? 1 : 0;
@@ -127,11 +136,15 @@ extern "C" int plb_grad_accum_add(PlbEngine* e, int32_t phase, float* norm_buf, 
   if (phase != 0 && e->grads_reduced != e->win_reduced)
     return fail("plb_grad_accum_add: this micro-step's gradients are %s, the window's are %s", e->grads_reduced ? "all-reduced" : "local",
                 e->win_reduced ? "all-reduced" : "local");
+  // What this micro-step produced | what the window holds so far. The encoder range is always both.
+  const bool head = e->head_grads_live, tok = e->tok_grads_live && e->NT > 0, pool = e->pool_grads_live;
+  const bool uhead = phase == 0 ? false : e->win_head, utok = phase == 0 ? false : e->win_tok, upool = phase == 0 ? false : e->win_pool;
+  if ((tok || utok) && (pool || upool))
+    return fail("plb_grad_accum_add: this window would hold gradients of both the token head (a dual-head loss call) and the "
+                "pooler (plb_encode_bwd_pooled with a d_pooled): the norm buffer has three sets of partial sums, and the two "
+                "share one");
   hipStream_t s = (hipStream_t)stream;
   if (join_comm(e, s)) return 1;   // this micro-step's all-reduce pieces
-  // What this micro-step produced | what the window holds so far. The encoder range is always both.
-  const bool head = e->head_grads_live, tok = e->tok_grads_live && e->NT > 0;
-  const bool uhead = phase == 0 ? false : e->win_head, utok = phase == 0 ? false : e->win_tok;
   const bool want_sq = norm_buf != nullptr;
   auto pick = [&](bool produced, bool in_union) -> int {   // -1: nothing to launch
     if (phase == 0) return produced ? 0 : -1;
@@ -140,13 +153,18 @@ extern "C" int plb_grad_accum_add(PlbEngine* e, int32_t phase, float* norm_buf, 
     return in_union ? 3 : -1;                                   // zeros from this micro-step: its part of grads is not read
   };
   const int64_t hw = e->poff[PLB_HEAD_W], tw = e->poff[PLB_TOK_W];
-  Seg seg[3];
+  Seg seg[4];
   int nseg = 0;
   seg[nseg++] = Seg{0, hw, pick(true, phase != 0)};
   const int ph = pick(head, uhead);
   if (ph >= 0) {
     if (ph == seg[0].phase) seg[0].b = e->ptrain;   // adjacent and alike: one launch
     else seg[nseg++] = Seg{hw, e->ptrain, ph};
+  }
+  const int pp = pick(pool, upool);
+  if (pp >= 0) {
+    if (seg[nseg - 1].b == e->ptrain && seg[nseg - 1].phase == pp) seg[nseg - 1].b = pool_end(e);   // adjacent and alike again
+    else seg[nseg++] = Seg{e->ptrain, pool_end(e), pp};
   }
   const int pt = e->NT > 0 ? pick(tok, utok) : -1;
   if (pt >= 0) seg[nseg++] = Seg{tw, e->ptotal, pt};
@@ -168,6 +186,7 @@ extern "C" int plb_grad_accum_add(PlbEngine* e, int32_t phase, float* norm_buf, 
   e->grads_fresh = false;
   e->win_head = uhead || head;
   e->win_tok = utok || tok;
+  e->win_pool = upool || pool;
   if (phase == 0) { e->win_open = true; e->win_reduced = e->grads_reduced; }
   if (phase == 2) {
     e->win_open = false;
@@ -175,6 +194,7 @@ extern "C" int plb_grad_accum_add(PlbEngine* e, int32_t phase, float* norm_buf, 
     // plb_allreduce_grads, plb_grad_norm and either AdamW entry now cover exactly what the window accumulated
     e->head_grads_live = e->win_head;
     e->tok_grads_live = e->win_tok;
+    e->pool_grads_live = e->win_pool;
     e->grads_reduced = e->win_reduced;
     e->norm_src = norm_buf; e->norm_nparts = nparts; e->norm_reduced = e->grads_reduced;
   }
@@ -243,7 +263,8 @@ extern "C" int plb_adamw_step_clipped(PlbEngine* e, double lr, double beta1, dou
 namespace {
 // The tensors the next AdamW entry steps, whatever the caller's groups say: plb_adamw_step's ranges
 bool steps_tensor(const PlbEngine* e, int i) {
-  if (e->psize[i] == 0 || i == PLB_POOL_W || i == PLB_POOL_B) return false;
+  if (e->psize[i] == 0) return false;
+  if (i == PLB_POOL_W || i == PLB_POOL_B) return e->pool_grads_live;
   if (i == PLB_HEAD_W || i == PLB_HEAD_B) return e->head_grads_live;
   if (i == PLB_TOK_W || i == PLB_TOK_B) return e->tok_grads_live && e->NT > 0;
   return true;
@@ -291,8 +312,9 @@ int plan_segments(const PlbEngine* e, const PlbAdamWGroup* groups, const int32_t
       s.group = group_of[i];
       group_scalars(groups[group_of[i]], in_token_head(i) ? e->tok_steps + 1 : step, &s);
     }
-    // (the pooler lies between the trainable range and the token head: no segment reaches from one launch into the other)
-    if (n && segs[n - 1].end == s.begin && same_scalars(segs[n - 1], s)) segs[n - 1].end = s.end;
+    // (a segment never reaches from one launch of step_ranges into the next: none is merged across PLB_POOL_W, and a dead
+    // pooler lies between the trainable range and the token head)
+    if (n && i != PLB_POOL_W && segs[n - 1].end == s.begin && same_scalars(segs[n - 1], s)) segs[n - 1].end = s.end;
     else segs[n++] = s;
   }
   return n;
@@ -385,10 +407,13 @@ extern "C" int plb_grad_norm_groups(PlbEngine* e, const int32_t* group_of, doubl
 
 // ---- LAMB (include/plbert.h: plb_lamb_floats, plb_lamb_plan, plb_lamb_step; kernels: lamb.hip)
 namespace {
-// lamb_buf: [4 * PLB_NPARAM results][partials of the trainable range][partials of the token head]. A range of n floats in
-// k tensors has at most n / 1024 + k workgroups (one pair of floats each).
+// lamb_buf: [4 * PLB_NPARAM results][partials of the trainable range][partials of the token head, or of the pooler: the two
+// are never live together]. A range of n floats in k tensors has at most n / 1024 + k workgroups (one pair of floats each).
 int64_t lamb_main_pairs(const PlbEngine* e) { return e->ptrain / 1024 + PLB_NPARAM; }
-int64_t lamb_tok_pairs(const PlbEngine* e) { return (e->ptotal - e->poff[PLB_TOK_W]) / 1024 + 2; }
+int64_t lamb_tok_pairs(const PlbEngine* e) {
+  const int64_t tok = e->ptotal - e->poff[PLB_TOK_W], pool = pool_end(e) - e->poff[PLB_POOL_W];
+  return (tok > pool ? tok : pool) / 1024 + 2;
+}
 
 // One segment per live tensor, never merged: the trust ratio is a tensor's own
 int plan_lamb(const PlbEngine* e, const PlbLambGroup* groups, const int32_t* group_of, int32_t step, PlbLambSegment* segs) {
@@ -446,15 +471,25 @@ extern "C" int plb_lamb_step(PlbEngine* e, const PlbLambGroup* groups, int32_t n
   HB_W(s, lamb_buf, plb_lamb_floats(e) * 4, "LAMB (writes the partial sums and the trust ratios)");
   PlbLambSegment all[PLB_NPARAM], part[PLB_NPARAM];
   const int n = plan_lamb(e, groups, group_of, step, all);
-  // a range without a live tensor launches nothing, and the finish of the range that does run marks every other tensor as a hole
+  // A range without a live tensor launches nothing. The finishes of the ranges that do run share the result slots between
+  // them, cut at the first tensor of each later range: every tensor that is in no range's table is marked as a hole.
+  StepRange run[3];
+  int nrun = 0;
+  if (step_ranges(e, step, [&](const StepRange& r) {
+        if (range_segments(all, n, r.a, r.b, part)) run[nrun++] = r;
+        return 0;
+      }))
+    return 1;
+  auto first_tensor = [&](const StepRange& r) { int i = 0; while (e->poff[i] < r.a) ++i; return i; };
+  int ri = 0;
   if (step_ranges(e, step, [&](const StepRange& r) {
         const int k = range_segments(all, n, r.a, r.b, part);
         if (!k) return 0;
-        const int other = n - k;   // (the pooler is never live: what is not in this range is in the other one)
-        const int lo = r.token && other ? (int)PLB_TOK_W : 0, hi = !r.token && other ? (int)PLB_TOK_W : (int)PLB_NPARAM;
+        const int lo = ri == 0 ? 0 : first_tensor(run[ri]), hi = ri + 1 < nrun ? first_tensor(run[ri + 1]) : (int)PLB_NPARAM;
+        ++ri;
         const Bufs x = bufs(e, r);
         const size_t nn = (size_t)part[k - 1].end;
-        float* partials = lamb_buf + 4 * PLB_NPARAM + (r.token ? 2 * lamb_main_pairs(e) : 0);
+        float* partials = lamb_buf + 4 * PLB_NPARAM + (r.a ? 2 * lamb_main_pairs(e) : 0);   // (the pooler in the token head's place)
         count_step(e, r);   // (the plan gave the token head's tensors this count)
         TRY(plb_launch_lamb_pass1(x.p, x.g, x.m, x.v, nn, part, k, grad_scale, x.skip, r.skip_slot, norm, r.count_nonfinite,
                                   partials, s));

@@ -301,6 +301,21 @@ int plb_launch_unpack_rows(const void* src, int src_is_bf16, int lds_, const int
 // positions. H a multiple of 4.
 int plb_launch_seed_dy(const float* d_hidden, const int32_t* lengths, const int32_t* row_start, int B, int S, int H, int Tp,
                        bf16_t* dy, hipStream_t stream);
+// ---- pooler backward (pooler_bwd.hip; include/plbert.h plb_encode_bwd_pooled)
+// pooled[b,:] = tanh(W · h[b,:] + bias) with h[b,:] the fp32 image of row rows[b] (rows == NULL: b*S) of hidden (bf16, row
+// stride ldh elements, 8-byte aligned, ldh % 4 == 0). From d_pooled fp32 [B,H]: y recomputed with plb_launch_pooler's
+// arithmetic (its bits), dpre = d_pooled * (1 - y*y) [B,H], dW[o,i] = sum_b dpre[b,o] h[b,i] [H,H], db[o] = sum_b dpre[b,o]
+// [H], dh0[b,i] = sum_o dpre[b,o] W[o,i] [B,H]; b ascending, o ascending within each quarter of the rows and the four quarter
+// sums added in order; no atomics: bitwise reproducible. Every element of the four
+// outputs is written exactly once. H a multiple of 64; W, dW and d_pooled 16-byte aligned.
+int plb_launch_pooler_bwd(const bf16_t* hidden, int ldh, const int32_t* rows, int B, int S, int H, const float* W,
+                          const float* bias, const float* d_pooled, float* dpre, float* dW, float* db, float* dh0,
+                          hipStream_t stream);
+// Behind plb_launch_seed_dy (or the clear that stands for a NULL d_hidden): row rows[b] (rows == NULL: b*S) of dy [*,H] =
+// bf16(d_hidden[b,0,:] + dh0[b,:]), one fp32 add and one round to nearest even; d_hidden == NULL (fp32 [B,S,H] otherwise): a
+// zero addend. Only these B rows are written. H a multiple of 4; d_hidden and dh0 16-byte, dy 8-byte aligned.
+int plb_launch_seed_dy_first_rows(const float* d_hidden, const float* dh0, const int32_t* rows, int B, int S, int H, bf16_t* dy,
+                                  hipStream_t stream);
 // ---- per-application outputs (layer_outputs.hip; include/plbert.h PlbLayerOutputs, plb_encode_bwd_layers)
 // The attention probabilities of one application from what it left behind: out fp32 [B,NH,S,S], out[b,h,i,j] =
 // exp(scale * q_i·k_j - LSE_i) for i, j < lengths[b] — qkv as PlbAttn.qkv (bf16 [T,ldqkv], Q | K | V, head h at columns

@@ -92,11 +92,14 @@ def packed_fp8_default():
 # ---- the encoder and loss entry points (include/plbert.h): which one a call reaches, and its parameters in order ------------
 # A call reaches the NARROWEST rung that carries what the caller gave: the error texts name the rung, and a library named
 # by PLBERT_HIP_LIB that predates a rung keeps serving the calls that do not need it.
-def encoder_entry(family, layers, inputs, key_mask, d_below=None, want_d_inputs_embeds=False):
+def encoder_entry(family, layers, inputs, key_mask, d_below=None, want_d_inputs_embeds=False, d_pooled=False):
     """The symbol of ``family`` ("forward", "encode", "encode_bwd") for a call with per-application outputs (``layers``),
     embedding inputs (``inputs``) and a key mask (``key_mask``): given or not. "encode_bwd" takes the inputs and the mask of
     its live encode, and ``d_below`` (a list, or None) / ``want_d_inputs_embeds`` in place of ``layers``. The plain
-    "forward" rung is HipEngine.forward's (with a plan: that name + "_packed"); forward_layers starts at the layers rung."""
+    "forward" rung is HipEngine.forward's (with a plan: that name + "_packed"); forward_layers starts at the layers rung.
+    ``d_pooled`` ("encode_bwd" only): a gradient of pooler_output is given — the widest rung, plb_encode_bwd_pooled."""
+    if family == "encode_bwd" and d_pooled:
+        return "plb_encode_bwd_pooled"
     if family == "encode_bwd":
         layers, inputs = d_below is not None, inputs or want_d_inputs_embeds
     return "plb_" + family + ("_masked" if key_mask else "_inputs" if inputs else "_layers" if layers else "")
@@ -134,6 +137,10 @@ ENTRY_ARGS = {
     "plb_loss_fwd_bwd_packed": _LOSS1 + ("packing", "loss", "stream"),
     "plb_loss_fwd_bwd_dual": _LOSS + ("loss", "loss_parts", "stream"),
     "plb_loss_fwd_bwd_dual_packed": _LOSS + ("packing", "loss", "loss_parts", "stream"),
+}
+# the rung only a gradient of pooler_output reaches (tests/test_pooler_bwd_host.py holds it to the header like the table above)
+POOLED_ENTRY_ARGS = {
+    "plb_encode_bwd_pooled": _ENC_KM + ("d_hidden", "d_below", "d_inputs_embeds", "d_pooled", "stream"),
 }
 
 
@@ -568,7 +575,8 @@ class HipEngine:
                 return v.data_ptr()
             return C.byref(v) if isinstance(v, C.Structure) else C.addressof(v)
         pieces = dict(pieces, e=self.handle, stream=self._stream())
-        _lib.check(getattr(self.L, name)(*[arg(pieces[k]) for k in ENTRY_ARGS[name]]), name)
+        names = ENTRY_ARGS[name] if name in ENTRY_ARGS else POOLED_ENTRY_ARGS[name]
+        _lib.check(getattr(self.L, name)(*[arg(pieces[k]) for k in names]), name)
 
     # ---- per-application outputs (include/plbert.h: PlbLayerOutputs) ----
     @staticmethod
@@ -684,7 +692,7 @@ class HipEngine:
         self._last_encoder_call = (int(B), int(S), lens, packing)
         return hid if layers is None else (hid, hs, at)
 
-    def encode_bwd(self, d_hidden, d_below=None, want_d_inputs_embeds=False):
+    def encode_bwd(self, d_hidden, d_below=None, want_d_inputs_embeds=False, d_pooled=None):
         """Backward of the live ``encode`` from ``d_hidden`` = d(loss)/d(hidden), fp32 [B,S,H] (values at pad positions
         are ignored): the encoder range of ``self.grads`` is overwritten, the phoneme head's is zeroed and the next
         ``adamw_step`` leaves the head alone (plb_encode_bwd). ``d_below`` (plb_encode_bwd_layers): a list of L entries,
@@ -692,7 +700,9 @@ class HipEngine:
         at the last slot). ``want_d_inputs_embeds`` (plb_encode_bwd_inputs): returns fp32 [B,S,embedding_size], the gradient
         of the pre-LayerNorm embedding sum per token (zeros at pad positions) — the gradient of ``inputs_embeds``, or the
         per-phoneme saliency of a call that took ids. The key mask of an ``encode(key_mask=...)`` is taken from the live
-        record (plb_encode_bwd_masked)."""
+        record (plb_encode_bwd_masked). ``d_pooled`` (plb_encode_bwd_pooled): d(loss)/d(pooler_output) fp32 [B,H] — the
+        pooler backward joins the call: the pooler's range of ``self.grads`` is overwritten, position 0 of every sample
+        receives its share, and the next optimizer step covers the pooler; ``d_hidden`` may then be None."""
         live = getattr(self, "_live_encode", None)
         if live is None:
             raise RuntimeError("encode_bwd: no live encode() on this engine (one backward per encode)")
@@ -710,7 +720,16 @@ class HipEngine:
             return d
 
         d = dev(d_hidden, "d_hidden")
-        if d_below is None and d is None:
+        dp = None
+        if d_pooled is not None:
+            dp = torch.as_tensor(d_pooled)
+            if dp.dtype != torch.float32 or dp.device != self.device or not dp.is_contiguous():
+                dp = dp.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(dp.shape) != (B, self.cfg.hidden_size):
+                raise ValueError(f"d_pooled must be {[B, self.cfg.hidden_size]}, got {tuple(dp.shape)}")
+            if dp.data_ptr() % 16:   # (a view into a larger buffer: the engine takes 16-byte aligned gradients)
+                dp = dp.clone()
+        if d_below is None and d is None and dp is None:
             raise ValueError("encode_bwd: d_hidden is None and no d_below is given")
         below = None if d_below is None else [dev(g, f"d_below[{l}]") for l, g in enumerate(d_below)]
         self._live_encode = None
@@ -719,9 +738,10 @@ class HipEngine:
             arr = None if below is None else self._ptr_array(below, self.cfg.num_hidden_layers, "d_below", shape)
             die = (torch.empty((B, S, self.cfg.embedding_size), dtype=torch.float32, device=self.device)
                    if want_d_inputs_embeds else None)
-            self._entry(encoder_entry("encode_bwd", None, ein is not None, km is not None, below, want_d_inputs_embeds),
+            self._entry(encoder_entry("encode_bwd", None, ein is not None, km is not None, below, want_d_inputs_embeds,
+                                      dp is not None),
                         dict(ids=ids, inputs=ein, key_mask=km, lengths=lens, B=B, S=S, packing=pk, d_hidden=d, d_below=arr,
-                             d_inputs_embeds=die))
+                             d_inputs_embeds=die, d_pooled=dp))
             del keep_in
         return die
 

@@ -21,8 +21,10 @@ where a forward joins torch's autograd graph: an encoder whose ``differentiable`
 (``AlbertModel(config, finetune=True)``, or ``model.encoder.differentiable = True`` on a wrapped one)
 returns a ``last_hidden_state`` that requires grad while the module is in training mode and grad is
 enabled; ``backward()`` runs plb_encode_bwd and hands every encoder Parameter its slice of the
-engine's gradient buffer.  ``pooler_output`` is returned DETACHED (the pooler gets no gradient), and
-``last_hidden_state`` is zero at pad positions.
+engine's gradient buffer.  ``pooler_output`` is returned DETACHED (the pooler gets no gradient) unless the encoder's
+``train_pooler`` attribute is set (``AlbertModel(config, finetune=True, train_pooler=True)``): then it joins the graph too — a
+loss on it reaches the pooler's two Parameters and, through position 0 of the last hidden state, the encoder
+(plb_encode_bwd_pooled).  ``last_hidden_state`` is zero at pad positions.
 
 ``attention_mask`` of ``AlbertModel.forward`` follows transformers' 2-D rule and need not be a prefix (left padding, keys
 knocked out, a sub-span of a buffer): key j of a sample takes part in the softmax of all its queries iff its entry is nonzero.
@@ -129,6 +131,9 @@ def _lengths_and_key_mask(attention_mask):
     return extent, (None if prefix else attention_mask)
 
 
+_POOLER_NAMES = ("encoder.pooler.weight", "encoder.pooler.bias")
+
+
 class _Encode(torch.autograd.Function):
     """The differentiable forward as ONE autograd node, whatever the call carries: HipEngine.encode / encode_bwd choose the
     entry points (plb_encode / plb_encode_bwd for the plain call, the _layers / _inputs / _masked rungs for the rest). The
@@ -137,23 +142,26 @@ class _Encode(torch.autograd.Function):
     which are marked non-differentiable. The backward hands the gradient of the last slot to the engine as d_hidden and those
     of the slots below as d_below; a slot nothing downstream used arrives as None and goes in as a NULL pointer. Every encoder
     Parameter receives the view of its slice of ``engine.grads`` (the scheme of train._FusedLoss), the pooler and the heads
-    receive None. ``inputs_embeds`` (or None) is an input of the node: when it requires grad it receives the gradient of the
+    receive None. ``train_pooler``: ``pooler_output`` (plb_pooler on the last hidden state) is one more output, the last one;
+    when its gradient arrives it goes to the engine as d_pooled and the two pooler Parameters receive their views too; when it
+    does not (None), the call and the Parameters' None are those of a forward without the flag. ``inputs_embeds`` (or None) is an input of the node: when it requires grad it receives the gradient of the
     pre-LayerNorm embedding sum, and the word table — which took no part — receives None, as in torch. ``key_mask`` (or
     None): a mask that is no prefix (the engine's live record hands it to the backward)."""
 
     @staticmethod
     def forward(ctx, engine, names, ids, lengths, packing, want_hs, want_at, token_type_ids, position_ids, inputs_embeds,
-                key_mask, *params):
+                key_mask, train_pooler, *params):
         layers = dict(hidden_states=want_hs, attentions=want_at) if want_hs or want_at else None
         out = engine.encode(ids, lengths, packing, layers=layers, token_type_ids=token_type_ids, position_ids=position_ids,
                             inputs_embeds=inputs_embeds, key_mask=key_mask)
         hid, hs, at = (out, None, None) if layers is None else out
         ctx.engine, ctx.names, ctx.serial, ctx.want_hs = engine, names, engine._encode_serial, want_hs
         ctx.embeds = inputs_embeds is not None
+        ctx.pooled = bool(train_pooler)
         ctx.set_materialize_grads(False)
         if want_at:
             ctx.mark_non_differentiable(*at)
-        return (*(hs if want_hs else [hid]), *(at if want_at else []))
+        return (*(hs if want_hs else [hid]), *(at if want_at else []), *([engine.pooler(hid)] if train_pooler else []))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -161,13 +169,14 @@ class _Encode(torch.autograd.Function):
         eng = ctx.engine
         nl = eng.cfg.num_hidden_layers
         g = [None if x is None else x.contiguous().float() for x in grads[:nl + 1 if ctx.want_hs else 1]]
+        gp = grads[-1].contiguous().float() if ctx.pooled and grads[-1] is not None else None
         gone = "a later engine call overwrote the activations of this forward (the engine keeps one differentiable " \
                "forward at a time: call backward() before the next forward, loss call or optimizer step)"
         if eng._live_encode is None or eng._encode_serial != ctx.serial:
             raise RuntimeError(gone)
         try:
             die = eng.encode_bwd(g[-1], d_below=g[:-1] if ctx.want_hs else None,
-                                 want_d_inputs_embeds=ctx.embeds and ctx.needs_input_grad[9])
+                                 want_d_inputs_embeds=ctx.embeds and ctx.needs_input_grad[9], d_pooled=gp)
         except RuntimeError as ex:
             if "no live plb_encode stash" in str(ex):
                 raise RuntimeError(f"{gone}: {ex}") from ex
@@ -177,16 +186,20 @@ class _Encode(torch.autograd.Function):
         pg = []
         for n in ctx.names:
             off, size, shp = eng.layout[n]
-            pg.append(eng.grads[off:off + size].view(shp) if off + size <= end and n not in without else None)
-        return (None,) * 9 + (die, None) + tuple(pg)
+            has = off + size <= end and n not in without or gp is not None and n in _POOLER_NAMES
+            pg.append(eng.grads[off:off + size].view(shp) if has else None)
+        return (None,) * 9 + (die, None, None) + tuple(pg)
 
 
 class AlbertModel(nn.Module):
     """Drop-in for ``transformers.AlbertModel`` on this path (modeling_albert.py:338-408)."""
 
     def __init__(self, config, add_pooling_layer=True, max_batch=_DEFAULT_MAX_BATCH, max_seq=None, device=None, seed=0,
-                 finetune=False):
-        """``finetune=True``: the encoder sits on a TRAINING engine of its own and is ``differentiable`` — the model a TTS
+                 finetune=False, train_pooler=False):
+        """``train_pooler=True`` (with ``finetune``; the attribute of the same name may be set later, also on a wrapped
+        encoder): ``pooler_output`` of a differentiable forward carries gradient — into ``pooler.weight`` / ``pooler.bias``
+        and, through position 0 of the last hidden state, into the encoder. Off (the default): it is detached.
+        ``finetune=True``: the encoder sits on a TRAINING engine of its own and is ``differentiable`` — the model a TTS
         training loop fine-tunes (reference README "Finetuning": ``bert(texts, attention_mask=...).last_hidden_state``
         feeding the caller's layers, ``optimizer.step('bert')``)."""
         super().__init__()
@@ -203,6 +216,7 @@ class AlbertModel(nn.Module):
         # wrapper's training engine before this one has allocated anything but them.
         # finetune: all layers' activations, gradients and AdamW moments (the stand-in head sizes stay: the head is unused)
         self.differentiable = bool(finetune)
+        self.train_pooler = bool(train_pooler)
         self._build(HipEngine(config, 4, 0, max_batch=self._max_batch, max_seq=self._max_seq, device=device,
                               train=bool(finetune)),
                     reference_init_state_dict(config, 4, 0, seed=seed), prefix="encoder.")
@@ -265,6 +279,7 @@ class AlbertModel(nn.Module):
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
         lengths, key_mask = _lengths_and_key_mask(attention_mask)
+        pooled = None
         want_hs, want_at = bool(output_hidden_states), bool(output_attentions)
         nl, eng = self.config.num_hidden_layers, self._engine
         given = {k: v for k, v in dict(token_type_ids=token_type_ids, position_ids=position_ids, inputs_embeds=inputs_embeds,
@@ -272,13 +287,15 @@ class AlbertModel(nn.Module):
         packing = _packing_from_lengths(self, lengths, input_ids if input_ids is not None else inputs_embeds)
         if getattr(self, "differentiable", False) and self.training and torch.is_grad_enabled():
             # fine-tuning: the forward joins the autograd graph (_Encode); pad positions of last_hidden_state are zeros and
-            # pooler_output is DETACHED (the pooler receives no gradient, as in every other call of this library)
+            # pooler_output is DETACHED (the pooler receives no gradient) unless train_pooler makes it an output of the node
+            pool_grad = bool(getattr(self, "train_pooler", False))
             names, params = [], []
             for n, p in self.named_parameters():
                 names.append("encoder." + n)
                 params.append(p)
             outs = _Encode.apply(eng, names, input_ids, lengths, packing, want_hs, want_at, token_type_ids, position_ids,
-                                 inputs_embeds, key_mask, *params)
+                                 inputs_embeds, key_mask, pool_grad, *params)
+            pooled, outs = (outs[-1], outs[:-1]) if pool_grad else (None, outs)
             hs = tuple(outs[:nl + 1]) if want_hs else None
             at = tuple(outs[-nl:]) if want_at else None
             hid = hs[-1] if want_hs else outs[0]
@@ -294,8 +311,9 @@ class AlbertModel(nn.Module):
             (hid, _, _), hs, at = eng.forward(input_ids, lengths, want_hidden=True, want_phoneme=False, packing=packing), None, None
         # pooler (modeling_albert.py:403): computed for API completeness (plb_pooler), never used by the loss; the pooler of
         # position 0, hole or not, as in transformers
-        return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=eng.pooler(hid.detach()), hidden_states=hs,
-                                          attentions=at)
+        if pooled is None:
+            pooled = eng.pooler(hid.detach())
+        return BaseModelOutputWithPooling(last_hidden_state=hid, pooler_output=pooled, hidden_states=hs, attentions=at)
 
 
 class _HeadModel(nn.Module):

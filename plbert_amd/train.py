@@ -126,6 +126,8 @@ def _clip_norm(owner, engine, grad_scale, **which):
     return norm_buf
 
 
+_POOLER_NAMES = ("encoder.pooler.weight", "encoder.pooler.bias")
+
 # torch.optim.AdamW's group keys beside the hyper-parameters, at its defaults: what its state_dict carries in every group
 TORCH_ADAMW_EXTRA = {"amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
                      "fused": None, "decoupled_weight_decay": True}
@@ -133,7 +135,7 @@ TORCH_ADAMW_EXTRA = {"amsgrad": False, "maximize": False, "foreach": None, "capt
 
 def _scatter_state(engine, selection):
     """``selection`` ({state-dict name: torch's {step, exp_avg, exp_avg_sq}}) into the flat moment buffers, zeroed first; the
-    pooler never trains and is left out. Returns (names written, step count outside the token head, the token head's; 0:
+    pooler (which has state once a ``train_pooler`` encoder has stepped it) shares the count of the encoder. Returns (names written, step count outside the token head, the token head's; 0:
     none). The fused update keeps ONE count each: differing counts are refused before anything is written."""
     e = engine
     ta = e.token_range[0]
@@ -141,8 +143,6 @@ def _scatter_state(engine, selection):
     for n, st in selection.items():
         off, size, _ = e.layout[n]
         is_tok = bool(e.num_tokens) and off >= ta
-        if off + size > e.trainable and not is_tok:
-            continue
         kept.append(n)
         (tok_steps if is_tok else steps).add(int(float(st["step"])))
     if len(steps) > 1 or len(tok_steps) > 1:
@@ -713,6 +713,7 @@ class AdamW:
         self.engine = model.engine
         self.defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.step_count = 0
+        self._pool_stepped = False   # the ungrouped step has covered the pooler (state_dict then holds its moments)
         self.grad_scale = 1.0
         self.engine._on_handoff_timeout.append(_rewind_steps(self))
         # (a stand-alone AlbertModel names its parameters without the "encoder." prefix of the engine's layout)
@@ -788,9 +789,10 @@ class AdamW:
             # autograd may have handed the Parameter a copy of its gradient slice (or user code replaced
             # / clipped .grad): whatever .grad holds now is what the fused update must consume
             off, size, shp = e.layout[n]
-            in_range = off + size <= e.trainable or off >= e.token_range[0]
-            if p.grad is not None and in_range and p.grad.data_ptr() != e.grads.data_ptr() + 4 * off:
+            if p.grad is not None and p.grad.data_ptr() != e.grads.data_ptr() + 4 * off:
                 e.grads[off:off + size].view(shp).copy_(p.grad)
+            if p.grad is not None and n in _POOLER_NAMES:
+                self._pool_stepped = True   # (a train_pooler backward: the engine steps the pooler with this count)
         self.step_count += 1
         d = self.defaults
         e.adamw_step(self.step_count, d["lr"], d["betas"], d["eps"], d["weight_decay"], self.grad_scale,
@@ -800,8 +802,9 @@ class AdamW:
         """torch.optim.AdamW layout ({'state': {index: {step, exp_avg, exp_avg_sq}}, 'param_groups': [...]}) with
         parameter indices in ``model.parameters()`` order, so the 'optimizer' entry of a checkpoint
         (train.py:417-421) can be loaded by either implementation. Parameters that never received a
-        gradient (the pooler; the token head before its first dual-head step) have no state, as in torch; the token
-        head carries its own step count (it may have started later than the encoder)."""
+        gradient (the pooler without ``train_pooler``; the token head before its first dual-head step) have no state, as in
+        torch; the token head carries its own step count (it may have started later than the encoder), the pooler shares
+        the encoder's."""
         e = self.engine
         d = self.defaults
         state = {}
@@ -813,8 +816,8 @@ class AdamW:
                 steps = self.step_count
             elif off >= ta and e.num_tokens:
                 steps = tok_steps
-            else:
-                steps = 0
+            else:   # the pooler: state once a step has covered it
+                steps = self.step_count if self._groups is not None or self._pool_stepped else 0
             if self._groups is not None and n not in self._first_step:
                 steps = 0   # (frozen so far: torch has no state for a parameter it never stepped)
             if steps > 0:
@@ -840,7 +843,8 @@ class AdamW:
             for k in ("lr", "betas", "eps", "weight_decay"):
                 if k in g:
                     self.defaults[k] = tuple(g[k]) if k == "betas" else g[k]
-            _, self.step_count, e.token_head_steps = _scatter_state(e, {self._names[int(i)]: st for i, st in sd["state"].items()})
+            kept, self.step_count, e.token_head_steps = _scatter_state(e, {self._names[int(i)]: st for i, st in sd["state"].items()})
+            self._pool_stepped = any(n in _POOLER_NAMES for n in kept)
             return
         self.step_count = int(sd["step"])  # compact form written by early versions of this class
         e.exp_avg[: e.trainable].copy_(sd["exp_avg"])
