@@ -10,20 +10,22 @@ tests/test_attention_rows_host.py shows on the CPU that it catches a one-row def
 Cases: every edge of the 32-query wave, the 64-key tile and the 128-row query tile as a length; sequences that end inside
 a tile; a sharp (near one-hot) and a flat softmax; heads of different magnitude; compact queries.
 
-Maxima of the row error of the model (attention_rounded against attention_fp64; the bound is 4 x these). The model
-column was evaluated on the CPU; THE KERNELS' COLUMN IS STILL MISSING: this module has not run on an MI355X yet (no device
-was available when it was written). The first -s run prints, per case and form, `rows <case> form <f>: <output> model <max>
-kernel <max>`; those lines belong here.
+Maxima of the row error of the model (attention_rounded against attention_fp64; the bound is 4 x these) and of the kernels
+on an MI355X, from the lines a -s run prints per case and form (`rows <case> form <f>: <output> model <max> kernel <max>`).
+The two forms of the backward are different kernels that agree bit for bit on all but a few elements (edges: 407 of
+1,474,560 elements of dqkv differ, sharp: 109 of 196,608), and the maxima they print coincide in every case to the digits
+shown: one kernel column serves both forms.
 
-    case      ctx        dq         dk         dv         kernel (form 0 | form 1)
-    edges     3.32e-03   4.13e-03   4.02e-03   3.84e-03   not measured
-    tail130   3.43e-03   4.43e-03   4.91e-03   4.22e-03   not measured
-    tail40    2.91e-03   2.84e-02   9.79e-03   3.20e-03   not measured
-    tail600   3.46e-03   4.11e-03   3.77e-03   3.53e-03   not measured (form 0 only)
-    sharp     2.99e-03   6.39e+00   8.42e-01   4.36e-03   not measured
-    flat      2.75e-03   3.31e-03   3.30e-03   3.14e-03   not measured
-    heads     3.05e-03   3.81e-02   1.03e-02   3.84e-03   not measured
-    compact   3.07e-03   3.59e-03   4.03e-03   3.65e-03   not measured (form 0 only)
+              model                                        kernel (form 0 and form 1)
+    case      ctx        dq         dk         dv          ctx        dq         dk         dv
+    edges     3.32e-03   4.13e-03   4.02e-03   3.84e-03    3.78e-03   4.09e-03   4.01e-03   3.85e-03
+    tail130   3.43e-03   4.43e-03   4.91e-03   4.22e-03    3.43e-03   4.43e-03   4.91e-03   4.22e-03
+    tail40    2.91e-03   2.84e-02   9.79e-03   3.20e-03    2.91e-03   2.84e-02   9.79e-03   3.20e-03
+    tail600   3.46e-03   4.11e-03   3.77e-03   3.53e-03    3.48e-03   4.11e-03   3.79e-03   3.53e-03   (form 0 only)
+    sharp     2.99e-03   6.39e+00   8.42e-01   4.36e-03    4.16e-03   6.39e+00   1.02e+00   4.36e-03
+    flat      2.75e-03   3.31e-03   3.30e-03   3.14e-03    2.69e-03   3.31e-03   3.29e-03   3.14e-03
+    heads     3.05e-03   3.81e-02   1.03e-02   3.84e-03    3.64e-03   3.81e-02   1.03e-02   3.84e-03
+    compact   3.07e-03   3.59e-03   4.03e-03   3.65e-03    3.26e-03   3.70e-03   4.05e-03   3.65e-03   (form 0 only)
 
 sharp: a row whose P is 0.9999 on one key has dS = P (dP - delta) a thousand times smaller than the bf16 rounding of the
 context that delta is formed from, so dq / dk of such rows are ill-conditioned for ANY kernel that reads a bf16 context: the
