@@ -825,7 +825,13 @@ int plb_profile_read(double* ms, int64_t* launches, double* flops, double* bytes
  *   plb_set_gemm_nt_tile / plb_set_gemm_nt_prefetch / plb_set_attn_bwd_fused
  *                                 force a tile, a K-loop form or the attention-backward form for the launches that
  *                                 follow (0 / -1 / -1 restore the per-shape policy; attention backward: 1 single-kernel
- *                                 form, 0 two kernels, 2 policy + split by sample), tests/test_gpu_kernels.py, tools/ */
+ *                                 form, 0 two kernels, 2 policy + split by sample), tests/test_gpu_kernels.py, tools/
+ *                                 plb_set_gemm_nt_tile(64 / -64): the kernel is still picked per shape, and every / no
+ *                                 launch that goes to the small NT kernel takes its 64x64 form (0: the shape rule of
+ *                                 csrc/gemm.hip decides; 128 forces the small kernel in its 128x128 form). The environment
+ *                                 variable PLBERT_NT_SMALL_TILE=128|64, read once per process, does the same for a whole
+ *                                 run (tools/step_ab.py); the setter's 64 / -64 / 128 go before it. Results are equal bit
+ *                                 for bit in both forms, tests/test_gpu_gemm_small_tile.py */
 void plb_debug_skip_piece(int index);
 void plb_debug_ln_fault(int mode, int launches);
 int plb_debug_hb_audit(PlbEngine* e, int32_t on, int32_t break_wait);

@@ -196,6 +196,11 @@ static int gemm_ln_bwd(PlbEngine* e, PlbGemmNT* g, const F8Op* f8, bool fused, c
 // zeros from their sums). Compact GEMMs of ~2,300 rows do not fill one-tile-per-CU grids, so this part runs on the
 // small-shape launches (GEMM + LayerNorm kernels, gelu by act 1 / 2): 168 -> 75 us forward, 164 -> 86 us backward, and the
 // three weight-gradient GEMMs that stack its rows read (L-1) Tp + Mc rows instead of L Tp (measured: profiles/r05_*).
+// Those figures are with the small NT kernel's 128x128 form (90-240 workgroups on 256 CUs). Its 64x64 form, which
+// plb_launch_gemm_nt picks for these grids, takes the three GEMMs of the forward from 62 to 44 us and the three of the
+// backward from 62 to 41 us at 1,920 rows (7.8 + 16.3 + 19.6 and 15.2 + 18.1 + 7.3 us by themselves; the head's logits
+// 13.7 -> 6.3, its dH 9.2 -> 5.1), results bit for bit the same: profiles/nt_small_tile_kernel_ab.txt; the step:
+// 9.085 -> 9.003 ms, profiles/nt_small_tile_step_ab_same_box.txt.
 // fp8 calls run this part in bf16 too and add the 1-byte images of the compact rows that their stacked weight-gradient
 // GEMMs read. Not taken by dual-head calls (the token loss reads every position), when more than half of the positions
 // are masked, and under PLBERT_PRUNE_LAST=0.

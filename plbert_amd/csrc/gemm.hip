@@ -8,7 +8,8 @@
 //            operands are token-major, so fragments come from transposed LDS reads).
 //
 // Tile 128x128, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16x32 tiles, fp32
-// accumulate. NT operands are staged by LDS-DMA (global_load_lds), TN operands through registers
+// accumulate (NT also as 64x64, waves of 32x32, for launches too small to fill the chip). NT operands
+// are staged by LDS-DMA (global_load_lds), TN operands through registers
 // (double buffered, one barrier per k-tile); LDS images are XOR-swizzled / strip-rotated so ds_read_b128 / ds_read_b64_tr_b16 and
 // the ds_write_b128 staging stores are bank-conflict free.
 #include "common.h"
@@ -20,15 +21,27 @@ namespace {
 constexpr int BM = 128, BN = 128, BK = 64;
 
 // ---- NT ------------------------------------------------------------------------------------------
-// LDS image of a [128 rows][64 k] bf16 tile: 128-B rows, 16-B chunk index XORed with (row>>1)&7.
+// LDS image of a [TILE rows][64 k] bf16 tile: 128-B rows, 16-B chunk index XORed with (row>>1)&7.
 DEVI int nt_lds_off(int row, int chunk) { return row * BK + ((chunk ^ ((row >> 1) & 7)) << 3); }
 
-template <int ACT, bool OUTF32>
+// TILE x TILE outputs per workgroup, 256 threads = 2x2 waves of (TILE/2) x (TILE/2) each.
+//   128: the form every launch took before the 64 form existed (64 KiB of LDS, 4x4 MFMA tiles per wave)
+//    64: for launches whose 128x128 grid leaves most of the chip idle: four times the workgroups, each staging half the
+//        bytes and issuing a quarter of the MFMAs per K-tile (32 KiB of LDS, 2x2 MFMA tiles per wave, two workgroups per
+//        CU and more)
+// An output element sees the same K-chunks of 32 in the same order through the same fragment layout and the same
+// epilogue in both forms: the tile only decides which wave computes which 16x16 patch, results are equal bit for bit
+// (tests/test_gpu_gemm_small_tile.py).
+template <int ACT, bool OUTF32, int TILE>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(PlbGemmNT p) {
-  __shared__ __attribute__((aligned(16))) bf16_t smem[2][2][BM * BK];  // [stage][A|B] 64 KiB
+  constexpr int WT = TILE / 2;    // rows and columns of a wave's patch
+  constexpr int FR = WT / 16;     // MFMA tiles per wave and direction
+  constexpr int SR = TILE / 4;    // rows of A and of B a wave stages per K-tile
+  constexpr int ND = SR / 8;      // DMA instructions per operand for them (8 rows x 128 B each)
+  __shared__ __attribute__((aligned(16))) bf16_t smem[2][2][TILE * BK];  // [stage][A|B] 64 KiB (32 KiB at TILE 64)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-  const int nbn = (p.N + BN - 1) / BN;
+  const int nbn = (p.N + TILE - 1) / TILE;
   const int nwg = gridDim.x;
   const int logical = xcd_remap(blockIdx.x, nwg);
   const int bm = logical / nbn, bn = logical % nbn;
@@ -36,51 +49,52 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(PlbGemmNT p) {
   // Staging: LDS-DMA (global_load_lds, 16 B per lane). One wave-instruction fills 8 rows x 128 B of
   // the image; the destination is wave-uniform base + lane*16, so the XOR swizzle is applied to the
   // per-lane SOURCE chunk (row r, stored chunk c' <- global chunk c' ^ ((r>>1)&7)). Each wave stages
-  // rows [32w, 32w+32) of A and of B: 8 DMA instructions per k-tile, no VGPR round trip.
+  // rows [SR w, SR w + SR) of A and of B: 2 ND DMA instructions per k-tile (8 / 4), no VGPR round trip.
+  // (SR w is a multiple of 16, so (r>>1)&7 of row SR w + 8 i + (lane>>3) is (4 i + (lane>>4)) & 7 in both forms.)
   const int uw = __builtin_amdgcn_readfirstlane(wave);
   const int drow = lane >> 3, dch = lane & 7;
-  const bf16_t* gA = p.A + (size_t)(bm * BM + uw * 32 + drow) * p.lda;
-  const bf16_t* gB = p.B + (size_t)(bn * BN + uw * 32 + drow) * p.ldb;
+  const bf16_t* gA = p.A + (size_t)(bm * TILE + uw * SR + drow) * p.lda;
+  const bf16_t* gB = p.B + (size_t)(bn * TILE + uw * SR + drow) * p.ldb;
   const size_t sa = (size_t)8 * p.lda, sb = (size_t)8 * p.ldb;
-  int sch[4];
+  int sch[ND];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) sch[i] = (dch ^ ((4 * i + (lane >> 4)) & 7)) * 8;
+  for (int i = 0; i < ND; ++i) sch[i] = (dch ^ ((4 * i + (lane >> 4)) & 7)) * 8;
   typedef __attribute__((address_space(1))) const void* gptr_t;
   typedef __attribute__((address_space(3))) void* lptr_t;
 #define NT_STAGE(st, kt)                                                                              \
   do {                                                                                                \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                   \
+    _Pragma("unroll") for (int i = 0; i < ND; ++i) {                                                  \
       __builtin_amdgcn_global_load_lds((gptr_t)(gA + i * sa + (size_t)(kt) * BK + sch[i]),            \
-                                       (lptr_t)&smem[st][0][(uw * 32 + i * 8) * BK], 16, 0, 0);       \
+                                       (lptr_t)&smem[st][0][(uw * SR + i * 8) * BK], 16, 0, 0);       \
       __builtin_amdgcn_global_load_lds((gptr_t)(gB + i * sb + (size_t)(kt) * BK + sch[i]),            \
-                                       (lptr_t)&smem[st][1][(uw * 32 + i * 8) * BK], 16, 0, 0);       \
+                                       (lptr_t)&smem[st][1][(uw * SR + i * 8) * BK], 16, 0, 0);       \
     }                                                                                                 \
   } while (0)
 #define NT_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
-  f32x4 acc[4][4];
+  f32x4 acc[FR][FR];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < FR; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < FR; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int frow = lane & 15, fq = lane >> 4;
-  // (row>>1)&7 of a fragment row depends on the lane only: rows are wr*64 + i*16 + frow
+  // (row>>1)&7 of a fragment row depends on the lane only: rows are wr*WT + i*16 + frow, WT a multiple of 16
   const int fsw = (frow >> 1) & 7;
-  const int offA = (wr * 64 + frow) * BK, offB = (wc * 64 + frow) * BK;
+  const int offA = (wr * WT + frow) * BK, offB = (wc * WT + frow) * BK;
 #define NT_COMPUTE(st)                                                                                   \
   do {                                                                                                   \
     const bf16_t* sA = smem[st][0];                                                                      \
     const bf16_t* sB = smem[st][1];                                                                      \
     _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                                   \
       const int ch = ((kk * 4 + fq) ^ fsw) << 3;                                                         \
-      bf16x8 af[4], bfr[4];                                                                              \
-      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                    \
+      bf16x8 af[FR], bfr[FR];                                                                            \
+      _Pragma("unroll") for (int i = 0; i < FR; ++i) {                                                   \
         af[i] = *(const bf16x8*)&sA[offA + i * 16 * BK + ch];                                            \
         bfr[i] = *(const bf16x8*)&sB[offB + i * 16 * BK + ch];                                           \
       }                                                                                                  \
-      _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                                   \
-        _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                                                 \
+      _Pragma("unroll") for (int mi = 0; mi < FR; ++mi)                                                  \
+        _Pragma("unroll") for (int ni = 0; ni < FR; ++ni)                                                \
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ni], af[mi], acc[mi][ni], 0, 0, 0);  \
     }                                                                                                    \
   } while (0)
@@ -103,11 +117,11 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(PlbGemmNT p) {
 
   // epilogue: lane holds C[m][n0..n0+3]
 #pragma unroll
-  for (int mi = 0; mi < 4; ++mi) {
-    const int m = bm * BM + wr * 64 + mi * 16 + frow;
+  for (int mi = 0; mi < FR; ++mi) {
+    const int m = bm * TILE + wr * WT + mi * 16 + frow;
 #pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-      nt_epilogue<ACT, OUTF32>(p, acc[mi][ni], m, bn * BN + wc * 64 + ni * 16 + fq * 4);
+    for (int ni = 0; ni < FR; ++ni)
+      nt_epilogue<ACT, OUTF32>(p, acc[mi][ni], m, bn * TILE + wc * WT + ni * 16 + fq * 4);
   }
 }
 
@@ -214,8 +228,33 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(PlbGemmTN p) {
 
 }  // namespace
 
-static int g_nt_tile = 0;  // 0: pick per shape; 128 / 256 / 384: force that tile where the shape allows
+// 0: pick per shape; 128 / 256 / 384 / 1256: force that tile where the shape allows; 64 / -64: per-shape choice of the
+// kernel, and every / no launch of the small kernel in its 64x64 form
+static int g_nt_tile = 0;
 extern "C" void plb_set_gemm_nt_tile(int tile) { g_nt_tile = tile; }
+
+// PLBERT_NT_SMALL_TILE = 128 | 64 (read once per process): every launch of the small kernel takes that form whatever
+// small_tile's rule says, so one library can be compared with itself. The setter's 64 / -64 / 128 go before it.
+static int nt_small_tile_env() {
+  static const int v = [] {
+    const char* e = getenv("PLBERT_NT_SMALL_TILE");
+    const int n = e ? atoi(e) : 0;
+    return (n == 64 || n == 128) ? n : 0;
+  }();
+  return v;
+}
+// Form of a launch that goes to the small kernel. The 128x128 grid of the compact rows of a pruned last application
+// (~2,000 rows: 96 workgroups at N 768 and 2048), of the phoneme head (32) and of the map-in's dE product (128) leaves
+// most of the 256 CUs idle while every workgroup walks its whole K chain at ~0.8 us per K-tile; the 64x64 form puts four
+// times the workgroups on the chip and halves the cost of a K-tile. Measured per shape class, kept where every run of
+// the 64 form was below every run of the 128 form: profiles/nt_small_tile_kernel_ab.txt.
+static int small_tile(const PlbGemmNT* p) {
+  if (g_nt_tile == 64) return 64;
+  if (g_nt_tile == -64 || g_nt_tile == 128) return 128;
+  if (nt_small_tile_env()) return nt_small_tile_env();
+  const long grid128 = (long)(p->M / BM) * ((p->N + BN - 1) / BN);
+  return grid128 < 256 ? 64 : 128;
+}
 
 // Tile policy: fill 256 CUs. efficiency = tiles / (rounds * 256) with one workgroup per CU for the
 // big tiles; 128x384 moves 4/3 the operand bytes per flop of 256x256, hence the small handicap.
@@ -226,6 +265,7 @@ static int pick_tile(const PlbGemmNT* p) {
   if (g_nt_tile == 256) return ok256 ? 256 : 128;
   if (g_nt_tile == 384) return ok384 ? 384 : (ok256 ? 256 : 128);
   if (g_nt_tile == 1256) return ok1256 ? 1256 : 128;
+  // (64 / -64 choose the small kernel's form only: the kernel is picked per shape)
   if ((long)p->M * p->N < 256L * 256 * 64) return 128;  // small problems: more, smaller workgroups
   double e256 = 0, e384 = 0, e1256 = 0;
   if (ok256) { const long t = (long)(p->M / 256) * (p->N / 256); e256 = (double)t / (double)(((t + 255) / 256) * 256); }
@@ -263,20 +303,21 @@ extern "C" int plb_launch_gemm_nt(const PlbGemmNT* p, int act, int out_f32, hipS
     plb_prof_end(tokb, stream);
     return rc;
   }
-  // the 128x128 kernel (head, map-in and other small products; some run on the engine's side stream, where a launch
+  // the small kernel, 128x128 or 64x64 (head, map-in and other small products; some run on the engine's side stream, where a launch
   // can sit behind the main stream's grid for longer than it runs) is a class of its own: "gemm_nt" is the pipeline kernel
+  if ((out_f32 && act != 0) || act < 0 || act > 2) return 1;
   const int tok = plb_prof_begin(out_f32 ? PLB_K_GEMM_NT_F32 : PLB_K_GEMM_NT_SMALL, stream, 2.0 * mnk, algo_bytes);
-  if (out_f32) {
-    if (act != 0) return 1;
-    hipLaunchKernelGGL((gemm_nt_kernel<0, true>), grid, block, 0, stream, *p);
-  } else if (act == 0) {
-    hipLaunchKernelGGL((gemm_nt_kernel<0, false>), grid, block, 0, stream, *p);
-  } else if (act == 1) {
-    hipLaunchKernelGGL((gemm_nt_kernel<1, false>), grid, block, 0, stream, *p);
-  } else if (act == 2) {
-    hipLaunchKernelGGL((gemm_nt_kernel<2, false>), grid, block, 0, stream, *p);
+  if (small_tile(p) == 64) {
+    const dim3 grid64((p->M / 64) * ((p->N + 63) / 64));
+    if (out_f32) hipLaunchKernelGGL((gemm_nt_kernel<0, true, 64>), grid64, block, 0, stream, *p);
+    else if (act == 0) hipLaunchKernelGGL((gemm_nt_kernel<0, false, 64>), grid64, block, 0, stream, *p);
+    else if (act == 1) hipLaunchKernelGGL((gemm_nt_kernel<1, false, 64>), grid64, block, 0, stream, *p);
+    else hipLaunchKernelGGL((gemm_nt_kernel<2, false, 64>), grid64, block, 0, stream, *p);
   } else {
-    return 1;
+    if (out_f32) hipLaunchKernelGGL((gemm_nt_kernel<0, true, 128>), grid, block, 0, stream, *p);
+    else if (act == 0) hipLaunchKernelGGL((gemm_nt_kernel<0, false, 128>), grid, block, 0, stream, *p);
+    else if (act == 1) hipLaunchKernelGGL((gemm_nt_kernel<1, false, 128>), grid, block, 0, stream, *p);
+    else hipLaunchKernelGGL((gemm_nt_kernel<2, false, 128>), grid, block, 0, stream, *p);
   }
   plb_prof_end(tok, stream);
   return hipGetLastError() == hipSuccess ? 0 : 2;

@@ -19,11 +19,20 @@ SHAPES = [(16384, 768, 768), (16384, 2304, 768), (16384, 2048, 768), (16384, 768
 MSTORE_ZERO = False
 WITH_RES = False
 
+# The launches of the small NT kernel in the bench step (--small-ab): (label, N, K, act, residual, fp32 output). The compact
+# rows of the pruned last application: dense, FFN up (gelu), FFN output forward; their three dX products backward.
+SMALL_COMPACT = [("dense fwd", 768, 768, 0, True, False), ("ffn fwd gelu", 2048, 768, 1, False, False),
+                 ("ffn_out fwd", 768, 2048, 0, True, False), ("ffn_out dX", 2048, 768, 2, False, False),
+                 ("ffn dX", 768, 2048, 0, False, False), ("dense dX", 768, 768, 0, False, False)]
+SMALL_AB = ([(f"{n} M{M}", M, N, K, a, r, f) for M in (1920, 2048) for (n, N, K, a, r, f) in SMALL_COMPACT] +
+            [("head logits", 2048, 180, 768, 0, False, True), ("head dH", 2048, 768, 256, 0, False, False),
+             ("map-in dE", 16384, 128, 768, 0, False, False)])
 
-def time_nt(L, M, N, K, act, iters=20):
+
+def time_nt(L, M, N, K, act, iters=20, res=None, out_f32=0):
     dev = "cuda"
     A = (torch.randn(M, K, device=dev)).to(torch.bfloat16)
-    B = (torch.randn(N, K, device=dev) * 0.05).to(torch.bfloat16)
+    B = (torch.randn((N + 127) // 128 * 128, K, device=dev) * 0.05).to(torch.bfloat16)  # the kernels read whole tiles of B rows
     Cb = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     C2 = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     bias = torch.randn(N, device=dev)
@@ -31,7 +40,10 @@ def time_nt(L, M, N, K, act, iters=20):
     p.A, p.lda, p.B, p.ldb, p.M, p.N, p.K, p.Mstore = A.data_ptr(), K, B.data_ptr(), K, M, N, K, (0 if MSTORE_ZERO else M)
     p.bias = bias.data_ptr()
     p.C, p.ldc, p.C2, p.ldc2 = Cb.data_ptr(), N, C2.data_ptr(), N
-    if WITH_RES:
+    if out_f32:
+        Cf = torch.empty(M, 256, dtype=torch.float32, device=dev)
+        p.Cf, p.ldcf = Cf.data_ptr(), 256
+    if WITH_RES if res is None else res:
         R = torch.randn(M, N, device=dev).to(torch.bfloat16)
         p.res, p.ldr = R.data_ptr(), N
     if act == 2:
@@ -39,11 +51,11 @@ def time_nt(L, M, N, K, act, iters=20):
         p.aux, p.ldaux = U.data_ptr(), N
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     for _ in range(3):
-        assert L.plb_launch_gemm_nt(C.byref(p), act, 0, s) == 0
+        assert L.plb_launch_gemm_nt(C.byref(p), act, out_f32, s) == 0
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(iters):
-        L.plb_launch_gemm_nt(C.byref(p), act, 0, s)
+        L.plb_launch_gemm_nt(C.byref(p), act, out_f32, s)
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / iters
@@ -86,6 +98,8 @@ def main():
     ap.add_argument("--tn", action="store_true")
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--small", action="store_true")
+    ap.add_argument("--small-ab", action="store_true",
+                    help="the step's small-kernel launches in the 128x128 form (tile -64) and the 64x64 form (tile 64)")
     ap.add_argument("--shapes", default="", help="M,N,K;M,N,K;... instead of the built-in NT list")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--libs", default="", help="other builds of libplbert_hip.so to time beside the product build")
@@ -97,6 +111,21 @@ def main():
     MSTORE_ZERO = args.nostore
     WITH_RES = args.res
     L = _lib.lib()
+    if args.small_ab:
+        time_nt(L, *SHAPES[0], 0)  # warm the clocks
+        res = {}
+        for rep in range(args.reps):
+            for (label, M, N, K, act, r, f32) in SMALL_AB:
+                for tile in (-64, 64):
+                    L.plb_set_gemm_nt_tile(tile)
+                    ms, _ = time_nt(L, M, N, K, act, iters=50, res=r, out_f32=int(f32))
+                    res.setdefault((label, M, N, K, tile), []).append(ms)
+        L.plb_set_gemm_nt_tile(0)
+        for (label, M, N, K, tile), v in res.items():
+            v = sorted(v)
+            print(f"{label:20s} M {M:6d} N {N:5d} K {K:5d}  form {abs(tile) if tile > 0 else 128:4d}  min {v[0]*1e3:7.2f} us  "
+                  f"median {v[len(v) // 2]*1e3:7.2f} us  max {v[-1]*1e3:7.2f} us", flush=True)
+        return
     if args.tn:
         libs = [("main", L)] + [(os.path.basename(q), _lib.declare(C.CDLL(os.path.abspath(q), mode=C.RTLD_LOCAL)))
                                 for q in args.libs.split(",") if q]
