@@ -335,6 +335,7 @@ INTERNAL = {
     "plb_launch_gemm_nt": (i32, [P(PlbGemmNT), i32, i32, vp]),
     "plb_launch_gemm_nt_big": (i32, [P(PlbGemmNT), i32, i32, i32, vp]),
     "plb_gemm_nt_colpart_rows": (i32, [i32, i32, i32]),
+    "plb_gemm_nt_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),   # (PlbGemmNTPlan*: csrc/gemm_nt_plan.h)
     "plb_launch_gemm_tn": (i32, [P(PlbGemmTN), vp]),
     "plb_launch_gemm_tn_fp8": (i32, [P(PlbGemmTN), vp]),
     "plb_launch_gemm_tn_big": (i32, [P(PlbGemmTN), vp]),
@@ -437,6 +438,19 @@ def lib():
     except OSError as ex:
         raise HipLibraryMissing(f"cannot load {LIB_PATH}: {ex}") from ex
     return _lib
+
+
+NT_PLAN_FIELDS = ("rc", "family", "tile", "tile_m", "tile_n", "kloop", "grid", "block", "cls", "colpart_rows", "flops", "bytes")
+
+
+def gemm_nt_plan(M, N, K, form=0, operands=0, opts=0, tile=0):
+    """The launch plan of an NT GEMM as a dict of csrc/gemm_nt_plan.h's PlbGemmNTPlan (ten ints, two doubles): what the
+    launcher of that form (0 plain, 1 / 2 gelu, 3 / 4 cross-entropy passes, 5 / 6 LayerNorm, 7 / 8 gelu-derivative stash, 9
+    fp32 out) and operand kind (0 bf16, 1 / 2 fp8 with e4m3 / e5m2 A) will do; tools size their buffers by it."""
+    import struct
+    buf = C.create_string_buffer(struct.calcsize("10i2d"))
+    lib().plb_gemm_nt_plan(M, N, K, form, operands, opts, tile, buf)
+    return dict(zip(NT_PLAN_FIELDS, struct.unpack("10i2d", buf.raw)))
 
 
 def profile_enable(on):

@@ -178,7 +178,8 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
     e->o_part2 = cv.take(L * e->part_rows * 3 * H * 4);
     e->o_parte = cv.take((int64_t)e->emb_blocks * 2 * E * 4);
     e->o_dxe = cv.take(Tp * E * 4);
-    e->o_ducol = cv.take(L * (2 * Tp / 128) * I * 4);  // column-sum partials of dU from the GEMM epilogue
+    e->ducol_rows = (int)(2 * Tp / 128);   // (2 per row tile of the narrowest pipeline tile, 128 rows)
+    e->o_ducol = cv.take(L * e->ducol_rows * I * 4);  // column-sum partials of dU from the GEMM epilogue
     e->qkvcol_rows = c.max_batch * ((c.max_seq + 127) / 128) * 4;
     // ... of dQKV from the attention-backward stores, one set per application: the kernels only STORE their partial rows
     // (summing over the applications in place made every wave end on a global read-modify-write: +0.19 ms per step)
@@ -208,7 +209,8 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
       e->o_wtT = cv.take(rup(H, 128) * NTp * 2);
       e->o_tdl = cv.take(Tp * NTp * 2);
       e->o_tscr = cv.take(32 * NTp * 4);
-      e->o_tcolp = cv.take(2 * (Tp / 128) * NTp * 4);
+      e->tcolp_rows = (int)(2 * (Tp / 128));
+      e->o_tcolp = cv.take(e->tcolp_rows * NTp * 4);
       e->o_tgrad = cv.take(NTp * H * 4);
     }
   }

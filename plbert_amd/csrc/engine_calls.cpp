@@ -289,8 +289,12 @@ static int token_head(PlbEngine* e, const Call& c, bool backward, const bf16_t* 
   const Rows& rw = c.rw;
   const int64_t Tp = rw.Tp;
   hipStream_t s = c.s;
-  const int tile = (Tp % 256 == 0) ? 256 : 1256;          // 256x256 or 128x256: both 256 columns wide
-  const int ntile = NTp / 256, cprows = tile == 256 ? 2 * (int)(Tp / 256) : 2 * (int)(Tp / 128);
+  // the two passes run on one tile, 256 columns wide (one per-tile maximum / sum per 256 columns); pass 2 leaves cprows rows
+  // of column sums
+  const PlbGemmNTPlan pass1 = nt_plan(Tp, NTp, H, PLB_NT_CE1), pass2 = nt_plan(Tp, NTp, H, PLB_NT_CE2, PLB_NT_BF16, PLB_NT_COLPART);
+  if (pass1.rc || pass2.rc || pass1.tile != pass2.tile) return fail("token_head: no fused GEMM + cross-entropy form for %lld x %d x %d", (long long)Tp, NTp, H);
+  const int tile = pass1.tile, ntile = NTp / pass1.tile_n, cprows = pass2.colpart_rows;
+  if (backward && cprows > e->tcolp_rows) return fail("token_head: pass 2 writes %d column-sum rows, %d are reserved", cprows, e->tcolp_rows);
   float* tlrows = e->at<float>(e->o_tlrows);
   float* tloss = e->at<float>(e->o_tloss);
   int64_t* ttgt = e->at<int64_t>(e->o_ttgt);
@@ -304,8 +308,7 @@ static int token_head(PlbEngine* e, const Call& c, bool backward, const bf16_t* 
   g.bias = e->at<float>(e->o_bt);
   g.ce_cols = NT; g.ce_tgt = ttgt;
   g.ce_pmax = e->at<float>(e->o_tpmax); g.ce_psum = e->at<float>(e->o_tpsum); g.ce_tlogit = e->at<float>(e->o_ttl);
-  const double ce_flops = 2.0 * (double)Tp * NTp * H;
-  int tok = plb_prof_begin(PLB_K_GEMM_NT_CE, s, ce_flops, 0.0);
+  int tok = plb_prof_begin(pass1.cls, s, pass1.flops, pass1.bytes);
   TRY(plb_launch_gemm_nt_big(&g, tile, 3, 0, s));
   plb_prof_end(tok, s);
   if (rw.row_start) {
@@ -323,7 +326,7 @@ static int token_head(PlbEngine* e, const Call& c, bool backward, const bf16_t* 
   bf16_t* tdl = e->at<bf16_t>(e->o_tdl);
   g.ce_lse = e->at<float>(e->o_tlse); g.ce_w = e->at<float>(e->o_tw);
   g.C = tdl; g.ldc = NTp; g.colpart = e->at<float>(e->o_tcolp);
-  tok = plb_prof_begin(PLB_K_GEMM_NT_CE, s, ce_flops, 0.0);
+  tok = plb_prof_begin(pass2.cls, s, pass2.flops, pass2.bytes);
   TRY(plb_launch_gemm_nt_big(&g, tile, 4, 0, s));
   plb_prof_end(tok, s);
   TRY(plb_launch_colsum(g.colpart, 0, (size_t)cprows, NTp, NTp, e->grd(PLB_TOK_B), NT, 0, e->at<float>(e->o_tscr), 1, s));

@@ -8,12 +8,19 @@ static int f8_w(const PlbEngine* e, int w) { return F8_NSITE * e->L + w; }
 static float* f8_amax(const PlbEngine* e, int i) { return e->at<float>(e->o_f8amax) + (int64_t)i * F8_AMAX_WORDS; }
 static float* f8_scale(const PlbEngine* e, int i) { return e->at<float>(e->o_f8scale) + i; }
 float* f8_deq(const PlbEngine* e, int i) { return e->at<float>(e->o_f8deq) + i; }
-// every GEMM of the fp8 set has a pipeline-tile form at this token count (else the whole call runs in bf16)
+// every GEMM of the fp8 set has a plan at this token count (else the whole call runs in bf16): the four products of the
+// forward on e4m3 activations, the four dX products of the backward on e5m2 gradients (the fused forms are taken where
+// they have a plan too, the unfused ones must exist)
 static bool fp8_shapes_ok(const PlbEngine* e, int64_t Tp) {
-  const int64_t H = e->H, I = e->I;
-  if (!(H == 768 || H == 1024) || I % 256 || H % 128 || I % 128) return false;
-  if (Tp % 128) return false;
-  return (3 * H) % 384 == 0 || (3 * H) % 256 == 0;
+  const int H = e->H, I = e->I;
+  if (!(H == 768 || H == 1024)) return false;
+  const struct { int N, K, form, ops; } set[8] = {
+      {3 * H, H, PLB_NT_PLAIN, PLB_NT_FP8_E4M3}, {H, H, PLB_NT_PLAIN, PLB_NT_FP8_E4M3}, {I, H, PLB_NT_GELU, PLB_NT_FP8_E4M3},
+      {H, I, PLB_NT_PLAIN, PLB_NT_FP8_E4M3}, {I, H, PLB_NT_GELUBWD, PLB_NT_FP8_E5M2}, {H, I, PLB_NT_PLAIN, PLB_NT_FP8_E5M2},
+      {H, H, PLB_NT_PLAIN, PLB_NT_FP8_E5M2}, {H, 3 * H, PLB_NT_PLAIN, PLB_NT_FP8_E5M2}};
+  for (const auto& g : set)
+    if (nt_plan(Tp, g.N, g.K, g.form, g.ops).rc) return false;
+  return true;
 }
 // per-tensor e4m3 copies of the fp8 GEMMs' weights.
 // exact = true (after plb_sync_weights / plb_set_fp8: the weights may be anything): maximum, scale, quantisation — three

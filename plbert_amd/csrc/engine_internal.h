@@ -90,6 +90,8 @@ struct PlbEngine {
   int64_t ws_bytes;
   int ln_blocks, emb_blocks;
   int part_rows = 0;            // rows per layer reserved in o_part1 / o_part2
+  int ducol_rows = 0;           // rows per layer reserved in o_ducol, rows reserved in o_tcolp: upper bounds of what a launch's
+  int tcolp_rows = 0;           // plan (gemm_nt_plan.h) may write at the token capacity; every call checks its plans against them
   int ln_fuse = 3;              // bit 0: LayerNorm forward in the producing GEMM's epilogue, bit 1: LayerNorm backward
   int64_t lnx_bytes = 0;
   bool gelu_dstash_on = true;   // PLBERT_GELU_STASH=u restores the pre-activation stash
@@ -347,6 +349,8 @@ bool f8_call(const PlbEngine* e, int64_t Tp, bool train);
 bool tn8_ok(const PlbEngine* e, int64_t Mtot);
 // engine_layers.cpp
 PlbGemmNT nt_desc(const bf16_t* A, const bf16_t* B, int64_t M, int N, int K);
+// the plan (gemm_nt_plan.h) of a packed [M, N] x K launch: what the launcher of that form and operand kind will do
+PlbGemmNTPlan nt_plan(int64_t M, int N, int K, int form, int operands = PLB_NT_BF16, int opts = 0);
 int qkvcol_rows(int B, int S);
 Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int prows = 0, int du_rows = 0);
 bool prune_enabled();

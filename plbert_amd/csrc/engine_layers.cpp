@@ -64,21 +64,27 @@ static PlbGemmNT f8_operands(const PlbGemmNT* g, const F8Op* f8) {
   q.deq_a = f8->deq_a; q.deq_b = f8->deq_b;
   return q;
 }
-static int gemm_nt_any(PlbGemmNT* g, int act, const F8Op* f8, hipStream_t s) {
-  if (!f8) return plb_launch_gemm_nt(g, act, 0, s);
-  PlbGemmNT q = f8_operands(g, f8);
-  return plb_launch_gemm_nt_fp8(&q, act, f8->a_bf8, s);
+// g in form `form` (PlbGemmNTForm: plain and gelu forms, LayerNorm forms, gelu-derivative-stash forms) on bf16 operands or,
+// with f8, on their 1-byte images: the launcher of that form and operand kind
+static int gemm_nt_any(PlbGemmNT* g, int form, const F8Op* f8, hipStream_t s) {
+  PlbGemmNT q;
+  if (f8) { q = f8_operands(g, f8); g = &q; }
+  const int a_bf8 = f8 ? f8->a_bf8 : 0;
+  switch (form) {
+    case PLB_NT_LNFWD: case PLB_NT_LNBWD:
+      return f8 ? plb_launch_gemm_nt_fp8_ln(g, form, a_bf8, s) : plb_launch_gemm_nt_ln(g, form, s);
+    case PLB_NT_GELUD: case PLB_NT_GELUDBWD:
+      return f8 ? plb_launch_gemm_nt_fp8_gelud(g, form == PLB_NT_GELUDBWD, a_bf8, s)
+                : plb_launch_gemm_nt_gelud(g, form == PLB_NT_GELUDBWD, s);
+  }
+  return f8 ? plb_launch_gemm_nt_fp8(g, form, a_bf8, s) : plb_launch_gemm_nt(g, form, 0, s);
 }
-// the LayerNorm forms (5 / 6) and the gelu-derivative-stash forms, bf16 or fp8 operands
-static int gemm_nt_ln_any(PlbGemmNT* g, int mode, const F8Op* f8, hipStream_t s) {
-  if (!f8) return plb_launch_gemm_nt_ln(g, mode, s);
-  PlbGemmNT q = f8_operands(g, f8);
-  return plb_launch_gemm_nt_fp8_ln(&q, mode, f8->a_bf8, s);
-}
-static int gemm_nt_gelud_any(PlbGemmNT* g, int backward, const F8Op* f8, hipStream_t s) {
-  if (!f8) return plb_launch_gemm_nt_gelud(g, backward, s);
-  PlbGemmNT q = f8_operands(g, f8);
-  return plb_launch_gemm_nt_fp8_gelud(&q, backward, f8->a_bf8, s);
+// What the launchers will do is asked, never restated: which fusions a call takes, and how many partial rows its launches
+// write, come from the plan of the launch at the call's shape.
+PlbGemmNTPlan nt_plan(int64_t M, int N, int K, int form, int operands, int opts) {
+  PlbGemmNTPlan pl;
+  plb_gemm_nt_plan((int)M, N, K, form, operands, opts, 0, &pl);
+  return pl;
 }
 // the 1-byte image + running maximum a launch writes beside its output (scale in, maxima out)
 static void f8_out(PlbGemmNT* g, uint8_t* img, int ld, const F8Site& q, int bf8) {
@@ -115,15 +121,17 @@ Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int
 // LayerNorm in the epilogue of the GEMM that produces its input (gemm_ln.hip, gemm_fp8_ln.hip): the shapes it exists for,
 // in bf16 and in fp8 calls alike (the fp8 forms write the 1-byte images the standalone LayerNorm kernels used to write);
 // an fp8 CALIBRATION call computes in bf16 (it must equal the bf16 path bit for bit: tests/test_gpu_fp8.py).
-static bool ln_fusable(const PlbEngine* e, int64_t Tp, int bit) {
-  const int H = e->H;
-  return (e->ln_fuse & bit) && Tp % 1024 == 0 && (H % 384 == 0 ? H / 384 : H % 256 == 0 ? H / 256 : 99) <= 4;
+// (bit 1: the forward forms of a call, bit 2: the backward forms, whose A operand is a gradient: e5m2 in an fp8 call. K is H,
+// I or 3H: multiples of 128 all, plb_create sees to that, so one query stands for the two launches of a direction.)
+static bool ln_fusable(const PlbEngine* e, int64_t Tp, int bit, bool f8) {
+  const int ops = !f8 ? PLB_NT_BF16 : bit == 1 ? PLB_NT_FP8_E4M3 : PLB_NT_FP8_E5M2;
+  return (e->ln_fuse & bit) && nt_plan(Tp, e->H, e->H, bit == 1 ? PLB_NT_LNFWD : PLB_NT_LNBWD, ops).rc == 0;
 }
 // Does the forward of this call stash gelu_new'(u) instead of u (plb_launch_gemm_nt_gelud)? Recorded in the engine: the
 // backward of the same call must read the stash the way the forward wrote it — the stash is in the LANE layout of the
-// tile that wrote it (256x256 in bf16 calls, 128x256 in fp8 calls), so forward and backward of a call run in one mode.
+// tile that wrote it (the plan's for the call's operand kind and row count), so forward and backward of a call run in one mode.
 static bool gelu_dstash(PlbEngine* e, int64_t Tp, bool f8_call) {
-  e->u_is_derivative = e->gelu_dstash_on && (f8_call ? Tp % 128 == 0 : Tp % 256 == 0) && e->I % 256 == 0;
+  e->u_is_derivative = e->gelu_dstash_on && nt_plan(Tp, e->I, e->H, PLB_NT_GELUD, f8_call ? PLB_NT_FP8_E4M3 : PLB_NT_BF16).rc == 0;
   return e->u_is_derivative;
 }
 static void ln_fields(const PlbEngine* e, PlbGemmNT* g, const float* gamma, const float* beta, float* mean, float* rstd) {
@@ -145,10 +153,10 @@ static int gemm_ln_fwd(PlbEngine* e, PlbGemmNT* g, const F8Op* f8, bool fused, c
     g->C2 = y; g->ldc2 = H;
     ln_fields(e, g, ln.gamma, ln.beta, ln.mean, ln.rstd);
     if (y8) f8_out(g, y8, H, q, 0);
-    TRY(gemm_nt_ln_any(g, 5, f8, s));
+    TRY(gemm_nt_any(g, PLB_NT_LNFWD, f8, s));
     return 0;
   }
-  TRY(gemm_nt_any(g, 0, f8, s));
+  TRY(gemm_nt_any(g, PLB_NT_PLAIN, f8, s));
   PlbLayerNorm p;
   memset(&p, 0, sizeof(p));
   p.x = g->C; p.ldx = H; p.gamma = ln.gamma; p.beta = ln.beta; p.eps = e->c.layer_norm_eps;
@@ -178,10 +186,10 @@ static int gemm_ln_bwd(PlbEngine* e, PlbGemmNT* g, const F8Op* f8, bool fused, c
     g->C = dx; g->aux = ln.pre; g->ldaux = e->H; g->colpart = ln.partials;
     ln_fields(e, g, ln.gamma, nullptr, ln.mean, ln.rstd);
     if (dx8) f8_out(g, dx8, e->H, q, 1);
-    TRY(gemm_nt_ln_any(g, 6, f8, s));
+    TRY(gemm_nt_any(g, PLB_NT_LNBWD, f8, s));
     return 0;
   }
-  TRY(gemm_nt_any(g, 0, f8, s));
+  TRY(gemm_nt_any(g, PLB_NT_PLAIN, f8, s));
   return ln_bwd(e, ln, nblocks, g->C, dx, T, Tzero, dx8, q, s);
 }
 
@@ -338,7 +346,7 @@ int run_encoder(PlbEngine* e, const Call& c, bool stash, bf16_t** xout, const Pr
     const float* sc1[1] = {sX.scale}; uint8_t* dst1[1] = {first.x8}; float* am1[1] = {sX.amax};
     TRY(plb_launch_quantize_multi(1, src1, bf1, n1, sc1, dst1, am1, s));
   }
-  const bool fuse_f = ln_fusable(e, Tp, 1);
+  const bool fuse_f = ln_fusable(e, Tp, 1, f8);
   const bool dstash = gelu_dstash(e, Tp, f8);
   // do the weight-gradient GEMMs of this call read the 1-byte images? Then gelu(u), dU and dQKV leave as images alone.
   // (Needs the derivative stash: forms 1 / 2 always write their bf16 outputs.)
@@ -353,7 +361,7 @@ int run_encoder(PlbEngine* e, const Call& c, bool stash, bf16_t** xout, const Pr
     g = nt_desc(sl.x, e->wbf(PLB_Q_W), Tp, 3 * H, H);
     g.bias = e->par(PLB_Q_B); g.C = sl.qkv; g.ldc = 3 * H;
     const F8Op oq = f8_op(sl.x8, sX, F8Weight(e, F8W_QKV), 0);
-    TRY(gemm_nt_any(&g, 0, f8 ? &oq : nullptr, s));
+    TRY(gemm_nt_any(&g, PLB_NT_PLAIN, f8 ? &oq : nullptr, s));
     PlbAttn at;
     memset(&at, 0, sizeof(at));
     at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = c.lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H;
@@ -407,9 +415,9 @@ int run_encoder(PlbEngine* e, const Call& c, bool stash, bf16_t** xout, const Pr
     // gradient take the image)
     if (dstash) {
       if (tn8) { g.C2 = nullptr; g.ldc2 = 0; }
-      TRY(gemm_nt_gelud_any(&g, 0, f8 ? &o1 : nullptr, s));
+      TRY(gemm_nt_any(&g, PLB_NT_GELUD, f8 ? &o1 : nullptr, s));
     } else {
-      TRY(gemm_nt_any(&g, 1, f8 ? &o1 : nullptr, s));
+      TRY(gemm_nt_any(&g, PLB_NT_GELU, f8 ? &o1 : nullptr, s));
     }
     if (calib) TRY(plb_launch_amax(sl.g, 1, (size_t)T, I, I, sG.amax, s));
     // FFN output + residual, LayerNorm 2 (+ the next application's input image)
@@ -486,9 +494,9 @@ static int post_attention_bwd(PlbEngine* e, const Bwd& c, int l, const Slots& sl
   const F8Op ou = f8_op(sl.dp8, sDP, F8Weight(e, F8W_2T), 1);
   if (e->u_is_derivative) {   // what the forward of THIS call stashed; fp8: dU leaves as its e5m2 image alone
     if (e->tn8_call) g.C = nullptr;
-    TRY(gemm_nt_gelud_any(&g, 1, c.f8 ? &ou : nullptr, s));
+    TRY(gemm_nt_any(&g, PLB_NT_GELUDBWD, c.f8 ? &ou : nullptr, s));
   } else {
-    TRY(gemm_nt_any(&g, 2, c.f8 ? &ou : nullptr, s));
+    TRY(gemm_nt_any(&g, PLB_NT_GELUBWD, c.f8 ? &ou : nullptr, s));
   }
   if (c.calib) TRY(plb_launch_amax(sl.du, 1, (size_t)T, I, I, sDU.amax, s));
   // dA = dU · W1 + dpre2 is the gradient of LayerNorm 1's output. Fused: its backward runs in this GEMM's epilogue and dA
@@ -504,7 +512,7 @@ static int post_attention_bwd(PlbEngine* e, const Bwd& c, int l, const Slots& sl
   g = nt_desc(sl.dpre1, e->at<bf16_t>(e->o_wdT), Tp, H, H);
   g.C = e->at<bf16_t>(e->o_dctx); g.ldc = H;
   const F8Op oc = f8_op(sl.dp18, sDP1, F8Weight(e, F8W_DT), 1);
-  TRY(gemm_nt_any(&g, 0, c.f8 ? &oc : nullptr, s));
+  TRY(gemm_nt_any(&g, PLB_NT_PLAIN, c.f8 ? &oc : nullptr, s));
   return 0;
 }
 
@@ -603,7 +611,7 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
   g.res = res; g.ldr = H; g.C = dx; g.ldc = H;
   const F8Op ox = f8_op(sl.dq8, sDQ, F8Weight(e, F8W_QKVT), 1);
   if (l == 0) {   // the gradient of the embeddings' map-in output: the tail takes it
-    TRY(gemm_nt_any(&g, 0, c.f8 ? &ox : nullptr, s));
+    TRY(gemm_nt_any(&g, PLB_NT_PLAIN, c.f8 ? &ox : nullptr, s));
     return 0;
   }
   const Slots below = slots(e, Tp, call.B, call.S, l - 1, true, c.prows, c.du_rows);
@@ -623,14 +631,19 @@ int encoder_bwd(PlbEngine* e, const Call& call, const Prune* pr, bf16_t** dy, in
   const int Tp = (int)call.rw.Tp;
   c.f8 = f8_call(e, Tp, true);
   c.calib = e->fp8_on && !c.f8;
-  // ffn.bias gradient from the dU GEMM's epilogue: 2 partial rows per row tile of the kernel that runs it
-  c.du_rows = e->u_is_derivative ? (c.f8 ? 2 * (Tp / plb_gemm_nt_fp8_gelud_tile_rows(Tp)) : 2 * (Tp / 256))
-                                 : (c.f8 ? 2 * (Tp / 128) : plb_gemm_nt_colpart_rows(Tp, I, e->H));
+  // ffn.bias gradient from the dU GEMM's epilogue: the partial rows its launch writes (none on the small kernel: the tail
+  // then sums dU itself)
+  const int ops = c.f8 ? PLB_NT_FP8_E5M2 : PLB_NT_BF16;
+  const PlbGemmNTPlan du = nt_plan(Tp, I, e->H, e->u_is_derivative ? PLB_NT_GELUDBWD : PLB_NT_GELUBWD, ops, PLB_NT_COLPART);
+  c.du_rows = du.rc ? 0 : du.colpart_rows;
   // LayerNorm backward inside the dX GEMM that produces its output gradient (gemm_ln.hip). Rows of partials per layer:
-  // 2 per 128-row tile in the fused form (the one standalone launch left — LayerNorm 2 of the last application, whose
-  // output gradient comes from the head — then uses as many blocks), else the LayerNorm kernel's block count.
-  c.fuse_b = ln_fusable(e, Tp, 2);
-  c.prows = c.fuse_b ? 2 * Tp / 128 : e->ln_blocks;
+  // the fused launch's (the one standalone launch left — LayerNorm 2 of the last application, whose output gradient comes
+  // from the head — then uses as many blocks), else the LayerNorm kernel's block count.
+  c.fuse_b = ln_fusable(e, Tp, 2, c.f8);
+  c.prows = c.fuse_b ? nt_plan(Tp, e->H, e->H, PLB_NT_LNBWD, ops).colpart_rows : e->ln_blocks;
+  if (c.du_rows > e->ducol_rows || c.prows > e->part_rows)
+    return fail("encoder_bwd: the plans write %d ffn.bias and %d LayerNorm partial rows per application, %d and %d are reserved",
+                c.du_rows, c.prows, e->ducol_rows, e->part_rows);
   e->part_rows_used = c.prows;
   bf16_t* dx = e->at<bf16_t>(e->o_dy1);
   for (int l = L - 1; l >= 0; --l) {

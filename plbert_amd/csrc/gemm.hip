@@ -18,7 +18,7 @@
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
+constexpr int BK = 64;
 
 // ---- NT ------------------------------------------------------------------------------------------
 // LDS image of a [TILE rows][64 k] bf16 tile: 128-B rows, 16-B chunk index XORed with (row>>1)&7.
@@ -228,99 +228,41 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(PlbGemmTN p) {
 
 }  // namespace
 
-// 0: pick per shape; 128 / 256 / 384 / 1256: force that tile where the shape allows; 64 / -64: per-shape choice of the
-// kernel, and every / no launch of the small kernel in its 64x64 form
-static int g_nt_tile = 0;
-extern "C" void plb_set_gemm_nt_tile(int tile) { g_nt_tile = tile; }
+int gemm_nt_big_run(const PlbGemmNT* p, const PlbGemmNTPlan& pl, int form, hipStream_t stream);   // gemm_big.hip
 
-// PLBERT_NT_SMALL_TILE = 128 | 64 (read once per process): every launch of the small kernel takes that form whatever
-// small_tile's rule says, so one library can be compared with itself. The setter's 64 / -64 / 128 go before it.
-static int nt_small_tile_env() {
-  static const int v = [] {
-    const char* e = getenv("PLBERT_NT_SMALL_TILE");
-    const int n = e ? atoi(e) : 0;
-    return (n == 64 || n == 128) ? n : 0;
-  }();
-  return v;
-}
-// Form of a launch that goes to the small kernel. The 128x128 grid of the compact rows of a pruned last application
-// (~2,000 rows: 96 workgroups at N 768 and 2048), of the phoneme head (32) and of the map-in's dE product (128) leaves
-// most of the 256 CUs idle while every workgroup walks its whole K chain at ~0.8 us per K-tile; the 64x64 form puts four
-// times the workgroups on the chip and halves the cost of a K-tile. Measured per shape class, kept where every run of
-// the 64 form was below every run of the 128 form: profiles/nt_small_tile_kernel_ab.txt.
-static int small_tile(const PlbGemmNT* p) {
-  if (g_nt_tile == 64) return 64;
-  if (g_nt_tile == -64 || g_nt_tile == 128) return 128;
-  if (nt_small_tile_env()) return nt_small_tile_env();
-  const long grid128 = (long)(p->M / BM) * ((p->N + BN - 1) / BN);
-  return grid128 < 256 ? 64 : 128;
-}
-
-// Tile policy: fill 256 CUs. efficiency = tiles / (rounds * 256) with one workgroup per CU for the
-// big tiles; 128x384 moves 4/3 the operand bytes per flop of 256x256, hence the small handicap.
-static int pick_tile(const PlbGemmNT* p) {
-  const bool ok256 = p->M % 256 == 0 && p->N % 256 == 0, ok384 = p->M % 128 == 0 && p->N % 384 == 0;
-  const bool ok1256 = p->M % 128 == 0 && p->N % 256 == 0;
-  if (g_nt_tile == 128) return 128;
-  if (g_nt_tile == 256) return ok256 ? 256 : 128;
-  if (g_nt_tile == 384) return ok384 ? 384 : (ok256 ? 256 : 128);
-  if (g_nt_tile == 1256) return ok1256 ? 1256 : 128;
-  // (64 / -64 choose the small kernel's form only: the kernel is picked per shape)
-  if ((long)p->M * p->N < 256L * 256 * 64) return 128;  // small problems: more, smaller workgroups
-  double e256 = 0, e384 = 0, e1256 = 0;
-  if (ok256) { const long t = (long)(p->M / 256) * (p->N / 256); e256 = (double)t / (double)(((t + 255) / 256) * 256); }
-  if (ok384) { const long t = (long)(p->M / 128) * (p->N / 384); e384 = 0.95 * (double)t / (double)(((t + 255) / 256) * 256); }
-  if (ok1256) { const long t = (long)(p->M / 128) * (p->N / 256); e1256 = 0.85 * (double)t / (double)(((t + 255) / 256) * 256); }
-  if (e256 == 0 && e384 == 0 && e1256 == 0) return 128;
-  if (e1256 > e256 && e1256 > e384) return 1256;
-  return e384 > e256 ? 384 : 256;
-}
-
-// Rows of column-sum partials (PlbGemmNT.colpart) the launch of this shape writes: 2 per row tile of
-// the big-tile kernel picked for it, 0 when the shape runs on the 128x128 kernel (no partials there).
-extern "C" int plb_gemm_nt_colpart_rows(int M, int N, int K) {
-  PlbGemmNT q;
-  q.M = M; q.N = N; q.K = K;
-  const int tile = pick_tile(&q);
-  return tile == 256 ? 2 * (M / 256) : (tile == 384 || tile == 1256) ? 2 * (M / 128) : 0;
-}
-
+// Which kernel, tile and grid a shape gets is the plan's (gemm_nt_plan.h); here: the small kernel's instantiations, and the
+// hand-over of the plan to the pipeline kernel's (gemm_big.hip). act 3 / 4 (the cross-entropy passes, which the token head
+// sends to plb_launch_gemm_nt_big itself) take the tile of the per-shape policy, as a plain launch of the shape would, and
+// exist on the pipeline kernel only.
 extern "C" int plb_launch_gemm_nt(const PlbGemmNT* p, int act, int out_f32, hipStream_t stream) {
-  if (p->M % BM || p->K % BK || p->N % 4 || p->M <= 0 || p->N <= 0 || p->K <= 0) return 1;
-  const int nbn = (p->N + BN - 1) / BN;
-  dim3 grid((p->M / BM) * nbn), block(256);
-  const int cls = out_f32 ? PLB_K_GEMM_NT_F32 : act == 1 ? PLB_K_GEMM_NT_GELU : act == 2 ? PLB_K_GEMM_NT_GELUBWD : PLB_K_GEMM_NT;
-  const int tile = pick_tile(p);
-  if (p->colpart && tile == 128) return 1;  // column-sum partials exist in the big-tile kernels only
-  // algorithmic HBM bytes of the launch: each operand and each output once
-  const double mnk = (double)p->M * p->N * p->K;
-  const double algo_bytes = 2.0 * ((double)p->M * p->K + (double)p->N * p->K) +
-                            (double)p->M * p->N * (out_f32 ? 4 : act == 1 ? 4 : 2) +
-                            (p->res ? 2.0 * p->M * p->N : 0.0) + (act == 2 ? 2.0 * p->M * p->N : 0.0);
-  if (tile != 128) {
-    const int tokb = plb_prof_begin(cls, stream, 2.0 * mnk, algo_bytes);
-    const int rc = plb_launch_gemm_nt_big(p, tile, act, out_f32, stream);
-    plb_prof_end(tokb, stream);
-    return rc;
-  }
-  // the small kernel, 128x128 or 64x64 (head, map-in and other small products; some run on the engine's side stream, where a launch
-  // can sit behind the main stream's grid for longer than it runs) is a class of its own: "gemm_nt" is the pipeline kernel
-  if ((out_f32 && act != 0) || act < 0 || act > 2) return 1;
-  const int tok = plb_prof_begin(out_f32 ? PLB_K_GEMM_NT_F32 : PLB_K_GEMM_NT_SMALL, stream, 2.0 * mnk, algo_bytes);
-  if (small_tile(p) == 64) {
-    const dim3 grid64((p->M / 64) * ((p->N + 63) / 64));
-    if (out_f32) hipLaunchKernelGGL((gemm_nt_kernel<0, true, 64>), grid64, block, 0, stream, *p);
-    else if (act == 0) hipLaunchKernelGGL((gemm_nt_kernel<0, false, 64>), grid64, block, 0, stream, *p);
-    else if (act == 1) hipLaunchKernelGGL((gemm_nt_kernel<1, false, 64>), grid64, block, 0, stream, *p);
-    else hipLaunchKernelGGL((gemm_nt_kernel<2, false, 64>), grid64, block, 0, stream, *p);
+  if ((out_f32 && act != 0) || act < 0 || act > 4) return 1;
+  const bool ce = act > 2;
+  const int form = out_f32 ? PLB_NT_F32 : ce ? PLB_NT_PLAIN : act;
+  PlbGemmNTPlan pl;
+  const int opts = (p->colpart ? PLB_NT_COLPART : 0) | (p->res ? PLB_NT_RES : 0);
+  if (plb_gemm_nt_plan(p->M, p->N, p->K, form, PLB_NT_BF16, opts, 0, &pl)) return pl.rc;
+  if (ce && pl.family == 0) return 1;
+  const int tok = plb_prof_begin(pl.cls, stream, pl.flops, pl.bytes);
+  int rc = 0;
+  if (pl.family == 1) {
+    rc = ce ? plb_launch_gemm_nt_big(p, pl.tile, act, 0, stream) : gemm_nt_big_run(p, pl, form, stream);
   } else {
-    if (out_f32) hipLaunchKernelGGL((gemm_nt_kernel<0, true, 128>), grid, block, 0, stream, *p);
-    else if (act == 0) hipLaunchKernelGGL((gemm_nt_kernel<0, false, 128>), grid, block, 0, stream, *p);
-    else if (act == 1) hipLaunchKernelGGL((gemm_nt_kernel<1, false, 128>), grid, block, 0, stream, *p);
-    else hipLaunchKernelGGL((gemm_nt_kernel<2, false, 128>), grid, block, 0, stream, *p);
+    const dim3 grid(pl.grid), block(pl.block);
+    if (pl.tile == 64) {
+      if (out_f32) hipLaunchKernelGGL((gemm_nt_kernel<0, true, 64>), grid, block, 0, stream, *p);
+      else if (act == 0) hipLaunchKernelGGL((gemm_nt_kernel<0, false, 64>), grid, block, 0, stream, *p);
+      else if (act == 1) hipLaunchKernelGGL((gemm_nt_kernel<1, false, 64>), grid, block, 0, stream, *p);
+      else hipLaunchKernelGGL((gemm_nt_kernel<2, false, 64>), grid, block, 0, stream, *p);
+    } else {
+      if (out_f32) hipLaunchKernelGGL((gemm_nt_kernel<0, true, 128>), grid, block, 0, stream, *p);
+      else if (act == 0) hipLaunchKernelGGL((gemm_nt_kernel<0, false, 128>), grid, block, 0, stream, *p);
+      else if (act == 1) hipLaunchKernelGGL((gemm_nt_kernel<1, false, 128>), grid, block, 0, stream, *p);
+      else hipLaunchKernelGGL((gemm_nt_kernel<2, false, 128>), grid, block, 0, stream, *p);
+    }
+    rc = hipGetLastError() == hipSuccess ? 0 : 2;
   }
   plb_prof_end(tok, stream);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return rc;
 }
 
 extern "C" int plb_launch_gemm_tn(const PlbGemmTN* p, hipStream_t stream) {

@@ -17,7 +17,7 @@
 //   128x384:  ph1 A,B0 -> nh 0   | ph2 B1 -> nh 1  | ph3 B2 -> nh 2
 // A slot is re-filled once the phase that read its previous occupant is behind a barrier. Barriers are raw
 // s_barrier (asm: __syncthreads() would drain vmcnt to 0). Two forms of the K loop exist, chosen per launch
-// by measurement (plb_launch_gemm_nt_big): "interleaved" (fragment reads of the next phase and the DMA
+// by measurement (the plan: gemm_nt_plan.cpp): "interleaved" (fragment reads of the next phase and the DMA
 // issues dealt into the MFMA shadows, one barrier per phase) and "staggered" (two barriers per phase, the
 // two waves of a SIMD half a phase apart) — see the comments at the loops.
 #include "gemm_nt_pipeline.h"
@@ -27,38 +27,24 @@
 // valid. The shipped library has 0.
 namespace {
 
+// the instantiations of this unit: tile V (1 128x256, 2 256x256, 3 128x384) x K-loop form PF x the forms 0 - 4 and 9
 template <int V, bool PF>
-int launch_big(const PlbGemmNT* p, int act, int out_f32, hipStream_t stream) {
-  constexpr int TM = (V == 2 ? 2 : 1) * 128, TN = (V == 3 ? 3 : 2) * 128;
-  if (p->M % TM || p->N % TN || p->K % 64 || p->M <= 0 || p->N <= 0 || p->K <= 0) return 1;
-  dim3 grid((p->M / TM) * (p->N / TN)), block(512);
-  if (out_f32) {
-    if (act != 0) return 1;
-    hipLaunchKernelGGL((gemm_nt_big_kernel<V, 0, true, PF>), grid, block, 0, stream, *p);
-  } else if (act == 0) {
-    if (p->colpart) hipLaunchKernelGGL((gemm_nt_big_kernel<V, 0, false, PF>), grid, block, 0, stream, *p);
-    else hipLaunchKernelGGL((gemm_nt_big_kernel<V, 0, false, PF, false, false, true>), grid, block, 0, stream, *p);
-  } else if (act == 1) {
-    hipLaunchKernelGGL((gemm_nt_big_kernel<V, 1, false, PF>), grid, block, 0, stream, *p);
-  } else if (act == 2) {
-    hipLaunchKernelGGL((gemm_nt_big_kernel<V, 2, false, PF>), grid, block, 0, stream, *p);
-  } else if (act == 3 || act == 4) {  // fused GEMM + cross-entropy passes: 256-column tiles only
-    if constexpr (TN == 256) {
-      if (!p->ce_tgt || p->ce_cols < 1 || p->ce_cols > p->N) return 1;
-      if (act == 3) {
-        if (!p->ce_pmax || !p->ce_psum || !p->ce_tlogit) return 1;
-        hipLaunchKernelGGL((gemm_nt_big_kernel<V, 3, false, PF>), grid, block, 0, stream, *p);
-      } else {
-        if (!p->ce_lse || !p->ce_w || !p->C) return 1;
-        hipLaunchKernelGGL((gemm_nt_big_kernel<V, 4, false, PF>), grid, block, 0, stream, *p);
+void launch_big(const PlbGemmNT* p, int form, dim3 grid, dim3 block, hipStream_t stream) {
+  switch (form) {
+    case PLB_NT_F32: hipLaunchKernelGGL((gemm_nt_big_kernel<V, 0, true, PF>), grid, block, 0, stream, *p); break;
+    case PLB_NT_PLAIN:   // (the column sums are compiled out where nobody wants them)
+      if (p->colpart) hipLaunchKernelGGL((gemm_nt_big_kernel<V, 0, false, PF>), grid, block, 0, stream, *p);
+      else hipLaunchKernelGGL((gemm_nt_big_kernel<V, 0, false, PF, false, false, true>), grid, block, 0, stream, *p);
+      break;
+    case PLB_NT_GELU: hipLaunchKernelGGL((gemm_nt_big_kernel<V, 1, false, PF>), grid, block, 0, stream, *p); break;
+    case PLB_NT_GELUBWD: hipLaunchKernelGGL((gemm_nt_big_kernel<V, 2, false, PF>), grid, block, 0, stream, *p); break;
+    case PLB_NT_CE1: case PLB_NT_CE2:   // fused GEMM + cross-entropy passes: 256-column tiles only (the plan refuses 128x384)
+      if constexpr (V != 3) {
+        if (form == PLB_NT_CE1) hipLaunchKernelGGL((gemm_nt_big_kernel<V, 3, false, PF>), grid, block, 0, stream, *p);
+        else hipLaunchKernelGGL((gemm_nt_big_kernel<V, 4, false, PF>), grid, block, 0, stream, *p);
       }
-    } else {
-      return 1;
-    }
-  } else {
-    return 1;
+      break;
   }
-  return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -335,20 +321,32 @@ extern "C" int plb_launch_gemm_tn_big(const PlbGemmTN* p, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// K-loop form: 1 interleaved (reads / DMA issues in the MFMA shadows), 0 staggered two-barrier loop,
-// -1 (default) per tile: measured on 16384 x {768, 2048, 2304} x {768, 2048, 2304}, interleaved wins by
-// 5-8 % on 128x384 and 128x256, staggered by 5-10 % on a plain 256x256 launch (whose phase 3 has nothing to
-// interleave and phase 4 twelve reads) — but with the GELU epilogues (the only 256x256 launches of the model:
-// 16384 x 2048 x 768) interleaved wins again by 6 %: 68.7 vs 72.8 us forward, 70.0 vs 74.7 us backward.
-static int g_nt_prefetch = -1;
-extern "C" void plb_set_gemm_nt_prefetch(int on) { g_nt_prefetch = on; }
+// The pipeline launch of a plan of this unit's forms (bf16 operands, forms 0 - 4 and 9). Not exported: plb_launch_gemm_nt
+// (gemm.hip), which has planned already, calls it too.
+int gemm_nt_big_run(const PlbGemmNT* p, const PlbGemmNTPlan& pl, int form, hipStream_t stream) {
+  if (nt_args_check(p, form, false)) return 1;
+  const dim3 grid(pl.grid), block(pl.block);
+  if (pl.kloop) {
+    if (pl.tile == 384) launch_big<3, true>(p, form, grid, block, stream);
+    else if (pl.tile == 1256) launch_big<1, true>(p, form, grid, block, stream);
+    else launch_big<2, true>(p, form, grid, block, stream);
+  } else {
+    if (pl.tile == 384) launch_big<3, false>(p, form, grid, block, stream);
+    else if (pl.tile == 1256) launch_big<1, false>(p, form, grid, block, stream);
+    else launch_big<2, false>(p, form, grid, block, stream);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
 
-// tile = 256: 256x256 (M % 256, N % 256); 384: 128x384 (M % 128, N % 384); 1256: 128x256 (M % 128, N % 256).
+// tile = 256: 256x256 (M % 256, N % 256); 384: 128x384 (M % 128, N % 384); 1256: 128x256 (M % 128, N % 256); any other
+// value: 256. The K-loop form is the plan's (gemm_nt_plan.h: plb_set_gemm_nt_prefetch). No profiler scope of its own: its
+// callers (plb_launch_gemm_nt, the token head) open one.
 extern "C" int plb_launch_gemm_nt_big(const PlbGemmNT* p, int tile, int act, int out_f32, hipStream_t stream) {
-  const bool pf = g_nt_prefetch < 0 ? (tile != 256 || act != 0) : (g_nt_prefetch != 0);
-  if (pf)
-    return tile == 384 ? launch_big<3, true>(p, act, out_f32, stream)
-           : tile == 1256 ? launch_big<1, true>(p, act, out_f32, stream) : launch_big<2, true>(p, act, out_f32, stream);
-  return tile == 384 ? launch_big<3, false>(p, act, out_f32, stream)
-         : tile == 1256 ? launch_big<1, false>(p, act, out_f32, stream) : launch_big<2, false>(p, act, out_f32, stream);
+  if ((out_f32 && act != 0) || act < 0 || act > 4) return 1;
+  const int form = out_f32 ? PLB_NT_F32 : act;
+  PlbGemmNTPlan pl;
+  if (plb_gemm_nt_plan(p->M, p->N, p->K, form, PLB_NT_BF16, p->colpart ? PLB_NT_COLPART : 0,
+                       tile == 384 || tile == 1256 ? tile : 256, &pl))
+    return pl.rc;
+  return gemm_nt_big_run(p, pl, form, stream);
 }

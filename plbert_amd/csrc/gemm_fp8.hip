@@ -8,43 +8,34 @@
 
 namespace {
 
-template <int V, int ACT, bool ABF8>
-int launch_fp8(const PlbGemmNT* p, hipStream_t stream) {
-  constexpr int TM = (V == 2 ? 2 : 1) * 128, TN = (V == 3 ? 3 : 2) * 128;
-  if (p->M % TM || p->N % TN || p->K % 128 || p->M <= 0 || p->N <= 0 || p->K <= 0) return 3;
-  if (!p->deq_a || !p->deq_b || !p->C) return 1;
-  if (p->C8 && (!p->q_scale || p->ldc8 % 16)) return 1;
-  dim3 grid((p->M / TM) * (p->N / TN)), block(512);
-  hipLaunchKernelGGL((gemm_nt_big_kernel<V, ACT, false, true, true, ABF8>), grid, block, 0, stream, *p);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
 // Tiles: 128x384 (N % 384 == 0, plain epilogue) and 128x256. The 256x256 tile is not built in fp8: its 128
 // accumulators + 96 registers of 8-register operand tuples do not fit 256 VGPRs without spilling, and at one byte per
 // element the 128x256 tile already moves fewer operand bytes per flop (170 FLOP/B) than the bf16 256x256 tile (128).
+template <int V, int ACT, bool ABF8>
+void launch_fp8(const PlbGemmNT* p, const PlbGemmNTPlan& pl, hipStream_t stream) {
+  hipLaunchKernelGGL((gemm_nt_big_kernel<V, ACT, false, true, true, ABF8>), dim3(pl.grid), dim3(pl.block), 0, stream, *p);
+}
 template <bool ABF8>
-int dispatch(const PlbGemmNT* p, int tile, int act, hipStream_t stream) {
-  if (act == 0) return tile == 384 ? launch_fp8<3, 0, ABF8>(p, stream) : launch_fp8<1, 0, ABF8>(p, stream);
-  if (act == 1) return launch_fp8<1, 1, ABF8>(p, stream);
-  if (act == 2) return launch_fp8<1, 2, ABF8>(p, stream);
-  return 1;
+void dispatch(const PlbGemmNT* p, const PlbGemmNTPlan& pl, int act, hipStream_t stream) {
+  if (act == 0 && pl.tile == 384) launch_fp8<3, 0, ABF8>(p, pl, stream);
+  else if (act == 0) launch_fp8<1, 0, ABF8>(p, pl, stream);
+  else if (act == 1) launch_fp8<1, 1, ABF8>(p, pl, stream);
+  else launch_fp8<1, 2, ABF8>(p, pl, stream);
 }
 
 }  // namespace
 
+// 3: a shape without an fp8 form (the caller runs the bf16 GEMM)
 extern "C" int plb_launch_gemm_nt_fp8(const PlbGemmNT* p, int act, int a_bf8, hipStream_t stream) {
-  if (p->M % 128 || p->K % 128) return 3;  // odd shape: the caller runs the bf16 GEMM
-  int tile;
-  if (act == 0 && p->N % 384 == 0) tile = 384;
-  else if (p->N % 256 == 0) tile = 1256;
-  else return 3;
-  const int cls = act == 1 ? PLB_K_GEMM_NT_GELU_FP8 : act == 2 ? PLB_K_GEMM_NT_GELUBWD_FP8 : PLB_K_GEMM_NT_FP8;
-  const double mnk = (double)p->M * p->N * p->K;
-  const double bytes = ((double)p->M * p->K + (double)p->N * p->K) + (double)p->M * p->N * (act == 1 ? 4 : 2) +
-                       (p->res ? 2.0 * p->M * p->N : 0.0) + (act == 2 ? 2.0 * p->M * p->N : 0.0) +
-                       (p->C8 ? (double)p->M * p->N : 0.0);
-  const int tok = plb_prof_begin(cls, stream, 2.0 * mnk, bytes);
-  const int rc = a_bf8 ? dispatch<true>(p, tile, act, stream) : dispatch<false>(p, tile, act, stream);
+  const bool known = act >= 0 && act <= 2;   // (another act is refused behind the shape, as a form with an epilogue)
+  PlbGemmNTPlan pl;
+  const int opts = (p->colpart ? PLB_NT_COLPART : 0) | (p->res ? PLB_NT_RES : 0) | (p->C8 ? PLB_NT_C8 : 0);
+  if (plb_gemm_nt_plan(p->M, p->N, p->K, known ? act : PLB_NT_GELU, a_bf8 ? PLB_NT_FP8_E5M2 : PLB_NT_FP8_E4M3, opts, 0, &pl))
+    return pl.rc;
+  if (!known || nt_args_check(p, act, true)) return 1;
+  const int tok = plb_prof_begin(pl.cls, stream, pl.flops, pl.bytes);
+  if (a_bf8) dispatch<true>(p, pl, act, stream);
+  else dispatch<false>(p, pl, act, stream);
   plb_prof_end(tok, stream);
-  return rc;
+  return hipGetLastError() == hipSuccess ? 0 : 2;
 }

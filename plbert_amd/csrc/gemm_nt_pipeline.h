@@ -1161,20 +1161,35 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(PlbGemmNT p) {
 #endif
 }
 
-// Argument checks shared by the launchers of the LayerNorm forms (gemm_ln.hip, gemm_fp8_ln.hip). kmult: the K-tile depth in
-// elements (64 bf16, 128 fp8). 0: launchable; 3: a shape these forms do not take (the caller runs the unfused path);
-// 1: a bad argument.
-inline int ln_launch_check(const PlbGemmNT* p, int mode, int kmult) {
-  if (mode != 5 && mode != 6) return 1;
-  if (p->M % 1024 || p->K % kmult || p->M <= 0 || p->N <= 0 || p->K <= 0) return 3;   // 8 XCDs x whole row blocks
-  const int tile = p->N % 384 == 0 ? 384 : p->N % 256 == 0 ? 256 : 0;
-  if (!tile || p->N / tile > 4) return 3;
-  if (!p->ln_gamma || !p->ln_mean || !p->ln_rstd || !p->ln_xchg || !p->ln_err || !p->C) return 1;
-  if (mode == 5 && (!p->ln_beta || !p->C2)) return 1;
-  if (mode == 6 && (!p->aux || !p->colpart)) return 1;
-  // the epilogue's operand tiles arrive by LDS-DMA, 16 bytes per lane: rows must start on 16-byte boundaries
-  if (p->res && (((uintptr_t)p->res & 15) || p->ldr % 8)) return 1;
-  if (mode == 6 && (((uintptr_t)p->aux & 15) || p->ldaux % 8)) return 1;
+// What the plan (gemm_nt_plan.h) cannot see of a pipeline launch: the descriptor's pointers, per form family. The launchers
+// call it behind the plan, so a shape without a form is reported (3) before a bad argument. 0: launchable; 1: a bad argument.
+inline int nt_args_check(const PlbGemmNT* p, int form, bool fp8) {
+  const bool bwd = form == PLB_NT_GELUDBWD;
+  switch (form) {
+    case PLB_NT_CE1: case PLB_NT_CE2:
+      if (!p->ce_tgt || p->ce_cols < 1 || p->ce_cols > p->N) return 1;
+      if (form == PLB_NT_CE1 ? (!p->ce_pmax || !p->ce_psum || !p->ce_tlogit) : (!p->ce_lse || !p->ce_w || !p->C)) return 1;
+      break;
+    case PLB_NT_LNFWD: case PLB_NT_LNBWD:
+      if (!p->ln_gamma || !p->ln_mean || !p->ln_rstd || !p->ln_xchg || !p->ln_err || !p->C) return 1;
+      if (form == PLB_NT_LNFWD ? (!p->ln_beta || !p->C2) : (!p->aux || !p->colpart)) return 1;
+      // the epilogue's operand tiles arrive by LDS-DMA, 16 bytes per lane: rows must start on 16-byte boundaries
+      if (p->res && (((uintptr_t)p->res & 15) || p->ldr % 8)) return 1;
+      if (form == PLB_NT_LNBWD && (((uintptr_t)p->aux & 15) || p->ldaux % 8)) return 1;
+      break;
+    case PLB_NT_GELUD: case PLB_NT_GELUDBWD:   // the stash (C forward, aux backward); fp8: gelu(u) / dU may leave as an image alone
+      if ((!bwd && !p->C) || (bwd && !p->aux)) return 1;
+      if (!(bwd ? p->C : p->C2) && !(fp8 && p->C8)) return 1;
+      break;
+    default:
+      if (fp8 && !p->C) return 1;
+  }
+  if (fp8) {
+    if (!p->deq_a || !p->deq_b) return 1;
+    // (the LayerNorm and derivative-stash forms store the image in 16-byte pieces; the plain and gelu forms do not ask for it)
+    const bool c8_16 = form == PLB_NT_LNFWD || form == PLB_NT_LNBWD || form == PLB_NT_GELUD || form == PLB_NT_GELUDBWD;
+    if (p->C8 && (!p->q_scale || p->ldc8 % 16 || (c8_16 && ((uintptr_t)p->C8 & 15)))) return 1;
+  }
   return 0;
 }
 

@@ -5,21 +5,14 @@
 #include <stdint.h>
 
 #include "../../include/plbert.h"   // PLB_NPARAM, PlbAdamWSegment (the segmented optimizer launches)
+#include "gemm_nt_plan.h"            // PlbGemmNTPlan and the form / operand / option names of the NT GEMM launchers (+ prof_classes.h)
 
 typedef uint16_t bf16_t;
 
 extern "C" {
 
-// ---- per-launch HIP-event profiler (engine.cpp). Off by default: begin() then returns -1 at once.
-enum PlbKernelClass {
-  PLB_K_GEMM_NT = 0, PLB_K_GEMM_NT_GELU, PLB_K_GEMM_NT_GELUBWD, PLB_K_GEMM_NT_F32, PLB_K_GEMM_TN,
-  PLB_K_ATTN_FWD, PLB_K_ATTN_BWD_DQ, PLB_K_ATTN_BWD_DKV, PLB_K_LN_FWD, PLB_K_LN_BWD, PLB_K_EMBED_FWD,
-  PLB_K_EMBED_BWD, PLB_K_COLSUM, PLB_K_REDUCE, PLB_K_ROWS, PLB_K_CE, PLB_K_ADAMW, PLB_K_CAST, PLB_K_TOKEN_CE, PLB_K_GEMM_NT_CE, PLB_K_GEMM_NT_SMALL, PLB_K_FP8, PLB_K_ATTN_BWD,
-  PLB_K_GEMM_NT_FP8, PLB_K_GEMM_NT_GELU_FP8, PLB_K_GEMM_NT_GELUBWD_FP8,  // the fp8 launches: priced against the fp8 MFMA peak
-  PLB_K_GEMM_NT_LNFWD, PLB_K_GEMM_NT_LNBWD,  // GEMM + LayerNorm epilogue (gemm_ln.hip)
-  PLB_K_GEMM_NT_LNFWD_FP8, PLB_K_GEMM_NT_LNBWD_FP8, PLB_K_GEMM_TN_FP8,  // fp8 forms of the same, and of the weight-gradient GEMM
-  PLB_K_NCLASS
-};
+// ---- per-launch HIP-event profiler (engine_prof.cpp; the classes: PlbKernelClass in prof_classes.h). Off by default: begin()
+// then returns -1 at once.
 int plb_prof_begin(int cls, hipStream_t s, double flops, double bytes);
 void plb_prof_end(int tok, hipStream_t s);
 
@@ -65,35 +58,45 @@ typedef struct {
                                 // 2 = column tile 0 reports a time-out and leaves the granules it consumed TAGGED (what a
                                 // producer's store landing after the time-out looks like to the next launch)
 } PlbGemmNT;
-// LayerNorm in the epilogue of the GEMM that produces its input (big-tile kernels with 128-row tiles; M % 1024 == 0,
-// N % 384 == 0 or N % 256 == 0):
+// ---- NT GEMM launchers. Each is: plan (gemm_nt_plan.h: kernel, tile, grid, K-loop form, profiler class, partial rows from
+// M, N, K, the form and the operand kind) -> argument check of the descriptor's pointers -> profiler scope -> the
+// instantiation the plan names. Return codes: 0 launched; 3 the shape has no form here (the caller takes its other path),
+// reported before 1, a refused argument; 2 the launch failed. No profiler scope is open behind a refusal.
+// The plan itself, for tests, tools and the engine (which sizes and indexes its buffers from it); declared in gemm_nt_plan.h:
+int plb_gemm_nt_plan(int M, int N, int K, int form, int operands, int opts, int tile, PlbGemmNTPlan* plan);
+// LayerNorm in the epilogue of the GEMM that produces its input (pipeline kernel, 128-row tiles, at most 4 column tiles):
 //  mode 5, forward:  C = bf16(A·B^T + bias + res) ("pre", kept for the backward), C2 = LayerNorm(C)·gamma + beta,
 //                    ln_mean / ln_rstd written
 //  mode 6, backward: dy = bf16(A·B^T + res) is the gradient of the LayerNorm's OUTPUT and is never stored; aux = the
 //                    forward's pre, ln_mean / ln_rstd read; C = the gradient of the LayerNorm's input;
-//                    colpart[2*M/128][3][N] = per (row tile, wave half) dgamma | dbeta | column sums of C
-// Returns 3 when the shape has no fused form (the caller runs the GEMM and the LayerNorm kernel separately).
+//                    colpart[plan rows][3][N] = per (row tile, wave half) dgamma | dbeta | column sums of C
+// 3: the caller runs the GEMM and the LayerNorm kernel separately. Takes plb_ln_fault_take() even when it then refuses.
 int plb_launch_gemm_nt_ln(const PlbGemmNT* p, int mode, hipStream_t stream);
 // gelu_new with the DERIVATIVE stashed: forward C = gelu_new'(A·B^T + bias), C2 = gelu_new(..); backward C = (A·B^T) * aux
-// (aux = the forward's C; colpart as in plb_launch_gemm_nt). M % 256 == 0 and N % 256 == 0, else 3.
+// (aux = the forward's C; colpart as in plb_launch_gemm_nt). 3: the caller uses act 1 / 2 for forward AND backward.
 int plb_launch_gemm_nt_gelud(const PlbGemmNT* p, int backward, hipStream_t stream);
-// fp8 (e4m3 weights; e4m3 or e5m2 activations / gradients) form of plb_launch_gemm_nt on the pipeline kernel.
-// Returns 3 when the shape has no big-tile form (the caller then uses the bf16 GEMM).
+// fp8 (e4m3 weights; e4m3 or e5m2 activations / gradients) form of plb_launch_gemm_nt on the pipeline kernel, act 0 - 2.
+// 3: the caller uses the bf16 GEMM.
 int plb_launch_gemm_nt_fp8(const PlbGemmNT* p, int act, int a_bf8, hipStream_t stream);
 // fp8-operand forms of plb_launch_gemm_nt_ln (modes 5 / 6) and plb_launch_gemm_nt_gelud (gemm_fp8_ln.hip). A / B are 1-byte
 // images, deq_a / deq_b their dequantisation factors; C8 (+ q_scale, q_amax, c8_bf8) is the 1-byte image of the output the
 // next fp8 GEMMs read — mode 5: of C2, mode 6: of C, gelu forward: of C2 = gelu(u), gelu backward: of C. In the gelu forms the
-// bf16 image (C2 / C) may be NULL: only the fp8 image leaves. Same shape rules as the bf16 forms, K % 128 == 0; 3 = no form.
+// bf16 image (C2 / C) may be NULL: only the fp8 image leaves.
 int plb_launch_gemm_nt_fp8_ln(const PlbGemmNT* p, int mode, int a_bf8, hipStream_t stream);
 int plb_launch_gemm_nt_fp8_gelud(const PlbGemmNT* p, int backward, int a_bf8, hipStream_t stream);
-int plb_gemm_nt_fp8_gelud_tile_rows(int M);  // rows of the tile that launcher uses at this M (colpart: 2 rows per row tile)
+int plb_gemm_nt_fp8_gelud_tile_rows(int M);  // the plan's tile rows of that launcher at this M (128 where M has no form)
 int plb_ln_fault_take(void);  // fault injection state shared by the LayerNorm launchers (plb_debug_ln_fault)
+// act 0 - 2, bf16 or fp32 out, on the small or the pipeline kernel as the plan's per-shape policy says; colpart on a shape
+// that goes to the small kernel: 1
 int plb_launch_gemm_nt(const PlbGemmNT* p, int act, int out_f32, hipStream_t stream);
-// the big-tile forms behind it (gemm_big.hip): tile 256 / 384 / 1256 = 128x256; act 3 / 4 = the fused GEMM + cross-entropy passes
+// the pipeline forms behind it (gemm_big.hip) on the caller's tile: 256 / 384 / 1256 = 128x256; act 3 / 4 = the fused GEMM +
+// cross-entropy passes. No profiler scope of its own.
 int plb_launch_gemm_nt_big(const PlbGemmNT* p, int tile, int act, int out_f32, hipStream_t stream);
-int plb_gemm_nt_colpart_rows(int M, int N, int K);  // rows of colpart written for this shape (0: unsupported)
-// Tuning / test hooks (not part of include/plbert.h): force a tile (0 = per-shape policy; 128, 256, 384, 1256 =
-// 128x256) or a K-loop form (-1 = per-launch policy, 1 interleaved, 0 staggered) for the launches that follow.
+int plb_gemm_nt_colpart_rows(int M, int N, int K);  // the plan's colpart rows of a plb_launch_gemm_nt of this shape (0: none)
+// Tuning / test hooks (not part of include/plbert.h), state of the plan unit: force a tile (0 = per-shape policy; 128, 256,
+// 384, 1256 = 128x256; 64 / -64 = every / no launch of the small kernel in its 64x64 form) or a K-loop form (-1 = per-launch
+// policy, 1 interleaved, 0 staggered) for the launches that follow. PLBERT_NT_SMALL_TILE = 128 | 64 (read once per process)
+// forces the small kernel's form where the setter does not.
 void plb_set_gemm_nt_tile(int tile);
 void plb_set_gemm_nt_prefetch(int on);
 

@@ -34,10 +34,12 @@ def one(M, N, K):
     res = torch.randn(M, N, device=dev).to(torch.bfloat16)
     pre, y, dx = (torch.empty(M, N, dtype=torch.bfloat16, device=dev) for _ in range(3))
     mean, rstd = torch.zeros(M, device=dev), torch.ones(M, device=dev)
-    nbn = N // (384 if N % 384 == 0 else 256)
-    xchg = torch.zeros(M // 128 * nbn * nbn * 256, dtype=torch.int64, device=dev)
+    plan = _lib.gemm_nt_plan(M, N, K, form=6)   # the fused backward: tile and partial rows as its launcher takes them
+    assert plan["rc"] == 0, f"no fused LayerNorm form at {M} x {N} x {K}"
+    nbn = N // plan["tile_n"]
+    xchg = torch.zeros(M // plan["tile_m"] * nbn * nbn * 256, dtype=torch.int64, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    colp = torch.empty(2 * M // 128, 3, N, device=dev)
+    colp = torch.empty(plan["colpart_rows"], 3, N, device=dev)
     part = torch.empty(1024, 3 * N, device=dev)
     g = _lib.PlbGemmNT()
     g.A, g.lda, g.B, g.ldb, g.M, g.N, g.K, g.Mstore = A.data_ptr(), K, B.data_ptr(), K, M, N, K, M

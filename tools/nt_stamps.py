@@ -31,10 +31,12 @@ if act in (5, 6):   # LayerNorm forms (gemm_ln.hip)
     y, dx = torch.empty_like(pre), torch.empty_like(pre)
     gam, bet = torch.randn(N, device="cuda"), torch.randn(N, device="cuda")
     mean, rstd = torch.zeros(M, device="cuda"), torch.ones(M, device="cuda")
-    nbn = N // (384 if N % 384 == 0 else 256)
-    xchg = torch.zeros(M // 128 * nbn * nbn * 256, dtype=torch.int64, device="cuda")
+    plan = _lib.gemm_nt_plan(M, N, K, form=6)   # tile and partial rows as the launcher takes them (csrc/gemm_nt_plan.h)
+    assert plan["rc"] == 0, f"no fused LayerNorm form at {M} x {N} x {K}"
+    nbn = N // plan["tile_n"]
+    xchg = torch.zeros(M // plan["tile_m"] * nbn * nbn * 256, dtype=torch.int64, device="cuda")
     err = torch.zeros(1, dtype=torch.int32, device="cuda")
-    colp = torch.empty(2 * M // 128, 3, N, device="cuda")
+    colp = torch.empty(plan["colpart_rows"], 3, N, device="cuda")
     g = _lib.PlbGemmNT()
     g.A, g.lda, g.B, g.ldb, g.M, g.N, g.K, g.Mstore = A.data_ptr(), K, Bw.data_ptr(), K, M, N, K, M
     g.res, g.ldr = res.data_ptr(), N
@@ -53,7 +55,9 @@ if act in (5, 6):   # LayerNorm forms (gemm_ln.hip)
 if act in (7, 8):   # gelu forms on a stashed derivative (gemm_ln.hip: plb_launch_gemm_nt_gelud)
     import ctypes as C
     Cb, C2 = torch.empty(M, N, dtype=torch.bfloat16, device="cuda"), torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
-    colp = torch.empty(2 * M // 128, N, device="cuda")
+    plan = _lib.gemm_nt_plan(M, N, K, form=8, opts=1)
+    assert plan["rc"] == 0, f"no derivative-stash form at {M} x {N} x {K}"
+    colp = torch.empty(plan["colpart_rows"], N, device="cuda")
     g = _lib.PlbGemmNT()
     g.A, g.lda, g.B, g.ldb, g.M, g.N, g.K, g.Mstore = A.data_ptr(), K, Bw.data_ptr(), K, M, N, K, M
     g.bias, g.C, g.ldc, g.C2, g.ldc2 = bias.data_ptr(), Cb.data_ptr(), N, C2.data_ptr(), N

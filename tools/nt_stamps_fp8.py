@@ -48,10 +48,13 @@ def run(M, N, K, act, fp8):
     qs, amax = torch.tensor([1.0], device="cuda"), torch.zeros(1024, device="cuda")
     gam, bet = torch.randn(N, device="cuda"), torch.randn(N, device="cuda")
     mean, rstd = torch.zeros(M, device="cuda"), torch.ones(M, device="cuda")
-    nbn = N // (384 if N % 384 == 0 else 256)
-    xchg = torch.zeros(M // 128 * nbn * nbn * 256, dtype=torch.int64, device="cuda")
+    # tile, column tiles of a row block and partial rows as the launcher of this form takes them (csrc/gemm_nt_plan.h)
+    plan = _lib.gemm_nt_plan(M, N, K, form=act, operands=(2 if bf8 else 1) if fp8 else 0, opts=1 if act >= 5 else 0)
+    assert plan["rc"] == 0, f"no form {act} at {M} x {N} x {K}"
+    nbn = N // plan["tile_n"]
+    xchg = torch.zeros(M // plan["tile_m"] * nbn * nbn * 256, dtype=torch.int64, device="cuda")
     err = torch.zeros(2, dtype=torch.int32, device="cuda")
-    colp = torch.empty(2 * M // 128, 3, N, device="cuda")
+    colp = torch.empty(max(plan["colpart_rows"], 1), 3, N, device="cuda")
     keep += [bias, res, pre, o1, o2, img, qs, amax, gam, bet, mean, rstd, xchg, err, colp]
     if fp8 and act != 0:   # (the engine's plain fp8 launches — QKV forward, dCtx, dX of application 0 — write no image)
         p.C8, p.ldc8, p.q_scale, p.q_amax, p.c8_bf8 = img.data_ptr(), N, qs.data_ptr(), amax.data_ptr(), int(bf8)
