@@ -336,6 +336,7 @@ INTERNAL = {
     "plb_launch_gemm_nt_big": (i32, [P(PlbGemmNT), i32, i32, i32, vp]),
     "plb_gemm_nt_colpart_rows": (i32, [i32, i32, i32]),
     "plb_gemm_nt_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),   # (PlbGemmNTPlan*: csrc/gemm_nt_plan.h)
+    "plb_gemm_tn_plan": (i32, [i64, i32, i32, i32, i32, vp]),   # (PlbGemmTNPlan*: csrc/gemm_tn_plan.h)
     "plb_launch_gemm_tn": (i32, [P(PlbGemmTN), vp]),
     "plb_launch_gemm_tn_fp8": (i32, [P(PlbGemmTN), vp]),
     "plb_launch_gemm_tn_big": (i32, [P(PlbGemmTN), vp]),
@@ -451,6 +452,18 @@ def gemm_nt_plan(M, N, K, form=0, operands=0, opts=0, tile=0):
     buf = C.create_string_buffer(struct.calcsize("10i2d"))
     lib().plb_gemm_nt_plan(M, N, K, form, operands, opts, tile, buf)
     return dict(zip(NT_PLAN_FIELDS, struct.unpack("10i2d", buf.raw)))
+
+
+TN_PLAN_FIELDS = ("rc", "kernel", "splits", "rows_per_split", "direct", "grid_x", "grid_y", "block", "slab_floats", "flops")
+
+
+def gemm_tn_plan(Mtot, Ncols, N, K, operands=0):
+    """The launch plan of a token-major weight-gradient GEMM as a dict of csrc/gemm_tn_plan.h's PlbGemmTNPlan (eight ints, an
+    int64, a double): kernel (0 small, 1 pipeline, 2 pipeline fp8), row splits and slab need for operands 0 bf16 / 1 fp8."""
+    import struct
+    buf = C.create_string_buffer(struct.calcsize("8iqd"))
+    lib().plb_gemm_tn_plan(Mtot, Ncols, N, K, operands, buf)
+    return dict(zip(TN_PLAN_FIELDS, struct.unpack("8iqd", buf.raw)))
 
 
 def profile_enable(on):

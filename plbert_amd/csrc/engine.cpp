@@ -68,6 +68,15 @@ struct Carve {  // bump allocator over the workspace, 256-B aligned regions
 };
 }  // namespace
 
+// fp32 floats of slab a weight-gradient GEMM of this shape needs (gemm_tn_plan.h): splits * N * K. A launch that writes
+// its output directly (one split: the token head) needs none, but its output's worth stays reserved as it always was, so
+// the workspace layout does not move.
+static int64_t tn_slab_floats(int64_t Mtot, int Ncols, int N, int K) {
+  PlbGemmTNPlan pl;
+  if (plb_gemm_tn_plan(Mtot, Ncols, N, K, PLB_TN_BF16, &pl)) return 0;
+  return pl.direct ? (int64_t)N * K : pl.slab_floats;
+}
+
 extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
   if (!cfg || !out) return fail("plb_create: null argument");
   const PlbConfig& c = *cfg;
@@ -159,16 +168,16 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
   if (tr) {
     e->o_dhm = cv.take(NM * H * 2);
     // reductions
+    // the slab of the weight-gradient GEMMs: the largest need over the four layer weights (all L applications stacked),
+    // map-in, the phoneme head (reads 256 columns, stores NP rows) and the token head
     int64_t slab = 0;
     {
       const int64_t Mtot = L * Tp;
       const int ntp = (int)rup(e->NT, 256);
-      const int shapes[7][2] = {{(int)(3 * H), (int)H}, {(int)H, (int)H}, {(int)I, (int)H}, {(int)H, (int)I}, {(int)H, (int)E}, {e->NP, (int)H}, {ntp, (int)H}};
+      const int shapes[7][3] = {{(int)(3 * H), (int)(3 * H), (int)H}, {(int)H, (int)H, (int)H}, {(int)I, (int)I, (int)H}, {(int)H, (int)H, (int)I},
+                                {(int)H, (int)H, (int)E}, {256, e->NP, (int)H}, {ntp, ntp, (int)H}};   // Ncols, N, K
       for (int i = 0; i < (e->NT ? 7 : 6); ++i) {
-        int rps;
-        const int64_t mt = i < 4 ? Mtot : Tp;
-        const int s = tn_splits(mt, shapes[i][0], shapes[i][1], &rps);
-        const int64_t f = (int64_t)s * shapes[i][0] * shapes[i][1];
+        const int64_t f = tn_slab_floats(i < 4 ? Mtot : Tp, shapes[i][0], shapes[i][1], shapes[i][2]);
         if (f > slab) slab = f;
       }
     }
@@ -186,12 +195,8 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
     e->o_qkvcol = cv.take((int64_t)L * e->qkvcol_rows * 3 * H * 4);
     e->o_scratch = cv.take(512 * (3 * H > I ? 3 * H : I) * 4);  // colsum partials: up to 512 row splits
     e->o_scratch2 = cv.take(512 * (3 * H > I ? 3 * H : I) * 4);
-    {
-      int rps;
-      const int s2 = tn_splits(Tp, (int)H, (int)E, &rps);
-      e->slab2_floats = (int64_t)s2 * H * E;
-      e->o_slab2 = cv.take(e->slab2_floats * 4);
-    }
+    e->slab2_floats = tn_slab_floats(Tp, (int)H, (int)H, (int)E);   // map-in on the side stream
+    e->o_slab2 = cv.take(e->slab2_floats * 4);
   }
   if (e->NT) {
     const int64_t NTp = rup(e->NT, 256);

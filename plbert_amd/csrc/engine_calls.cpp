@@ -442,11 +442,11 @@ static int backward_tail_streams(PlbEngine* e, const Call& c, bf16_t* dy, int du
   const bool t8 = e->tn8_call;   // fp8 call: gradient (e5m2) x activation (e4m3) images of all L applications
   float* const slab = e->at<float>(e->o_slab);
   HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_Q_W), 3 * H * H * 4, "Q/K/V weight gradients");
-  if (t8 ? weight_grad8(e, st.dq8, st.x8, Mtot, 3 * H, H, F8_DQ, F8_X, e->grd(PLB_Q_W), s)
+  if (t8 ? weight_grad(e, st.dq8, 3 * H, 3 * H, st.x8, H, Mtot, 3 * H, H, e->grd(PLB_Q_W), s, false, F8_DQ, F8_X)
          : weight_grad(e, st.dqkv, 3 * H, 3 * H, st.x, H, Mtot, 3 * H, H, e->grd(PLB_Q_W), s)) return 1;
   if (ov && reduce_pieces(e, kPieceQkvW, kPieceFfnW, s)) return 1;
   HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_FFN_W), (int64_t)I * H * 4, "ffn.weight gradient");
-  if (t8 ? weight_grad8(e, st.du8, st.a8, Mtot_c, I, H, F8_DU, F8_A, e->grd(PLB_FFN_W), s)
+  if (t8 ? weight_grad(e, st.du8, I, I, st.a8, H, Mtot_c, I, H, e->grd(PLB_FFN_W), s, false, F8_DU, F8_A)
          : weight_grad(e, st.du, I, I, st.a, H, Mtot_c, I, H, e->grd(PLB_FFN_W), s)) return 1;
   if (ov && reduce_pieces(e, kPieceFfnW, kPieceSmall, s)) return 1;
   if (ov) {
@@ -460,11 +460,11 @@ static int backward_tail_streams(PlbEngine* e, const Call& c, bf16_t* dy, int du
     if (reduce_pieces(e, kPieceSmall, kPieceFfnoW, s2)) return 1;
   }
   HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_FFNO_W), (int64_t)I * H * 4, "ffn_output.weight gradient");
-  if (t8 ? weight_grad8(e, st.dp8, st.g8, Mtot_c, H, I, F8_DP, F8_G, e->grd(PLB_FFNO_W), s)
+  if (t8 ? weight_grad(e, st.dp8, H, H, st.g8, I, Mtot_c, H, I, e->grd(PLB_FFNO_W), s, false, F8_DP, F8_G)
          : weight_grad(e, st.dpre2, H, H, st.g, I, Mtot_c, H, I, e->grd(PLB_FFNO_W), s)) return 1;
   if (ov && reduce_pieces(e, kPieceFfnoW, kPieceDenseW, s)) return 1;
   HB_W(s, slab, e->slab_floats * 4, "weight-gradient slab"); HB_W(s, e->grd(PLB_DENSE_W), (int64_t)H * H * 4, "dense.weight gradient");
-  if (t8 ? weight_grad8(e, st.dp18, st.c8, Mtot_c, H, H, F8_DP1, F8_C, e->grd(PLB_DENSE_W), s)
+  if (t8 ? weight_grad(e, st.dp18, H, H, st.c8, H, Mtot_c, H, H, e->grd(PLB_DENSE_W), s, false, F8_DP1, F8_C)
          : weight_grad(e, st.dpre1, H, H, st.ctx, H, Mtot_c, H, H, e->grd(PLB_DENSE_W), s)) return 1;
   if (ov && reduce_pieces(e, kPieceDenseW, kNPieces, s)) return 1;   // the smallest weight goes last
   return 0;

@@ -87,8 +87,16 @@ F8Weight::F8Weight(const PlbEngine* e, int w) {
 bool f8_call(const PlbEngine* e, int64_t Tp, bool train) {
   return e->fp8_on && e->fp8_ready && (!train || e->fp8_bwd_ready) && fp8_shapes_ok(e, Tp);
 }
+// Shapes of a call whose weight gradients may read the 1-byte images: each of the four layer weights goes to the pipeline
+// kernel in bf16 (gemm_tn_plan.h: 256-column multiples, 8192 rows and more) and has an fp8 form.
 bool tn8_ok(const PlbEngine* e, int64_t Mtot) {
-  return Mtot % 128 == 0 && e->H % 256 == 0 && e->I % 256 == 0 && Mtot >= 8192;
+  const int H = e->H, I = e->I, shapes[4][2] = {{3 * H, H}, {H, H}, {I, H}, {H, I}};
+  for (const auto& nk : shapes) {
+    PlbGemmTNPlan bf, f8;
+    if (plb_gemm_tn_plan(Mtot, nk[0], nk[0], nk[1], PLB_TN_BF16, &bf) || bf.kernel != PLB_TN_PIPELINE) return false;
+    if (plb_gemm_tn_plan(Mtot, nk[0], nk[0], nk[1], PLB_TN_FP8, &f8)) return false;
+  }
+  return true;
 }
 
 extern "C" int plb_set_fp8(PlbEngine* e, int32_t on, void* stream) {

@@ -357,11 +357,8 @@ bool prune_enabled();
 int run_encoder(PlbEngine* e, const Call& c, bool stash, bf16_t** xout, const Prune* pr);
 PlbEmbed embed_desc(const PlbEngine* e, const Call& c);
 PlbEmbedIn embed_in_desc(const PlbEngine* e, const EmbedCall& ec, const PlbEmbed* base);
-int tn_splits(int64_t Mtot, int N, int K, int* rows_per_split);
-int weight_grad(PlbEngine* e, const bf16_t* A, int lda, int Ncols, const bf16_t* Bm, int ldb, int64_t Mtot, int N,
-                int K, float* out, hipStream_t s, bool side_slab = false);
-int weight_grad8(PlbEngine* e, const uint8_t* A8, const uint8_t* B8, int64_t Mtot, int N, int K, int site_a, int site_b,
-                 float* out, hipStream_t s);
+int weight_grad(PlbEngine* e, const void* A, int lda, int Ncols, const void* Bm, int ldb, int64_t Mtot, int N, int K,
+                float* out, hipStream_t s, bool side_slab = false, int site_a = -1, int site_b = -1);   // sites: an fp8 call
 int encoder_bwd(PlbEngine* e, const Call& c, const Prune* pr, bf16_t** dy, int* du_rows, const float* const* d_below);
 // engine_calls.cpp
 void drop_stash(PlbEngine* e, const char* by);

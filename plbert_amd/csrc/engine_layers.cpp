@@ -1,51 +1,8 @@
 // Launch sequences of the shared layer: embeddings + L applications forward (run_encoder), the layer loop of the backward
-// (encoder_bwd), both with the last application full or pruned to the masked rows, and the token-major weight-gradient
-// GEMMs with their split rule. Only writer of u_is_derivative, tn8_call and part_rows_used, which the forward of a call
-// leaves for its backward.
+// (encoder_bwd), both with the last application full or pruned to the masked rows, and the launch of a token-major
+// weight-gradient GEMM as its plan (gemm_tn_plan.h) says. Only writer of u_is_derivative, tn8_call and part_rows_used,
+// which the forward of a call leaves for its backward.
 #include "engine_internal.h"
-
-// Row splits of a token-major weight-gradient GEMM. Shapes that fit the 256x256 pipeline kernel get
-// one workgroup per CU (tiles x splits <= 256); the rest use the 128x128 kernel at ~3 workgroups per CU.
-static bool tn_big(int64_t Mtot, int Ncols, int K) { return Ncols % 256 == 0 && K % 256 == 0 && Mtot >= 8192; }
-// PLBERT_TN_SPLITS=xcd restores round 1's rule (8 * s splits, s * tiles <= 32: whole splits per XCD, but only 192-216
-// of the 256 CUs busy on the model's shapes); default: as many splits as fit one workgroup per CU.
-static bool tn_fill_chip() {
-  static const bool v = [] { const char* e = getenv("PLBERT_TN_SPLITS"); return !(e && !strcmp(e, "xcd")); }();
-  return v;
-}
-// PLBERT_TN_CUS = n (64..256, default 256): workgroups a big weight-gradient GEMM may occupy. The tail of the backward is
-// where the gradient pieces travel; RCCL's kernels need CUs of their own and the one-workgroup-per-CU grids leave 4-16
-// (dense.weight: 4). Lowering n trades GEMM width for CUs the collective finds free — a knob for the first real N > 1 run
-// (bench.py reports the tail's GEMM time with and without the exchange), read once per process.
-static int tn_cus() {
-  static const int v = [] {
-    const char* e = getenv("PLBERT_TN_CUS");
-    const int n = e ? atoi(e) : 256;
-    return (n >= 64 && n <= 256) ? n : 256;
-  }();
-  return v;
-}
-int tn_splits(int64_t Mtot, int N, int K, int* rows_per_split) {
-  const bool big = tn_big(Mtot, N, K);
-  const int tiles = big ? (N / 256) * (K / 256) : ((N + 127) / 128) * ((K + 127) / 128);
-  int splits = 768 / tiles;
-  if (big) {
-    // One workgroup per CU (128 KiB of LDS each): tiles * splits <= 256 and as close to it as the tile count allows —
-    // 24 tiles (the two FFN weights) -> 10 splits = 240 workgroups, 27 (QKV) -> 9 = 243, 9 (dense) -> 28 = 252. The
-    // kernel deals the (split, tile) pairs to the XCDs in contiguous runs (xcd_remap), so an XCD still streams a
-    // contiguous range of token rows through its L2 (a split may straddle two XCDs).
-    int s = 32 / tiles;
-    if (s < 1) s = 1;
-    splits = tiles >= 256 ? 1 : (tn_fill_chip() ? (tn_cus() / tiles > 0 ? tn_cus() / tiles : 1) : 8 * s);  // a wide output (token head) needs no row splits
-  }
-  const int64_t maxs = Mtot / 64;
-  if (splits > maxs) splits = (int)maxs;
-  if (splits < 1) splits = 1;
-  int64_t rps = rup((Mtot + splits - 1) / splits, 64);
-  splits = (int)((Mtot + rps - 1) / rps);
-  *rows_per_split = (int)rps;
-  return splits;
-}
 
 // ---- launch descriptors -----------------------------------------------------------------------------------------------
 // C[M, N] = A[M, K] · B[N, K]^T on packed operands (lda = ldb = K), every row stored: the callers add bias, residual and
@@ -434,45 +391,31 @@ int run_encoder(PlbEngine* e, const Call& c, bool stash, bf16_t** xout, const Pr
   return 0;
 }
 
-// dW[N,K] = A^T B over Mtot rows -> grads[which] (overwrite)
-int weight_grad(PlbEngine* e, const bf16_t* A, int lda, int Ncols, const bf16_t* Bm, int ldb, int64_t Mtot, int N,
-                       int K, float* out, hipStream_t s, bool side_slab) {
+// dW[N,K] = A^T B over Mtot rows -> out (overwrite): the kernel, the row splits and the slab need are the plan's
+// (gemm_tn_plan.h). site_a >= 0: an fp8 call on the per-layer 1-byte images, A = e5m2 gradient image [Mtot, N], B = e4m3
+// activation image [Mtot, K] (lda / ldb in bytes), one dequantisation factor per operand site (shared by the L applications).
+int weight_grad(PlbEngine* e, const void* A, int lda, int Ncols, const void* Bm, int ldb, int64_t Mtot, int N, int K,
+                float* out, hipStream_t s, bool side_slab, int site_a, int site_b) {
+  const bool f8 = site_a >= 0;
+  PlbGemmTNPlan pl;
+  if (plb_gemm_tn_plan(Mtot, Ncols, N, K, f8 ? PLB_TN_FP8 : PLB_TN_BF16, &pl)) return fail("weight_grad: no kernel takes the shape");
   PlbGemmTN t;
   memset(&t, 0, sizeof(t));
-  t.A = A; t.lda = lda; t.Ncols = Ncols; t.B = Bm; t.ldb = ldb; t.Mtot = (int)Mtot; t.N = N; t.K = K;
-  t.splits = tn_splits(Mtot, N, K, &t.rows_per_split);
-  const bool direct = t.splits == 1 && N == Ncols;  // every element is written exactly once: no slab, no reduce
-  if (!direct && (int64_t)t.splits * N * K > (side_slab ? e->slab2_floats : e->slab_floats)) return fail("weight_grad: slab too small");
+  t.A = static_cast<const bf16_t*>(A); t.lda = lda; t.Ncols = Ncols; t.B = static_cast<const bf16_t*>(Bm); t.ldb = ldb;
+  t.Mtot = (int)Mtot; t.N = N; t.K = K; t.splits = pl.splits; t.rows_per_split = pl.rows_per_split;
+  const bool direct = pl.direct != 0;   // every element is written exactly once: no slab, no reduce
+  if (pl.slab_floats > (side_slab ? e->slab2_floats : e->slab_floats))
+    return fail(f8 ? "weight_grad8: slab too small" : "weight_grad: slab too small");
   t.slab = direct ? out : e->at<float>(side_slab ? e->o_slab2 : e->o_slab);
-  if (N == Ncols && tn_big(Mtot, Ncols, K)) {
-    const int tok = plb_prof_begin(PLB_K_GEMM_TN, s, 2.0 * (double)Mtot * N * K, 0.0);
-    TRY(plb_launch_gemm_tn_big(&t, s));
-    plb_prof_end(tok, s);
+  if (f8) { t.deq_a = f8_deq(e, f8_site(e, site_a, 0)); t.deq_b = f8_deq(e, f8_site(e, site_b, 0)); }
+  if (pl.kernel == PLB_TN_SMALL) {
+    TRY(plb_launch_gemm_tn(&t, s));   // (opens its own profiler scope)
   } else {
-    TRY(plb_launch_gemm_tn(&t, s));
+    const int tok = plb_prof_begin(f8 ? PLB_K_GEMM_TN_FP8 : PLB_K_GEMM_TN, s, pl.flops, 0.0);
+    TRY(f8 ? plb_launch_gemm_tn_fp8(&t, s) : plb_launch_gemm_tn_big(&t, s));
+    plb_prof_end(tok, s);
   }
   if (!direct) TRY(plb_launch_reduce_slabs(t.slab, t.splits, (size_t)N * K, out, 0, s));
-  return 0;
-}
-
-// The same on the per-layer 1-byte images of an fp8 call: A8 = e5m2 gradient image [Mtot, N], B8 = e4m3 activation image
-// [Mtot, K] (row strides = widths in bytes), one dequantisation factor per operand site (shared by the L applications).
-int weight_grad8(PlbEngine* e, const uint8_t* A8, const uint8_t* B8, int64_t Mtot, int N, int K, int site_a, int site_b,
-                        float* out, hipStream_t s) {
-  PlbGemmTN t;
-  memset(&t, 0, sizeof(t));
-  t.A = reinterpret_cast<const bf16_t*>(A8); t.lda = N; t.Ncols = N; t.B = reinterpret_cast<const bf16_t*>(B8); t.ldb = K;
-  t.Mtot = (int)Mtot; t.N = N; t.K = K;
-  t.splits = tn_splits(Mtot, N, K, &t.rows_per_split);
-  t.rows_per_split = (int)rup(t.rows_per_split, 128);   // K-tiles of 128 tokens
-  t.splits = (int)((Mtot + t.rows_per_split - 1) / t.rows_per_split);
-  if ((int64_t)t.splits * N * K > e->slab_floats) return fail("weight_grad8: slab too small");
-  t.slab = e->at<float>(e->o_slab);
-  t.deq_a = f8_deq(e, f8_site(e, site_a, 0)); t.deq_b = f8_deq(e, f8_site(e, site_b, 0));
-  const int tok = plb_prof_begin(PLB_K_GEMM_TN_FP8, s, 2.0 * (double)Mtot * N * K, 0.0);
-  TRY(plb_launch_gemm_tn_fp8(&t, s));
-  plb_prof_end(tok, s);
-  TRY(plb_launch_reduce_slabs(t.slab, t.splits, (size_t)N * K, out, 0, s));
   return 0;
 }
 

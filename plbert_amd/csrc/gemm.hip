@@ -1,17 +1,14 @@
-// bf16 MFMA GEMMs of the ALBERT step, gfx950.
+// bf16 MFMA GEMMs of the ALBERT step, gfx950: the small NT kernel and the NT entry.
 //
 //  gemm_nt : C[M,N] = A[M,K] · B[N,K]^T (+bias) (+residual) with fused epilogues
 //            forward projections (Y = X·W^T with W stored [out,in] as in the reference state-dict,
 //            modeling_albert.py:166-170,196,228-230,272; model.py:28) and the dX products of the
 //            backward pass (dX = dY·W computed as dY·(W^T)^T against the transposed weight copy).
-//  gemm_tn : dW[N,K] = A[Mtot,N]^T · B[Mtot,K]   (reduction over tokens, split over the grid; both
-//            operands are token-major, so fragments come from transposed LDS reads).
+// (The token-major weight-gradient GEMMs, dW = A^T · B, are gemm_tn.hip's.)
 //
 // Tile 128x128, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16x32 tiles, fp32
-// accumulate (NT also as 64x64, waves of 32x32, for launches too small to fill the chip). NT operands
-// are staged by LDS-DMA (global_load_lds), TN operands through registers
-// (double buffered, one barrier per k-tile); LDS images are XOR-swizzled / strip-rotated so ds_read_b128 / ds_read_b64_tr_b16 and
-// the ds_write_b128 staging stores are bank-conflict free.
+// accumulate (also as 64x64, waves of 32x32, for launches too small to fill the chip). Operands
+// are staged by LDS-DMA (global_load_lds); LDS images are XOR-swizzled so ds_read_b128 is bank-conflict free.
 #include "common.h"
 #include "plbert_kernels.h"
 #include "gemm_epilogue.h"
@@ -20,7 +17,6 @@ namespace {
 
 constexpr int BK = 64;
 
-// ---- NT ------------------------------------------------------------------------------------------
 // LDS image of a [TILE rows][64 k] bf16 tile: 128-B rows, 16-B chunk index XORed with (row>>1)&7.
 DEVI int nt_lds_off(int row, int chunk) { return row * BK + ((chunk ^ ((row >> 1) & 7)) << 3); }
 
@@ -125,107 +121,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(PlbGemmNT p) {
   }
 }
 
-// ---- TN ------------------------------------------------------------------------------------------
-// LDS image of a [64 t][128 cols] bf16 tile for transposed reads: 16-column strips, each strip a
-// run of 64 32-byte units (one per t) ordered so that t and t+8 are 4 units apart (bits 2,3 of t
-// swapped) and rotated by the strip index: a half-wave's ds_read_b64_tr_b16 (8 rows x 32 B) then
-// covers one contiguous 256-B window, and an 8-lane ds_write_b128 group covers 128 B.
-DEVI int tn_unit(int t) { return (t & 3) | (((t >> 3) & 1) << 2) | (((t >> 2) & 1) << 3) | (t & 48); }
-DEVI int tn_lds_off(int t, int col) {
-  int s = col >> 4;
-  return s * 1024 + (((tn_unit(t) + s) & 63) << 4) + (col & 15);
-}
-
-__global__ __launch_bounds__(256) void gemm_tn_kernel(PlbGemmTN p) {
-  __shared__ __attribute__((aligned(16))) bf16_t smem[2][2][64 * 128];  // [stage][A|B] 64 KiB
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wn = wave >> 1, wk = wave & 1;
-  const int nbk = (p.K + 127) / 128;
-  const int bn = blockIdx.x / nbk, bk = blockIdx.x % nbk;
-  const int split = blockIdx.y;
-  const int t_begin = split * p.rows_per_split;
-  int t_end = t_begin + p.rows_per_split;
-  if (t_end > p.Mtot) t_end = p.Mtot;
-  const int nt = (t_end - t_begin) / 64;
-
-  const int lc = tid & 15, lr = tid >> 4;  // staging: 16 rows x 16 chunks per pass, 4 passes
-  const int colA = bn * 128 + lc * 8, colB = bk * 128 + lc * 8;
-  const bool okA = colA < p.Ncols, okB = colB < p.K;
-  uint4 ra[4], rb[4];
-  auto load_tile = [&](int it) {
-    const size_t t0 = (size_t)t_begin + (size_t)it * 64 + lr;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      ra[i] = okA ? *(const uint4*)(p.A + (t0 + 16 * i) * p.lda + colA) : make_uint4(0, 0, 0, 0);
-      rb[i] = okB ? *(const uint4*)(p.B + (t0 + 16 * i) * p.ldb + colB) : make_uint4(0, 0, 0, 0);
-    }
-  };
-  auto store_tile = [&](int st) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int off = tn_lds_off(lr + 16 * i, lc * 8);
-      *(uint4*)&smem[st][0][off] = ra[i];
-      *(uint4*)&smem[st][1][off] = rb[i];
-    }
-  };
-
-  f32x4 acc[4][4];  // [n tile][k tile]
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-  if (nt > 0) {
-    load_tile(0);
-    store_tile(0);
-  }
-  __syncthreads();
-  for (int it = 0; it < nt; ++it) {
-    const int cur = it & 1;
-    if (it + 1 < nt) load_tile(it + 1);
-    const bf16_t* sA = smem[cur][0];
-    const bf16_t* sB = smem[cur][1];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int t0 = ks * 32 + 8 * g + q;
-      bf16x8 af[4], bfr[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int ca = wn * 64 + i * 16 + 4 * pp, cb = wk * 64 + i * 16 + 4 * pp;
-        s16x4 a0 = lds_read_tr16(&sA[tn_lds_off(t0, ca)]);
-        s16x4 a1 = lds_read_tr16(&sA[tn_lds_off(t0 + 4, ca)]);
-        s16x4 b0 = lds_read_tr16(&sB[tn_lds_off(t0, cb)]);
-        s16x4 b1 = lds_read_tr16(&sB[tn_lds_off(t0 + 4, cb)]);
-        af[i] = bf16x8{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-        bfr[i] = bf16x8{b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-      }
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int ki = 0; ki < 4; ++ki)
-          // D[row = k col][col = n]: lane owns 4 consecutive k of one output row n
-          acc[ni][ki] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ki], af[ni], acc[ni][ki], 0, 0, 0);
-    }
-    if (it + 1 < nt) store_tile(cur ^ 1);
-    __syncthreads();
-  }
-
-  float* out = p.slab + (size_t)split * p.N * p.K;
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int n = bn * 128 + wn * 64 + ni * 16 + li;
-    if (n >= p.N) continue;
-#pragma unroll
-    for (int ki = 0; ki < 4; ++ki) {
-      const int k0 = bk * 128 + wk * 64 + ki * 16 + 4 * g;
-      if (k0 >= p.K) continue;
-      f32x4 v = acc[ni][ki];
-      *(float4*)(out + (size_t)n * p.K + k0) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  }
-}
-
 }  // namespace
 
 int gemm_nt_big_run(const PlbGemmNT* p, const PlbGemmNTPlan& pl, int form, hipStream_t stream);   // gemm_big.hip
@@ -263,15 +158,4 @@ extern "C" int plb_launch_gemm_nt(const PlbGemmNT* p, int act, int out_f32, hipS
   }
   plb_prof_end(tok, stream);
   return rc;
-}
-
-extern "C" int plb_launch_gemm_tn(const PlbGemmTN* p, hipStream_t stream) {
-  if (p->Mtot % 64 || p->rows_per_split % 64 || p->K % 4 || p->N <= 0 || p->splits <= 0) return 1;
-  if ((long)p->splits * p->rows_per_split < p->Mtot) return 1;
-  dim3 grid(((p->N + 127) / 128) * ((p->K + 127) / 128), p->splits), block(256);
-  const int tok = plb_prof_begin(PLB_K_GEMM_TN, stream, 2.0 * p->Mtot * (double)p->N * p->K,
-                                 2.0 * p->Mtot * ((double)p->N + p->K) + 4.0 * p->splits * (double)p->N * p->K);
-  hipLaunchKernelGGL(gemm_tn_kernel, grid, block, 0, stream, *p);
-  plb_prof_end(tok, stream);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/plbert.h"   // PLB_NPARAM, PlbAdamWSegment (the segmented optimizer launches)
+#include "gemm_tn_plan.h"            // PlbGemmTNPlan: kernel, row splits and slab need of a token-major weight-gradient GEMM
 #include "gemm_nt_plan.h"            // PlbGemmNTPlan and the form / operand / option names of the NT GEMM launchers (+ prof_classes.h)
 
 typedef uint16_t bf16_t;
@@ -100,6 +101,9 @@ int plb_gemm_nt_colpart_rows(int M, int N, int K);  // the plan's colpart rows o
 void plb_set_gemm_nt_tile(int tile);
 void plb_set_gemm_nt_prefetch(int on);
 
+// ---- TN (token-major weight-gradient) GEMM launchers (gemm_tn.hip, gemm_tn_fp8.hip). They run the splits their caller
+// hands them; which kernel a shape gets and with what splits is the plan's, declared in gemm_tn_plan.h:
+int plb_gemm_tn_plan(int64_t Mtot, int Ncols, int N, int K, int operands, PlbGemmTNPlan* plan);
 // slab[split][N][K] = A[rows,N]^T · B[rows,K] over the split's rows; Mtot%64==0, rows_per_split%64==0,
 // Ncols (readable columns of A) %8==0, K%8==0.
 typedef struct {
@@ -114,7 +118,7 @@ int plb_launch_gemm_tn(const PlbGemmTN* p, hipStream_t stream);
 // fp8 form of plb_launch_gemm_tn_big (gemm_tn_fp8.hip): A = e5m2 image [rows, Ncols], B = e4m3 image [rows, K], lda / ldb in
 // bytes (multiples of 16); Ncols % 256 == 0, K % 256 == 0, rows_per_split % 128 == 0, Mtot % 128 == 0
 int plb_launch_gemm_tn_fp8(const PlbGemmTN* p, hipStream_t stream);
-// 256x256-tile pipeline version: Ncols % 256 == 0, K % 256 == 0 (gemm_big.hip)
+// 256x256-tile pipeline version: Ncols % 256 == 0, K % 256 == 0 (gemm_tn.hip)
 int plb_launch_gemm_tn_big(const PlbGemmTN* p, hipStream_t stream);
 
 // out[n] (+)= sum over splits of slab[s][n]   (n = count of floats)

@@ -452,6 +452,11 @@ TN_BIG = tuple((mt, nc, n, k, sp, rps, nc + 8, k + 8) for mt, nc, n, k, sp, rps 
 TN_FP8 = tuple((mt, nc, nc, k, sp, rps, nc + 16, k + 32) for mt, nc, k, sp, rps in (
     (256, 256, 256, 2, 128), (512, 512, 256, 2, 256), (768, 256, 512, 2, 384), (1024, 512, 512, 2, 512),
     (1280, 256, 256, 2, 640), (384, 256, 512, 2, 256), (256, 512, 256, 2, 256), (384, 256, 256, 1, 384)))
+# (kind, Mtot, Ncols, N, K, lda, ldb): splits and rows_per_split are the PLAN's (csrc/gemm_tn_plan.h), not a table's. 8192 rows
+# is the smallest call the plan sends to the pipeline kernels: 128 splits of 64 rows in bf16, 64 of 128 in fp8, so every
+# split runs the one-K-tile path; the small kernel with N < Ncols (the phoneme head's form): 6 splits of 64 rows
+TN_PLANNED = (("big", 8192, 256, 256, 256, 264, 264), ("fp8", 8192, 256, 256, 256, 272, 288), ("small", 384, 256, 188, 136, 264, 136))
+TN_PLANNED_SPLITS = ((128, 64), (64, 128), (6, 64))
 
 
 def int_operands(shape, lo, hi, seed, kind="bf16", unit=1.0):
@@ -714,6 +719,13 @@ def exact_cases():
     for i, (Mtot, Ncols, N, K, splits, rps, lda, ldb) in enumerate(TN_FP8):
         A, B = tn_operands(Mtot, Ncols, K, 6500 + i, kinds=("e5m2", "e4m3"))
         yield f"tn fp8 {i}", operand_values(A, "e5m2").T * FP8_DEQ[0], operand_values(B, "e4m3").T * FP8_DEQ[1], None, None, unit8
+    for i, (kind, Mtot, Ncols, N, K, lda, ldb) in enumerate(TN_PLANNED):
+        if kind == "fp8":
+            A, B = tn_operands(Mtot, Ncols, K, 6600 + i, kinds=("e5m2", "e4m3"))
+            yield f"tn planned {i}", operand_values(A, "e5m2").T * FP8_DEQ[0], operand_values(B, "e4m3").T * FP8_DEQ[1], None, None, unit8
+        else:
+            A, B = tn_operands(Mtot, Ncols, K, 6600 + i)
+            yield f"tn planned {i}", A.T, B.T, None, None, 1.0
 
 
 # ---- the LayerNorm element contract (tests/test_gpu_layernorm_rows.py, tests/test_layernorm_rows_host.py) -----------------

@@ -37,7 +37,8 @@ import torch
 
 from plbert_amd import _lib
 from gpu_util import (CE_COLS, CE_SHAPE, CE_TILES, EXACT_LIMIT, FP8_DEQ, FP8_KTILES, FP8_NT_FORMS, GELU_KTILES, GELU_UNIT,
-                      LN_CASES, NT_FORM_PARAMS, NT_FORMS, NT_STRIDE_KTILES, NT_TAILS, SENTINEL, TN_BIG, TN_FP8, TN_SMALL, Ln,
+                      LN_CASES, NT_FORM_PARAMS, NT_FORMS, NT_STRIDE_KTILES, NT_TAILS, SENTINEL, TN_BIG, TN_FP8, TN_PLANNED,
+                      TN_PLANNED_SPLITS, TN_SMALL, Ln,
                       assert_exact, assert_untouched, exact_bound, exact_nt, exact_tn, first_mismatch, gelu64, gelu_grad64,
                       gemm_nt, gemm_nt_fp8, gemm_tn_slabs, int_operands, nt_operands, operand_values, reduce_slabs, rne_bf16,
                       spacing_bf16, stream, tn_operands)
@@ -364,6 +365,16 @@ def test_tn_big_bitwise(case):
 @pytest.mark.parametrize("case", range(len(TN_FP8)))
 def test_tn_fp8_bitwise(case):
     check_tn("fp8", TN_FP8[case], 6500 + case)
+
+
+@pytest.mark.parametrize("case", range(len(TN_PLANNED)))
+def test_tn_bitwise_on_the_plans_splits(case):
+    """The same check with the splits the engine launches: kernel, splits and rows per split from plb_gemm_tn_plan."""
+    kind, Mtot, Ncols, N, K, lda, ldb = TN_PLANNED[case]
+    p = _lib.gemm_tn_plan(Mtot, Ncols, N, K, int(kind == "fp8"))
+    assert (p["rc"], p["kernel"]) == (0, {"small": 0, "big": 1, "fp8": 2}[kind]), p
+    assert (p["splits"], p["rows_per_split"]) == TN_PLANNED_SPLITS[case], p
+    check_tn(kind, (Mtot, Ncols, N, K, p["splits"], p["rows_per_split"], lda, ldb), 6600 + case)
 
 
 @pytest.mark.parametrize("splits", [3, 5])

@@ -66,20 +66,29 @@ TN_SHAPES = [(196608, 2304, 768), (196608, 768, 768), (196608, 2048, 768), (1966
              (16384, 2304, 768), (16384, 768, 768), (32768, 2304, 768)]
 
 
-def time_tn(L, Mtot, N, K, big, iters=5):
+def time_tn(L, Mtot, N, K, kind, iters=5):
+    """kind "bf16": the kernel the plan picks for the shape (pipeline or small); "fp8": the pipeline kernel on 1-byte images
+    with unit dequantisation factors. Splits and rows per split are the plan's (csrc/gemm_tn_plan.h), i.e. the engine's."""
     dev = "cuda"
-    A = torch.randn(Mtot, N, device=dev).to(torch.bfloat16)
-    B = torch.randn(Mtot, K, device=dev).to(torch.bfloat16)
-    tiles = (N // 256) * (K // 256) if big else ((N + 127) // 128) * ((K + 127) // 128)
-    splits = 8 * max(1, 32 // tiles) if big else max(1, 768 // tiles)
-    rps = ((Mtot + splits - 1) // splits + 63) // 64 * 64
-    splits = (Mtot + rps - 1) // rps
+    fp8 = kind == "fp8"
+    pl = _lib.gemm_tn_plan(Mtot, N, N, K, int(fp8))
+    assert pl["rc"] == 0, (Mtot, N, K, kind)
+    if fp8:
+        A = torch.randint(0, 256, (Mtot, N), dtype=torch.uint8, device=dev) & 0x77   # finite in e5m2 and e4m3
+        B = torch.randint(0, 256, (Mtot, K), dtype=torch.uint8, device=dev) & 0x77
+        deq = torch.ones(2, dtype=torch.float32, device=dev)
+    else:
+        A = torch.randn(Mtot, N, device=dev).to(torch.bfloat16)
+        B = torch.randn(Mtot, K, device=dev).to(torch.bfloat16)
+    splits, rps = pl["splits"], pl["rows_per_split"]
     slab = torch.empty(splits * N * K, dtype=torch.float32, device=dev)
     p = _lib.PlbGemmTN()
     p.A, p.lda, p.Ncols, p.B, p.ldb = A.data_ptr(), N, N, B.data_ptr(), K
     p.Mtot, p.N, p.K, p.rows_per_split, p.splits, p.slab = Mtot, N, K, rps, splits, slab.data_ptr()
+    if fp8:
+        p.deq_a, p.deq_b = deq.data_ptr(), deq.data_ptr() + 4
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    fn = L.plb_launch_gemm_tn_big if big else L.plb_launch_gemm_tn
+    fn = (L.plb_launch_gemm_tn, L.plb_launch_gemm_tn_big, L.plb_launch_gemm_tn_fp8)[pl["kernel"]]
     assert fn(C.byref(p), s) == 0
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -96,6 +105,7 @@ def main():
     ap.add_argument("--tiles", default="128,256,384,0")
     ap.add_argument("--act", type=int, default=0)
     ap.add_argument("--tn", action="store_true")
+    ap.add_argument("--tn-kinds", default="bf16,fp8", help="--tn: operand kinds to time (the plan picks kernel and splits)")
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--small-ab", action="store_true",
@@ -134,13 +144,14 @@ def main():
         for rep in range(args.reps):
             for (M, N, K) in shapes_tn:
                 for (ln, lib) in libs:
-                    ms, tf, sp = time_tn(lib, M, N, K, 1, iters=3)
-                    res.setdefault((ln, M, N, K, sp), []).append(ms)
-        for (ln, M, N, K, sp), v in res.items():
+                    for kind in args.tn_kinds.split(","):
+                        ms, tf, sp = time_tn(lib, M, N, K, kind, iters=3)
+                        res.setdefault((ln, kind, M, N, K, sp), []).append(ms)
+        for (ln, kind, M, N, K, sp), v in res.items():
             v = sorted(v)
             med = v[len(v) // 2]
-            print(f"{ln:14s} tn big Mtot {M} N {N:5d} K {K:5d} splits {sp:3d}  median {med*1e3:9.1f} us  "
-                  f"{2.0*M*N*K/(med*1e-3)/1e12:7.1f} TFLOP/s", flush=True)
+            print(f"{ln:14s} tn {kind:4s} Mtot {M} N {N:5d} K {K:5d} splits {sp:3d}  median {med*1e3:9.1f} us  min {v[0]*1e3:9.1f} us  "
+                  f"max {v[-1]*1e3:9.1f} us  {2.0*M*N*K/(med*1e-3)/1e12:7.1f} TFLOP/s", flush=True)
         return
     shapes = [tuple(int(v) for v in t.split(",")) for t in args.shapes.split(";")] if args.shapes else SHAPES
     # A/B protocol: box-to-box and minute-to-minute drift is 5-10 %, so variants are timed round-robin

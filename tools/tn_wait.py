@@ -1,4 +1,4 @@
-"""Is the token-major weight-gradient GEMM waiting for memory? (build: python tools/build_variant.py tndbg --only gemm_big.hip
+"""Is the token-major weight-gradient GEMM waiting for memory? (build: python tools/build_variant.py tndbg --only gemm_tn.hip
 -DTN_DBG=1; run on the GPU box with PLBERT_HIP_LIB=plbert_amd/build/ab/lib_tndbg.so)
 Prints, per shape, the kernel's own stamps (time per K-tile, share of the loop spent in the vmcnt wait) for a COLD run
 (operands far larger than the 256 MB Infinity Cache) and for a small problem replayed from the caches."""
