@@ -358,6 +358,8 @@ INTERNAL = {
     "plb_launch_colsum": (i32, [vp, i32, sz, i32, i32, vp, i32, i32, vp, i32, vp]),
     "plb_launch_copy_cols": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "plb_launch_pooler": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    "plb_attn_plan": (i32, [i32, i32, i32, i32, vp]),   # (PlbAttnPlan*: csrc/attn_plan.h)
+    "plb_attn_args_check": (i32, [P(PlbAttn), i32]),
     "plb_launch_attn_fwd": (i32, [P(PlbAttn), vp]),
     "plb_launch_attn_bwd": (i32, [P(PlbAttn), vp]),
     "plb_launch_attn_bwd_fused": (i32, [P(PlbAttn), vp]),
@@ -464,6 +466,23 @@ def gemm_tn_plan(Mtot, Ncols, N, K, operands=0):
     buf = C.create_string_buffer(struct.calcsize("8iqd"))
     lib().plb_gemm_tn_plan(Mtot, Ncols, N, K, operands, buf)
     return dict(zip(TN_PLAN_FIELDS, struct.unpack("8iqd", buf.raw)))
+
+
+ATTN_PLAN_FIELDS = ("rc", "grid", "block", "km", "bwd_form", "bwd_one_samples", "bwd_one_grid", "colpart_rows", "colpart_sample_rows",
+                    "unwritten_rows", "cls_fwd", "cls_bwd_dq", "cls_bwd_dkv", "cls_bwd_one", "stat_floats", "fwd_flops", "fwd_bytes",
+                    "bwd_flops", "bwd_bytes")
+ATTN_PLAN_FORMAT = "14iq4d"
+ATTN_PACKED, ATTN_KEYMASK, ATTN_COMPACT, ATTN_OUT_ROWS, ATTN_OUT_IMAGE = 1, 2, 4, 8, 16   # csrc/attn_plan.h: PlbAttnFlags
+
+
+def attn_plan(B, S, NH, flags=0):
+    """The launch plan of the attention kernels as a dict of csrc/attn_plan.h's PlbAttnPlan (fourteen ints, an int64, four
+    doubles): grid, kernel variant, the form of the backward under the policy in force (0 two kernels, 1 the single kernel, 2
+    hybrid: the first bwd_one_samples samples to the single kernel), partial rows, statistics floats and profiler credit."""
+    import struct
+    buf = C.create_string_buffer(struct.calcsize(ATTN_PLAN_FORMAT))
+    lib().plb_attn_plan(B, S, NH, flags, buf)
+    return dict(zip(ATTN_PLAN_FIELDS, struct.unpack(ATTN_PLAN_FORMAT, buf.raw)))
 
 
 def profile_enable(on):

@@ -8,11 +8,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libplbert_hip.so")
-SOURCES = ["gemm_nt_plan.cpp", "gemm_tn_plan.cpp", "gemm.hip", "gemm_big.hip", "gemm_tn.hip", "gemm_fp8.hip", "gemm_fp8_ln.hip", "gemm_tn_fp8.hip", "gemm_ln.hip", "attn.hip", "attn_bwd_fused.hip", "mask.hip",
+SOURCES = ["gemm_nt_plan.cpp", "gemm_tn_plan.cpp", "attn_plan.cpp", "gemm.hip", "gemm_big.hip", "gemm_tn.hip", "gemm_fp8.hip", "gemm_fp8_ln.hip", "gemm_tn_fp8.hip", "gemm_ln.hip", "attn.hip", "attn_bwd_fused.hip", "mask.hip",
            "embed.hip", "embed_inputs.hip", "layernorm.hip", "reduce.hip", "loss_rows.hip", "pooler_bwd.hip", "eval_rows.hip", "token_topk.hip", "layer_outputs.hip", "key_mask.hip", "optim.hip", "lamb.hip", "operand_images.hip",
            "engine.cpp", "engine_prof.cpp", "engine_comm.cpp", "engine_fp8.cpp", "engine_layers.cpp", "engine_calls.cpp", "engine_eval.cpp", "engine_optim.cpp"]
 # what a rebuild depends on beside the sources: the headers and the linker version script
-HEADERS = ["exports.map", "common.h", "plbert_kernels.h", "gemm_nt_plan.h", "gemm_tn_plan.h", "prof_classes.h", "gemm_epilogue.h", "gemm_nt_pipeline.h", "gemm_tn_pipeline.h", "attn_common.h", "attn_kernels.h", "row_common.h", "engine_internal.h", os.path.join("..", "..", "include", "plbert.h")]
+HEADERS = ["exports.map", "common.h", "plbert_kernels.h", "gemm_nt_plan.h", "gemm_tn_plan.h", "attn_plan.h", "prof_classes.h", "gemm_epilogue.h", "gemm_nt_pipeline.h", "gemm_tn_pipeline.h", "attn_common.h", "attn_kernels.h", "row_common.h", "engine_internal.h", os.path.join("..", "..", "include", "plbert.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # Per-source flags. attn_bwd_fused.hip is a one-wave-per-SIMD kernel with the whole 512-entry register file: by default
 # hipcc then selects the AGPR form for EVERY MFMA, so the S / dP tiles that the softmax arithmetic consumes land in

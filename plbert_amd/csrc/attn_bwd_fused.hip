@@ -21,10 +21,11 @@
 // dK^T) arrive by LDS-DMA a block ahead; delta = rowsum(dO∘O) and LSE of the next block are formed from plain loads
 // meanwhile. LDS: K image 64 KiB + 2 x 32 KiB exchange + 2 x 8 KiB staging + statistics = 144.5 KiB.
 #include "attn_common.h"
+#include "row_common.h"
 
 namespace {
 
-constexpr int FB_KIMG = 0;                  // [512 keys][128 B], 32-B quarter q of a row stored at q ^ kt(key)
+constexpr int FB_KIMG = 0;                 // [512 keys][128 B], 32-B quarter q of a row stored at q ^ kt(key)
 constexpr int FB_EXCH = 65536;              // 2 x [512 keys][64 B], 8-B unit u (4 queries) of a row stored at u ^ ((key>>1)&7)
 constexpr int FB_STG = FB_EXCH + 65536;     // 2 stages x (Q | dO), each [32 q][128 B] dual-use image
 constexpr int FB_STAT = FB_STG + 16384;     // 2 stages x (lse[32] | delta[32]) fp32
@@ -498,20 +499,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused_kernel(PlbAttn p) {
 
 // S <= 512: the single-kernel form. p->delta is not written (the kernel keeps delta in LDS).
 extern "C" int plb_launch_attn_bwd_fused(const PlbAttn* p, hipStream_t stream) {
-  if (p->H != p->NH * 64 || p->S < 1 || p->S > 512 || p->B < 1) return 1;
-  if (p->row_start && !p->lengths) return 1;
-  if (p->ldqkv % 8 || p->ldctx % 8 || p->lddctx % 8 || p->lddqkv % 8) return 1;
-  if ((!p->dqkv && !p->dqkv8) || (p->dqkv8 && (!p->dqkv_scale || p->lddqkv8 % 8))) return 1;
-  dim3 grid(p->NH * p->B), block(256);
-  const double unit = (double)p->B * p->NH * (double)p->S * p->S * 64.0;
-  const double io = 2.0 * p->B * p->S * (double)p->H;
-  // algorithmic work of the backward = 4 products (dP, dQ, dV, dK); the S recomputation is not credited
-  const int tok = plb_prof_begin(PLB_K_ATTN_BWD, stream, 8.0 * unit, 6.0 * io);
-  // (bf16 rows AND the image in one call — an fp8 call whose weight gradients read bf16 operands — would need 4 more
-  // registers than the file has: that combination takes the two-kernel form, plb_launch_attn_bwd)
-  if (p->dqkv && p->dqkv8) return 1;
+  if (plb_attn_args_check(p, PLB_ATTN_BWD_SINGLE)) return 1;
+  PlbAttnPlan pl;
+  plb_attn_plan(p->B, p->S, p->NH, plb_attn_flags(p), &pl);
+  const dim3 grid(p->NH * p->B), block(pl.block);   // (the whole call, whatever share of it the policy's form would give this kernel)
+  ProfScope ps(pl.cls_bwd_one, stream, pl.bwd_flops, pl.bwd_bytes);
   if (!p->dqkv8) hipLaunchKernelGGL(attn_bwd_fused_kernel<0>, grid, block, 0, stream, *p);
   else hipLaunchKernelGGL(attn_bwd_fused_kernel<1>, grid, block, 0, stream, *p);
-  plb_prof_end(tok, stream);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return LAUNCH_OK();
 }

@@ -178,6 +178,34 @@ DEVI void store_transposed(const f32x16& a0, const f32x16& a1, float mult, bf16_
   }
 }
 
+// -------------------------------------------------------------------------------------- work item
+// What a workgroup of the 128-row kernels (forward, dQ, dK/dV; the probabilities of layer_outputs.hip) works on, from its
+// block id. 1-D grid, XCD-aware: the 128-row tiles of one (batch, head) read the same K / V (the dK/dV kernel: the same Q /
+// dO), so they get consecutive logical ids = the same XCD's L2 (block id % 8 labels the XCD; placement affects speed only).
+// ATTN_TILE_OF_BLOCK defines QT (128-row tiles of a sample), bx (this workgroup's tile), bh, hd and b. ATTN_WORK_ITEM, for a
+// kernel that takes the descriptor p_, adds S, H, len (the sample's length, clamped to [1, S]), ROW0 (the name the kernel
+// gives the first of this wave's 32 rows in the sample; needs `wave`) and tok0 (the sample's first row: row_start[b] with
+// token-packed rows, PlbAttn.row_start, else b * S). (The order of the statements is the kernels' of old: hipcc's
+// instruction order follows it.)
+#define ATTN_TILE_OF_BLOCK(S_, NH_)                                                                       \
+  const int QT = ((S_) + 127) >> 7;                                                                       \
+  const int logical = xcd_remap(blockIdx.x, gridDim.x);                                                   \
+  const int bx = logical % QT, bh = logical / QT;                                                         \
+  const int hd = bh % (NH_), b = bh / (NH_)
+#define ATTN_WORK_ITEM(p_, ROW0)                                                                          \
+  ATTN_TILE_OF_BLOCK((p_).S, (p_).NH);                                                                    \
+  const int S = (p_).S, H = (p_).H;                                                                       \
+  int len = (p_).lengths ? (p_).lengths[b] : S;                                                           \
+  len = len < 1 ? 1 : (len > S ? S : len);                                                                \
+  const int ROW0 = bx * 128 + wave * 32;                                                                  \
+  const size_t tok0 = (p_).row_start ? (size_t)(p_).row_start[b] : (size_t)b * S
+// Compact-query mode (PlbAttn.qoff): sample b's queries are rows [qlo, qlo + Sq) of p.q, outputs go by compact row;
+// without it the queries are the sample's S rows.
+#define ATTN_QUERY_WINDOW(p_, S_)                                                                         \
+  const bool cq = (p_).qoff != nullptr;                                                                   \
+  const int qlo = cq ? (p_).qoff[b] : 0;                                                                  \
+  const int Sq = cq ? (p_).qoff[b + 1] - qlo : (S_)
+
 // ---------------------------------------------------------------------------------------- staging
 // K / V (forward, dQ) and Q / dO (dK,dV) tiles reach LDS by LDS-DMA straight from global memory (global_load_lds, 1 KiB
 // per wave instruction): no staging registers, no ds_write, no per-tile address arithmetic. An image's swizzle is applied

@@ -25,25 +25,12 @@ __global__ __launch_bounds__(256, ATTN_KM ? 4 : FWD_WAVES) void ATTN_KERNEL(attn
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   DBG_EARLY_EXIT(p);
-  // 1-D grid, XCD-aware: the q-tiles of one (batch, head) read the same K/V, so they get consecutive
-  // logical ids = the same XCD's L2 (block id % 8 labels the XCD; placement affects speed only)
-  const int QT = (p.S + 127) >> 7;
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
-  const int bx = logical % QT, bh = logical / QT;
-  const int hd = bh % p.NH, b = bh / p.NH;
-  const int S = p.S, H = p.H;
-  int len = p.lengths ? p.lengths[b] : S;
-  len = len < 1 ? 1 : (len > S ? S : len);
-  const int q0 = bx * 128 + wave * 32;
-  const size_t tok0 = p.row_start ? (size_t)p.row_start[b] : (size_t)b * S;   // (token-packed rows: PlbAttn.row_start)
+  ATTN_WORK_ITEM(p, q0);
   const bf16_t* kbase = p.qkv + H + hd * 64;
   const bf16_t* vbase = p.qkv + 2 * H + hd * 64;
   const int ld = p.ldqkv;
   const int lq = lane & 31, h = lane >> 5;
-  // compact-query mode (PlbAttn.qoff): this sample's queries are rows [qlo, qlo + Sq) of p.q; outputs by compact row
-  const bool cq = p.qoff != nullptr;
-  const int qlo = cq ? p.qoff[b] : 0;
-  const int Sq = cq ? p.qoff[b + 1] - qlo : S;
+  ATTN_QUERY_WINDOW(p, S);
   if (bx * 128 >= Sq || (p.row_start && bx * 128 >= len)) return;   // (wave-uniform, before any barrier: a q tile without a query)
   const size_t qrow0 = cq ? (size_t)qlo : tok0;   // first query row of the sample in q / ctx
   const int ldq = cq ? p.ldq : ld;
@@ -199,25 +186,12 @@ __global__ __launch_bounds__(256, 3) void ATTN_KERNEL(attn_bwd_dq)(PlbAttn p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   DBG_EARLY_EXIT(p);
-  // 1-D grid, XCD-aware: the q-tiles of one (batch, head) read the same K/V, so they get consecutive
-  // logical ids = the same XCD's L2 (block id % 8 labels the XCD; placement affects speed only)
-  const int QT = (p.S + 127) >> 7;
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
-  const int bx = logical % QT, bh = logical / QT;
-  const int hd = bh % p.NH, b = bh / p.NH;
-  const int S = p.S, H = p.H;
-  int len = p.lengths ? p.lengths[b] : S;
-  len = len < 1 ? 1 : (len > S ? S : len);
-  const int q0 = bx * 128 + wave * 32;
-  const size_t tok0 = p.row_start ? (size_t)p.row_start[b] : (size_t)b * S;   // (token-packed rows: PlbAttn.row_start)
+  ATTN_WORK_ITEM(p, q0);
   const bf16_t* kbase = p.qkv + H + hd * 64;
   const bf16_t* vbase = p.qkv + 2 * H + hd * 64;
   const int ld = p.ldqkv;
   const int lq = lane & 31, h = lane >> 5;
-  // compact-query mode (PlbAttn.qoff): see the forward
-  const bool cq = p.qoff != nullptr;
-  const int qlo = cq ? p.qoff[b] : 0;
-  const int Sq = cq ? p.qoff[b + 1] - qlo : S;
+  ATTN_QUERY_WINDOW(p, S);
   if (bx * 128 >= Sq || (p.row_start && bx * 128 >= len)) {   // a q tile without a query (compact mode, packed rows): its bias-gradient partial rows are zeros
     if (p.colpart && !p.colpart_accumulate) p.colpart[((size_t)(b * QT + bx) * 4 + wave) * (3 * H) + hd * 64 + lane] = 0.f;
     return;
@@ -377,15 +351,7 @@ __global__ __launch_bounds__(256, 2) void ATTN_KERNEL(attn_bwd_dkv)(PlbAttn p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   DBG_EARLY_EXIT(p);
-  const int QT = (p.S + 127) >> 7;  // key tiles of one (batch, head) share Q / dO: same XCD
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
-  const int bx = logical % QT, bh = logical / QT;
-  const int hd = bh % p.NH, b = bh / p.NH;
-  const int S = p.S, H = p.H;
-  int len = p.lengths ? p.lengths[b] : S;
-  len = len < 1 ? 1 : (len > S ? S : len);
-  const int key0 = bx * 128 + wave * 32;
-  const size_t tok0 = p.row_start ? (size_t)p.row_start[b] : (size_t)b * S;   // (token-packed rows: PlbAttn.row_start)
+  ATTN_WORK_ITEM(p, key0);   // (bx: the key tile)
   const int ld = p.ldqkv, ldo = p.lddctx;
   const int lk = lane & 31, h = lane >> 5;
   const int mykey = key0 + lk;
@@ -418,9 +384,7 @@ __global__ __launch_bounds__(256, 2) void ATTN_KERNEL(attn_bwd_dkv)(PlbAttn p) {
   const float sl2 = p.scale * LOG2E;
 
   // compact-query mode (PlbAttn.qoff): the queries are rows [qlo, qlo + qrows) of p.q / dctx, statistics [NH][Nq]
-  const bool cq = p.qoff != nullptr;
-  const int qlo = cq ? p.qoff[b] : 0;
-  const int Sq = cq ? p.qoff[b + 1] - qlo : S;    // query rows that exist (clamp bound of the staging)
+  ATTN_QUERY_WINDOW(p, S);                        // Sq: query rows that exist (clamp bound of the staging)
   const int qlen = cq ? Sq : len;                 // query rows that count
   const int ldq = cq ? p.ldq : ld;
   // queries past the length carry exactly zero dO in this model (no loss there), so tiles stop at len

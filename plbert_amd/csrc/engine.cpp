@@ -189,7 +189,7 @@ extern "C" int plb_create(const PlbConfig* cfg, PlbEngine** out) {
     e->o_dxe = cv.take(Tp * E * 4);
     e->ducol_rows = (int)(2 * Tp / 128);   // (2 per row tile of the narrowest pipeline tile, 128 rows)
     e->o_ducol = cv.take(L * e->ducol_rows * I * 4);  // column-sum partials of dU from the GEMM epilogue
-    e->qkvcol_rows = c.max_batch * ((c.max_seq + 127) / 128) * 4;
+    e->qkvcol_rows = qkvcol_rows(e, c.max_batch, c.max_seq);
     // ... of dQKV from the attention-backward stores, one set per application: the kernels only STORE their partial rows
     // (summing over the applications in place made every wave end on a global read-modify-write: +0.19 ms per step)
     e->o_qkvcol = cv.take((int64_t)L * e->qkvcol_rows * 3 * H * 4);

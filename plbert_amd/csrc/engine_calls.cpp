@@ -361,7 +361,7 @@ static int backward_tail_streams(PlbEngine* e, const Call& c, bf16_t* dy, int du
   const int64_t Mtot_c = e->pruned_rows ? (int64_t)(L - 1) * Tp + e->pruned_rows : Mtot;
   // the stacks the layer loop wrote: application 0's slots, L blocks of partial rows behind them
   const Slots st = slots(e, Tp, B, S, 0, true, e->part_rows_used, du_rows);
-  const int64_t qkvcol_all = (int64_t)L * qkvcol_rows(B, S);
+  const int64_t qkvcol_all = (int64_t)L * qkvcol_rows(e, B, S);
   // side stream -------------------------------------------------------------------------------------------------------
   // (HB_R / HB_W: the happens-before audit's view of each launch — what it reads that another stream wrote, what it
   // writes that another stream reads. The stash operands of the GEMMs are only ever written in the layer loop, which the

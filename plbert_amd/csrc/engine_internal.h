@@ -84,7 +84,7 @@ struct PlbEngine {
   int64_t NMcap;  // padded masked-row capacity
   int NTp = 0;    // token (grapheme) head: NT padded to 256 columns (NT > 0 only)
   bool infer = false;           // inference-only workspace: one layer of activations, no gradient stash
-  int qkvcol_rows = 0;  // partial rows per layer of the Q/K/V bias gradient: max_batch * ceil(max_seq / 128) * 4
+  int qkvcol_rows = 0;  // partial rows per layer of the Q/K/V bias gradient: the attention plan's at (max_batch, max_seq)
   int64_t slab2_floats;
   int64_t slab_floats;
   int64_t ws_bytes;
@@ -351,7 +351,7 @@ bool tn8_ok(const PlbEngine* e, int64_t Mtot);
 PlbGemmNT nt_desc(const bf16_t* A, const bf16_t* B, int64_t M, int N, int K);
 // the plan (gemm_nt_plan.h) of a packed [M, N] x K launch: what the launcher of that form and operand kind will do
 PlbGemmNTPlan nt_plan(int64_t M, int N, int K, int form, int operands = PLB_NT_BF16, int opts = 0);
-int qkvcol_rows(int B, int S);
+int qkvcol_rows(const PlbEngine* e, int B, int S);   // the attention plan's colpart_rows at the call's shape
 Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int prows = 0, int du_rows = 0);
 bool prune_enabled();
 int run_encoder(PlbEngine* e, const Call& c, bool stash, bf16_t** xout, const Prune* pr);

@@ -48,8 +48,30 @@ static void f8_out(PlbGemmNT* g, uint8_t* img, int ld, const F8Site& q, int bf8)
   g->C8 = img; g->ldc8 = ld; g->q_scale = q.scale; g->q_amax = q.amax; g->c8_bf8 = bf8;
 }
 
+// The attention launches of one application of call c on slots sl: the fields forward, backward and the probabilities
+// share; the callers add their outputs (and the context buffer of a pruned last application)
+static PlbAttn attn_desc(const PlbEngine* e, const Call& c, const Slots& sl) {
+  PlbAttn at;
+  memset(&at, 0, sizeof(at));
+  at.qkv = sl.qkv; at.ldqkv = 3 * e->H; at.lengths = c.lengths; at.B = c.B; at.S = c.S; at.NH = e->NH; at.H = e->H;
+  at.scale = 0.125f;
+  at.row_start = c.rw.row_start;
+  at.key_words = c.rw.key_words; at.ldkw = c.rw.ldkw;
+  at.ctx = sl.ctx; at.ldctx = e->H; at.lse = sl.lse;
+  return at;
+}
+// what the attention launchers will do with a descriptor (attn_plan.h), asked like nt_plan
+static PlbAttnPlan attn_plan(const PlbAttn& at) {
+  PlbAttnPlan pl;
+  plb_attn_plan(at.B, at.S, at.NH, plb_attn_flags(&at), &pl);
+  return pl;
+}
 // partial rows per application of the Q/K/V bias gradient that the attention backward stores in a call of B x S
-int qkvcol_rows(int B, int S) { return B * ((S + 127) / 128) * 4; }
+int qkvcol_rows(const PlbEngine* e, int B, int S) {
+  PlbAttnPlan pl;
+  plb_attn_plan(B, S, e->NH, 0, &pl);
+  return pl.colpart_rows;
+}
 Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int prows, int du_rows) {
   const int64_t H = e->H, I = e->I, sl = stash ? l : 0;
   auto bf = [&](int64_t off, int64_t width) { return e->at<bf16_t>(off) + sl * Tp * width; };
@@ -62,14 +84,16 @@ Slots slots(const PlbEngine* e, int64_t Tp, int B, int S, int l, bool stash, int
   v.qkv = bf(e->o_qkv, 3 * H); v.ctx = bf(e->o_ctx, H); v.pre1 = bf(e->o_pre1, H); v.a = bf(e->o_a, H);
   v.u = bf(e->o_u, I); v.g = bf(e->o_g, I); v.pre2 = bf(e->o_pre2, H);
   v.mean1 = f32(e->o_mean1, Tp); v.rstd1 = f32(e->o_rstd1, Tp); v.mean2 = f32(e->o_mean2, Tp); v.rstd2 = f32(e->o_rstd2, Tp);
-  v.lse = f32(e->o_lse, (int64_t)B * e->NH * S);
+  PlbAttnPlan ap;   // the per-application strides of the attention statistics and of the Q/K/V bias partial rows
+  plb_attn_plan(B, S, e->NH, 0, &ap);
+  v.lse = f32(e->o_lse, ap.stat_floats);
   v.x8 = u8(e->o_x8, H); v.c8 = u8(e->o_c8, H); v.a8 = u8(e->o_a8, H); v.g8 = u8(e->o_g8, I);
   v.x8n = e->at<uint8_t>(e->o_x8) + (stash ? l + 1 : 0) * Tp * H;   // (one slot: consumed before it is rewritten)
   if (stash) {
     v.dqkv = bf(e->o_dqkv, 3 * H); v.dpre1 = bf(e->o_dpre1, H); v.du = bf(e->o_du, I); v.dpre2 = bf(e->o_dpre2, H);
     v.dp8 = u8(e->o_dp8, H); v.du8 = u8(e->o_du8, I); v.dp18 = u8(e->o_dp18, H); v.dq8 = u8(e->o_dq8, 3 * H);
     v.part1 = f32(e->o_part1, (int64_t)prows * 3 * H); v.part2 = f32(e->o_part2, (int64_t)prows * 3 * H);
-    v.qkvcol = f32(e->o_qkvcol, (int64_t)qkvcol_rows(B, S) * 3 * H); v.ducol = f32(e->o_ducol, (int64_t)du_rows * I);
+    v.qkvcol = f32(e->o_qkvcol, (int64_t)ap.colpart_rows * 3 * H); v.ducol = f32(e->o_ducol, (int64_t)du_rows * I);
   }
   return v;
 }
@@ -319,30 +343,26 @@ int run_encoder(PlbEngine* e, const Call& c, bool stash, bf16_t** xout, const Pr
     g.bias = e->par(PLB_Q_B); g.C = sl.qkv; g.ldc = 3 * H;
     const F8Op oq = f8_op(sl.x8, sX, F8Weight(e, F8W_QKV), 0);
     TRY(gemm_nt_any(&g, PLB_NT_PLAIN, f8 ? &oq : nullptr, s));
-    PlbAttn at;
-    memset(&at, 0, sizeof(at));
-    at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = c.lengths; at.B = B; at.S = S; at.NH = e->NH; at.H = H;
-    at.row_start = rw.row_start;
-    at.key_words = rw.key_words; at.ldkw = rw.ldkw;
+    PlbAttn at = attn_desc(e, c, sl);
     // pruned last application: the attention output of ALL rows goes to a buffer of its own (training: a backward temporary
     // that the attention backward of this application reads again — its slot holds the compact rows), then only the masked
     // rows continue
     const bool pruned_layer = pr != nullptr && l == L - 1;
     bf16_t* const ctx_att = (pruned_layer && stash) ? e->at<bf16_t>(e->o_dy1) : sl.ctx;
-    at.scale = 0.125f; at.ctx = ctx_att; at.ldctx = H; at.lse = sl.lse;
+    at.ctx = ctx_att;
     // (pruned: nobody reads the context's image of all rows — the compact rows' image is made with the others, below)
     if (f8 && !pruned_layer) { at.ctx8 = sl.c8; at.ldctx8 = H; at.ctx_scale = sC.scale; at.ctx_amax = sC.amax; }
-    // packed fp8-mode call, S no multiple of 128: the slot of a full-length sample runs past position S, rows no attention
-    // workgroup stores. The calibration maxima and the images are taken over every row of the slots: zeros there, not what
-    // an earlier call left (bf16 calls leave them alone: finite is enough there)
-    if (rw.row_start && e->fp8_on && S % 128) {
+    // packed fp8-mode call with rows of a slot that no attention workgroup stores (the plan's unwritten_rows). The
+    // calibration maxima and the images are taken over every row of the slots: zeros there, not what an earlier call left
+    // (bf16 calls leave them alone: finite is enough there)
+    if (e->fp8_on && attn_plan(at).unwritten_rows) {
       HIPTRY(hipMemsetAsync(ctx_att, 0, (size_t)T * H * 2, s));
       if (at.ctx8) HIPTRY(hipMemsetAsync(sl.c8, 0, (size_t)T * H, s));
     }
     TRY(plb_launch_attn_fwd(&at, s));
     if (float* const probs = (c.taps && c.taps->attentions) ? c.taps->attentions[l] : nullptr)
-      TRY(plb_launch_attn_probs_masked(sl.qkv, 3 * H, sl.lse, c.lengths, rw.row_start, rw.key_words, rw.ldkw, B, S, e->NH, at.scale,
-                                       probs, s));
+      TRY(plb_launch_attn_probs_masked(at.qkv, at.ldqkv, at.lse, at.lengths, at.row_start, at.key_words, at.ldkw, at.B, at.S, at.NH,
+                                       at.scale, probs, s));
     // packed: the tail behind the last slot (up to 1,023 rows) is written by no attention workgroup, and what sits there
     // goes through dense / LayerNorm / FFN into the stash the weight-gradient GEMMs read: zeros, not whatever was there
     if (rw.row_start && Tp > T) {
@@ -526,24 +546,21 @@ static int attention_bwd_dx(PlbEngine* e, const Bwd& c, int l, const Slots& sl, 
     res = res_in;
   }
   const F8Site sDQ(e, F8_DQ, l);
-  PlbAttn at;
-  memset(&at, 0, sizeof(at));
-  at.qkv = sl.qkv; at.ldqkv = 3 * H; at.lengths = call.lengths; at.B = call.B; at.S = call.S; at.NH = e->NH; at.H = H; at.scale = 0.125f;
-  at.row_start = rw.row_start;
-  at.key_words = rw.key_words; at.ldkw = rw.ldkw;
-  at.ctx = ctx; at.ldctx = H; at.lse = sl.lse;
+  PlbAttn at = attn_desc(e, call, sl);
+  at.ctx = ctx;
   at.dctx = e->at<bf16_t>(e->o_dctx); at.lddctx = H; at.delta = e->at<float>(e->o_delta); at.dqkv = sl.dqkv; at.lddqkv = 3 * H;
   at.colpart = sl.qkvcol; at.colpart_accumulate = 0;
   if (c.f8) {   // dQKV leaves as its e5m2 image (alone, once the weight gradient reads images too)
     at.dqkv8 = sl.dq8; at.lddqkv8 = 3 * H; at.dqkv_scale = sDQ.scale; at.dqkv_amax = sDQ.amax;
     if (e->tn8_call) at.dqkv = nullptr;
   }
-  // packed, S no multiple of 128: the backward kernels store no row of a sample at or past position S, and the slot of a
-  // full-length sample runs on to the next multiple of 128 — rows no launch of this call writes, which the weight-gradient
-  // GEMMs read: zeros (their true value: no token sits there), not what an earlier call left
-  if (rw.row_start && call.S % 128 && at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv, 0, (size_t)T * 3 * H * 2, s));
-  // (their e5m2 image likewise: a stale byte there can be a NaN encoding, and 0 x NaN in the stacked weight-gradient GEMM is NaN)
-  if (rw.row_start && call.S % 128 && at.dqkv8) HIPTRY(hipMemsetAsync(sl.dq8, 0, (size_t)T * 3 * H, s));
+  // rows of a packed slot that no launch of this call writes (the plan's unwritten_rows) and the weight-gradient GEMMs
+  // read: zeros (their true value: no token sits there), not what an earlier call left — and their e5m2 image likewise: a
+  // stale byte there can be a NaN encoding, and 0 x NaN in the stacked weight-gradient GEMM is NaN
+  if (attn_plan(at).unwritten_rows) {
+    if (at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv, 0, (size_t)T * 3 * H * 2, s));
+    if (at.dqkv8) HIPTRY(hipMemsetAsync(sl.dq8, 0, (size_t)T * 3 * H, s));
+  }
   TRY(plb_launch_attn_bwd(&at, s));
   if (Tp > T) {
     if (at.dqkv) HIPTRY(hipMemsetAsync(sl.dqkv + (int64_t)T * 3 * H, 0, (size_t)(Tp - T) * 3 * H * 2, s));
@@ -584,9 +601,10 @@ int encoder_bwd(PlbEngine* e, const Call& call, const Prune* pr, bf16_t** dy, in
   // from the head — then uses as many blocks), else the LayerNorm kernel's block count.
   c.fuse_b = ln_fusable(e, Tp, 2, c.f8);
   c.prows = c.fuse_b ? nt_plan(Tp, e->H, e->H, PLB_NT_LNBWD, ops).colpart_rows : e->ln_blocks;
-  if (c.du_rows > e->ducol_rows || c.prows > e->part_rows)
-    return fail("encoder_bwd: the plans write %d ffn.bias and %d LayerNorm partial rows per application, %d and %d are reserved",
-                c.du_rows, c.prows, e->ducol_rows, e->part_rows);
+  const int qkv_rows = qkvcol_rows(e, call.B, call.S);
+  if (c.du_rows > e->ducol_rows || c.prows > e->part_rows || qkv_rows > e->qkvcol_rows)
+    return fail("encoder_bwd: the plans write %d ffn.bias, %d LayerNorm and %d Q/K/V bias partial rows per application, %d, %d and %d are reserved",
+                c.du_rows, c.prows, qkv_rows, e->ducol_rows, e->part_rows, e->qkvcol_rows);
   e->part_rows_used = c.prows;
   bf16_t* dx = e->at<bf16_t>(e->o_dy1);
   for (int l = L - 1; l >= 0; --l) {

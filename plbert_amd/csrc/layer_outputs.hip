@@ -51,11 +51,8 @@ DEVI void attn_probs_body(const bf16_t* qkv, int ld, const float* lse, const int
   __shared__ __attribute__((aligned(16))) float spatch[4][32 * PPS];  // per-wave transpose patches, 34 KiB
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // 1-D grid, XCD-aware as the forward: the q-tiles of one (batch, head) read the same K
-  const int QT = (S + 127) >> 7;
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
-  const int bx = logical % QT, bh = logical / QT;
-  const int hd = bh % NH, b = bh / NH, H = NH * 64;
+  ATTN_TILE_OF_BLOCK(S, NH);   // (1-D grid, XCD-aware as the forward: the q-tiles of one (batch, head) read the same K)
+  const int H = NH * 64;
   const int len = clamp_len(lengths ? lengths[b] : S, S);
   const int q0 = bx * 128 + wave * 32;
   const int lq = lane & 31, h = lane >> 5;
@@ -183,30 +180,25 @@ extern "C" int plb_launch_attn_probs(const bf16_t* qkv, int ldqkv, const float* 
 extern "C" int plb_launch_attn_probs_masked(const bf16_t* qkv, int ldqkv, const float* lse, const int32_t* lengths,
                                             const int32_t* row_start, const uint32_t* key_words, int ldkw, int B, int S, int NH,
                                             float scale, float* out, hipStream_t stream) {
-  if (!qkv || !lse || !out || B < 1 || S < 1 || NH < 1) return 1;
-  if (key_words && (S > 2048 || ldkw < 2 * ((S + 63) / 64))) return 1;
-  if (ldqkv < 3 * NH * 64 || ldqkv % 8 || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 3)) return 1;
-  if (row_start && !lengths) return 1;   // token-packed rows are defined by the lengths
-  if ((int64_t)S * ldqkv * 2 >= ((int64_t)1 << 32)) return 1;   // (the staging's 32-bit byte offsets count from the sample's first row)
-  const int64_t grid = (int64_t)((S + 127) / 128) * NH * B;
-  if (grid >= ((int64_t)1 << 31)) return 1;
+  // the shape part of the attention launchers' check, on the descriptor these arguments would make
+  PlbAttn a = {};
+  a.qkv = qkv; a.ldqkv = ldqkv; a.lse = const_cast<float*>(lse); a.lengths = lengths; a.row_start = row_start;
+  a.key_words = key_words; a.ldkw = ldkw; a.B = B; a.S = S; a.NH = NH; a.H = (int)((int64_t)NH * 64);
+  if (plb_attn_args_check(&a, PLB_ATTN_PROBS)) return 1;
+  if (!out || ldqkv < (int64_t)3 * NH * 64 || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 3)) return 1;
+  PlbAttnPlan pl;
+  plb_attn_plan(B, S, NH, plb_attn_flags(&a), &pl);
+  const dim3 grid(pl.grid), block(pl.block);
   const double elems = (double)B * NH * (double)S * S;
   ProfScope ps(PLB_K_ROWS, stream, 2.0 * elems * 64.0, 4.0 * elems);
-  if (key_words) {
-    if (S % 4 == 0 && !((uintptr_t)out & 15))
-      hipLaunchKernelGGL(attn_probs_km_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, qkv, ldqkv, lse, lengths, row_start,
-                         S, NH, scale, out, key_words, ldkw);
-    else
-      hipLaunchKernelGGL(attn_probs_km_kernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, qkv, ldqkv, lse, lengths, row_start,
-                         S, NH, scale, out, key_words, ldkw);
-    return LAUNCH_OK();
+  const bool vec = S % 4 == 0 && !((uintptr_t)out & 15);
+  if (pl.km) {
+    if (vec) hipLaunchKernelGGL(attn_probs_km_kernel<true>, grid, block, 0, stream, qkv, ldqkv, lse, lengths, row_start, S, NH, scale, out, key_words, ldkw);
+    else hipLaunchKernelGGL(attn_probs_km_kernel<false>, grid, block, 0, stream, qkv, ldqkv, lse, lengths, row_start, S, NH, scale, out, key_words, ldkw);
+  } else {
+    if (vec) hipLaunchKernelGGL(attn_probs_kernel<true>, grid, block, 0, stream, qkv, ldqkv, lse, lengths, row_start, S, NH, scale, out);
+    else hipLaunchKernelGGL(attn_probs_kernel<false>, grid, block, 0, stream, qkv, ldqkv, lse, lengths, row_start, S, NH, scale, out);
   }
-  if (S % 4 == 0 && !((uintptr_t)out & 15))
-    hipLaunchKernelGGL(attn_probs_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, qkv, ldqkv, lse, lengths, row_start, S, NH,
-                       scale, out);
-  else
-    hipLaunchKernelGGL(attn_probs_kernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, qkv, ldqkv, lse, lengths, row_start, S,
-                       NH, scale, out);
   return LAUNCH_OK();
 }
 

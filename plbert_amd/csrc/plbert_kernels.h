@@ -7,6 +7,7 @@
 #include "../../include/plbert.h"   // PLB_NPARAM, PlbAdamWSegment (the segmented optimizer launches)
 #include "gemm_tn_plan.h"            // PlbGemmTNPlan: kernel, row splits and slab need of a token-major weight-gradient GEMM
 #include "gemm_nt_plan.h"            // PlbGemmNTPlan and the form / operand / option names of the NT GEMM launchers (+ prof_classes.h)
+#include "attn_plan.h"               // PlbAttnPlan: grid, kernel variant, backward form and partial rows of the attention launches
 
 typedef uint16_t bf16_t;
 
@@ -266,12 +267,29 @@ typedef struct {
   // softmax of the sample's queries; bits at or past lengths[b] are clear. A masked key below the length (a hole) stays a
   // query like any other: it has a context row, a statistic and a dQ row; its dK / dV rows are exact zeros. NULL selects
   // the kernels without the mask; a row of all-ones bits below the length gives their results bit for bit. S <= 2048; not
-  // with compact queries; the backward runs in the two-kernel form whatever plb_set_attn_bwd_fused says.
+  // with compact queries; the form of the backward: attn_plan.h.
   const uint32_t* key_words; int ldkw;
 } PlbAttn;
+// the modes of a descriptor as the plan's flags (attn_plan.h: PlbAttnFlags)
+static inline int plb_attn_flags(const PlbAttn* p) {
+  return (p->row_start ? PLB_ATTN_PACKED : 0) | (p->key_words ? PLB_ATTN_KEYMASK : 0) | (p->qoff ? PLB_ATTN_COMPACT : 0) |
+         (p->dqkv ? PLB_ATTN_OUT_ROWS : 0) | (p->dqkv8 ? PLB_ATTN_OUT_IMAGE : 0);
+}
+// ---- attention launchers. Each is: plan (attn_plan.h: grid, kernel variant, form of the backward, profiler credit) -> one
+// argument check -> profiler scope -> launch. Return codes: 0 launched, 1 refused (no profiler scope is open behind a
+// refusal), 2 the launch failed. The plan itself, for tests, tools and the engine; declared in attn_plan.h:
+int plb_attn_plan(int B, int S, int NH, int flags, PlbAttnPlan* plan);
+// The one argument check of the four launchers: 0 when descriptor p can be launched in `direction`, else 1. Runs before any
+// HIP call. Every direction: the plan of (B, S, NH, the descriptor's modes) runs, H = NH * 64, qkv and lse are given,
+// ldqkv % 8 == 0, S * ldqkv * 2 < 2^32 (the staging's 32-bit byte offsets count from a sample's first row), packed rows
+// come with lengths, key-mask words with ldkw >= 2 * ceil(S / 64). Forward and backward: ctx and the row strides in use
+// (multiples of 8), an image with its scale, compact queries with q (and a backward with dq or dq8). Backward: dctx, and
+// dqkv or dqkv8. The single kernel: S <= 512, no key mask, no compact queries, not rows AND image.
+enum PlbAttnDirection { PLB_ATTN_FWD = 0, PLB_ATTN_BWD = 1, PLB_ATTN_BWD_SINGLE = 2, PLB_ATTN_PROBS = 3 };
+int plb_attn_args_check(const PlbAttn* p, int direction);
 int plb_launch_attn_fwd(const PlbAttn* p, hipStream_t stream);
-// Default: the two-kernel form, dq (+delta) then dk,dv. plb_set_attn_bwd_fused(1) / PLBERT_ATTN_BWD=fused: ONE kernel for
-// S <= 512 (attn_bwd_fused.hip: 5 products, dQ complete inside the workgroup; delta is not written)
+// The backward in the form the plan names for the call (attn_plan.h: PlbAttnBwdForm and the policy behind it);
+// plb_launch_attn_bwd_fused is the single kernel itself (S <= 512; delta is not written).
 int plb_launch_attn_bwd(const PlbAttn* p, hipStream_t stream);
 int plb_launch_attn_bwd_fused(const PlbAttn* p, hipStream_t stream);
 // Test hook of the gradient exchange (tests/test_gpu_comm_fake_rccl.py): the next loss call leaves out its index-th

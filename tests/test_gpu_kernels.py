@@ -244,7 +244,7 @@ def test_attention_race_screen(bwd_form):
 @pytest.mark.parametrize("B,NH,policy,nf", [(16, 16, -1, 16), (32, 12, -1, 0), (8, 12, -1, 0), (32, 12, 2, 21), (22, 12, 2, 21),
                                              (8, 12, 2, 0)])
 def test_attention_bwd_policy_and_hybrid_split(B, NH, policy, nf):
-    """The per-shape policy (attn.hip: plb_launch_attn_bwd); nf = samples the single-kernel form must take. Policy -1 (auto,
+    """The per-shape policy (attn_plan.cpp, run by plb_launch_attn_bwd); nf = samples the single-kernel form must take. Policy -1 (auto,
     the default): B x heads that fills the CUs in whole rounds takes it entirely (16 x 16 = 256 items = one round),
     everything else the two kernels. Policy 2 (auto + hybrid; measured slower at config A and off by default): a batch with
     at least one (nearly) full round of whole samples and a short remainder is SPLIT BY SAMPLE between the two forms (32 x
@@ -265,6 +265,13 @@ def test_attention_bwd_policy_and_hybrid_split(B, NH, policy, nf):
     qmask = (torch.arange(S, device=DEV)[None, :] < lengths[:, None]).reshape(B * S, 1)
     dctx = dctx * qmask.to(dctx.dtype)
     delta = torch.zeros((B, NH, S), dtype=torch.float32, device=DEV)
+    L.plb_set_attn_bwd_fused(policy)
+    try:   # the plan (csrc/attn_plan.h) says what the launcher is about to do: the literals above pin the policy itself
+        plan = _lib.attn_plan(B, S, NH, _lib.ATTN_OUT_ROWS)
+    finally:
+        L.plb_set_attn_bwd_fused(-1)
+    assert (plan["bwd_one_samples"], plan["bwd_one_grid"], plan["colpart_rows"]) == (nf, nf * NH, B * QT * 4)
+    assert plan["bwd_form"] == (0 if nf == 0 else 1 if nf == B else 2)
     outs = {}
     for form in (1, 0, policy):
         dqkv = torch.full((B * S, 3 * H), 7.0, dtype=torch.bfloat16, device=DEV)

@@ -20,8 +20,10 @@ def bench(L, B, S, NH, iters=30):
     ctx = torch.empty(T, H, dtype=torch.bfloat16, device=dev)
     dctx = torch.randn(T, H, device=dev).to(torch.bfloat16)
     dqkv = torch.empty(T, 3 * H, dtype=torch.bfloat16, device=dev)
-    lse = torch.empty(B * NH * S, device=dev)
-    delta = torch.empty(B * NH * S, device=dev)
+    plan = _lib.attn_plan(B, S, NH, _lib.ATTN_OUT_ROWS)   # csrc/attn_plan.h: buffer sizes and the form of the backward
+    assert plan["rc"] == 0, (B, S, NH)
+    lse = torch.empty(plan["stat_floats"], device=dev)
+    delta = torch.empty(plan["stat_floats"], device=dev)
     p = _lib.PlbAttn()
     p.qkv, p.ldqkv, p.lengths, p.B, p.S, p.NH, p.H, p.scale = qkv.data_ptr(), 3 * H, None, B, S, NH, H, 0.125
     p.ctx, p.ldctx, p.lse = ctx.data_ptr(), H, lse.data_ptr()
@@ -52,6 +54,7 @@ def bench(L, B, S, NH, iters=30):
     split = {names[i]: ms[i] / cnt[i] * 1e3 for i in range(n) if cnt[i]}
     out.append(split.get("attn_bwd_dq", 0.0))
     out.append(split.get("attn_bwd_dkv", 0.0) + split.get("attn_bwd", 0.0))   # single-kernel form: all under "attn_bwd"
+    out.append(("two kernels", "single kernel", f"hybrid ({plan['bwd_one_samples']} samples single kernel)")[plan["bwd_form"]])
     return out
 
 
@@ -71,15 +74,15 @@ def main():
     for rep in range(args.reps):
         for (B, S, NH) in [tuple(int(x) for x in sh.split("x")) for sh in args.shapes.split(",")]:
             for name, L in libs:
-                f, b, dq, dkv = bench(L, B, S, NH)
-                res.setdefault((name, B, S, NH), []).append((f, b, dq, dkv))
-    for (name, B, S, NH), v in res.items():
+                f, b, dq, dkv, form = bench(L, B, S, NH)   # (form: the main library's plan under the same policy)
+                res.setdefault((name, B, S, NH, form), []).append((f, b, dq, dkv))
+    for (name, B, S, NH, form), v in res.items():
         f = sorted(x[0] for x in v)[len(v) // 2]
         b = sorted(x[1] for x in v)[len(v) // 2]
         dq = sorted(x[2] for x in v)[len(v) // 2]
         dkv = sorted(x[3] for x in v)[len(v) // 2]
         unit = B * NH * S * S * 64.0
-        print(f"{name:14s} fwd {f:6.2f} us ({4*unit/f/1e6:5.0f} TF)  bwd {b:7.2f} us ({8*unit/b/1e6:5.0f} TF credited) = dq {dq:6.2f} + dkv {dkv:6.2f}", flush=True)
+        print(f"{name:14s} fwd {f:6.2f} us ({4*unit/f/1e6:5.0f} TF)  bwd {b:7.2f} us ({8*unit/b/1e6:5.0f} TF credited) = dq {dq:6.2f} + dkv {dkv:6.2f}  [{form}]", flush=True)
 
 
 if __name__ == "__main__":

@@ -19,8 +19,10 @@ qkv = torch.randn(T, 3 * H, device=dev).to(torch.bfloat16)
 ctx = torch.empty(T, H, dtype=torch.bfloat16, device=dev)
 dctx = torch.randn(T, H, device=dev).to(torch.bfloat16)
 dqkv = torch.empty(T, 3 * H, dtype=torch.bfloat16, device=dev)
-lse = torch.empty(B * NH * S, device=dev)
-delta = torch.zeros(max(B * NH * S, B * NH * 32), device=dev)
+plan = _lib.attn_plan(B, S, NH, _lib.ATTN_OUT_ROWS)   # csrc/attn_plan.h
+assert plan["rc"] == 0 and S <= 512, "the single kernel takes S <= 512"
+lse = torch.empty(plan["stat_floats"], device=dev)
+delta = torch.zeros(max(plan["stat_floats"], B * NH * 32), device=dev)   # (the stamps leave through delta: 32 floats per workgroup)
 p = _lib.PlbAttn()
 p.qkv, p.ldqkv, p.lengths, p.B, p.S, p.NH, p.H, p.scale = qkv.data_ptr(), 3 * H, None, B, S, NH, H, 0.125
 p.ctx, p.ldctx, p.lse = ctx.data_ptr(), H, lse.data_ptr()
@@ -33,5 +35,7 @@ torch.cuda.synchronize()
 st = delta[: B * NH * 32].reshape(B * NH, 4, 8).cpu()
 names = ["stage issue", "key-owner", "dQ phase+store", "stat store", "wait+barrier", "loop head", "loop total"]
 med = st.median(dim=0).values
+print(f"{B} x {S} x {NH}: {NH * B} workgroups; the policy in force would give this call form {plan['bwd_form']} "
+      f"(0 two kernels, 1 single kernel, 2 hybrid), {plan['bwd_one_samples']} samples to the single kernel")
 for w in range(4):
     print(f"wave {w}: " + "  ".join(f"{n} {med[w, k]:.1f}" for k, n in enumerate(names)) + "  (kilo-cycles, median over workgroups)")

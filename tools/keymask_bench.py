@@ -45,8 +45,11 @@ def main():
     qkv = torch.randn(B * S, 3 * H, generator=g).to(torch.bfloat16).to(dev)
     dctx = torch.randn(B * S, H, generator=g).to(torch.bfloat16).to(dev)
     ctx = torch.zeros((B * S, H), dtype=torch.bfloat16, device=dev)
-    lse = torch.zeros((B, NH, S), dtype=torch.float32, device=dev)
-    delta = torch.zeros((B, NH, S), dtype=torch.float32, device=dev)
+    # csrc/attn_plan.h: the statistics' size, and the form a call with words gets whatever the policy says
+    plan = _lib.attn_plan(B, S, NH, _lib.ATTN_KEYMASK | _lib.ATTN_OUT_ROWS)
+    assert plan["rc"] == 0 and plan["bwd_form"] == 0 and plan["km"] == 1, plan
+    lse = torch.zeros(plan["stat_floats"], dtype=torch.float32, device=dev)
+    delta = torch.zeros(plan["stat_floats"], dtype=torch.float32, device=dev)
     dqkv = torch.zeros((B * S, 3 * H), dtype=torch.bfloat16, device=dev)
     ldkw = 2 * ((S + 63) // 64)
 
